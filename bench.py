@@ -18,7 +18,7 @@ when 20 of them are timed, 4.1 us when thousands are; profiles/r02_k20_steps.jso
           (8192 x 8192/N), stripes are independent images, so there is NO data-path collective; RCCL carries
           only the barrier, the max-over-ranks of the elapsed time and the pixel-count sum.  `value` is that
           strong split.  The weak-scaling number (global frame 8192 x 8192*N, one full 8192x8192 stripe per
-          rank) is measured afterwards in the same process and reported beside it as "weak": {...}, and the
+          rank) is measured afterwards in the same process (--full) and reported beside it as "weak": {...}, and the
           north star's "single RCCL halo exchange" -- the same frame pre-partitioned at rows that are NOT aligned,
           one neighbour send/recv of the boundary rows -- as "halo_exchange": {...}.
 
@@ -28,6 +28,12 @@ with the next issue mode -- a one-shot 8-GPU run must end with a JSON line or a 
 
 Frames rotate through a ring of distinct device buffers (16 GiB of input per GPU by default) far larger
 than the 256 MiB Infinity Cache, so the kernel streams from HBM, not from L3.
+
+A plain run does only what the headline needs: set-up, pre-warm and warm-up, the K timed steps and the line.  Everything
+measured or checked beside the headline -- the CPU / JVM baselines and the `sustained` leg, `verified` against the oracle,
+the event-pair and copy-ceiling diagnostics, `reconstruct`, the `hip_streams` / `direct_dispatch` / `pitched` side
+objects, and at N > 1 the other scaling mode, the other issue mode and `halo_exchange` -- runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 
 Prints ONE JSON line on rank 0.
 """
@@ -221,6 +227,59 @@ def verify_against_oracle(wl, order, avg, keep, torch):
     if not equal:
         res["mismatching_pixels"] = int((got != want.reshape(-1)).sum()) if got.shape == want.reshape(-1).shape else -1
     return res
+
+
+DUMP_BYTES = 48 << 20      # --dump-outputs: sample bytes written in all (the files stay under 64 MB)
+DUMP_SEED = 20251016       # --dump-outputs: seed of the sampled pixel positions
+
+
+def dump_outputs(wl, launches, out_dir, prefix=""):
+    """--dump-outputs: what the last timed step computed, as a caller of the timed path receives it, written as
+    out_dir/<prefix><name>.npy.  The timed region is run_steps(0, launches); its last args.batch launches are the last step,
+    and the frames are those its launches wrote, in launch order.  Packed ARGB plans: `argb` (frames, S) float64, the uint32
+    pixels at S fixed, seeded, sorted positions of each frame, and `argb_checksum` (frames, 2) float64, the high and low 32 bits
+    of csic_checksum_device over the WHOLE frame, so that no pixel goes unchecked.  Planar plans: `y`, `cb`, `cr`
+    (frames, S) float32, the same kind of sample of each plane.  S keeps the files under DUMP_BYTES.  The inputs are the seeded
+    synthetic ring (csic_synth_frame_device): the same arguments give the same inputs, and so the same files."""
+    import numpy as np
+    torch = wl.torch
+    slots = list(dict.fromkeys(wl.launch_slots(0, launches)[-wl.args.batch:]))
+    frames = []                                                   # per frame: {name: 1-D contiguous device tensor}
+    for k in slots:
+        for j in range(wl.fps):
+            if wl.planar:
+                lay = wl.plan.planar_layout
+                b = wl.outs[k][j * wl.out_words:(j + 1) * wl.out_words].view(torch.uint8)
+                frames.append({"y": b[lay.y_offset:lay.y_offset + lay.y_width * lay.y_height],
+                               "cb": b[lay.cb_offset:lay.cb_offset + lay.chroma_samples],
+                               "cr": b[lay.cr_offset:lay.cr_offset + lay.chroma_samples]})
+            elif wl.pad:                                          # one frame per launch, rows at out_pitch
+                rows = wl.outs[k][:wl.plan.out_height * wl.out_pitch].view(wl.plan.out_height, wl.out_pitch)
+                frames.append({"argb": rows[:, :wl.plan.out_width].contiguous().view(-1)})
+            else:
+                frames.append({"argb": wl.outs[k][j * wl.out_words:j * wl.out_words + wl.out_px]})
+    os.makedirs(out_dir, exist_ok=True)
+    names = list(frames[0])
+    itemsize = 4 if wl.planar else 8
+    cap = max(1, DUMP_BYTES // (len(names) * itemsize * len(frames)))
+    written = []
+    for name in names:
+        n = frames[0][name].numel()
+        idx = np.arange(n) if n <= cap else np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+        idx_d = torch.from_numpy(idx).to(wl.dev)
+        got = torch.stack([fr[name].index_select(0, idx_d) for fr in frames]).cpu().numpy()
+        arr = got.astype(np.float32) if wl.planar else got.view(np.uint32).astype(np.float64)
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), arr)
+        written.append(prefix + name + ".npy")
+    if not wl.planar:
+        sums = []
+        for fr in frames:
+            s = C.c_uint64()
+            wl.N.check(wl.lib.csic_checksum_device(C.c_void_p(fr["argb"].data_ptr()), fr["argb"].numel(), C.byref(s), wl.sh))
+            sums.append((s.value >> 32, s.value & 0xFFFFFFFF))
+        np.save(os.path.join(out_dir, prefix + "argb_checksum.npy"), np.array(sums, dtype=np.float64))
+        written.append(prefix + "argb_checksum.npy")
+    return written
 
 
 def cpu_quota_cores():
@@ -525,6 +584,26 @@ class Workload:
                 i += 1
         return st
 
+    def launch_slots(self, first, count):
+        """The ring slot that each of launches first .. first+count-1 of run_steps(first, count) writes: launch i of an eager
+        step (and replay i of the per-frame graphs) uses slot i % nring, launch j of a graph replay slot j % nring."""
+        nring = self.nring
+        if self.step_graph is None:
+            return [i % nring for i in range(first, first + count)]
+        glen, i, end, slots = self.graph_len, first, first + count, []
+        rem = self.rem_graph.nframes if self.rem_graph is not None else 0
+        while i < end:                                      # the same walk as run_steps
+            if end - i >= glen:
+                slots += [j % nring for j in range(glen)]
+                i += glen
+            elif rem and end - i == rem:
+                slots += [j % nring for j in range(rem)]
+                i += rem
+            else:
+                slots.append(i % nring)
+                i += 1
+        return slots
+
     def checked_steps(self, first, count, phase):
         """run_steps for the protocol: a non-zero launch status becomes the library's exception (its message names the
         failure); `phase` feeds the test hook."""
@@ -684,6 +763,12 @@ def main(argv=None):
                     help="untimed conditioning before the W warm-up steps: replay the same launches for this long so "
                          "the GPU reaches its steady-state clocks (a 33 us step does not ramp DPM in 40 launches: "
                          "cfg4 measures 33.9 us/step cold vs 32.5 us/step conditioned)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64 / float32: a fixed, "
+                         "seeded sample of every frame's output and, for packed output, a checksum of every whole frame; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything measured or checked beside the headline (baselines, `verified`, diagnostics, side objects; "
+                         "see the module docstring).  Without it a run does only what the headline needs")
     ap = top.add_argument_group("workload (default: BASELINE.json configs[3]; the others are parity / study configs)")
     ap.add_argument("--config", default="cfg4", choices=sorted(CONFIGS))
     ap.add_argument("--order", default="csq", choices=["csq", "scq"],
@@ -898,21 +983,25 @@ def main(argv=None):
     value = total_px / elapsed / 1e6
     achieved = wl.alg_bytes / (kern_ms_avg * 1e-3) / 1e9
     stream = wl.stream
+    if args.dump_outputs:                                          # before anything else launches on the ring
+        dump_outputs(wl, KL, args.dump_outputs, "" if world == 1 else f"rank{rank}_")
 
     # ---- diagnostic (untimed): an event pair around each of a few launches --------------------------
-    npair = min(KL, 50)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(npair)]
-    for i in range(npair):
-        ev[i][0].record(stream)
-        wl.step(i)
-        ev[i][1].record(stream)
-    torch.cuda.synchronize(dev)
-    pair_ms = sorted(s.elapsed_time(e) for s, e in ev)
-    kern_ms_pair_med = pair_ms[npair // 2] / wl.launches_per_step
+    kern_ms_pair_med = None
+    if args.full:
+        npair = min(KL, 50)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(npair)]
+        for i in range(npair):
+            ev[i][0].record(stream)
+            wl.step(i)
+            ev[i][1].record(stream)
+        torch.cuda.synchronize(dev)
+        pair_ms = sorted(s.elapsed_time(e) for s, e in ev)
+        kern_ms_pair_med = pair_ms[npair // 2] / wl.launches_per_step
 
     # ---- measured streaming ceiling on the same buffers (untimed): plain 16 B/lane non-temporal copy ----
     copy_gbs = None
-    if world == 1 and wl.nring >= 2 and (wl.ins[0].numel() % 4 == 0):
+    if args.full and world == 1 and wl.nring >= 2 and (wl.ins[0].numel() % 4 == 0):
         lib, sh, nring = wl.lib, wl.sh, wl.nring
         ncopy = 200
         npx = wl.ins[0].numel()
@@ -943,7 +1032,7 @@ def main(argv=None):
                 "how": how_txt}
 
     head_host_ordered = None
-    if issue == "direct" and (wl.step_graph is not None or wl.per_frame_graph):
+    if args.full and issue == "direct" and (wl.step_graph is not None or wl.per_frame_graph):
         head_host_ordered = host_ordered_object(wl, "the headline's graphs through csic_frame_graph_submit/_wait: no gate, no stream "
                                                     "waits, host wall clock")
 
@@ -952,7 +1041,7 @@ def main(argv=None):
     keep = {}
     order_ops = SCQ if args.order == "scq" else CSQ
     is_avg = args.config in AVG_CONFIGS or args.config.endswith("_avg")
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         box = {}
 
         def cpu_leg():
@@ -996,7 +1085,7 @@ def main(argv=None):
         cpu_res = box.get("res")
     # ---- planar configs: the reconstruct kernel beside the forward one (N = 1; its own roofline) -------------------------------
     recon = None
-    if wl.planar and world == 1:
+    if args.full and wl.planar and world == 1:
         try:
             lay = wl.plan.planar_layout
             lib, sh, nring = wl.lib, wl.sh, wl.nring
@@ -1037,7 +1126,7 @@ def main(argv=None):
             recon = {"unavailable": f"{type(exc).__name__}: {exc}"}
     # ---- the line checks its own output (rank 0, untimed, local: no collective) -----------------------------------------
     verified = None
-    if rank == 0 and not args.no_verify:
+    if args.full and rank == 0 and not args.no_verify:
         try:
             verified = verify_against_oracle(wl, order_ops, is_avg, keep, torch)
         except Exception as exc:                                   # noqa: BLE001 -- reported, never fatal for the measurement
@@ -1090,7 +1179,7 @@ def main(argv=None):
             sides[key] = {"unavailable": f"{type(exc).__name__}: {exc}"}
 
     if args.batch > 1 and head["fps"] == 1 and args.streams <= 1 and not args.pitch_pad and issue != "fused" and not args.no_side \
-            and (world > 1 or args.stripe_of > 1 or args.one_launch):
+            and (args.one_launch or (args.full and (world > 1 or args.stripe_of > 1))):
         # the same steps with ONE launch per step instead of one launch per frame: what batching the frames of a step buys
         # (not the headline: configs[3] names single frames, and a frame per launch is what a stream of arriving frames allows)
         safe_side("one_launch_per_step", headline_mode, "fused")
@@ -1099,24 +1188,26 @@ def main(argv=None):
                                                     "ms_per_launch and roofline_frac_rank0 are per FRAME")
     can_graph = args.streams <= 1 and (head["fps"] == 1 or (args.per_frame_graph and head["fps"] > 1))
     if world > 1:
-        # the other scaling mode, issued the same way as the headline
-        other_mode = "weak" if headline_mode == "strong" else "strong"
-        safe_side(other_mode, other_mode, issue)
-        if can_graph and not args.no_side and issue in ("direct", "hip"):
+        if args.full:
+            # the other scaling mode, issued the same way as the headline
+            other_mode = "weak" if headline_mode == "strong" else "strong"
+            safe_side(other_mode, other_mode, issue)
+            if can_graph and not args.no_side and issue in ("direct", "hip"):
+                other_issue = "hip" if issue == "direct" else "direct"
+                safe_side("hip_streams" if other_issue == "hip" else "direct_dispatch", headline_mode, other_issue)
+            want_halo = not args.no_halo and args.config not in AVG_CONFIGS
+    elif args.stripe_of > 1 and can_graph and not args.no_side:
+        if args.full:
             other_issue = "hip" if issue == "direct" else "direct"
             safe_side("hip_streams" if other_issue == "hip" else "direct_dispatch", headline_mode, other_issue)
-        want_halo = not args.no_halo and args.config not in AVG_CONFIGS
-    elif args.stripe_of > 1 and can_graph and not args.no_side:
-        other_issue = "hip" if issue == "direct" else "direct"
-        safe_side("hip_streams" if other_issue == "hip" else "direct_dispatch", headline_mode, other_issue)
-        safe_side("serial_launches", headline_mode, "serial")
+            safe_side("serial_launches", headline_mode, "serial")
     elif args.direct and can_graph and issue != "direct":
         safe_side("direct_dispatch", headline_mode, "direct")
     profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")
     # `pitched`: the same frames laid out at the row pitches csic_plan_preferred_pitch names (the caller's choice of layout; the
     # headline stays packed).  Measured where the rule pads; where it names the packed layout -- every plan on the round-4
     # kernels -- the object says so and nothing is run twice.
-    if world == 1 and args.stripe_of <= 1 and issue == "serial" and not args.pitch_pad and not head["planar"] \
+    if args.full and world == 1 and args.stripe_of <= 1 and issue == "serial" and not args.pitch_pad and not head["planar"] \
             and not args.per_frame_graph and not args.busy_streams and args.streams <= 1 and not args.no_pitched and args.frames_per_step <= 0:
         if head["preferred_pitch"] == (W, head["out_w"]):
             sides["pitched"] = {"in_pitch_px": W, "out_pitch_px": head["out_w"],
@@ -1127,7 +1218,7 @@ def main(argv=None):
             if isinstance(sides.get("pitched"), dict) and "value" in sides["pitched"]:
                 sides["pitched"]["note"] = ("rows at csic_plan_preferred_pitch (1 KiB of padding per row for factor-1 plans); same frames, same "
                                             "kernel, same timing; never `value`")
-    if world == 1 and args.stripe_of <= 1 and args.config == "cfg4" and can_graph and issue == "serial" and args.batch > 1 \
+    if args.full and world == 1 and args.stripe_of <= 1 and args.config == "cfg4" and can_graph and issue == "serial" and args.batch > 1 \
             and not args.pitch_pad and not args.no_same_mechanism and not args.busy_streams:
         # Like for like across N: `value` at N = 2 comes from hipGraph chains and at N = 4 / 8 from direct dispatch (see --issue);
         # the SAME full frame through those two mechanisms here, so that efficiency(N) = value(N) / (N * <this>) compares one
@@ -1195,10 +1286,10 @@ def main(argv=None):
                 "algorithmic_bytes_strict": None if head["planar"] else 8 * out_px * lpf,
                 "algorithmic_bytes_full": None if head["planar"] else (4 * in_px + 4 * out_px) * lpf,
                 "kernel_ms_avg": round(kern_ms_avg, 5),
-                "kernel_ms_event_pair_median": round(kern_ms_pair_med, 5),
+                "kernel_ms_event_pair_median": None if kern_ms_pair_med is None else round(kern_ms_pair_med, 5),
                 "timing": "kernel_ms_avg = (HIP event after step K - HIP event before step 1) / launches on the launch "
                           "stream (torch current stream), inside the timed region, rank 0; event_pair_median = untimed "
-                          "diagnostic, one event pair per step (inflated by the marker packets)",
+                          "diagnostic, one event pair per step (inflated by the marker packets; --full only)",
             },
         }
         for key, obj in sides.items():

@@ -1,11 +1,14 @@
 """bench.py's contract pieces that can be checked without a GPU: the CPU-baseline leg (the only place
-outside tests/ and smoke() that may touch the oracle), the config table and the argument surface."""
+outside tests/ and smoke() that may touch the oracle), the config table and the argument surface; and one GPU test of a plain
+run and its --dump-outputs files."""
 import importlib.util
 import json
 import re
 import os
 import subprocess
 import sys
+
+import pytest
 
 from conftest import ROOT
 
@@ -238,3 +241,134 @@ def test_every_native_source_of_the_package_is_inside_the_source_hash():
     assert not stray, f"native sources outside csrc/ (not covered by tools/srchash.py): {stray}"
     inc = [f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h")]
     assert inc == ["csic.h"], f"include/*.h must be exactly what srchash hashes: {inc}"
+
+
+def test_launch_slots_follow_run_steps():
+    """--dump-outputs reads the ring slots the last timed step wrote: launch_slots must name, launch for launch, the slots that
+    run_steps writes, whatever mix of graph replays, the shorter graph and eager launches it takes (no GPU: counters)."""
+    bench = _load_bench()
+
+    class SlotGraph:
+        def __init__(self, n, nring, log):
+            self.nframes, self.nring, self.log = n, nring, log
+
+        def launch(self, stream):
+            self.log.extend(j % self.nring for j in range(self.nframes))
+
+    for total, cap, nring in ((1280, 4096, 64), (5000, 4096, 256), (100, 16, 7), (7, 4096, 64), (64, 16, 2)):
+        log = []
+        wl = bench.Workload.__new__(bench.Workload)
+        wl.stream, wl.nring = None, nring
+        wl.graph_len = glen = min(total, cap)
+        wl.step_graph = SlotGraph(glen, nring, log)
+        wl.rem_graph = SlotGraph(total % glen, nring, log) if total % glen else None
+        wl.step = lambda i: (log.append(i % nring), 0)[1]
+        for first, count in ((0, total), (0, glen + 3), (3, 5)):
+            log.clear()
+            wl.run_steps(first, count)
+            assert wl.launch_slots(first, count) == log, (total, cap, nring, first, count)
+    wl = bench.Workload.__new__(bench.Workload)
+    wl.step_graph, wl.nring = None, 5
+    assert wl.launch_slots(8, 4) == [3, 4, 0, 1]
+
+
+def test_dump_outputs_on_a_fake_workload(tmp_path, monkeypatch):
+    """--dump-outputs without a GPU: CPU tensors stand in for the ring.  The files hold the frames of the LAST step only, in
+    launch order, as float64 (packed ARGB, exact for uint32) or float32 (planar bytes); a frame larger than the budget is
+    sampled at fixed, seeded, sorted positions, the same on every call; and the whole-frame checksum is split exactly."""
+    import types
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    sums = {}
+
+    def fake_checksum(ptr, n, ref, sh):
+        ref._obj.value = sums[ptr.value]
+        return 0
+
+    def workload(nring, batch, fps, out_px, **kw):
+        outs = [torch.arange(fps * out_px, dtype=torch.int64).add(k << 20).to(torch.int32) | (-(1 << 31)) for k in range(nring)]
+        wl = types.SimpleNamespace(torch=torch, dev="cpu", sh=None, nring=nring, fps=fps, out_px=out_px, out_words=out_px, planar=False,
+                                   pad=0, outs=outs, args=types.SimpleNamespace(batch=batch), step_graph=None,
+                                   lib=types.SimpleNamespace(csic_checksum_device=fake_checksum), N=types.SimpleNamespace(check=lambda st: None))
+        wl.__dict__.update(kw)
+        wl.launch_slots = types.MethodType(bench.Workload.launch_slots, wl)
+        return wl
+
+    # packed, 3 launches per step, 2 frames per launch; 5 steps over a ring of 4: the last step is launches 12..14 = slots 0, 1, 2
+    wl = workload(4, 3, 2, 1000)
+    for k in range(3):
+        for j in range(2):
+            sums[wl.outs[k][j * 1000:].data_ptr()] = (0xDEADBEEF << 32) | (k * 2 + j)
+    d = tmp_path / "packed"
+    assert sorted(bench.dump_outputs(wl, 15, str(d))) == ["argb.npy", "argb_checksum.npy"]
+    argb = np.load(d / "argb.npy")
+    assert argb.dtype == np.float64 and argb.shape == (6, 1000)
+    want = np.stack([wl.outs[k][j * 1000:(j + 1) * 1000].numpy().view(np.uint32) for k in range(3) for j in range(2)])
+    assert np.array_equal(argb, want.astype(np.float64)) and argb.max() >= 2 ** 31
+    ck = np.load(d / "argb_checksum.npy")
+    assert ck.dtype == np.float64 and ck.tolist() == [[0xDEADBEEF, n] for n in range(6)]
+
+    # a frame over the budget: a seeded sample, identical from call to call
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 2 * 100)
+    wl = workload(2, 3, 1, 5000)
+    sums.update({t.data_ptr(): 1 for t in wl.outs})
+    bench.dump_outputs(wl, 6, str(tmp_path / "a"))
+    bench.dump_outputs(wl, 6, str(tmp_path / "b"))
+    a, b = np.load(tmp_path / "a" / "argb.npy"), np.load(tmp_path / "b" / "argb.npy")
+    assert a.shape == (2, 100) and np.array_equal(a, b)                       # launches 3..5 = slots 1, 0, 1: two frames
+    assert np.all(np.diff(a[0]) > 0) and np.all(a[0] - a[1] == 1 << 20)       # sorted positions, the same in every frame
+
+    # rows at a pitch: only the out_width pixels of each row
+    monkeypatch.setattr(bench, "DUMP_BYTES", 48 << 20)
+    wl = workload(2, 1, 1, 0, pad=8, out_pitch=24, plan=types.SimpleNamespace(out_width=16, out_height=5))
+    wl.outs = [torch.arange(5 * 24, dtype=torch.int32) + 1000 * k for k in range(2)]
+    sums.update({0: 0})
+    wl.lib.csic_checksum_device = lambda ptr, n, ref, sh: 0
+    bench.dump_outputs(wl, 3, str(tmp_path / "pitched"))
+    got = np.load(tmp_path / "pitched" / "argb.npy")
+    assert np.array_equal(got, (np.arange(5 * 24).reshape(5, 24)[:, :16].reshape(1, -1) + 0.0))
+
+    # planar: the three planes, padding between them left out
+    lay = types.SimpleNamespace(y_offset=0, y_width=8, y_height=4, cb_offset=256, cr_offset=512, chroma_samples=8)
+    wl = workload(3, 2, 1, 0, planar=True, out_words=192, plan=types.SimpleNamespace(planar_layout=lay))
+    wl.outs = [torch.arange(768, dtype=torch.int32).to(torch.uint8).view(torch.int32) for _ in range(3)]
+    assert sorted(bench.dump_outputs(wl, 4, str(tmp_path / "planar"))) == ["cb.npy", "cr.npy", "y.npy"]
+    y, cb, cr = (np.load(tmp_path / "planar" / f"{n}.npy") for n in ("y", "cb", "cr"))
+    assert y.dtype == np.float32 and y.shape == (2, 32) and cb.shape == cr.shape == (2, 8)
+    assert y[0].tolist() == list(range(32)) and cb[0].tolist() == list(range(8)) and cr[1].tolist() == list(range(8))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_its_last_step(tmp_path, oracle):
+    """A plain run (no --full) times exactly --steps steps and prints the headline line without the objects --full adds, and
+    --dump-outputs writes the frames of the LAST timed step: here every pixel, bit for bit the oracle's output for the seeded ring
+    slots those launches used, plus the checksum of every whole frame; for a planar plan its three planes."""
+    import numpy as np
+    bench = _load_bench()
+
+    def run(out, *extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--ring-mib", "8", "--prewarm-ms", "0",
+                            "--dump-outputs", str(out), *extra], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+
+    # cfg3: 512x512 frames of 1 MiB, a ring of 8; 4 steps of 3 launches: the last step is launches 9..11 = ring slots 1, 2, 3
+    line = run(tmp_path / "packed", "--config", "cfg3", "--batch-frames", "3", "--steps", "4", "--warmup", "1")
+    assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["value"] > 0 and line["config"]["launches_per_step"] == 3
+    assert line["unit"] == "Mpixels/s" and line["higher_is_better"] is True and line["dtype"] == "u8" and "Mpixels/s" in line["metric"]
+    assert not {"verified", "cpu_baseline", "sustained", "hip_streams", "direct_dispatch", "pitched"} & set(line)
+    p = oracle.OracleParams(width=512, height=512, chroma_a=2, chroma_b=0, y_bits=3, cb_bits=3, cr_bits=2, factor=2, op=(3, 1, 2))
+    want = np.stack([oracle.process(p, oracle.synth_frame(512 * 512, k * 512 * 512)).reshape(-1) for k in (1, 2, 3)])
+    argb = np.load(tmp_path / "packed" / "argb.npy")
+    assert argb.dtype == np.float64 and np.array_equal(argb, want.astype(np.float64))
+    ck = np.load(tmp_path / "packed" / "argb_checksum.npy")
+    assert ck.tolist() == [[float(c >> 32), float(c & 0xFFFFFFFF)] for c in map(bench.frame_checksum, want)]
+
+    # planar output at 512x256 (frames of 0.5 MiB, a ring of 16): 2 steps of one launch, the last one on slot 1
+    run(tmp_path / "planar", "--config", "planar_cfg4", "--shape", "512,256", "--steps", "2", "--warmup", "1")
+    p = oracle.OracleParams(width=512, height=256, chroma_a=2, chroma_b=0, y_bits=8, cb_bits=8, cr_bits=8, factor=2, op=(3, 1, 2))
+    _, y, cb, cr = oracle.planar(p, oracle.synth_frame(512 * 256, 512 * 256))
+    for name, plane in (("y", y), ("cb", cb), ("cr", cr)):
+        got = np.load(tmp_path / "planar" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, plane.reshape(1, -1).astype(np.float32)), name

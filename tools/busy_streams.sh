@@ -11,10 +11,10 @@ cd "$ROOT"
 J=$OUT/busy_streams.jsonl; : > "$J"
 for k in 0 1 2; do
   for mode in "--issue hip" "--issue direct" "--issue direct --direct-queues 4" "--issue fused"; do
-    timeout -k 10 200 python bench.py --no-cpu-baseline --config cfg5 --per-frame-graph $mode --steps 400 --warmup 100 --busy-streams $k \
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --config cfg5 --per-frame-graph $mode --steps 400 --warmup 100 --busy-streams $k \
         >> "$J" 2>> "$OUT/busy_streams.err" || { tail -3 "$OUT/busy_streams.err"; exit 1; }
   done
-  timeout -k 10 200 python bench.py --no-cpu-baseline --config cfg5 --steps 400 --warmup 100 --busy-streams $k \
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --config cfg5 --steps 400 --warmup 100 --busy-streams $k \
       >> "$J" 2>> "$OUT/busy_streams.err" || { tail -3 "$OUT/busy_streams.err"; exit 1; }
 done
 python - "$J" > "$OUT/busy_streams.md" <<'PY'

@@ -22,11 +22,11 @@ bash tools/artifacts.sh profile_rows $TAG >> "$OUT/profile_stage.log" 2>&1 || { 
 echo "profiles done"
 exit 0
 fi
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
 : > "$OUT/bench_repeat.jsonl"
-for i in 1 2 3 4 5; do python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline >> "$OUT/bench_repeat.jsonl" 2>> "$OUT/bench.err" || exit 1; done
+for i in 1 2 3 4 5; do python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline >> "$OUT/bench_repeat.jsonl" 2>> "$OUT/bench.err" || exit 1; done
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_ns" -o trace -- python3 "$ROOT/bench.py" --no-sustained > "$OUT/trace_no_sustained_bench.json" 2> "$OUT/trace_ns.err" || { tail -5 "$OUT/trace_ns.err"; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_ns" -o trace -- python3 "$ROOT/bench.py" --full --no-sustained > "$OUT/trace_no_sustained_bench.json" 2> "$OUT/trace_ns.err" || { tail -5 "$OUT/trace_ns.err"; exit 1; }
 cd "$ROOT"
 python - "$OUT" <<'PY'
 import json, sys

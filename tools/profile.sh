@@ -18,9 +18,9 @@ export TMPDIR=/tmp
 # the sources this binary was built from, hashed HERE (on the box that profiles), not where the results are collected
 python3 "$ROOT/tools/srchash.py" > "$OUT/source_sha256.txt"
 cd /tmp
-# the kernel trace runs bench.py exactly as the driver does (defaults); the PMC passes skip the CPU baseline
-BENCH="python3 $ROOT/bench.py $FLAGS --no-cpu-baseline --batch-frames 1 --steps 600 --warmup 100"
-if [ "$CONFIG" = "cfg4" ]; then TRACE="python3 $ROOT/bench.py"; else TRACE="$BENCH"; fi
+# the kernel trace runs bench.py --full with its default workload; the PMC passes skip the CPU baseline
+BENCH="python3 $ROOT/bench.py --full $FLAGS --no-cpu-baseline --batch-frames 1 --steps 600 --warmup 100"
+if [ "$CONFIG" = "cfg4" ]; then TRACE="python3 $ROOT/bench.py --full"; else TRACE="$BENCH"; fi
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- $TRACE > "$OUT/trace_bench.json" 2> "$OUT/trace.err" &&
 { find "$OUT/trace" -name '*kernel_trace.csv' -size +8M -delete; true; } &&   # the --stats summary is what is kept (the default run's `sustained` leg is ~200k launches)
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o fetch -- $BENCH > "$OUT/fetch_bench.json" 2> "$OUT/fetch.err" &&

@@ -16,9 +16,9 @@ LOG=$OUT/${TAG}_rccl_ws1.log
 : > "$LOG"
 run() { echo "## $*" >> "$LOG"; timeout -k 10 300 "$@" >> "$LOG" 2>&1; }
 L="python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port"
-run $L 29531 bench.py --gpus 1 --force-pg --backend nccl --stripe-of 8 --steps 20 --warmup 5 --no-cpu-baseline || { tail -5 "$LOG"; exit 1; }
-run python bench.py --gpus 1 --stripe-of 8 --steps 20 --warmup 5 --no-cpu-baseline || { tail -5 "$LOG"; exit 1; }
-run $L 29532 bench.py --gpus 1 --force-pg --backend nccl --steps 20 --warmup 5 --no-cpu-baseline || { tail -5 "$LOG"; exit 1; }
+run $L 29531 bench.py --full --gpus 1 --force-pg --backend nccl --stripe-of 8 --steps 20 --warmup 5 --no-cpu-baseline || { tail -5 "$LOG"; exit 1; }
+run python bench.py --full --gpus 1 --stripe-of 8 --steps 20 --warmup 5 --no-cpu-baseline || { tail -5 "$LOG"; exit 1; }
+run $L 29532 bench.py --full --gpus 1 --force-pg --backend nccl --steps 20 --warmup 5 --no-cpu-baseline || { tail -5 "$LOG"; exit 1; }
 python - "$LOG" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

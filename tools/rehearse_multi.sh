@@ -20,7 +20,7 @@ tail -n 4 "$OUT/${TAG}_multi_rehearsal${SUF}.halo.log"
 [ $rc -eq 0 ] || exit $rc
 fi
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $NP --master-addr 127.0.0.1 --master-port 29518 \
-    bench.py --gpus $NP --backend gloo --steps 20 --warmup 5 > "$OUT/${TAG}_multi_rehearsal${SUF}.bench.log" 2>&1
+    bench.py --full --gpus $NP --backend gloo --steps 20 --warmup 5 > "$OUT/${TAG}_multi_rehearsal${SUF}.bench.log" 2>&1
 rc=$?
 tail -n 2 "$OUT/${TAG}_multi_rehearsal${SUF}.bench.log"
 [ $rc -eq 0 ] || exit $rc
@@ -29,7 +29,7 @@ tail -n 2 "$OUT/${TAG}_multi_rehearsal${SUF}.bench.log"
 ISSUE=direct; [ "$NP" = "2" ] && ISSUE=hip
 CSIC_BENCH_INJECT_FAIL="rank=$((NP-1)),issue=$ISSUE,phase=timed" timeout -k 10 400 python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node $NP --master-addr 127.0.0.1 --master-port 29520 \
-    bench.py --gpus $NP --backend gloo --steps 20 --warmup 5 --no-side > "$OUT/${TAG}_multi_rehearsal${SUF}.inject.log" 2>&1
+    bench.py --full --gpus $NP --backend gloo --steps 20 --warmup 5 --no-side > "$OUT/${TAG}_multi_rehearsal${SUF}.inject.log" 2>&1
 rc=$?
 tail -n 1 "$OUT/${TAG}_multi_rehearsal${SUF}.inject.log" | python -c "
 import json, sys
