@@ -20,7 +20,7 @@ EIO, EFORMAT = -30, -31
 
 OP_NOOP, OP_SPATIAL, OP_QUANT, OP_CHROMA = 0, 1, 2, 3
 ROUND_FLOOR_HW, ROUND_TRUNC_SW = 0, 1
-FMT_ARGB8888, FMT_YCBCR888X, FMT_PLANAR = 0, 1, 2
+FMT_ARGB8888, FMT_YCBCR888X, FMT_PLANAR, FMT_PLANAR_BITS = 0, 1, 2, 3
 TUNE_VARIANT, TUNE_FORCE_GENERIC, TUNE_NONTEMPORAL, TUNE_NO_VECTOR, TUNE_BLOCK_THREADS = 1, 2, 3, 4, 5
 FRAME_GRAPH_HIP, FRAME_GRAPH_DIRECT, FRAME_GRAPH_FUSED, FRAME_GRAPH_AUTO = 0, 1, 2, 3
 FRAME_GRAPH_DEFAULT_BRANCHES, FRAME_GRAPH_DEFAULT_QUEUES = 4, 3
@@ -73,6 +73,13 @@ class CsicPlanarLayout(C.Structure):
                 ("frame_bytes", C.c_int64), ("payload_bytes", C.c_int64)]
 
 
+class CsicPlanarBitsLayout(C.Structure):
+    _fields_ = [("geometry", CsicPlanarLayout), ("y_bits", C.c_int32), ("cb_bits", C.c_int32), ("cr_bits", C.c_int32),
+                ("reserved", C.c_int32), ("y_bytes", C.c_int64), ("cb_bytes", C.c_int64), ("cr_bytes", C.c_int64),
+                ("y_offset", C.c_int64), ("cb_offset", C.c_int64), ("cr_offset", C.c_int64),
+                ("frame_bytes", C.c_int64), ("payload_bytes", C.c_int64)]
+
+
 class CsicFilesStats(C.Structure):
     _fields_ = [("frames", C.c_int64), ("wall_s", C.c_double), ("decode_s", C.c_double), ("encode_s", C.c_double),
                 ("gpu_wait_s", C.c_double), ("slot_wait_s", C.c_double), ("decode_threads", C.c_int32), ("encode_threads", C.c_int32),
@@ -100,6 +107,8 @@ PROTOTYPES = {
     "csic_stripe_halo": (C.c_int, [C.POINTER(CsicParams), C.c_int32, C.c_int32, C.POINTER(C.c_int32)] + [C.POINTER(C.c_int32)] * 6),
     "csic_planar_layout_of": (C.c_int, [C.POINTER(CsicParams), C.POINTER(CsicPlanarLayout)]),
     "csic_reconstruct_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "csic_planar_bits_layout_of": (C.c_int, [C.POINTER(CsicParams), C.POINTER(CsicPlanarBitsLayout)]),
+    "csic_reconstruct_bits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "csic_plan_preferred_pitch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "csic_debug_build": (C.c_int, []),
     "csic_debug_probe_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),

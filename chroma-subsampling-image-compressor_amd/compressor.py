@@ -82,6 +82,22 @@ class Plan:
         return lay
 
     @property
+    def planar_bits(self) -> bool:
+        return self.c_params.out_format == N.FMT_PLANAR_BITS
+
+    @property
+    def planar_bits_layout(self) -> N.CsicPlanarBitsLayout:
+        """csic_planar_bits_layout of these parameters (whatever the plan's out_format is)."""
+        lay = N.CsicPlanarBitsLayout()
+        N.check(N.lib().csic_planar_bits_layout_of(C.byref(self.c_params), C.byref(lay)))
+        return lay
+
+    @property
+    def frame_bytes(self) -> int:
+        """Bytes of one output frame buffer of a planar (PLANAR / PLANAR_BITS) plan."""
+        return self.planar_bits_layout.frame_bytes if self.planar_bits else self.planar_layout.frame_bytes
+
+    @property
     def preferred_pitch(self) -> Tuple[int, int]:
         """(in_pitch_px, out_pitch_px) at which a caller that owns its surfaces should lay frames out (csic_plan_preferred_pitch)."""
         ip, op = C.c_int32(), C.c_int32()
@@ -103,9 +119,10 @@ class Plan:
             raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: tensor is on a different device than the plan")
         if d_in.numel() != nframes * self.width * self.height:
             raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: expected {nframes * self.width * self.height} input pixels, got {d_in.numel()}")
-        if self.planar:
-            # planar frame buffers: frame_bytes bytes per frame (csic_planar_layout), a uint8 tensor (nframes, frame_bytes)
-            fb = self.planar_layout.frame_bytes
+        if self.planar or self.planar_bits:
+            # planar frame buffers: frame_bytes bytes per frame (csic_planar_layout / csic_planar_bits_layout), a uint8 tensor
+            # (nframes, frame_bytes)
+            fb = self.frame_bytes
             if d_out is None:
                 d_out = torch.empty((nframes, fb) if nframes > 1 else (fb,), dtype=torch.uint8, device=d_in.device)
             elif d_out.numel() * d_out.element_size() != nframes * fb or not d_out.is_contiguous() or d_out.device != d_in.device:
@@ -156,6 +173,39 @@ class Plan:
                                                 int(out_format), self._stream()))
         return d_out
 
+    def reconstruct_bits_device(self, d_bits, d_out=None, nframes: int = 1, out_format: int = N.FMT_ARGB8888):
+        """Bit-packed planar frame buffers of these parameters -> packed pixels (csic_reconstruct_bits_device), as
+        reconstruct_device does for PLANAR frames.  reconstruct_bits(bits(x)) == the packed output of the same parameters."""
+        import torch
+        fb = self.planar_bits_layout.frame_bytes
+        if not d_bits.is_cuda or not d_bits.is_contiguous() or d_bits.numel() * d_bits.element_size() != nframes * fb:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_bits must hold nframes * planar_bits_layout.frame_bytes bytes")
+        shape = (self.out_height, self.out_width) if nframes == 1 else (nframes, self.out_height, self.out_width)
+        if d_out is None:
+            d_out = torch.empty(shape, dtype=torch.int32, device=d_bits.device)
+        elif d_out.numel() != nframes * self.out_width * self.out_height or d_out.element_size() != 4 or not d_out.is_contiguous():
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_out has the wrong size/layout")
+        N.check(N.lib().csic_reconstruct_bits_device(self._h, C.c_void_p(d_bits.data_ptr()), C.c_void_p(d_out.data_ptr()), nframes,
+                                                     int(out_format), self._stream()))
+        return d_out
+
+    def unpack_planar_bits(self, buf) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """One bit-packed planar frame buffer (bytes on the host) -> (Y (Ho, Wo), Cb, Cr) with the restored 8-bit values
+        (code << (8 - q)): what split_planar gives for the PLANAR frame of the same parameters."""
+        lay = self.planar_bits_layout
+        b = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+        g = lay.geometry
+
+        def plane(off, nbytes, count, q):
+            bits = np.unpackbits(b[off:off + nbytes], bitorder="little")[:count * q].reshape(count, q)
+            codes = (bits.astype(np.uint16) << np.arange(q, dtype=np.uint16)).sum(axis=1)
+            return (codes << (8 - q)).astype(np.uint8)
+
+        n = g.y_width * g.y_height
+        return (plane(lay.y_offset, lay.y_bytes, n, lay.y_bits).reshape(g.y_height, g.y_width),
+                plane(lay.cb_offset, lay.cb_bytes, g.chroma_samples, lay.cb_bits),
+                plane(lay.cr_offset, lay.cr_bytes, g.chroma_samples, lay.cr_bits))
+
     def split_planar(self, buf) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """One planar frame buffer (bytes on the host: numpy uint8, or anything np.frombuffer takes) -> (Y (Ho, Wo), Cb, Cr):
         the chroma planes as flat arrays of planar_layout.chroma_samples values in sample order."""
@@ -167,8 +217,8 @@ class Plan:
 
     def process_host(self, argb: np.ndarray) -> np.ndarray:
         a = np.ascontiguousarray(argb, dtype=np.uint32).reshape(-1)
-        if self.planar:
-            out = np.zeros(self.planar_layout.frame_bytes // 4, dtype=np.uint32)
+        if self.planar or self.planar_bits:
+            out = np.zeros(self.frame_bytes // 4, dtype=np.uint32)
             N.check(N.lib().csic_process_host(self._h, a.ctypes.data_as(C.c_void_p), a.size, out.ctypes.data_as(C.c_void_p), out.size))
             return out.view(np.uint8)
         out = np.empty(self.out_width * self.out_height, dtype=np.uint32)
@@ -310,6 +360,11 @@ class ImageCompressorTop:
     def processYCbCr(self, argb):
         """ARGB frame in -> the PixelYCbCrBundle stream io.out carries (byte0=Y, byte1=Cb, byte2=Cr)."""
         return self.plan(PixelFormat.YCBCR888X).process(argb)
+
+    def processPlanarBits(self, argb):
+        """ARGB frame in -> one bit-packed planar frame buffer (CSIC_FMT_PLANAR_BITS, uint8: planar_bits_layout.frame_bytes on the
+        host, a CUDA uint8 tensor for a CUDA input); Plan.unpack_planar_bits cuts it into the three planes."""
+        return self.plan(PixelFormat.PLANAR_BITS).process(argb)
 
     def close(self) -> None:
         for p in self._plans.values():

@@ -303,6 +303,8 @@ int csic_process_png_files(csic_plan *plan, const char *const *in_paths, const c
     if (png_level < 0 || png_level > 9) return set_error(CSIC_EINVAL_SIZE, "png_level must be in 0..9. Got %d", png_level);
     if (plan_params(plan).out_format == CSIC_FMT_PLANAR)
         return set_error(CSIC_EINVAL_FORMAT, "the file pools write packed pixels: the plan's out_format must not be CSIC_FMT_PLANAR");
+    if (plan_params(plan).out_format == CSIC_FMT_PLANAR_BITS)
+        return set_error(CSIC_EINVAL_FORMAT, "the file pools write packed pixels: the plan's out_format must not be CSIC_FMT_PLANAR_BITS");
     Shared sh;
     sh.plan = plan;
     sh.device = plan_device(plan);

@@ -905,6 +905,8 @@ int csic_frame_graph_create_ex(csic_plan *plan, const void *const *d_in, void *c
     // stream-ordered way through them at every frame size (profiles/r02_small_launch.md); the per-frame-launch backends are
     // for callers that ask for per-frame launches by name.
     if (backend == CSIC_FRAME_GRAPH_AUTO) backend = CSIC_FRAME_GRAPH_FUSED;
+    if (plan_params(plan).out_format == CSIC_FMT_PLANAR_BITS)
+        return set_error(CSIC_EINVAL_FORMAT, "a CSIC_FMT_PLANAR_BITS plan has no frame graph (no backend, FUSED included, takes it)");
     if (plan_params(plan).out_format == CSIC_FMT_PLANAR && backend != CSIC_FRAME_GRAPH_FUSED)
         return set_error(CSIC_EINVAL_FORMAT, "a planar plan's frame graph is one fused launch (CSIC_FRAME_GRAPH_AUTO / _FUSED); the per-frame-launch "
                                               "backends take packed formats only");

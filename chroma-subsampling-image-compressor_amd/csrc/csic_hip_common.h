@@ -101,6 +101,9 @@ int planar_prepare_table(const csic_plan *pl, const void *const *d_in_tab, void 
                          PlanarLaunchDesc *d);
 int planar_enqueue(const PlanarLaunchDesc &d, hipStream_t stream);
 void planar_kernel_name(const csic_plan *pl, char *buf, size_t len);
+// csic_planar_bits.hip: out_format = CSIC_FMT_PLANAR_BITS (forward: packed input -> bit-packed planar frame buffers; kernel name)
+int planar_bits_forward(const csic_plan *pl, const void *d_in, void *d_bits, int nframes, hipStream_t stream);
+void planar_bits_kernel_name(const csic_plan *pl, char *buf, size_t len);
 int planar_avg_geometry(const csic_plan *pl, int nframes, LaunchDesc *d, bool *tile);   // k_avg's geometry for a planar AVG plan
 void plan_sizes(const csic_plan *pl, size_t *in_px, size_t *out_px);
 int32_t plan_width(const csic_plan *pl);

@@ -136,8 +136,11 @@ static int validate_impl(const csic_params *p)
         return set_error(CSIC_EINVAL_SAMPLING, "the AVG extension is defined for the order chroma -> spatial -> quant only");
     if (p->in_format != CSIC_FMT_ARGB8888 && p->in_format != CSIC_FMT_YCBCR888X)
         return set_error(CSIC_EINVAL_FORMAT, "in_format must be ARGB8888(0) or YCBCR888X(1). Got %d", p->in_format);
-    if (p->out_format != CSIC_FMT_ARGB8888 && p->out_format != CSIC_FMT_YCBCR888X && p->out_format != CSIC_FMT_PLANAR)
-        return set_error(CSIC_EINVAL_FORMAT, "out_format must be ARGB8888(0), YCBCR888X(1) or PLANAR(2). Got %d", p->out_format);
+    if (p->out_format != CSIC_FMT_ARGB8888 && p->out_format != CSIC_FMT_YCBCR888X && p->out_format != CSIC_FMT_PLANAR &&
+        p->out_format != CSIC_FMT_PLANAR_BITS)
+        return set_error(CSIC_EINVAL_FORMAT, "out_format must be ARGB8888(0), YCBCR888X(1), PLANAR(2) or PLANAR_BITS(3). Got %d", p->out_format);
+    if (p->out_format == CSIC_FMT_PLANAR_BITS && p->in_format != CSIC_FMT_ARGB8888)
+        return set_error(CSIC_EINVAL_FORMAT, "out_format PLANAR_BITS(3) takes ARGB8888(0) input only. Got in_format %d", p->in_format);
     // ImageProcessor.scala:25 -- a rule of ImageProcessorParams only; the raw RTL accepts any size
     if (p->strict_divisible && (p->width % p->factor != 0 || p->height % p->factor != 0))
         return set_error(CSIC_EINVAL_NOT_DIVISIBLE,
@@ -195,6 +198,26 @@ void planar_layout(const Geometry &g, const csic_params *p, csic_planar_layout *
     L->cr_offset = L->cb_offset + up(plane);
     L->frame_bytes = L->cr_offset + up(plane);
     L->payload_bytes = n + 2 * L->chroma_samples;
+}
+
+// csic.h: CSIC_FMT_PLANAR_BITS -- the planar sample geometry, each plane at its quantised bit width
+void planar_bits_layout(const Geometry &g, const csic_params *p, csic_planar_bits_layout *L)
+{
+    std::memset(L, 0, sizeof *L);
+    planar_layout(g, p, &L->geometry);
+    const csic_planar_layout &G = L->geometry;
+    auto up = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
+    auto bytes = [](int64_t s, int32_t q) { return (s * q + 7) / 8; };
+    const int64_t n = (int64_t)G.y_width * G.y_height, plane = (int64_t)G.chroma_width * G.chroma_height;
+    L->y_bits = p->y_bits; L->cb_bits = p->cb_bits; L->cr_bits = p->cr_bits;
+    L->y_bytes = bytes(n, p->y_bits);
+    L->cb_bytes = bytes(G.chroma_samples, p->cb_bits);
+    L->cr_bytes = bytes(G.chroma_samples, p->cr_bits);
+    L->y_offset = 0;
+    L->cb_offset = up(L->y_bytes);
+    L->cr_offset = L->cb_offset + up(bytes(plane, p->cb_bits));
+    L->frame_bytes = L->cr_offset + up(bytes(plane, p->cr_bits));
+    L->payload_bytes = L->y_bytes + L->cb_bytes + L->cr_bytes;
 }
 
 void magic_div(uint32_t d, uint32_t *m, uint32_t *k)
@@ -263,6 +286,11 @@ int csic_algorithmic_bytes(const csic_params *p, int64_t *bytes)
         planar_layout(g, p, &L);
         out_bytes = L.payload_bytes;
     }
+    if (p->out_format == CSIC_FMT_PLANAR_BITS) {
+        csic_planar_bits_layout L;
+        planar_bits_layout(g, p, &L);
+        out_bytes = L.payload_bytes;
+    }
     if (p->sampling == CSIC_SAMPLING_AVG) *bytes = 4ll * g.W * g.H + out_bytes;
     else                                  *bytes = 4ll * g.W * g.Ho + out_bytes;
     clear_error();
@@ -277,6 +305,17 @@ int csic_planar_layout_of(const csic_params *p, csic_planar_layout *layout)
     if (st != CSIC_OK) return st;
     std::memset(layout, 0, sizeof *layout);
     planar_layout(g, p, layout);
+    clear_error();
+    return CSIC_OK;
+}
+
+int csic_planar_bits_layout_of(const csic_params *p, csic_planar_bits_layout *layout)
+{
+    if (!layout) return set_error(CSIC_EINVAL_NULL, "layout is NULL");
+    Geometry g;
+    int st = derive_geometry(p, &g);
+    if (st != CSIC_OK) return st;
+    planar_bits_layout(g, p, layout);
     clear_error();
     return CSIC_OK;
 }

@@ -907,6 +907,11 @@ static void select(csic_plan *pl)
         planar_kernel_name(pl, pl->name, sizeof pl->name);
         return;
     }
+    if (pl->p.out_format == CSIC_FMT_PLANAR_BITS) {      // csic_planar_bits.hip picks and names its kernels
+        pl->fam = FAM_GENERIC; pl->fn = nullptr; pl->units_per_row = pl->g.Wo; pl->k_per_lane = 1;
+        planar_bits_kernel_name(pl, pl->name, sizeof pl->name);
+        return;
+    }
     const int r = pl->p.rounding, f = pl->p.out_format;
     if (r == R_FLOOR && f == F_ARGB) select_rf<R_FLOOR, F_ARGB>(pl);
     else if (r == R_FLOOR) select_rf<R_FLOOR, F_YCC>(pl);
@@ -941,6 +946,9 @@ static int prepare_common(const csic_plan *pl, uintptr_t align_bits, int nframes
 {
     if (nframes <= 0 || nframes > 65535)
         return set_error(CSIC_EINVAL_SIZE, "nframes per launch must be in 1..65535. Got %d", nframes);
+    if (pl->p.out_format == CSIC_FMT_PLANAR_BITS)
+        return set_error(CSIC_EINVAL_FORMAT, "CSIC_FMT_PLANAR_BITS plans go through csic_process_device / csic_process_batch_device / "
+                                              "csic_process_host and csic_pipeline_* only (no row pitches, frame graphs, file pools or csic_multi)");
     if (pl->p.out_format == CSIC_FMT_PLANAR)
         return set_error(CSIC_EINVAL_FORMAT, "planar plans go through csic_process_device / csic_process_batch_device / csic_process_host, "
                                               "csic_pipeline_* and fused frame graphs only (no row pitches, per-frame-launch graphs, file pools or csic_multi)");
@@ -1155,6 +1163,13 @@ static int launch(csic_plan *pl, const void *d_in, void *d_out, int nframes, hip
         if (st == CSIC_OK) clear_error();
         return st;
     }
+    if (pl->p.out_format == CSIC_FMT_PLANAR_BITS) {
+        if (in_pitch > 0 || out_pitch > 0)
+            return set_error(CSIC_EINVAL_FORMAT, "CSIC_FMT_PLANAR_BITS output takes packed input rows and its own plane layout: no row pitches");
+        const int st = planar_bits_forward(pl, d_in, d_out, nframes, stream);
+        if (st == CSIC_OK) clear_error();
+        return st;
+    }
     for (int f0 = 0; f0 < nframes; f0 += 65535) {     // grid z limit
         const int nz = (nframes - f0 < 65535) ? nframes - f0 : 65535;
         LaunchDesc d;
@@ -1192,6 +1207,11 @@ void plan_sizes(const csic_plan *pl, size_t *in_px, size_t *out_px)
     if (pl->p.out_format == CSIC_FMT_PLANAR) {           // what csic_process_host moves: the planar frame buffer, in 4-byte words
         csic_planar_layout L;
         planar_layout(pl->g, &pl->p, &L);
+        *out_px = (size_t)(L.frame_bytes / 4);
+    }
+    if (pl->p.out_format == CSIC_FMT_PLANAR_BITS) {
+        csic_planar_bits_layout L;
+        planar_bits_layout(pl->g, &pl->p, &L);
         *out_px = (size_t)(L.frame_bytes / 4);
     }
 }

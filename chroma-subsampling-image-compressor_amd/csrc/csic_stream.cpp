@@ -190,6 +190,8 @@ int csic_stream_create(const csic_params *p, int32_t kind, csic_stream **out)
     int st = derive_geometry(p, &g);                      // every require() of the generators
     if (st != CSIC_OK) return st;
     if (kind < CSIC_STREAM_TOP || kind > CSIC_STREAM_QUANT) return set_error(CSIC_EINVAL_SIZE, "unknown stream-model kind %d", kind);
+    if (p->out_format == CSIC_FMT_PLANAR_BITS)
+        return set_error(CSIC_EINVAL_FORMAT, "the cycle-level model emits pixels one by one: out_format must not be CSIC_FMT_PLANAR_BITS");
     if (p->sampling != CSIC_SAMPLING_HOLD_DECIMATE)
         return set_error(CSIC_EINVAL_SAMPLING, "the cycle-level model describes the reference's RTL: HOLD_DECIMATE only");
     const bool has_rgb = kind == CSIC_STREAM_TOP || kind == CSIC_STREAM_PROCESSOR || kind == CSIC_STREAM_RGB2YCBCR;

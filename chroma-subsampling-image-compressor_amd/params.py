@@ -46,6 +46,7 @@ class PixelFormat(enum.IntEnum):
     ARGB8888 = N.FMT_ARGB8888
     YCBCR888X = N.FMT_YCBCR888X
     PLANAR = N.FMT_PLANAR          # out_format only: Y plane + Cb / Cr planes at the chroma sample points (csic_planar_layout)
+    PLANAR_BITS = N.FMT_PLANAR_BITS  # out_format only, ARGB input: the same planes at the quantised bit widths (csic_planar_bits_layout)
 
 
 def make_c_params(width, height, a, b, yq, cbq, crq, sf, ops, rounding=Rounding.FLOOR_HW,

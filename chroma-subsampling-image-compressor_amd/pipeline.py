@@ -27,8 +27,9 @@ class FramePipeline:
         N.check(N.lib().csic_pipeline_create(plan._h, self.depth, C.byref(self._h)))
         N.check(N.lib().csic_pipeline_set_mode(self._h, N.PIPELINE_ZERO_COPY if zero_copy else N.PIPELINE_STAGED))
         self._in_shape = (plan.height, plan.width)
-        # a planar plan hands back its planar frame buffer (bytes; Plan.split_planar cuts it into the three planes)
-        self._out_shape = (plan.planar_layout.frame_bytes // 4,) if plan.planar else (plan.out_height, plan.out_width)
+        # a planar plan hands back its planar frame buffer (bytes; Plan.split_planar / Plan.unpack_planar_bits cuts it into the planes)
+        self._bytes_out = plan.planar or plan.planar_bits
+        self._out_shape = (plan.frame_bytes // 4,) if self._bytes_out else (plan.out_height, plan.out_width)
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -69,7 +70,7 @@ class FramePipeline:
         t = C.c_int64()
         N.check(N.lib().csic_pipeline_collect(self._h, C.byref(p), C.byref(t)))
         out = np.ctypeslib.as_array(p, shape=self._out_shape)
-        return t.value, (out.view(np.uint8) if self.plan.planar else out)
+        return t.value, (out.view(np.uint8) if self._bytes_out else out)
 
     def run(self, frames: Iterable[np.ndarray]) -> Iterator[np.ndarray]:
         """Streams `frames` ((H, W) uint32 ARGB arrays) through the pipeline, keeping up to `depth` in

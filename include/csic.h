@@ -90,6 +90,7 @@ typedef enum csic_status {
 #define CSIC_FMT_ARGB8888  0
 #define CSIC_FMT_YCBCR888X 1
 #define CSIC_FMT_PLANAR    2   /* out_format only: Y plane + Cb / Cr planes at the chroma sample points (csic_planar_layout) */
+#define CSIC_FMT_PLANAR_BITS 3 /* out_format only, ARGB input only: the same planes, each sample at its quantised bit width (csic_planar_bits_layout) */
 
 /* ---- parameters ---------------------------------------------------------------------------------
  * Field-for-field the constructor list of
@@ -203,6 +204,45 @@ typedef struct csic_planar_layout {
 /* usable without a GPU; p->out_format need not be CSIC_FMT_PLANAR (the layout of "these parameters, planar") */
 int  csic_planar_layout_of(const csic_params *p, csic_planar_layout *layout);
 
+/* ---- bit-packed planar output (out_format = CSIC_FMT_PLANAR_BITS) -------------------------------------------------------
+ * CSIC_FMT_PLANAR stores 8 bits per sample although the quantiser keeps only the top y_bits / cb_bits / cr_bits of each channel
+ * (ColorQuantizer.scala:40-44): 3 to 6 of those bits are always zero for the reference's Q16bit (6/5/5) and Q8bit (3/3/2).  This
+ * format stores each sample at its quantised width.  Sample geometry is exactly csic_planar_layout_of's (module_width, hold_h,
+ * hold_v, k(j), replay_last, chroma_samples); only the storage of each plane changes.  Valid as out_format only, and only with
+ * in_format = CSIC_FMT_ARGB8888 (csic_validate: CSIC_EINVAL_FORMAT otherwise).
+ *
+ * A plane with q bits per sample (q = y_bits, cb_bits or cr_bits): sample i of value v stores its code c = v >> (8 - q) at bit
+ * positions [i*q, i*q + q) of the plane; bit position b is bit b % 8 of byte b / 8 (LSB first, little endian: a dword read at byte
+ * 4m holds bits [32m, 32m + 32) in their natural order, and 32 samples fill exactly q dwords).  The unused high bits of a plane's
+ * last byte are 0.  Reconstruct expands c << (8 - q).  Worked vectors:
+ *     q = 3, codes 1,2,3,4,5,6,7,0  -> bytes d1 58 1f          q = 5, codes 0x1f, 0, 0x15 -> bytes 1f 54
+ * Lossless with respect to the packed output for every valid parameter set: under HOLD_DECIMATE every stage after the quantiser
+ * only copies values, and AVG is defined for the order chroma, spatial, quant only, so the quantiser runs last.
+ *
+ * Layout, with up(x) = x rounded up to 256 and B(s, q) = ceil(s * q / 8), n = y_width * y_height:
+ *     y_offset = 0,  cb_offset = up(B(n, y_bits)),  cr_offset = cb_offset + up(B(chroma_width * chroma_height, cb_bits)),
+ *     frame_bytes = cr_offset + up(B(chroma_width * chroma_height, cr_bits)),
+ *     payload_bytes = B(n, y_bits) + B(chroma_samples, cb_bits) + B(chroma_samples, cr_bits)
+ * (y_bytes, cb_bytes, cr_bytes = the three B terms of payload_bytes).  At 8/8/8 every offset, frame_bytes and payload_bytes equal
+ * csic_planar_layout's and the frame is byte-identical to a CSIC_FMT_PLANAR frame.  Bytes between a plane's last byte and the next
+ * offset are never written.
+ *
+ * csic_process_device / csic_process_batch_device / csic_process_host and csic_pipeline_* take such a plan: d_out is a 256-byte
+ * aligned buffer of frame_bytes per frame.  Row pitches, every frame-graph backend (FUSED included), the file pools, csic_multi_*
+ * and csic_stream_create refuse it with CSIC_EINVAL_FORMAT.  csic_reconstruct_bits_device is csic_reconstruct_device for these
+ * frames: `nframes` bit-packed frames of `plan`'s parameters (any out_format) -> packed ARGB8888 or YCBCR888X, the same replay
+ * rule, asynchronous, no allocation, capturable. */
+typedef struct csic_planar_bits_layout {
+    csic_planar_layout geometry;          /* csic_planar_layout_of of the same parameters (its offsets / sizes are PLANAR's)     */
+    int32_t y_bits, cb_bits, cr_bits, reserved;
+    int64_t y_bytes, cb_bytes, cr_bytes;  /* bytes each plane's samples occupy: B(n, y_bits), B(chroma_samples, cb / cr_bits)  */
+    int64_t y_offset, cb_offset, cr_offset; /* byte offsets of the planes inside a frame's buffer                               */
+    int64_t frame_bytes;                  /* bytes per frame buffer (multiple of 256)                                           */
+    int64_t payload_bytes;                /* y_bytes + cb_bytes + cr_bytes                                                      */
+} csic_planar_bits_layout;
+/* usable without a GPU; p->out_format need not be CSIC_FMT_PLANAR_BITS */
+int  csic_planar_bits_layout_of(const csic_params *p, csic_planar_bits_layout *layout);
+
 const char *csic_strerror(int status);
 const char *csic_last_error(void);       /* thread-local; "" when the last call succeeded */
 
@@ -223,7 +263,7 @@ const char *csic_plan_kernel_name(const csic_plan *plan);
 /* Tuning knobs for A/B measurements; a knob the selected kernel does not have is ignored.
  *   CSIC_TUNE_VARIANT : kernel-family specific variant index (0 = default; 1, 2 = the 16-byte f = 2 kernels, 4 = k_dec for
  *                       f = 1, 5 = k_dec instead of k_decflat on rows that do not tile into whole blocks / waves, 6 = k_decflat wherever it applies, 7 = the one-pixel-per-lane k_generic instead of k_flatgen,
- *                       8 = AVG: the tile kernel only for frames of whole tiles, as in rounds 1-3, 9 = planar: the general kernels instead of the fast paths,
+ *                       8 = AVG: the tile kernel only for frames of whole tiles, as in rounds 1-3, 9 = planar (and planar bits): the general kernels instead of the fast paths,
  *                       10 = planar, factor >= 2: 4 consecutive positions per lane (k_planar_flat) instead of the transposing k_planar_strided,
  *                       11 = factor 1: k_f1x4 (rounds 1-3's kernel) instead of k_f1flat,
  *                       12 = planar AVG at factor 1 on frames of whole tiles: k_avg's body with the planar sink instead of k_planar_avg_f1)
@@ -270,6 +310,9 @@ int  csic_process_pitched_device(csic_plan *plan, const void *d_in, int32_t in_p
  * frame back to back; asynchronous on `hip_stream`, no allocation, capturable. */
 int  csic_reconstruct_device(csic_plan *plan, const void *d_planar, void *d_out, int32_t nframes, int32_t out_format,
                              void *hip_stream);
+/* The same for CSIC_FMT_PLANAR_BITS frames (frame_bytes of csic_planar_bits_layout_of apart, 256-byte aligned). */
+int  csic_reconstruct_bits_device(csic_plan *plan, const void *d_bits, void *d_out, int32_t nframes, int32_t out_format,
+                                  void *hip_stream);
 
 /* Row pitches, in pixels, at which frames of this plan stream fastest when the CALLER lays them out
  * (csic_process_pitched_device).  Measured on 2048- to 16384-pixel rows x every factor x 13 (input pad, output pad) pairs

@@ -41,7 +41,8 @@ inline int check(int status)
 
 enum class ProcessingStep : int32_t { NoOp = 0, SpatialSampling = 1, ColorQuantization = 2, ChromaSubsampling = 3 };
 enum class Rounding : int32_t { FLOOR_HW = CSIC_ROUND_FLOOR_HW, TRUNC_SW = CSIC_ROUND_TRUNC_SW };
-enum class PixelFormat : int32_t { ARGB8888 = CSIC_FMT_ARGB8888, YCBCR888X = CSIC_FMT_YCBCR888X, PLANAR = CSIC_FMT_PLANAR };
+enum class PixelFormat : int32_t { ARGB8888 = CSIC_FMT_ARGB8888, YCBCR888X = CSIC_FMT_YCBCR888X, PLANAR = CSIC_FMT_PLANAR,
+                                   PLANAR_BITS = CSIC_FMT_PLANAR_BITS };
 
 struct ImageProcessorParams {
     int width, height, factor, chromaParamA, chromaParamB;
@@ -97,6 +98,13 @@ struct PlanarFrame {
     const uint8_t *y() const { return bytes.data() + layout.y_offset; }
     const uint8_t *cb() const { return bytes.data() + layout.cb_offset; }
     const uint8_t *cr() const { return bytes.data() + layout.cr_offset; }
+};
+
+// One frame in the bit-packed planar format (CSIC_FMT_PLANAR_BITS, csic.h: csic_planar_bits_layout): the frame buffer as the device
+// wrote it; plane p holds its samples LSB first at layout.y_bits / cb_bits / cr_bits bits each.
+struct PlanarBitsFrame {
+    csic_planar_bits_layout layout{};
+    std::vector<uint8_t> bytes;                                   // layout.frame_bytes long
 };
 
 class ImageCompressorTop {
@@ -160,6 +168,28 @@ public:
     {
         check(csic_reconstruct_device(plan(PixelFormat::PLANAR), d_planar, d_out, nframes, (int32_t)f, hip_stream));
     }
+    // The same planes with every sample at its quantised bit width (CSIC_FMT_PLANAR_BITS): planarBitsLayout() needs no GPU,
+    // processPlanarBits() moves one host frame, reconstructBitsDevice() is reconstructDevice() for such frames.
+    csic_planar_bits_layout planarBitsLayout() const
+    {
+        csic_planar_bits_layout lay;
+        check(csic_planar_bits_layout_of(&params_, &lay));
+        return lay;
+    }
+    PlanarBitsFrame processPlanarBits(const std::vector<uint32_t> &argb)
+    {
+        PlanarBitsFrame fr;
+        fr.layout = planarBitsLayout();
+        std::vector<uint32_t> words((size_t)(fr.layout.frame_bytes / 4));
+        check(csic_process_host(plan(PixelFormat::PLANAR_BITS), argb.data(), argb.size(), words.data(), words.size()));
+        fr.bytes.resize((size_t)fr.layout.frame_bytes);
+        std::memcpy(fr.bytes.data(), words.data(), fr.bytes.size());
+        return fr;
+    }
+    void reconstructBitsDevice(const void *d_bits, void *d_out, int nframes, void *hip_stream, PixelFormat f = PixelFormat::ARGB8888)
+    {
+        check(csic_reconstruct_bits_device(plan(PixelFormat::PLANAR_BITS), d_bits, d_out, nframes, (int32_t)f, hip_stream));
+    }
     // what row pitch (pixels, input / output) a caller that owns its surfaces should allocate for csic_process_pitched_device
     std::pair<int, int> preferredPitch(PixelFormat f = PixelFormat::ARGB8888)
     {
@@ -189,7 +219,7 @@ private:
         return out;
     }
     csic_params params_{};
-    csic_plan *plan_[3] = {nullptr, nullptr, nullptr};     // one per PixelFormat
+    csic_plan *plan_[4] = {nullptr, nullptr, nullptr, nullptr};     // one per PixelFormat
     int32_t out_w_ = 0, out_h_ = 0;
     int device_;
 };
