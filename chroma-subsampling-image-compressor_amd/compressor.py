@@ -13,6 +13,7 @@ the launch goes to torch's current stream.  numpy inputs take csic_process_host 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Tuple
 
 import numpy as np
@@ -23,6 +24,41 @@ from .params import (ImageProcessorParams, PixelFormat, ProcessingStep, Rounding
 
 def _is_torch_tensor(x) -> bool:
     return type(x).__module__.split(".")[0] == "torch"
+
+
+class Distortion:
+    """The six sums of squared errors of one frame (csic_distortion_*; definition in include/csic.h), in the order
+    R, G, B, Y, Cb, Cr, over `pixels` input pixels; mse / psnr per channel (index or name), psnr_rgb over R, G and B
+    together.  PSNR is +inf at zero error."""
+
+    CHANNELS = ("R", "G", "B", "Y", "Cb", "Cr")
+
+    def __init__(self, sse, pixels: int):
+        self.sse = tuple(int(v) for v in sse)
+        if len(self.sse) != N.DIST_CHANNELS:
+            raise ValueError(f"need {N.DIST_CHANNELS} sums (R, G, B, Y, Cb, Cr), got {len(self.sse)}")
+        self.pixels = int(pixels)
+
+    def _index(self, ch) -> int:
+        return self.CHANNELS.index(ch) if isinstance(ch, str) else int(ch)
+
+    def mse(self, ch) -> float:
+        return self.sse[self._index(ch)] / self.pixels
+
+    def psnr(self, ch) -> float:
+        e = self.sse[self._index(ch)]
+        return math.inf if e == 0 else 10.0 * math.log10(255.0 * 255.0 * self.pixels / e)
+
+    @property
+    def psnr_rgb(self) -> float:
+        e = self.sse[0] + self.sse[1] + self.sse[2]
+        return math.inf if e == 0 else 10.0 * math.log10(255.0 * 255.0 * 3 * self.pixels / e)
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Distortion) and (self.sse, self.pixels) == (other.sse, other.pixels)
+
+    def __repr__(self) -> str:
+        return f"Distortion(sse={self.sse}, pixels={self.pixels})"
 
 
 class Plan:
@@ -103,6 +139,64 @@ class Plan:
         ip, op = C.c_int32(), C.c_int32()
         N.check(N.lib().csic_plan_preferred_pitch(self._h, C.byref(ip), C.byref(op)))
         return ip.value, op.value
+
+    # -- distortion (csic_distortion_*) ----------------------------------------------------------
+    @property
+    def distortion_kernel_name(self) -> str:
+        return N.lib().csic_distortion_kernel_name(self._h).decode()
+
+    def distortion_workspace_bytes(self, nframes: int = 1) -> int:
+        b = C.c_size_t()
+        N.check(N.lib().csic_distortion_workspace_bytes(self._h, int(nframes), C.byref(b)))
+        return b.value
+
+    def distortion_device(self, d_in, nframes: int = 1, d_sse=None):
+        """d_in: contiguous 4-byte CUDA tensor of nframes * W * H input pixels.  Returns an int64 tensor (nframes, 6) on the
+        device: the sums R, G, B, Y, Cb, Cr of each frame (never above 2^63).  Asynchronous on torch's current stream; the plan
+        keeps its workspace between calls (allocate it with a first call before capturing the call into a graph)."""
+        import torch
+        if not d_in.is_cuda or d_in.element_size() != 4 or not d_in.is_contiguous():
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_in must be a contiguous 4-byte CUDA tensor")
+        if d_in.device.index != self.device:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: tensor is on a different device than the plan")
+        if d_in.numel() != nframes * self.width * self.height:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: expected {nframes * self.width * self.height} input pixels, got {d_in.numel()}")
+        need = self.distortion_workspace_bytes(nframes)
+        ws = getattr(self, "_dist_ws", None)
+        if ws is None or ws.numel() * 8 < need or ws.device != d_in.device:
+            ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=d_in.device)
+            self._dist_ws = ws
+        if d_sse is None:
+            d_sse = torch.empty((nframes, N.DIST_CHANNELS), dtype=torch.int64, device=d_in.device)
+        elif d_sse.numel() != nframes * N.DIST_CHANNELS or d_sse.element_size() != 8 or not d_sse.is_contiguous():
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_sse must be a contiguous 8-byte tensor of nframes * 6")
+        N.check(N.lib().csic_distortion_device(self._h, C.c_void_p(d_in.data_ptr()), int(nframes), C.c_void_p(d_sse.data_ptr()),
+                                               C.c_void_p(ws.data_ptr()), ws.numel() * 8, self._stream()))
+        return d_sse
+
+    def distortion_host(self, frames: np.ndarray, nframes: int = 1) -> np.ndarray:
+        """csic_distortion_host: nframes * W * H host pixels -> uint64 array (nframes, 6)."""
+        a = np.ascontiguousarray(frames, dtype=np.uint32).reshape(-1)
+        sse = np.zeros((nframes, N.DIST_CHANNELS), dtype=np.uint64)
+        N.check(N.lib().csic_distortion_host(self._h, a.ctypes.data_as(C.c_void_p), a.size, int(nframes),
+                                             sse.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return sse
+
+    def distortion(self, frames):
+        """One frame ((H, W), or flat W * H) -> Distortion; a stack (n, H, W) -> list of Distortion.  numpy input goes through
+        csic_distortion_host, a CUDA tensor through distortion_device (synchronised here)."""
+        px = self.width * self.height
+        if _is_torch_tensor(frames):
+            n = frames.numel() // px if px else 0
+            sse = self.distortion_device(frames.contiguous(), n).cpu().numpy()
+            single = frames.dim() != 3
+        else:
+            a = np.asarray(frames)
+            n = a.size // px if px else 0
+            sse = self.distortion_host(a, n)
+            single = a.ndim != 3
+        out = [Distortion(row, px) for row in sse]
+        return out[0] if single and n == 1 else out
 
     # -- compute ----------------------------------------------------------------------------------
     def _stream(self):
@@ -360,6 +454,11 @@ class ImageCompressorTop:
     def processYCbCr(self, argb):
         """ARGB frame in -> the PixelYCbCrBundle stream io.out carries (byte0=Y, byte1=Cb, byte2=Cr)."""
         return self.plan(PixelFormat.YCBCR888X).process(argb)
+
+    def distortion(self, argb):
+        """What these parameters cost in image quality on `argb` (one frame, or a stack (n, H, W)): Distortion (list of them for a
+        stack) -- the per-channel sums of squared errors against the packed ARGB / YCbCr outputs and their PSNR."""
+        return self.plan(PixelFormat.ARGB8888).distortion(argb)
 
     def processPlanarBits(self, argb):
         """ARGB frame in -> one bit-packed planar frame buffer (CSIC_FMT_PLANAR_BITS, uint8: planar_bits_layout.frame_bytes on the

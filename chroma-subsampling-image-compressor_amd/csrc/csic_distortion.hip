@@ -1,0 +1,434 @@
+// csic_distortion.hip -- csic_distortion_device: the per-channel sums of squared errors between input frames and the output their
+// plan's parameters produce (R, G, B against the packed ARGB output, Y, Cb, Cr against the packed YCbCr output; input pixel (r, c)
+// is paired with output pixel (r / f, c / f); definition in include/csic.h).  Fused: every input byte is read once and the output
+// is never written -- only a 48-byte partial per block.
+//
+// Kernels (wave64, 256-thread blocks; integer byte work, no MFMA, LDS only for the block sum):
+//   k_dist_fast<ROUND, F, HH, VV, VEC, NT>  HOLD_DECIMATE, ARGB input, factor F in {1, 2} (chroma before spatial at F = 2; at F = 1
+//                      the order classes coincide), width % 4 == 0, height % F == 0.  A "unit" is F input rows x 4 columns: one
+//                      16-byte load per row (VEC; four 4-byte loads when d_in is only 4-byte aligned, the packed path's rule), so a
+//                      lane holds every input pixel of its unit AND the pixel(s) its output takes Y and held chroma from: the
+//                      in-unit chroma hold is a register select (HH in {1, 2, 4} divides 4; at F = 2 the held column 2co & ~(h-1)
+//                      is inside the unit too), and only a 4:x:0 odd row at F = 1 needs one more pixel -- the last sample of the row
+//                      above, one row-uniform load issued only by waves that sit on such a row (as k_f1flat).  K = 4 / F units per
+//                      lane spaced by the block: 16 input pixels per lane, 4096 per block, all loads issued before any arithmetic.
+//   k_dist_gen<ROUND, AVG, INFMT>   anything csic_validate accepts: one output pixel per lane, computed as k_generic (HOLD) or
+//                      avg_pixel_generic (AVG) compute it, then its f x f input block, clamped at the frame edge.
+//   k_dist_reduce      one block per frame: the frame's partials, summed in a fixed order, -> d_sse[frame * 6 + channel].
+// Accumulation widths: a lane sums squared 8-bit errors in 32 bits (it sees at most 64 input pixels -- 16 in k_dist_fast, f * f <= 64
+// in k_dist_gen), and so does the wave reduction (at most 64 * 64 = 4096 pixels; 2^32 / 255^2 = 66 051).  The block sum, the partials
+// and the per-frame sums are 64-bit.  No atomics: each block writes its own partial with plain vector stores.
+#include <cstdio>
+#include <cstring>
+
+#include "csic_kernel_ops.h"
+
+namespace csic {
+
+constexpr int DIST_T = 256;          // threads per block, every kernel here
+constexpr int DIST_CH = CSIC_DIST_CHANNELS;
+
+struct DExtra {
+    uint64_t *part;                  // workspace: nblk partials of DIST_CH uint64 per frame, frames back to back
+    uint32_t nblk;                   // blocks (= partials) per frame
+    uint32_t nunits;                 // k_dist_fast: units per frame; k_dist_gen: output pixels per frame
+};
+
+typedef uint64_t CSIC_GLOBAL *gpart_t;
+
+// (R, G, B) of (Y, Cb, Cr) through YCbCrUtils.ycbcr2rgb, as finish_y computes it for the packed ARGB output
+struct DRgb { int r, g, b; };
+__device__ __forceinline__ DRgb rgb_of(uint32_t y, const ChromaTerm &t)
+{
+    const int yy = __mul24((int)y, 298);
+    return DRgb{min(max(yy + t.kr, 0), 65535) >> 8, min(max(yy + t.kg, 0), 65535) >> 8, min(max(yy + t.kb, 0), 65535) >> 8};
+}
+
+__device__ __forceinline__ void sq_add(uint32_t &s, int e) { s += (uint32_t)__mul24(e, e); }
+
+// one input pixel against its output pixel: reference RGB (rr, rg, rb) and YCbCr (ry, rcb, rcr) vs output RGB o and YCbCr (y, cb, cr)
+__device__ __forceinline__ void acc_px(uint32_t (&s)[DIST_CH], int rr, int rg, int rb, uint32_t ry, uint32_t rcb, uint32_t rcr,
+                                       const DRgb &o, uint32_t y, uint32_t cb, uint32_t cr)
+{
+    sq_add(s[0], rr - o.r);
+    sq_add(s[1], rg - o.g);
+    sq_add(s[2], rb - o.b);
+    sq_add(s[3], (int)ry - (int)y);
+    sq_add(s[4], (int)rcb - (int)cb);
+    sq_add(s[5], (int)rcr - (int)cr);
+}
+__device__ __forceinline__ void acc_argb(uint32_t (&s)[DIST_CH], uint32_t px, uint32_t ry, uint32_t rcb, uint32_t rcr,
+                                         const DRgb &o, uint32_t y, uint32_t cb, uint32_t cr)
+{
+    acc_px(s, (int)((px >> 16) & 0xFFu), (int)((px >> 8) & 0xFFu), (int)(px & 0xFFu), ry, rcb, rcr, o, y, cb, cr);
+}
+
+// lane sums -> wave sums (32-bit, see the header) -> this block's 64-bit partial
+__device__ __forceinline__ void block_partial(const DExtra &e, uint32_t (&s)[DIST_CH])
+{
+    __shared__ uint64_t red[DIST_T / 64][DIST_CH];
+#pragma unroll
+    for (int ch = 0; ch < DIST_CH; ++ch)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s[ch] += (uint32_t)__shfl_xor((int)s[ch], off, 64);
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    if (lane == 0)
+#pragma unroll
+        for (int ch = 0; ch < DIST_CH; ++ch) red[wave][ch] = s[ch];
+    __syncthreads();
+    if (threadIdx.x < (unsigned)DIST_CH) {
+        uint64_t t = 0;
+#pragma unroll
+        for (int w = 0; w < DIST_T / 64; ++w) t += red[w][threadIdx.x];
+        CSIC_CHECK(blockIdx.x < e.nblk);
+        ((gpart_t)(uintptr_t)e.part)[((uint64_t)blockIdx.z * e.nblk + blockIdx.x) * DIST_CH + threadIdx.x] = t;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_dist_fast
+// ------------------------------------------------------------------------------------------------
+template <bool VEC, bool NT>
+__device__ __forceinline__ u32x4 dld4(const KArgs &a, gin_t in, uint32_t off)
+{
+    if (VEC) return in4n<NT>(a, in, off);
+    const u32x4 v = {in1n<NT>(a, in, off), in1n<NT>(a, in, off + 1u), in1n<NT>(a, in, off + 2u), in1n<NT>(a, in, off + 3u)};
+    return v;
+}
+
+template <int ROUND, int F, int HH, int VV, bool VEC, bool NT, bool CHECK>
+__device__ __forceinline__ void dist_fast_body(const KArgs &a, gin_t in, uint32_t u0, uint32_t nunits, uint32_t (&s)[DIST_CH])
+{
+    constexpr int K = 4 / F;
+    const uint32_t W = (uint32_t)a.W;
+    uint32_t off[K], cpx[K];
+    bool odd[K];
+    u32x4 p[K][F];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        // the frame's last block: clamp instead of branching, so that every load still issues ahead of the arithmetic
+        const uint32_t u = CHECK ? min(u0 + (uint32_t)(k * DIST_T), nunits - 1u) : u0 + (uint32_t)(k * DIST_T);
+        const uint32_t j0 = 4u * u;                                         // < 2^30 (dist_kind)
+        const uint32_t ur = (uint32_t)(((uint64_t)j0 * a.mW) >> a.kW);      // unit row = j0 / W, exact
+        off[k] = F == 1 ? j0 : j0 + __umul24(ur, W);                        // rows F * ur .. : (F * ur) * W + (j0 - ur * W)
+        odd[k] = F == 1 && VV == 2 && (ur & 1u);
+        cpx[k] = 0;
+        if constexpr (F == 1 && VV == 2) {
+            // 4:x:0 odd row: every pixel holds the chroma latched at the last sample of the row above (ChromaSubsampler.scala:52-65)
+            if (__builtin_amdgcn_ballot_w64(odd[k]) != 0)
+                cpx[k] = in1n<false>(a, in, odd[k] ? __umul24(ur - 1u, W) + (uint32_t)a.last_sample_col : off[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int i = 0; i < F; ++i) p[k][i] = dld4<VEC, NT>(a, in, off[k] + (uint32_t)i * W);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (CHECK && u0 + (uint32_t)(k * DIST_T) >= nunits) continue;
+        const uint32_t q0[4] = {p[k][0].x, p[k][0].y, p[k][0].z, p[k][0].w};
+        uint32_t ry[4], rcb[4], rcr[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { ry[i] = fwd_y(q0[i]); fwd_c<ROUND>(q0[i], rcb[i], rcr[i]); }
+        if constexpr (F == 1) {
+            uint32_t ocb = 0, ocr = 0;
+            if (VV == 2) fwd_c<ROUND>(cpx[k], ocb, ocr);
+#pragma unroll
+            for (int g = 0; g < 4; g += HH) {
+                const uint32_t cb = ((VV == 2 && odd[k]) ? ocb : rcb[g]) & a.mcb;     // held chroma, quantised
+                const uint32_t cr = ((VV == 2 && odd[k]) ? ocr : rcr[g]) & a.mcr;
+                const ChromaTerm t = chroma_term_q<F_ARGB>(cb, cr);
+#pragma unroll
+                for (int i = g; i < g + HH; ++i) {
+                    const uint32_t y = ry[i] & a.my;
+                    acc_argb(s, q0[i], ry[i], rcb[i], rcr[i], rgb_of(y, t), y, cb, cr);
+                }
+            }
+        } else {
+            const uint32_t q1[4] = {p[k][1].x, p[k][1].y, p[k][1].z, p[k][1].w};
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                // output (ro, co) = (ur, 2 ug + o): Y of input column 2 co = unit column 2 o; chroma held from column 2 co & ~(h - 1)
+                const int src = HH == 4 ? 0 : 2 * o;
+                const uint32_t y = ry[2 * o] & a.my, cb = rcb[src] & a.mcb, cr = rcr[src] & a.mcr;
+                const DRgb rgb = rgb_of(y, chroma_term_q<F_ARGB>(cb, cr));
+#pragma unroll
+                for (int i = 2 * o; i < 2 * o + 2; ++i) {
+                    acc_argb(s, q0[i], ry[i], rcb[i], rcr[i], rgb, y, cb, cr);
+                    uint32_t b1, c1;
+                    fwd_c<ROUND>(q1[i], b1, c1);
+                    acc_argb(s, q1[i], fwd_y(q1[i]), b1, c1, rgb, y, cb, cr);
+                }
+            }
+        }
+    }
+}
+
+template <int ROUND, int F, int HH, int VV, bool VEC, bool NT>
+__global__ void __launch_bounds__(DIST_T) k_dist_fast(KArgs a, DExtra e)
+{
+    pin_args(a);
+    const gin_t in = frame_in(a);
+    constexpr uint32_t per_block = DIST_T * (4 / F);
+    const uint32_t b0 = blockIdx.x * per_block;
+    uint32_t s[DIST_CH] = {0, 0, 0, 0, 0, 0};
+    if (b0 + per_block <= e.nunits) dist_fast_body<ROUND, F, HH, VV, VEC, NT, false>(a, in, b0 + threadIdx.x, e.nunits, s);
+    else                            dist_fast_body<ROUND, F, HH, VV, VEC, NT, true>(a, in, b0 + threadIdx.x, e.nunits, s);
+    block_partial(e, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_dist_gen
+// ------------------------------------------------------------------------------------------------
+template <int ROUND, bool AVG, int INFMT>
+__global__ void __launch_bounds__(DIST_T) k_dist_gen(KArgs a, DExtra e)
+{
+    pin_args(a);
+    const gin_t in = frame_in(a);
+    const uint32_t j = blockIdx.x * (uint32_t)DIST_T + threadIdx.x;
+    uint32_t s[DIST_CH] = {0, 0, 0, 0, 0, 0};
+    if (j < e.nunits) {
+        const int ro = (int)(((uint64_t)j * a.mWo) >> a.kWo), co = (int)j - ro * a.Wo;      // j / Wo, exact for j < 2^31
+        uint32_t y, cb, cr;                                                                 // the output pixel, packed-YCbCr values
+        if (AVG) {
+            const uint32_t o = avg_pixel_generic<ROUND, F_YCC, INFMT>(a, in, ro, co);
+            y = o & 0xFFu; cb = (o >> 8) & 0xFFu; cr = (o >> 16) & 0xFFu;
+        } else {
+            // k_generic's sources
+            const int64_t y_idx = (int64_t)(ro * a.f) * a.ip + co * a.f;
+            int64_t c_idx;
+            if (!a.s_first) {
+                const int r = ro * a.f, c = co * a.f;
+                c_idx = ((r & a.vmask) == 0) ? (int64_t)r * a.ip + (c & ~a.hmask) : (int64_t)(r - 1) * a.ip + a.last_sample_col;
+            } else {
+                const int jj = ro * a.Wo + co;
+                const int r = (int)(((uint64_t)(uint32_t)jj * a.mW) >> a.kW), c = jj - r * a.W;
+                const int src = ((r & a.vmask) == 0) ? (jj - (c & a.hmask)) : ((r - 1) * a.W + a.last_sample_col);
+                const int sro = (int)(((uint64_t)(uint32_t)src * a.mWo) >> a.kWo), sco = src - sro * a.Wo;
+                c_idx = (int64_t)(sro * a.f) * a.ip + sco * a.f;
+            }
+            in_c<ROUND, INFMT>(in1<false>(a, in, c_idx), cb, cr);
+            cb &= a.mcb; cr &= a.mcr;
+            y = in_y<ROUND, INFMT>(in1<false>(a, in, y_idx)) & a.my;
+        }
+        const DRgb rgb = rgb_of(y, chroma_term_q<F_ARGB>(cb, cr));
+        const int r0 = ro * a.f, c0 = co * a.f, r1 = min(r0 + a.f, a.H), c1 = min(c0 + a.f, a.W);
+        for (int r = r0; r < r1; ++r) {
+            for (int c = c0; c < c1; ++c) {
+                const uint32_t px = in1<false>(a, in, (int64_t)r * a.ip + c);
+                if (INFMT == F_YCC) {
+                    const uint32_t py = px & 0xFFu, pb = (px >> 8) & 0xFFu, pr = (px >> 16) & 0xFFu;
+                    const DRgb ref = rgb_of(py, chroma_term_q<F_ARGB>(pb, pr));
+                    acc_px(s, ref.r, ref.g, ref.b, py, pb, pr, rgb, y, cb, cr);
+                } else {
+                    uint32_t pb, pr;
+                    fwd_c<ROUND>(px, pb, pr);
+                    acc_argb(s, px, fwd_y(px), pb, pr, rgb, y, cb, cr);
+                }
+            }
+        }
+    }
+    block_partial(e, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_dist_reduce: frame blockIdx.x's partials -> its DIST_CH sums
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(DIST_T) k_dist_reduce(const uint64_t *part, uint32_t nblk, uint64_t *sse)
+{
+    typedef const uint64_t CSIC_GLOBAL *gcpart_t;
+    const gcpart_t p = (gcpart_t)(uintptr_t)part + (uint64_t)blockIdx.x * nblk * DIST_CH;
+    uint64_t t[DIST_CH] = {0, 0, 0, 0, 0, 0};
+    for (uint32_t b = threadIdx.x; b < nblk; b += DIST_T)
+#pragma unroll
+        for (int ch = 0; ch < DIST_CH; ++ch) t[ch] += p[(uint64_t)b * DIST_CH + ch];
+    __shared__ uint64_t red[DIST_T][DIST_CH];
+#pragma unroll
+    for (int ch = 0; ch < DIST_CH; ++ch) red[threadIdx.x][ch] = t[ch];
+    __syncthreads();
+    for (int w = DIST_T / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+#pragma unroll
+            for (int ch = 0; ch < DIST_CH; ++ch) red[threadIdx.x][ch] += red[threadIdx.x + w][ch];
+        __syncthreads();
+    }
+    if (threadIdx.x < (unsigned)DIST_CH) ((gpart_t)(uintptr_t)sse)[(uint64_t)blockIdx.x * DIST_CH + threadIdx.x] = red[0][threadIdx.x];
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+using DistFn = void (*)(KArgs, DExtra);
+
+// 0 = k_dist_gen, 1 / 2 = k_dist_fast at factor 1 / 2
+static int dist_kind(const csic_plan *pl)
+{
+    const csic_params &p = plan_params(pl);
+    const Geometry &g = plan_geometry(pl);
+    if (plan_force_generic(pl) || p.sampling != CSIC_SAMPLING_HOLD_DECIMATE || p.in_format != CSIC_FMT_ARGB8888) return 0;
+    if (g.f > 2 || (g.f == 2 && g.s_first)) return 0;
+    if (g.W % 4 != 0 || g.H % g.f != 0) return 0;
+    // 32-bit offsets (in1n / in4n) and 24-bit row multiplies
+    if ((int64_t)g.W * g.H > (1ll << 30) || g.W >= (1 << 24) || g.H >= (1 << 24)) return 0;
+    return g.f;
+}
+
+static uint32_t dist_units(const csic_plan *pl, int kind)
+{
+    const Geometry &g = plan_geometry(pl);
+    if (kind == 0) return (uint32_t)((int64_t)g.Wo * g.Ho);
+    return (uint32_t)((int64_t)(g.W / 4) * (g.H / kind));
+}
+
+static uint32_t dist_blocks(const csic_plan *pl, int kind)
+{
+    const int64_t per_block = kind == 0 ? DIST_T : (int64_t)DIST_T * (4 / kind);
+    return (uint32_t)((dist_units(pl, kind) + per_block - 1) / per_block);
+}
+
+template <int ROUND, int F, int HH, bool VEC, bool NT>
+static DistFn pick_fast_v(int v)
+{
+    if (F == 1 && v == 2) return k_dist_fast<ROUND, F, HH, 2, VEC, NT>;
+    return k_dist_fast<ROUND, F, HH, 1, VEC, NT>;       // at F = 2 the output rows are sample rows: v does not matter
+}
+
+template <int ROUND, int F, bool VEC, bool NT>
+static DistFn pick_fast_h(int h, int v)
+{
+    if (h == 1) return pick_fast_v<ROUND, F, 1, VEC, NT>(v);
+    if (h == 2) return pick_fast_v<ROUND, F, 2, VEC, NT>(v);
+    return pick_fast_v<ROUND, F, 4, VEC, NT>(v);
+}
+
+template <int ROUND, bool VEC, bool NT>
+static DistFn pick_fast(int f, int h, int v)
+{
+    return f == 1 ? pick_fast_h<ROUND, 1, VEC, NT>(h, v) : pick_fast_h<ROUND, 2, VEC, NT>(h, v);
+}
+
+template <int ROUND>
+static DistFn pick_dist(const csic_plan *pl, int kind, bool vec, bool nt)
+{
+    const csic_params &p = plan_params(pl);
+    const Geometry &g = plan_geometry(pl);
+    if (kind == 0) {
+        const bool avg = p.sampling == CSIC_SAMPLING_AVG, ycc = p.in_format == CSIC_FMT_YCBCR888X;
+        if (avg) return ycc ? k_dist_gen<ROUND, true, F_YCC> : k_dist_gen<ROUND, true, F_ARGB>;
+        return ycc ? k_dist_gen<ROUND, false, F_YCC> : k_dist_gen<ROUND, false, F_ARGB>;
+    }
+    if (vec) return nt ? pick_fast<ROUND, true, true>(kind, g.h, g.v) : pick_fast<ROUND, true, false>(kind, g.h, g.v);
+    return nt ? pick_fast<ROUND, false, true>(kind, g.h, g.v) : pick_fast<ROUND, false, false>(kind, g.h, g.v);
+}
+
+static int dist_workspace(const csic_plan *pl, int32_t nframes, size_t *bytes)
+{
+    if (nframes <= 0 || nframes > 65535)
+        return set_error(CSIC_EINVAL_SIZE, "nframes must be in 1..65535. Got %d", nframes);
+    *bytes = (size_t)nframes * dist_blocks(pl, dist_kind(pl)) * DIST_CH * sizeof(uint64_t);
+    return CSIC_OK;
+}
+
+} // namespace csic
+
+using namespace csic;
+
+extern "C" {
+
+int csic_distortion_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes)
+{
+    if (!plan || !bytes) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    const int st = dist_workspace(plan, nframes, bytes);
+    if (st == CSIC_OK) clear_error();
+    return st;
+}
+
+const char *csic_distortion_kernel_name(const csic_plan *plan)
+{
+    if (!plan) return "";
+    const csic_params &p = plan_params(plan);
+    const bool ycc = p.in_format == CSIC_FMT_YCBCR888X;
+    switch (dist_kind(plan)) {
+    case 1: return "k_dist_fast<f1>";
+    case 2: return "k_dist_fast<f2>";
+    default:
+        if (p.sampling == CSIC_SAMPLING_AVG) return ycc ? "k_dist_gen<avg,ycc-in>" : "k_dist_gen<avg>";
+        return ycc ? "k_dist_gen<hold,ycc-in>" : "k_dist_gen<hold>";
+    }
+}
+
+int csic_distortion_device(csic_plan *plan, const void *d_in, int32_t nframes, uint64_t *d_sse, void *d_workspace,
+                           size_t workspace_bytes, void *hip_stream)
+{
+    if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
+    if (!d_in || !d_sse || !d_workspace) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
+    size_t need = 0;
+    int st = dist_workspace(plan, nframes, &need);
+    if (st != CSIC_OK) return st;
+    if (workspace_bytes < need)
+        return set_error(CSIC_EINVAL_SIZE, "workspace of %zu bytes is smaller than the %zu bytes csic_distortion_workspace_bytes asks for",
+                         workspace_bytes, need);
+    if ((uintptr_t)d_sse & 7u) return set_error(CSIC_EINVAL_SIZE, "d_sse must be 8-byte aligned");
+    if ((uintptr_t)d_workspace & 7u) return set_error(CSIC_EINVAL_SIZE, "the workspace must be 8-byte aligned");
+    if ((uintptr_t)d_in & 3u) return set_error(CSIC_EINVAL_SIZE, "the input must be 4-byte aligned");
+    const csic_params &p = plan_params(plan);
+    const Geometry &g = plan_geometry(plan);
+    const int kind = dist_kind(plan);
+    // 16-byte loads only for a 16-byte aligned d_in (the frame stride W * H * 4 is a multiple of 16 whenever width % 4 == 0)
+    const bool vec = ((uintptr_t)d_in & 15u) == 0;
+    const bool nt = plan_nontemporal(plan);
+    const DistFn fn = p.rounding == CSIC_ROUND_FLOOR_HW ? pick_dist<R_FLOOR>(plan, kind, vec, nt) : pick_dist<R_TRUNC>(plan, kind, vec, nt);
+    CSIC_DEVICE_SCOPE(plan_device(plan));
+    KArgs a;
+    fill_base_args(g, g.W, g.Wo, &a);
+    a.in = static_cast<const uint32_t *>(d_in);
+    a.bdx = DIST_T; a.bdy = 1; a.row_step = 1;
+    DExtra e;
+    std::memset(&e, 0, sizeof e);
+    e.part = static_cast<uint64_t *>(d_workspace);
+    e.nblk = dist_blocks(plan, kind);
+    e.nunits = dist_units(plan, kind);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    void *params[2] = {&a, &e};
+    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3(e.nblk, 1, (unsigned)nframes), dim3(DIST_T, 1, 1), params, 0, stream));
+    const uint64_t *part = e.part;
+    uint32_t nblk = e.nblk;
+    void *rparams[3] = {&part, &nblk, &d_sse};
+    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(k_dist_reduce), dim3((unsigned)nframes, 1, 1), dim3(DIST_T, 1, 1), rparams, 0,
+                            stream));
+    clear_error();
+    return CSIC_OK;
+}
+
+int csic_distortion_host(csic_plan *plan, const uint32_t *in, size_t in_px, int32_t nframes, uint64_t *sse)
+{
+    if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
+    if (!in || !sse) return set_error(CSIC_EINVAL_NULL, "host buffer is NULL");
+    size_t ws = 0;
+    int st = dist_workspace(plan, nframes, &ws);
+    if (st != CSIC_OK) return st;
+    const Geometry &g = plan_geometry(plan);
+    const size_t need = (size_t)nframes * (size_t)g.W * (size_t)g.H;
+    if (in_px != need) return set_error(CSIC_EINVAL_SIZE, "expected %zu input pixels (%d frames), got %zu", need, nframes, in_px);
+    CSIC_DEVICE_SCOPE(plan_device(plan));
+    void *d_in = nullptr, *d_ws = nullptr, *d_sse = nullptr;
+    const size_t sse_bytes = (size_t)nframes * DIST_CH * sizeof(uint64_t);
+    hipError_t e = hipMalloc(&d_in, need * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_ws, ws);
+    if (e == hipSuccess) e = hipMalloc(&d_sse, sse_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, need * 4, hipMemcpyHostToDevice, nullptr);
+    if (e == hipSuccess) {
+        st = csic_distortion_device(plan, d_in, nframes, static_cast<uint64_t *>(d_sse), d_ws, ws, nullptr);
+        if (st == CSIC_OK) e = hipMemcpyAsync(sse, d_sse, sse_bytes, hipMemcpyDeviceToHost, nullptr);
+        if (st == CSIC_OK && e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    }
+    if (d_in) (void)hipFree(d_in);
+    if (d_ws) (void)hipFree(d_ws);
+    if (d_sse) (void)hipFree(d_sse);
+    if (st != CSIC_OK) return st;
+    if (e != hipSuccess) return set_error(CSIC_EHIP, "csic_distortion_host: %s", hipGetErrorString(e));
+    clear_error();
+    return CSIC_OK;
+}
+
+} // extern "C"

@@ -77,6 +77,7 @@ const Geometry &plan_geometry(const csic_plan *pl);
 int plan_variant(const csic_plan *pl);                       // CSIC_TUNE_VARIANT
 bool plan_nontemporal(const csic_plan *pl);                  // CSIC_TUNE_NONTEMPORAL
 int plan_block_threads(const csic_plan *pl);                 // CSIC_TUNE_BLOCK_THREADS (0 = the library's choice)
+bool plan_force_generic(const csic_plan *pl);                // CSIC_TUNE_FORCE_GENERIC
 void fill_base_args(const Geometry &g, int32_t ip, int32_t op, KArgs *a);
 // csic_planar.hip: out_format = CSIC_FMT_PLANAR (forward: packed input -> planar frame buffers; name of the kernel a plan takes)
 // csic_planar.hip: the second kernel argument of the planar kernels, and a prepared planar launch (as LaunchDesc for the packed ones)

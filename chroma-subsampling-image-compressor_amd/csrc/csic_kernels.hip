@@ -1195,6 +1195,7 @@ const Geometry &plan_geometry(const csic_plan *pl) { return pl->g; }
 int plan_variant(const csic_plan *pl) { return pl->variant; }
 bool plan_nontemporal(const csic_plan *pl) { return !pl->no_nt; }
 int plan_block_threads(const csic_plan *pl) { return pl->block_threads; }
+bool plan_force_generic(const csic_plan *pl) { return pl->force_generic != 0; }
 int64_t plan_algorithmic_bytes(const csic_plan *pl)
 {
     int64_t b = 0;

@@ -243,6 +243,39 @@ typedef struct csic_planar_bits_layout {
 /* usable without a GPU; p->out_format need not be CSIC_FMT_PLANAR_BITS */
 int  csic_planar_bits_layout_of(const csic_params *p, csic_planar_bits_layout *layout);
 
+/* ---- distortion: what a parameter set costs in image quality -------------------------------------------------------------
+ * For a plan with parameters p and one input frame x (width x height pixels in p.in_format, frames back to back as for
+ * csic_process_batch_device):
+ *   o_rgb = the packed output of p with out_format = CSIC_FMT_ARGB8888, o_ycc = the packed output with CSIC_FMT_YCBCR888X
+ *   (out_width x out_height each).  The plan's own out_format does not matter: PLANAR and PLANAR_BITS are lossless with respect
+ *   to the packed output.
+ *   Input pixel (r, c) is paired with output pixel (r / f, c / f) (integer division, the plan's factor f): replication
+ *   upsampling.  Every input pixel is counted exactly once, ragged edges included, for every order class and for AVG.
+ *   RGB reference of an input pixel: its R, G, B bytes (ARGB input; alpha ignored), or YCbCrUtils.ycbcr2rgb of its Y, Cb, Cr
+ *   (YCbCr input; the inverse the packed ARGB output uses).
+ *   YCbCr reference: the forward transform under the plan's rounding (ARGB input), or its own Y, Cb, Cr bytes (YCbCr input).
+ *   Six sums per frame, uint64, in the order R, G, B, Y, Cb, Cr: sse_k = sum over the width * height input pixels of
+ *   (reference_k - output_k)^2, against o_rgb for R, G, B and o_ycc for Y, Cb, Cr.  Integer sums: exact and bit-reproducible.
+ *   PSNR (host layers): 10 log10(255^2 * W * H / sse_k), +inf when sse_k = 0; combined RGB: 10 log10(255^2 * 3 W H / (sse_R +
+ *   sse_G + sse_B)).
+ *
+ * csic_distortion_workspace_bytes : the workspace csic_distortion_device needs for `nframes` (1..65535) frames of this plan (one
+ *                                   48-byte partial per block; the answer depends on the kernel the plan selects, so query it
+ *                                   again after csic_plan_tune).  Needs no device.
+ * csic_distortion_device          : d_in -> d_sse[nframes * 6] (8-byte aligned), through d_workspace (8-byte aligned, at least the
+ *                                   queried size, else CSIC_EINVAL_SIZE).  Asynchronous on `hip_stream`, no allocation, no
+ *                                   synchronisation, hipGraph-capturable; NULL arguments fail with CSIC_EINVAL_NULL before any
+ *                                   device is touched.  16-byte loads when d_in is 16-byte aligned, 4-byte loads otherwise.
+ * csic_distortion_host            : the same from host memory (in_px = nframes * width * height) into sse[nframes * 6];
+ *                                   synchronous, allocates its staging.
+ * csic_distortion_kernel_name     : the kernel csic_distortion_device takes for a 16-byte aligned d_in (static string). */
+#define CSIC_DIST_CHANNELS 6   /* R, G, B, Y, Cb, Cr */
+int  csic_distortion_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes);
+int  csic_distortion_device(csic_plan *plan, const void *d_in, int32_t nframes, uint64_t *d_sse,
+                            void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int  csic_distortion_host(csic_plan *plan, const uint32_t *in, size_t in_px, int32_t nframes, uint64_t *sse);
+const char *csic_distortion_kernel_name(const csic_plan *plan);
+
 const char *csic_strerror(int status);
 const char *csic_last_error(void);       /* thread-local; "" when the last call succeeded */
 
@@ -268,6 +301,7 @@ const char *csic_plan_kernel_name(const csic_plan *plan);
  *                       11 = factor 1: k_f1x4 (rounds 1-3's kernel) instead of k_f1flat,
  *                       12 = planar AVG at factor 1 on frames of whole tiles: k_avg's body with the planar sink instead of k_planar_avg_f1)
  *   CSIC_TUNE_FORCE_GENERIC : 1 = always use the one-thread-per-pixel generic kernel
+ *                             (csic_distortion_device: its general kernel k_dist_gen; nothing else changes for the other entry points)
  *   CSIC_TUNE_NONTEMPORAL   : 1 (default) = non-temporal loads/stores for the frame stream, 0 = cached
  *   CSIC_TUNE_NO_VECTOR     : 1 = never use the 16-byte-per-lane kernels
  *   CSIC_TUNE_BLOCK_THREADS : threads per block, 64 / 128 / 256 (0 = the library's choice) */

@@ -10,7 +10,9 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cmath>
 #include <cstring>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -107,6 +109,24 @@ struct PlanarBitsFrame {
     std::vector<uint8_t> bytes;                                   // layout.frame_bytes long
 };
 
+// The six sums of squared errors of one frame (csic.h: csic_distortion_*), in the order R, G, B, Y, Cb, Cr, over `pixels` input
+// pixels, with the PSNR helpers (+inf at zero error).
+struct Distortion {
+    enum Channel { R = 0, G = 1, B = 2, Y = 3, Cb = 4, Cr = 5 };
+    uint64_t sse[CSIC_DIST_CHANNELS] = {0, 0, 0, 0, 0, 0};
+    int64_t pixels = 0;
+    double mse(int ch) const { return (double)sse[ch] / (double)pixels; }
+    double psnr(int ch) const { return psnrOf(sse[ch], 1); }
+    double psnrRgb() const { return psnrOf(sse[R] + sse[G] + sse[B], 3); }
+
+private:
+    double psnrOf(uint64_t e, int channels) const
+    {
+        if (e == 0) return std::numeric_limits<double>::infinity();
+        return 10.0 * std::log10(255.0 * 255.0 * (double)channels * (double)pixels / (double)e);
+    }
+};
+
 class ImageCompressorTop {
 public:
     ImageCompressorTop(int width, int height, int chroma_param_a_config, int chroma_param_b_config,
@@ -198,6 +218,36 @@ public:
         return {ip, op};
     }
     const char *kernelName(PixelFormat f = PixelFormat::ARGB8888) { return csic_plan_kernel_name(plan(f)); }
+    // What these parameters cost in image quality: `nframes` ARGB frames back to back (host memory) -> one Distortion per frame.
+    std::vector<Distortion> distortion(const uint32_t *argb, int nframes = 1)
+    {
+        std::vector<uint64_t> sse((size_t)nframes * CSIC_DIST_CHANNELS);
+        const size_t px = (size_t)params_.width * (size_t)params_.height;
+        check(csic_distortion_host(plan(PixelFormat::ARGB8888), argb, px * (size_t)(nframes > 0 ? nframes : 0), nframes, sse.data()));
+        return toDistortion(sse, nframes);
+    }
+    // device-resident: d_in holds `nframes` frames, d_sse receives nframes * 6 sums (8-byte aligned), d_workspace at least
+    // distortionWorkspaceBytes(nframes) bytes; asynchronous on `hip_stream`, no allocation, capturable.
+    size_t distortionWorkspaceBytes(int nframes = 1)
+    {
+        size_t b = 0;
+        check(csic_distortion_workspace_bytes(plan(PixelFormat::ARGB8888), nframes, &b));
+        return b;
+    }
+    void distortionDevice(const void *d_in, int nframes, uint64_t *d_sse, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+    {
+        check(csic_distortion_device(plan(PixelFormat::ARGB8888), d_in, nframes, d_sse, d_workspace, workspace_bytes, hip_stream));
+    }
+    // the sums of distortionDevice, copied to the host by the caller -> one Distortion per frame
+    std::vector<Distortion> toDistortion(const std::vector<uint64_t> &sse, int nframes) const
+    {
+        std::vector<Distortion> out((size_t)(nframes > 0 ? nframes : 0));
+        for (size_t k = 0; k < out.size(); ++k) {
+            for (int c = 0; c < CSIC_DIST_CHANNELS; ++c) out[k].sse[c] = sse[k * CSIC_DIST_CHANNELS + (size_t)c];
+            out[k].pixels = (int64_t)params_.width * params_.height;
+        }
+        return out;
+    }
     // the plan behind process(): what FrameGraph records launches of (owned by this object)
     csic_plan *nativePlan(PixelFormat f = PixelFormat::ARGB8888) { return plan(f); }
 

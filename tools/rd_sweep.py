@@ -1,0 +1,75 @@
+#!/usr/bin/env python3
+"""tools/rd_sweep.py [OUT_PREFIX] -- the rate-distortion table of the committed golden inputs (tests/golden/inputs/in128.png and
+in512.png) on the GPU: chroma 4:4:4 / 4:2:2 / 4:2:0 / 4:1:1 x bits 8/8/8, 6/5/5, 4/4/4, 3/3/2 x factor 1, 2 x HOLD / AVG (order
+chroma, spatial, quant).  Rate: bits per input pixel of the bit-packed planar frame, 8 * csic_planar_bits_layout_of(...).payload_bytes
+/ (W * H).  Distortion: csic_distortion_host -> PSNR-RGB and PSNR-Y / Cb / Cr (dB, inf when lossless).  Writes OUT_PREFIX.jsonl and
+OUT_PREFIX.md (default profiles/r06_rd_sweep)."""
+import ctypes as C
+import json
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import csic_amd as csic  # noqa: E402
+
+N = csic._native
+PREFIX = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r06_rd_sweep")
+CSQ = (3, 1, 2)
+CHROMA = (("4:4:4", 4, 4), ("4:2:2", 2, 2), ("4:2:0", 2, 0), ("4:1:1", 1, 1))
+BITS = ((8, 8, 8), (6, 5, 5), (4, 4, 4), (3, 3, 2))
+
+
+def read_png(path):
+    w, h = C.c_int32(), C.c_int32()
+    N.check(N.lib().csic_png_info(path.encode(), C.byref(w), C.byref(h)))
+    px = np.empty(w.value * h.value, dtype=np.uint32)
+    N.check(N.lib().csic_png_read_argb(path.encode(), px.ctypes.data_as(C.c_void_p), px.size))
+    return px.reshape(h.value, w.value)
+
+
+def fmt_db(v):
+    return "inf" if math.isinf(v) else f"{v:.2f}"
+
+
+def main():
+    rows = []
+    for name in ("in128", "in512"):
+        img = read_png(os.path.join(ROOT, "tests", "golden", "inputs", name + ".png"))
+        H, W = img.shape
+        for cname, a, b in CHROMA:
+            for bits in BITS:
+                for f in (1, 2):
+                    for sampling in ("HOLD", "AVG"):
+                        cp = csic.make_c_params(W, H, a, b, *bits, f, CSQ, sampling=1 if sampling == "AVG" else 0)
+                        lay = N.CsicPlanarBitsLayout()
+                        N.check(N.lib().csic_planar_bits_layout_of(C.byref(cp), C.byref(lay)))
+                        with csic.Plan(cp, 0) as pl:
+                            d = pl.distortion(img)
+                            kernel = pl.distortion_kernel_name
+                        r = {"image": name, "shape": f"{W}x{H}", "chroma": cname, "bits": list(bits), "factor": f, "sampling": sampling,
+                             "bpp": round(8 * lay.payload_bytes / (W * H), 4), "psnr_rgb": round(d.psnr_rgb, 3),
+                             "psnr_y": round(d.psnr("Y"), 3), "psnr_cb": round(d.psnr("Cb"), 3), "psnr_cr": round(d.psnr("Cr"), 3),
+                             "sse": list(d.sse), "kernel": kernel}
+                        rows.append(r)
+                        print(json.dumps(r), flush=True)
+    os.makedirs(os.path.dirname(PREFIX) or ".", exist_ok=True)
+    with open(PREFIX + ".jsonl", "w") as fh:
+        for r in rows:
+            fh.write(json.dumps(r) + "\n")
+    with open(PREFIX + ".md", "w") as fh:
+        fh.write("# Rate-distortion of the golden inputs (tools/rd_sweep.py)\n\n"
+                 "Order chroma, spatial, quant; floor rounding.  bpp = bits per input pixel of the bit-packed planar frame "
+                 "(csic_planar_bits_layout_of payload); PSNR in dB against the input, every input pixel paired with its output "
+                 "pixel by replication (csic_distortion_*).\n\n")
+        fh.write("| image | chroma | bits | f | sampling | bpp | PSNR-RGB | PSNR-Y | PSNR-Cb | PSNR-Cr |\n"
+                 "|---|---|---|---|---|---:|---:|---:|---:|---:|\n")
+        for r in rows:
+            fh.write(f"| {r['image']} | {r['chroma']} | {'/'.join(map(str, r['bits']))} | {r['factor']} | {r['sampling']} | {r['bpp']:.3f} | "
+                     f"{fmt_db(r['psnr_rgb'])} | {fmt_db(r['psnr_y'])} | {fmt_db(r['psnr_cb'])} | {fmt_db(r['psnr_cr'])} |\n")
+
+
+if __name__ == "__main__":
+    main()
