@@ -17,15 +17,18 @@ bench: build
 asm:
 	$(MAKE) -C $(PKG)/csrc asm
 
+# what the tools link next to their own copy of csic_kernels.hip: the host sources, the planner and the planar units its launch path calls
+TOOL_HOST = $(PKG)/csrc/csic_host.cpp $(PKG)/csrc/csic_select.cpp $(PKG)/csrc/csic_png.cpp $(PKG)/csrc/csic_inflate.cpp \
+	$(PKG)/csrc/csic_planar.hip $(PKG)/csrc/csic_planar_bits.hip
 ubench: build
 	/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -I$(PKG)/csrc tools/ubench.hip \
-		$(PKG)/csrc/csic_host.cpp $(PKG)/csrc/csic_png.cpp $(PKG)/csrc/csic_inflate.cpp -lz -pthread -o tools/ubench
+		$(TOOL_HOST) -lz -pthread -o tools/ubench
 
 # every developer micro-benchmark under tools/ (binaries are git-ignored; they travel to the GPU box with gpurun)
 HIPCC_TOOL = /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -I$(PKG)/csrc
 tools: ubench
 	for t in ubench_k ubench_overlap ubench_aql ubench_order; do \
-		$(HIPCC_TOOL) tools/$$t.hip $(PKG)/csrc/csic_host.cpp $(PKG)/csrc/csic_png.cpp $(PKG)/csrc/csic_inflate.cpp -lz -pthread -L/opt/rocm/lib -lhsa-runtime64 -o tools/$$t || exit 1; done
+		$(HIPCC_TOOL) tools/$$t.hip $(TOOL_HOST) -lz -pthread -L/opt/rocm/lib -lhsa-runtime64 -o tools/$$t || exit 1; done
 	$(HIPCC_TOOL) tools/ubench_rows.hip -o tools/ubench_rows
 
 clean:

@@ -189,7 +189,7 @@ __device__ __forceinline__ uint32_t avg_edge_output(const KArgs &a, gin_t in, in
 //
 // Tiles the frame cuts produce nothing here.  The output pixels they would have produced -- the columns co >= Cw and the rows
 // ro >= Rw that whole tiles do not reach -- belong to the EDGE BLOCKS appended to the grid (block rows blockIdx.y >= a.edge_y0;
-// the host sizes them, prepare_common: the grid is a few blocks wide and hundreds tall, so rows of blocks waste none):
+// the host sizes them, launch_avg in csic_select.cpp: the grid is a few blocks wide and hundreds tall, so rows of blocks waste none):
 // one output pixel per lane through avg_edge_output, so that a wave of edge work is 64 lanes of edge work.  Two other placements were measured and dropped (profiles/r04_avg_edge_ab.log): evaluating a cut tile's outputs in
 // the lane that owns the tile makes one lane of a wave do two to three tiles' work while 63 wait (1004x1000 f = 8: 73 % against
 // 82 % for 1000x1000; 1020x1020: 64 %), and merely having that branch inside the tile loop cost the f = 2 tile path five

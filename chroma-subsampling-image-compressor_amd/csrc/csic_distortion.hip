@@ -263,9 +263,9 @@ using DistFn = void (*)(KArgs, DExtra);
 // 0 = k_dist_gen, 1 / 2 = k_dist_fast at factor 1 / 2
 static int dist_kind(const csic_plan *pl)
 {
-    const csic_params &p = plan_params(pl);
-    const Geometry &g = plan_geometry(pl);
-    if (plan_force_generic(pl) || p.sampling != CSIC_SAMPLING_HOLD_DECIMATE || p.in_format != CSIC_FMT_ARGB8888) return 0;
+    const csic_params &p = pl->p;
+    const Geometry &g = pl->g;
+    if (pl->tune.force_generic || p.sampling != CSIC_SAMPLING_HOLD_DECIMATE || p.in_format != CSIC_FMT_ARGB8888) return 0;
     if (g.f > 2 || (g.f == 2 && g.s_first)) return 0;
     if (g.W % 4 != 0 || g.H % g.f != 0) return 0;
     // 32-bit offsets (in1n / in4n) and 24-bit row multiplies
@@ -275,7 +275,7 @@ static int dist_kind(const csic_plan *pl)
 
 static uint32_t dist_units(const csic_plan *pl, int kind)
 {
-    const Geometry &g = plan_geometry(pl);
+    const Geometry &g = pl->g;
     if (kind == 0) return (uint32_t)((int64_t)g.Wo * g.Ho);
     return (uint32_t)((int64_t)(g.W / 4) * (g.H / kind));
 }
@@ -286,39 +286,26 @@ static uint32_t dist_blocks(const csic_plan *pl, int kind)
     return (uint32_t)((dist_units(pl, kind) + per_block - 1) / per_block);
 }
 
-template <int ROUND, int F, int HH, bool VEC, bool NT>
-static DistFn pick_fast_v(int v)
+// the kernel of a plan: `kind` from dist_kind, `vec` = 16-byte loads
+static DistFn dist_kernel(const csic_plan *pl, int kind, bool vec)
 {
-    if (F == 1 && v == 2) return k_dist_fast<ROUND, F, HH, 2, VEC, NT>;
-    return k_dist_fast<ROUND, F, HH, 1, VEC, NT>;       // at F = 2 the output rows are sample rows: v does not matter
-}
-
-template <int ROUND, int F, bool VEC, bool NT>
-static DistFn pick_fast_h(int h, int v)
-{
-    if (h == 1) return pick_fast_v<ROUND, F, 1, VEC, NT>(v);
-    if (h == 2) return pick_fast_v<ROUND, F, 2, VEC, NT>(v);
-    return pick_fast_v<ROUND, F, 4, VEC, NT>(v);
-}
-
-template <int ROUND, bool VEC, bool NT>
-static DistFn pick_fast(int f, int h, int v)
-{
-    return f == 1 ? pick_fast_h<ROUND, 1, VEC, NT>(h, v) : pick_fast_h<ROUND, 2, VEC, NT>(h, v);
-}
-
-template <int ROUND>
-static DistFn pick_dist(const csic_plan *pl, int kind, bool vec, bool nt)
-{
-    const csic_params &p = plan_params(pl);
-    const Geometry &g = plan_geometry(pl);
-    if (kind == 0) {
-        const bool avg = p.sampling == CSIC_SAMPLING_AVG, ycc = p.in_format == CSIC_FMT_YCBCR888X;
-        if (avg) return ycc ? k_dist_gen<ROUND, true, F_YCC> : k_dist_gen<ROUND, true, F_ARGB>;
-        return ycc ? k_dist_gen<ROUND, false, F_YCC> : k_dist_gen<ROUND, false, F_ARGB>;
-    }
-    if (vec) return nt ? pick_fast<ROUND, true, true>(kind, g.h, g.v) : pick_fast<ROUND, true, false>(kind, g.h, g.v);
-    return nt ? pick_fast<ROUND, false, true>(kind, g.h, g.v) : pick_fast<ROUND, false, false>(kind, g.h, g.v);
+    const csic_params &p = pl->p;
+    const Geometry &g = pl->g;
+    return with_const<R_FLOOR, R_TRUNC>(p.rounding, [&](auto round) -> DistFn {
+        constexpr int ROUND = CSIC_CONST(round);
+        if (kind == 0)
+            return with_const<true, false>(p.sampling == CSIC_SAMPLING_AVG, [&](auto avg) {
+                return with_const<F_YCC, F_ARGB>(p.in_format, [](auto in) -> DistFn { return k_dist_gen<ROUND, CSIC_CONST(avg), CSIC_CONST(in)>; });
+            });
+        return with_const<true, false>(vec, [&](auto v16) {
+        return with_const<true, false>(!pl->tune.no_nt, [&](auto nt) {
+        return with_const<1, 2>(kind, [&](auto f) {
+        return with_const<1, 2, 4>(g.h, [&](auto h) {
+        // at F = 2 the output rows are sample rows: v does not matter
+        return with_const<2, 1>(CSIC_CONST(f) == 1 ? g.v : 1, [](auto v) -> DistFn {
+            return k_dist_fast<ROUND, CSIC_CONST(f), CSIC_CONST(h), CSIC_CONST(v), CSIC_CONST(v16), CSIC_CONST(nt)>;
+        }); }); }); }); });
+    });
 }
 
 static int dist_workspace(const csic_plan *pl, int32_t nframes, size_t *bytes)
@@ -346,7 +333,7 @@ int csic_distortion_workspace_bytes(const csic_plan *plan, int32_t nframes, size
 const char *csic_distortion_kernel_name(const csic_plan *plan)
 {
     if (!plan) return "";
-    const csic_params &p = plan_params(plan);
+    const csic_params &p = plan->p;
     const bool ycc = p.in_format == CSIC_FMT_YCBCR888X;
     switch (dist_kind(plan)) {
     case 1: return "k_dist_fast<f1>";
@@ -371,14 +358,12 @@ int csic_distortion_device(csic_plan *plan, const void *d_in, int32_t nframes, u
     if ((uintptr_t)d_sse & 7u) return set_error(CSIC_EINVAL_SIZE, "d_sse must be 8-byte aligned");
     if ((uintptr_t)d_workspace & 7u) return set_error(CSIC_EINVAL_SIZE, "the workspace must be 8-byte aligned");
     if ((uintptr_t)d_in & 3u) return set_error(CSIC_EINVAL_SIZE, "the input must be 4-byte aligned");
-    const csic_params &p = plan_params(plan);
-    const Geometry &g = plan_geometry(plan);
+    const Geometry &g = plan->g;
     const int kind = dist_kind(plan);
     // 16-byte loads only for a 16-byte aligned d_in (the frame stride W * H * 4 is a multiple of 16 whenever width % 4 == 0)
     const bool vec = ((uintptr_t)d_in & 15u) == 0;
-    const bool nt = plan_nontemporal(plan);
-    const DistFn fn = p.rounding == CSIC_ROUND_FLOOR_HW ? pick_dist<R_FLOOR>(plan, kind, vec, nt) : pick_dist<R_TRUNC>(plan, kind, vec, nt);
-    CSIC_DEVICE_SCOPE(plan_device(plan));
+    const DistFn fn = dist_kernel(plan, kind, vec);
+    CSIC_DEVICE_SCOPE(plan->device);
     KArgs a;
     fill_base_args(g, g.W, g.Wo, &a);
     a.in = static_cast<const uint32_t *>(d_in);
@@ -407,10 +392,10 @@ int csic_distortion_host(csic_plan *plan, const uint32_t *in, size_t in_px, int3
     size_t ws = 0;
     int st = dist_workspace(plan, nframes, &ws);
     if (st != CSIC_OK) return st;
-    const Geometry &g = plan_geometry(plan);
+    const Geometry &g = plan->g;
     const size_t need = (size_t)nframes * (size_t)g.W * (size_t)g.H;
     if (in_px != need) return set_error(CSIC_EINVAL_SIZE, "expected %zu input pixels (%d frames), got %zu", need, nframes, in_px);
-    CSIC_DEVICE_SCOPE(plan_device(plan));
+    CSIC_DEVICE_SCOPE(plan->device);
     void *d_in = nullptr, *d_ws = nullptr, *d_sse = nullptr;
     const size_t sse_bytes = (size_t)nframes * DIST_CH * sizeof(uint64_t);
     hipError_t e = hipMalloc(&d_in, need * 4);

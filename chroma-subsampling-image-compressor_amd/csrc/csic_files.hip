@@ -301,15 +301,15 @@ int csic_process_png_files(csic_plan *plan, const char *const *in_paths, const c
     for (int i = 0; i < nfiles; ++i)
         if (!in_paths[i] || !out_paths[i]) return set_error(CSIC_EINVAL_NULL, "file %d: path is NULL", i);
     if (png_level < 0 || png_level > 9) return set_error(CSIC_EINVAL_SIZE, "png_level must be in 0..9. Got %d", png_level);
-    if (plan_params(plan).out_format == CSIC_FMT_PLANAR)
+    if (plan->p.out_format == CSIC_FMT_PLANAR)
         return set_error(CSIC_EINVAL_FORMAT, "the file pools write packed pixels: the plan's out_format must not be CSIC_FMT_PLANAR");
-    if (plan_params(plan).out_format == CSIC_FMT_PLANAR_BITS)
+    if (plan->p.out_format == CSIC_FMT_PLANAR_BITS)
         return set_error(CSIC_EINVAL_FORMAT, "the file pools write packed pixels: the plan's out_format must not be CSIC_FMT_PLANAR_BITS");
     Shared sh;
     sh.plan = plan;
-    sh.device = plan_device(plan);
+    sh.device = plan->device;
     plan_sizes(plan, &sh.in_px, &sh.out_px);
-    plan_out_dims(plan, &sh.out_w, &sh.out_h);
+    sh.out_w = plan->g.Wo; sh.out_h = plan->g.Ho;
     sh.final_w = final_width > 0 ? final_width : sh.out_w;
     sh.final_h = final_height > 0 ? final_height : sh.out_h;
     sh.final_px = (size_t)sh.final_w * (size_t)sh.final_h;
@@ -327,9 +327,9 @@ int csic_process_png_files(csic_plan *plan, const char *const *in_paths, const c
             const int st = csic_png_info(in_paths[i], &w, &h);
             if (st != CSIC_OK) return st;
         }
-        if ((size_t)w * (size_t)h != sh.in_px || w != plan_width(plan))
-            return set_error(CSIC_EINVAL_SIZE, "%s is %dx%d, the plan processes %dx%zu frames", in_paths[i], w, h, plan_width(plan),
-                             sh.in_px / (size_t)plan_width(plan));
+        if ((size_t)w * (size_t)h != sh.in_px || w != plan->g.W)
+            return set_error(CSIC_EINVAL_SIZE, "%s is %dx%d, the plan processes %dx%zu frames", in_paths[i], w, h, plan->g.W,
+                             sh.in_px / (size_t)plan->g.W);
     }
     // Defaults from the CPU time the process may really use (affinity mask and cgroup quota, host_cpu_budget) -- not from the
     // CPUs the machine shows: a GPU box shows 256 and grants 16.  Twice the budget, because a worker also waits (file reads,

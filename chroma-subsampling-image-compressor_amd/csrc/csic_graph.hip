@@ -517,7 +517,7 @@ static int build_fused(csic_frame_graph *g, csic_plan *plan, const void *const *
     HIP_TRY(hipMemcpy(static_cast<uint8_t *>(g->d_tables) + bytes, d_out, bytes, hipMemcpyHostToDevice));
     const void *const *tin = static_cast<const void *const *>(g->d_tables);
     void *const *tout = reinterpret_cast<void *const *>(static_cast<uint8_t *>(g->d_tables) + bytes);
-    const bool planar = plan_params(plan).out_format == CSIC_FMT_PLANAR;
+    const bool planar = plan->p.out_format == CSIC_FMT_PLANAR;
     if (planar)
         for (int k = 0; k < n; ++k)
             if ((uintptr_t)d_out[k] & 255u)
@@ -905,9 +905,9 @@ int csic_frame_graph_create_ex(csic_plan *plan, const void *const *d_in, void *c
     // stream-ordered way through them at every frame size (profiles/r02_small_launch.md); the per-frame-launch backends are
     // for callers that ask for per-frame launches by name.
     if (backend == CSIC_FRAME_GRAPH_AUTO) backend = CSIC_FRAME_GRAPH_FUSED;
-    if (plan_params(plan).out_format == CSIC_FMT_PLANAR_BITS)
+    if (plan->p.out_format == CSIC_FMT_PLANAR_BITS)
         return set_error(CSIC_EINVAL_FORMAT, "a CSIC_FMT_PLANAR_BITS plan has no frame graph (no backend, FUSED included, takes it)");
-    if (plan_params(plan).out_format == CSIC_FMT_PLANAR && backend != CSIC_FRAME_GRAPH_FUSED)
+    if (plan->p.out_format == CSIC_FMT_PLANAR && backend != CSIC_FRAME_GRAPH_FUSED)
         return set_error(CSIC_EINVAL_FORMAT, "a planar plan's frame graph is one fused launch (CSIC_FRAME_GRAPH_AUTO / _FUSED); the per-frame-launch "
                                               "backends take packed formats only");
     if (backend != CSIC_FRAME_GRAPH_HIP && backend != CSIC_FRAME_GRAPH_DIRECT && backend != CSIC_FRAME_GRAPH_FUSED)
@@ -930,11 +930,11 @@ int csic_frame_graph_create_ex(csic_plan *plan, const void *const *d_in, void *c
     if (branches > nframes) branches = nframes;
     for (int k = 0; k < nframes; ++k)
         if (!d_in[k] || !d_out[k]) return set_error(CSIC_EINVAL_NULL, "frame %d: device buffer is NULL", k);
-    CSIC_DEVICE_SCOPE(plan_device(plan));
+    CSIC_DEVICE_SCOPE(plan->device);
 
     csic_frame_graph *g = new (std::nothrow) csic_frame_graph();
     if (!g) return set_error(CSIC_ENOMEM, "out of host memory");
-    g->device = plan_device(plan);
+    g->device = plan->device;
     g->backend = backend;
     g->nframes = nframes;
     g->branches = branches;

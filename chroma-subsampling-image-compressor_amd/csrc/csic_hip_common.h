@@ -1,11 +1,28 @@
 // csic_hip_common.h -- shared by the HIP translation units (csic_kernels.hip, csic_pipeline.hip,
-// csic_multi.hip, csic_graph.hip): error macro, the HIP instantiation of the device guard and the launch
-// descriptor that csic_kernels.hip prepares for the other units.
+// csic_multi.hip, csic_graph.hip): error macro, the HIP instantiation of the device guard, the plan, the launch
+// descriptor that csic_kernels.hip prepares for the other units and the run-time-value -> template-argument helper.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "csic_device_guard.h"
 #include "csic_internal.h"
+#include "csic_select.h"
+
+// The plan behind the opaque handle of csic.h.  `sel` / `name` are what select_kernel / kernel_name give for (p, g, tune) with
+// no launch constraints (the planar formats: FAM_PLANAR and the name of their own kernel); refreshed by csic_plan_tune.
+struct csic_plan {
+    csic_params p;
+    csic::Geometry g;
+    int device;
+    csic::Tune tune;
+    csic::Selection sel;
+    char name[96];
+    // host path staging
+    void *d_in, *d_out;
+    unsigned long long *d_sum;
+};
 
 namespace csic {
 
@@ -30,28 +47,6 @@ using DeviceGuard = BasicDeviceGuard<HipDeviceApi>;
         return ::csic::set_error(CSIC_EHIP, "cannot make device %d current: %s", (int)(dev),                \
                                  hipGetErrorString((hipError_t)csic_device_guard_.status()))
 
-// ---- kernel arguments (kernarg segment -> SGPRs) ----------------------------------------------------
-struct KArgs {
-    const uint32_t *in;
-    uint32_t *out;
-    int32_t W, H, Wo, Ho;
-    int32_t last_sample_col;
-    uint32_t my, mcb, mcr;
-    int32_t f, hmask, vmask, s_first;   // hmask = h-1, vmask = v-1 (generic kernel; vmask also k_dec SROWS)
-    int32_t sc_shift, bc_row_off, bc_col_in;   // k_dec SROWS: log2 f; held-sample decimated row offset / input column
-    int32_t edge_y0;                    // k_avg: first row of edge blocks along grid y (in what used to be padding: the size stays 152)
-    int64_t in_frame_px, out_frame_px;  // batch strides (grid z = frame)
-    int32_t bdx, bdy, row_step;         // block width/height and gridDim.y * bdy, passed explicitly (see pin_args)
-    int32_t ip, op;                     // row pitch of the input / output frame in pixels (>= W / Wo; == when packed)
-    uint32_t mW, mWo, kW, kWo;          // k_generic: exact n / W and n / Wo for n < 2^31 as (n * m) >> k (see magic_div)
-    const uint32_t *const *in_tab;      // frame-table mode (CSIC_FRAME_GRAPH_FUSED): frame z reads in_tab[z] and writes out_tab[z];
-    uint32_t *const *out_tab;           //   null = frames lie back to back behind `in` / `out`
-};
-
-// The direct-dispatch engine copies sizeof(KArgs) bytes into raw kernarg memory (csic_graph.hip): every translation unit must
-// see this one layout -- there is exactly one copy of this header (tests/test_bench_contract.py checks that, too).
-static_assert(sizeof(KArgs) == 152 && alignof(KArgs) == 8, "KArgs layout changed: check the kernarg blocks built in csic_graph.hip");
-
 using KernelFn = void (*)(KArgs);
 
 // One fully resolved launch of the fused kernel: what hipLaunchKernel / hipGraphAddKernelNode need.
@@ -71,14 +66,6 @@ int prepare_launch_table(const csic_plan *pl, const void *const *d_in_tab, void 
                          LaunchDesc *d);
 int enqueue(const LaunchDesc &d, hipStream_t stream);
 int launch_on_stream(csic_plan *pl, const void *d_in, void *d_out, int nframes, hipStream_t stream);
-int plan_device(const csic_plan *pl);
-const csic_params &plan_params(const csic_plan *pl);
-const Geometry &plan_geometry(const csic_plan *pl);
-int plan_variant(const csic_plan *pl);                       // CSIC_TUNE_VARIANT
-bool plan_nontemporal(const csic_plan *pl);                  // CSIC_TUNE_NONTEMPORAL
-int plan_block_threads(const csic_plan *pl);                 // CSIC_TUNE_BLOCK_THREADS (0 = the library's choice)
-bool plan_force_generic(const csic_plan *pl);                // CSIC_TUNE_FORCE_GENERIC
-void fill_base_args(const Geometry &g, int32_t ip, int32_t op, KArgs *a);
 // csic_planar.hip: out_format = CSIC_FMT_PLANAR (forward: packed input -> planar frame buffers; name of the kernel a plan takes)
 // csic_planar.hip: the second kernel argument of the planar kernels, and a prepared planar launch (as LaunchDesc for the packed ones)
 struct PExtra {
@@ -105,10 +92,19 @@ void planar_kernel_name(const csic_plan *pl, char *buf, size_t len);
 // csic_planar_bits.hip: out_format = CSIC_FMT_PLANAR_BITS (forward: packed input -> bit-packed planar frame buffers; kernel name)
 int planar_bits_forward(const csic_plan *pl, const void *d_in, void *d_bits, int nframes, hipStream_t stream);
 void planar_bits_kernel_name(const csic_plan *pl, char *buf, size_t len);
-int planar_avg_geometry(const csic_plan *pl, int nframes, LaunchDesc *d, bool *tile);   // k_avg's geometry for a planar AVG plan
 void plan_sizes(const csic_plan *pl, size_t *in_px, size_t *out_px);
-int32_t plan_width(const csic_plan *pl);
-void plan_out_dims(const csic_plan *pl, int32_t *wo, int32_t *ho);
 int64_t plan_algorithmic_bytes(const csic_plan *pl);          // per frame (csic_algorithmic_bytes of the plan's parameters)
+
+
+// with_const<V0, V1, ...>(v, fn): calls fn with v as a compile-time constant -- std::integral_constant<.., Vi> for the Vi equal
+// to v, the last one listed if none is (the callers' values are validated long before).  The one place a run-time value turns
+// into a template argument: only the listed values are ever instantiated.
+template <auto V0, auto... Vs, class T, class Fn>
+auto with_const(T v, Fn &&fn)
+{
+    if constexpr (sizeof...(Vs) == 0) return fn(std::integral_constant<decltype(V0), V0>{});
+    else return v == (T)V0 ? fn(std::integral_constant<decltype(V0), V0>{}) : with_const<Vs...>(v, fn);
+}
+#define CSIC_CONST(x) decltype(x)::value     // the value of a with_const argument, usable as a template argument inside nested lambdas
 
 } // namespace csic

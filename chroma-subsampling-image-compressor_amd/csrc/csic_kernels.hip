@@ -1,4 +1,6 @@
-// csic_kernels.hip -- the fused pixel pipeline for gfx950 (MI355X) and the device half of the C ABI.
+// csic_kernels.hip -- the fused pixel pipeline for gfx950 (MI355X) and the device half of the C ABI: the packed kernels,
+// resolve() (kernel identity -> instantiation), the launch path and the entry points.  Which kernel a plan takes, under what
+// name and with what grid, block and KArgs is decided in csic_select.cpp (host only; tests/cpp/launch_table.cpp prints it).
 //
 // One launch turns packed ARGB input pixels into packed reconstructed ARGB (or YCbCr) output pixels:
 //   forward RGB->YCbCr  (RGB2YCbCr.scala:33-65 floor form / :95-121 trunc form)
@@ -110,7 +112,7 @@ __device__ __forceinline__ void f1flat_body(const KArgs &a, gin_t in, gout_t out
             const uint32_t j0 = 4u * g;
             r = (uint32_t)(((uint64_t)j0 * a.mW) >> a.kW);
             col = j0 - __umul24(r, W);
-            io = __umul24(r, ip) + col;                                          // rows and pitches fit 24 bits (prepare_common)
+            io = __umul24(r, ip) + col;                                          // rows and pitches fit 24 bits (plan_launch)
             ooff = __umul24(r, op) + col;
         } else {
             const bool wrap = col + rT >= W;
@@ -293,7 +295,7 @@ __global__ void __launch_bounds__(256) k_dec(KArgs a)
 // (ro / F) odd -- every pixel replays the last sample of the chroma row above; lanes of one wave may sit in different rows
 // here, so the held pixel is a per-lane load whose address is SELECTED (own pixel on even rows: a cache hit), not branched on.
 // Addressing (round 4): the flat kernels are launched only for frames whose extents fit 2^30 pixels and whose rows and pitches fit
-// 24 bits (prepare_common sends anything larger to the row kernels), so a pixel's BYTE offset inside its frame is a uint32 and
+// 24 bits (plan_launch sends anything larger to the row kernels), so a pixel's BYTE offset inside its frame is a uint32 and
 // every access takes the "scalar base + 32-bit lane offset" form of global_load / global_store; row * pitch is one full-rate
 // v_mad_u32_u24.  Only the first of a lane's K indices is divided (the exact multiply-shift); the others follow by stepping:
 // T = qT * Wo + rT, so (ro, co) += (qT, rT) with one conditional wrap, and the two offsets advance by one of two wave-uniform
@@ -323,7 +325,7 @@ __device__ __forceinline__ void decflat_body(const KArgs &a, gin_t in, gout_t ou
             const uint32_t i = CHECK ? min(i0 + (uint32_t)k * T, n - 1) : i0;
             ro = (uint32_t)(((uint64_t)i * a.mWo) >> a.kWo);                     // i / Wo, exact for i < 2^31
             co = i - __umul24(ro, Wo);
-            yoff = (__umul24(ro, ip) + co) * F;                                  // rows and pitches fit 24 bits (prepare_common):
+            yoff = (__umul24(ro, ip) + co) * F;                                  // rows and pitches fit 24 bits (plan_launch):
             ooff = __umul24(ro, op) + co;                                        // one full-rate v_mad_u32_u24 each
         } else {
             const bool wrap = co + rT >= Wo;
@@ -526,7 +528,7 @@ __device__ __forceinline__ void flatgen_body(const KArgs &a, gin_t in, gout_t ou
             co = wrap ? co + rT - Wo : co + rT;
             ro += qT + (wrap ? 1u : 0u);
         }
-        yo[k] = __umul24(ro, rstep) + co * f;                                    // rows, pitches and f * pitch fit 24 bits (prepare_common)
+        yo[k] = __umul24(ro, rstep) + co * f;                                    // rows, pitches and f * pitch fit 24 bits (plan_launch)
         px[k] = in1n<NT>(a, in, yo[k]);
         oo[k] = __umul24(ro, (uint32_t)a.op) + co;
         int r, d;
@@ -614,494 +616,73 @@ __global__ void __launch_bounds__(64) k_debug_probe(KArgs a, int64_t off, uint32
 }
 
 // ------------------------------------------------------------------------------------------------
-// plan
+// resolve: the one place that names instantiations of the packed kernels.  Selection, names and launch geometry are
+// csic_select.cpp's (host only); a KernelId carries exactly the template arguments.
 // ------------------------------------------------------------------------------------------------
-enum Family { FAM_F1X4, FAM_DEC, FAM_DEC2V1, FAM_DEC2V2, FAM_GENERIC, FAM_AVG, FAM_AVG_GENERIC, FAM_DECFLAT, FAM_F1FLAT };
-
-} // namespace csic
-
-struct csic_plan {
-    csic_params p;
-    csic::Geometry g;
-    int device;
-    int variant;
-    int force_generic;
-    int no_vec;          // 1 = no 16-byte vector kernels (set per launch for pointers that are only 4-byte aligned)
-    int no_flat;         // 1 = no flat kernels (set per launch for frames whose extents pass 2^30 pixels: they address with 32-bit byte offsets)
-    int dec_hold;        // k_dec: lane-hold distance of the selected kernel (1, 2 or 4)
-    int no_nt;           // 1 = plain (cached) loads/stores instead of non-temporal ones
-    int block_threads;   // 0 = default (256); 64 / 128 = smaller blocks (CSIC_TUNE_BLOCK_THREADS)
-    // selection (recomputed by select())
-    csic::Family fam;
-    csic::KernelFn fn;
-    int units_per_row;   // lanes needed along x
-    int k_per_lane;      // x units consumed per lane (k_dec only)
-    char name[96];
-    // host path staging
-    void *d_in, *d_out;
-    unsigned long long *d_sum;
-};
-
-namespace csic {
-
-template <int ROUND, int FMT, bool NT>
-static KernelFn pick_f1x4(int h, int v)
+KernelFn resolve(const KernelId &id)
 {
-    if (v == 1) {
-        if (h == 1) return k_f1x4<ROUND, FMT, 1, 1, NT>;
-        if (h == 2) return k_f1x4<ROUND, FMT, 2, 1, NT>;
-        return k_f1x4<ROUND, FMT, 4, 1, NT>;
-    }
-    if (h == 1) return k_f1x4<ROUND, FMT, 1, 2, NT>;
-    if (h == 2) return k_f1x4<ROUND, FMT, 2, 2, NT>;
-    return k_f1x4<ROUND, FMT, 4, 2, NT>;
-}
-
-template <int ROUND, int FMT, bool NT>
-static KernelFn pick_f1flat(int h, int v)
-{
-    if (v == 1) {
-        if (h == 1) return k_f1flat<ROUND, FMT, 1, 1, NT>;
-        if (h == 2) return k_f1flat<ROUND, FMT, 2, 1, NT>;
-        return k_f1flat<ROUND, FMT, 4, 1, NT>;
-    }
-    if (h == 1) return k_f1flat<ROUND, FMT, 1, 2, NT>;
-    if (h == 2) return k_f1flat<ROUND, FMT, 2, 2, NT>;
-    return k_f1flat<ROUND, FMT, 4, 2, NT>;
-}
-
-constexpr int DEC_K = 4;
-
-template <int ROUND, int FMT, int F, bool NT>
-static KernelFn pick_dec_f(int hold, bool srows)
-{
-    if (srows) {
-        if (hold == 1) return k_dec<ROUND, FMT, F, 1, true, DEC_K, NT>;
-        if (hold == 2) return k_dec<ROUND, FMT, F, 2, true, DEC_K, NT>;
-        return k_dec<ROUND, FMT, F, 4, true, DEC_K, NT>;
-    }
-    if (hold == 1) return k_dec<ROUND, FMT, F, 1, false, DEC_K, NT>;
-    if (hold == 2) return k_dec<ROUND, FMT, F, 2, false, DEC_K, NT>;
-    return k_dec<ROUND, FMT, F, 4, false, DEC_K, NT>;
-}
-
-template <int ROUND, int FMT, bool NT>
-static KernelFn pick_dec(int f, int hold, bool srows)
-{
-    if (f == 1) return pick_dec_f<ROUND, FMT, 1, NT>(hold, srows);
-    if (f == 2) return pick_dec_f<ROUND, FMT, 2, NT>(hold, srows);
-    if (f == 4) return pick_dec_f<ROUND, FMT, 4, NT>(hold, srows);
-    return pick_dec_f<ROUND, FMT, 8, NT>(hold, srows);
-}
-
-template <int ROUND, int FMT, int F, bool NT>
-static KernelFn pick_decflat_f(int hold, bool srows)
-{
-    if (srows) {
-        if (hold == 1) return k_decflat<ROUND, FMT, F, 1, true, DEC_K, NT>;
-        if (hold == 2) return k_decflat<ROUND, FMT, F, 2, true, DEC_K, NT>;
-        return k_decflat<ROUND, FMT, F, 4, true, DEC_K, NT>;
-    }
-    if (hold == 1) return k_decflat<ROUND, FMT, F, 1, false, DEC_K, NT>;
-    if (hold == 2) return k_decflat<ROUND, FMT, F, 2, false, DEC_K, NT>;
-    return k_decflat<ROUND, FMT, F, 4, false, DEC_K, NT>;
-}
-
-template <int ROUND, int FMT, bool NT>
-static KernelFn pick_decflat(int f, int hold, bool srows)
-{
-    if (f == 2) return pick_decflat_f<ROUND, FMT, 2, NT>(hold, srows);
-    if (f == 4) return pick_decflat_f<ROUND, FMT, 4, NT>(hold, srows);
-    return pick_decflat_f<ROUND, FMT, 8, NT>(hold, srows);
-}
-
-// Block width k_dec would take for `lanes_x` lanes per row in blocks of `tpb` threads (prepare_common): a width that divides
-// the row exactly when there is one between tpb / 2 and tpb lanes, else the power of two that leaves a partial chunk.
-static int dec_block_x(int lanes_x, int tpb, int hold)
-{
-    int bx = 1;
-    while (bx < lanes_x) bx <<= 1;
-    if (bx > tpb) bx = tpb;
-    if (lanes_x <= tpb) {
-        if (lanes_x % hold == 0) bx = lanes_x;
-    } else {
-        for (int m = (lanes_x + tpb - 1) / tpb; m <= lanes_x / (tpb / 2); ++m)
-            if (lanes_x % m == 0 && (lanes_x / m) % hold == 0) { bx = lanes_x / m; break; }
-    }
-    return bx;
-}
-
-// One-wave blocks for narrow rows (a row needs at most two waves and tiles into them): see prepare_common.
-static bool dec_one_wave_blocks(int lanes_x, int f, int hold)
-{
-    if (lanes_x < 16 || lanes_x > 128) return false;
-    bool tiles = (f >= 4 && lanes_x < 64) || (lanes_x & (lanes_x - 1)) == 0;       // 16, 32, 64, 128; any < 64 for f >= 4
-    for (int w = 64; !tiles && w >= 48; --w) tiles = lanes_x % w == 0 && w % hold == 0;
-    return tiles && (lanes_x >= 64 || lanes_x % hold == 0);
-}
-
-// Should a chroma-before-spatial, hold-free plan cover the flat decimated stream (k_decflat) instead of rows (k_dec)?
-// Measured over 22 shapes (tools/probe_flat.py, profiles/r03_probe_flat.log; batched launches, k_dec | flat):
-//  * rows k_dec cannot cut into whole blocks -- not a whole number of K-pixel lanes, or lanes without a usable divisor: every
-//    block of k_dec runs its bounds-checked path (1000x1000 f = 4 / 8: 66 / 63 | 73 / 71 %; 1366x768 f = 2: 68 | 79 %);
-//  * rows of a few partly filled waves that straddle two rows at odd offsets (1000x1000 f = 2: 70 | 78 %, 720x480 f = 2:
-//    70 | 78 %, 352x288 f = 2: 70 | 81 %, 1280x720 f = 2: 78.5 | 81.5 %);
-//  * rows of whole waves: level or slightly ahead (8192x8192 f = 2 / 4 / 8: 79.8 | 82.6, 76.3 | 76.9, 74.3 | 77.0 %; 3840x2160
-//    f = 4: 75.3 | 76.7 %; 1080p / 4K f = 2: 79.6 | 80.4 %), and on the headline -- ONE 8192x8192 frame per launch -- four
-//    interleaved repeats give 32.09 | 31.85 us = 78.4 | 79.0 % (profiles/r03_headline_flat_ab.jsonl);
-//  * the one exception: shapes that take k_dec's one-wave blocks (512x512 f = 2: 77 | 65-73 %; 1024x1024 f = 8: 79 | 70-78 %;
-//    640x480 f = 4 and 1920x1080 f = 4 level) stay with k_dec;
-//  * the same picture with a lane hold and with spatial before chroma (profiles/r03_probe_flat_{csq411,scq444,scq422,scq420}.log;
-//    4:2:0 spatial before chroma: 1000x1000 f = 2: 60 | 78 %, 352x288 f = 2: 61 | 80 %, 8192x8192 f = 2 / 4 / 8: 79.4 | 82.6,
-//    77.0 | 77.8, 75.2 | 77.5 % -- once the held-pixel load of the odd chroma rows is skipped wave-uniformly; loaded
-//    unconditionally it cost 8192x8192 f = 8 twenty points).
-static bool dec_prefers_flat(const Geometry &g, int hold)
-{
-    if (g.Wo % DEC_K != 0) return true;
-    return !dec_one_wave_blocks(g.Wo / DEC_K, g.f, hold);
-}
-
-template <int ROUND, int FMT, int F, bool NT>
-static KernelFn pick_avg_f(int h, int v)
-{
-    if (v == 1) {
-        if (h == 1) return k_avg<ROUND, FMT, F, 1, 1, NT>;
-        if (h == 2) return k_avg<ROUND, FMT, F, 2, 1, NT>;
-        return k_avg<ROUND, FMT, F, 4, 1, NT>;
-    }
-    if (h == 1) return k_avg<ROUND, FMT, F, 1, 2, NT>;
-    if (h == 2) return k_avg<ROUND, FMT, F, 2, 2, NT>;
-    return k_avg<ROUND, FMT, F, 4, 2, NT>;
-}
-
-template <int ROUND, int FMT, bool NT>
-static KernelFn pick_avg(int f, int h, int v)
-{
-    if (f == 1) return pick_avg_f<ROUND, FMT, 1, NT>(h, v);
-    if (f == 2) return pick_avg_f<ROUND, FMT, 2, NT>(h, v);
-    if (f == 4) return pick_avg_f<ROUND, FMT, 4, NT>(h, v);
-    return pick_avg_f<ROUND, FMT, 8, NT>(h, v);
-}
-
-// Can the k_dec family handle this geometry?  Chroma before spatial: always, except that a hold across
-// lanes (4:1:1 with f = 2) needs whole quads in a row.  Spatial before chroma: only when chroma rows
-// coincide with groups of decimated rows (f | W) and the in-row hold is lane-aligned (h | Wo).
-static bool dec_fast_ok(const Geometry &g)
-{
-    const int hold = (g.s_first || g.f == 1) ? g.h : (g.h > g.f ? g.h / g.f : 1);
-    const int lanes_x = (g.Wo + DEC_K - 1) / DEC_K;
-    if (hold > 1 && lanes_x < 3) return false;            // block width < 4 lanes: quads would span rows
-    if (!g.s_first) return true;
-    return (g.W % g.f == 0) && (g.Wo % g.h == 0);
-}
-
-template <int ROUND, int FMT>
-static void select_rf(csic_plan *pl)
-{
-    const Geometry &g = pl->g;
-    const char *rn = ROUND == R_FLOOR ? "floor" : "trunc";
-    const char *fn = FMT == F_ARGB ? "argb" : "ycc";
-    const bool nt = !pl->no_nt;
-    const char *ntn = nt ? "nt" : "cached";
-    // A YCbCr input stream (single-stage driving, the reference's spec style) is a test-oriented path:
-    // it is served by the run-time-parameter kernels only.
-    const bool ycc_in = pl->p.in_format == CSIC_FMT_YCBCR888X;
-    if (pl->p.sampling == CSIC_SAMPLING_AVG) {
-        const int th = g.f > g.v ? g.f : g.v;
-        const int tw = g.f == 8 ? 8 : 4;
-        // any shape with at least one whole tile (pair of tiles at f = 8) and tile row: the frame's cut tiles take the definition's
-        // clamped form inside k_avg; variant 8 keeps the rule of rounds 1-3 (whole tiles only, everything else generic) for A/B
-        const bool whole = g.W % tw == 0 && g.H % th == 0;
-        if (!pl->force_generic && !ycc_in && !pl->no_vec && g.W >= tw && g.H >= th && (whole || pl->variant != 8)) {
-            pl->fam = FAM_AVG;
-            pl->fn = nt ? pick_avg<ROUND, FMT, true>(g.f, g.h, g.v) : pick_avg<ROUND, FMT, false>(g.f, g.h, g.v);
-            pl->units_per_row = (g.W + 3) / 4;
-            pl->k_per_lane = (g.f <= 2) ? 2 : 1;          // TILES of k_avg
-            snprintf(pl->name, sizeof pl->name, "k_avg<%s,%s,f%d,h%d,v%d,%s>", rn, fn, g.f, g.h, g.v, ntn);
-        } else {
-            pl->fam = FAM_AVG_GENERIC;
-            pl->fn = ycc_in ? (KernelFn)k_avg_generic<ROUND, FMT, F_YCC> : (KernelFn)k_avg_generic<ROUND, FMT, F_ARGB>;
-            pl->units_per_row = g.Wo;
-            pl->k_per_lane = 1;
-            snprintf(pl->name, sizeof pl->name, "k_avg_generic<%s,%s%s>", rn, fn, ycc_in ? ",ycc-in" : "");
+    return with_const<R_FLOOR, R_TRUNC>(id.round, [&](auto round) {
+    return with_const<F_ARGB, F_YCC>(id.fmt, [&](auto fmt) {
+    return with_const<true, false>(id.nt, [&](auto nontemporal) -> KernelFn {
+        constexpr int ROUND = CSIC_CONST(round), FMT = CSIC_CONST(fmt);
+        constexpr bool NT = CSIC_CONST(nontemporal);
+        const auto hv = [&](auto pick) {                 // pick(h, v) over chroma holds 1 / 2 / 4 x 1 / 2
+            return with_const<1, 2, 4>(id.h, [&](auto h) { return with_const<1, 2>(id.v, [&](auto v) { return pick(h, v); }); });
+        };
+        const auto hold_srows = [&](auto pick) {         // pick(hold, srows) over lane holds 1 / 2 / 4, both row classes
+            return with_const<1, 2, 4>(id.h, [&](auto h) { return with_const<true, false>(id.srows, [&](auto s) { return pick(h, s); }); });
+        };
+        switch (id.fam) {
+        case FAM_F1X4:
+            return hv([](auto h, auto v) -> KernelFn { return k_f1x4<ROUND, FMT, CSIC_CONST(h), CSIC_CONST(v), NT>; });
+        case FAM_F1FLAT:
+            return hv([](auto h, auto v) -> KernelFn { return k_f1flat<ROUND, FMT, CSIC_CONST(h), CSIC_CONST(v), NT>; });
+        case FAM_DEC:
+            return with_const<1, 2, 4, 8>(id.f, [&](auto f) {
+                return hold_srows([](auto h, auto s) -> KernelFn { return k_dec<ROUND, FMT, CSIC_CONST(f), CSIC_CONST(h), CSIC_CONST(s), DEC_K, NT>; });
+            });
+        case FAM_DECFLAT:
+            return with_const<2, 4, 8>(id.f, [&](auto f) {
+                return hold_srows([](auto h, auto s) -> KernelFn { return k_decflat<ROUND, FMT, CSIC_CONST(f), CSIC_CONST(h), CSIC_CONST(s), DEC_K, NT>; });
+            });
+        case FAM_DEC2V1: return k_dec2v<ROUND, FMT, 1, NT>;
+        case FAM_DEC2V2: return k_dec2v<ROUND, FMT, 2, NT>;
+        case FAM_AVG:
+            return with_const<1, 2, 4, 8>(id.f, [&](auto f) {
+                return hv([](auto h, auto v) -> KernelFn { return k_avg<ROUND, FMT, CSIC_CONST(f), CSIC_CONST(h), CSIC_CONST(v), NT>; });
+            });
+        case FAM_AVG_GENERIC:
+            return with_const<F_YCC, F_ARGB>(id.infmt, [](auto in) -> KernelFn { return k_avg_generic<ROUND, FMT, CSIC_CONST(in)>; });
+        case FAM_FLATGEN: return k_flatgen<ROUND, FMT, DEC_K, NT>;
+        case FAM_GENERIC:
+            return with_const<F_YCC, F_ARGB>(id.infmt, [](auto in) -> KernelFn { return k_generic<ROUND, FMT, CSIC_CONST(in)>; });
+        case FAM_PLANAR: break;
         }
-        return;
-    }
-    // f = 1: the 16-byte kernel wins whenever it applies (8192^2: 4:4:4 84.0 vs 88.0 us, 4:2:0 84.5 vs 85.9 us for
-    // the 4-byte k_dec<f1>, which serves the other widths / alignments; variant 4 forces k_dec<f1> for A/B).
-    const bool f1x4_ok = !pl->force_generic && !ycc_in && !pl->no_vec && g.f == 1 && g.W % 4 == 0;
-    if (f1x4_ok && pl->variant != 11 && pl->variant != 4 && !pl->no_flat) {
-        // the flat mapping (round 4): ahead of k_f1x4 at every chroma mode and on 10 of 12 frame sizes -- 8192x8192 4:2:0 77.0 ->
-        // 79.3 %, 4:2:2 77.5 -> 80.3 %, 4:4:4 78.8 -> 79.8 %, 4:1:0 76.5 -> 79.5 %, 4096x4096 76.5 -> 79.1 %, 1000x1000 76.6 -> 78.9 %;
-        // level (-0.5) on 3840x2160 and 1920x1080 (profiles/r04_f1flat_ab.log).  CSIC_TUNE_VARIANT 11 keeps k_f1x4 for A/B.
-        pl->fam = FAM_F1FLAT;
-        pl->fn = nt ? pick_f1flat<ROUND, FMT, true>(g.h, g.v) : pick_f1flat<ROUND, FMT, false>(g.h, g.v);
-        pl->units_per_row = g.W / 4;
-        pl->k_per_lane = 1;
-        snprintf(pl->name, sizeof pl->name, "k_f1flat<%s,%s,h%d,v%d,%s>", rn, fn, g.h, g.v, ntn);
-    } else if (f1x4_ok && (pl->variant != 4 || !dec_fast_ok(g))) {
-        pl->fam = FAM_F1X4;
-        pl->fn = nt ? pick_f1x4<ROUND, FMT, true>(g.h, g.v) : pick_f1x4<ROUND, FMT, false>(g.h, g.v);
-        pl->units_per_row = g.W / 4;
-        pl->k_per_lane = 1;
-        snprintf(pl->name, sizeof pl->name, "k_f1x4<%s,%s,h%d,v%d,%s>", rn, fn, g.h, g.v, ntn);
-    } else if (!pl->force_generic && !ycc_in && dec_fast_ok(g)) {
-        // in-row chroma hold distance in decimated lanes; srows = chroma rows follow the decimated stream
-        // (with f = 1 the decimated stream IS the image and both order classes coincide: any width, any
-        // 4-byte-aligned pointer, 4-byte accesses)
-        const bool srows = g.s_first != 0 || g.f == 1;
-        const int hold = srows ? g.h : (g.h > g.f ? g.h / g.f : 1);
-        if (g.f == 2 && hold == 1 && !srows && !pl->no_vec && g.W % 8 == 0 && (pl->variant == 1 || pl->variant == 2)) {
-            pl->fam = pl->variant == 1 ? FAM_DEC2V1 : FAM_DEC2V2;
-            if (pl->variant == 1) pl->fn = nt ? (KernelFn)k_dec2v<ROUND, FMT, 1, true> : (KernelFn)k_dec2v<ROUND, FMT, 1, false>;
-            else                  pl->fn = nt ? (KernelFn)k_dec2v<ROUND, FMT, 2, true> : (KernelFn)k_dec2v<ROUND, FMT, 2, false>;
-            pl->units_per_row = g.Wo / (pl->variant == 1 ? 2 : 4);
-            pl->k_per_lane = 1;
-            snprintf(pl->name, sizeof pl->name, "k_dec2v<%s,%s,var%d,%s>", rn, fn, pl->variant, ntn);
-        } else if (g.f >= 2 && g.Wo % hold == 0 && pl->variant != 5 && !pl->no_flat && (pl->variant == 6 || dec_prefers_flat(g, hold))) {
-            // lanes over the flat decimated stream (variant 5 keeps k_dec, variant 6 takes k_decflat wherever it applies: A/B);
-            // a hold group must not straddle two rows: hold | Wo (spatial before chroma has that from dec_fast_ok)
-            const bool sr = srows && g.v == 2;
-            pl->fam = FAM_DECFLAT;
-            pl->dec_hold = hold;
-            pl->fn = nt ? pick_decflat<ROUND, FMT, true>(g.f, hold, sr) : pick_decflat<ROUND, FMT, false>(g.f, hold, sr);
-            pl->units_per_row = g.Wo;
-            pl->k_per_lane = DEC_K;
-            if (hold == 1 && !srows)
-                snprintf(pl->name, sizeof pl->name, "k_decflat<%s,%s,f%d,K%d,%s>", rn, fn, g.f, DEC_K, ntn);
-            else
-                snprintf(pl->name, sizeof pl->name, "k_decflat<%s,%s,f%d,hold%d,%s,K%d,%s>", rn, fn, g.f, hold,
-                         srows ? (g.v == 2 ? "s>c,v2" : "s>c") : "c>s", DEC_K, ntn);
-        } else {
-            pl->fam = FAM_DEC;
-            pl->dec_hold = hold;
-            pl->fn = nt ? pick_dec<ROUND, FMT, true>(g.f, hold, srows && g.v == 2)
-                        : pick_dec<ROUND, FMT, false>(g.f, hold, srows && g.v == 2);
-            pl->units_per_row = g.Wo;
-            pl->k_per_lane = DEC_K;
-            snprintf(pl->name, sizeof pl->name, "k_dec<%s,%s,f%d,hold%d,%s,K%d,%s>", rn, fn, g.f, hold,
-                     g.f == 1 ? (g.v == 2 ? "v2" : "v1") : srows ? (g.v == 2 ? "s>c,v2" : "s>c") : "c>s", DEC_K, ntn);
-        }
-    } else if (!pl->force_generic && !ycc_in && g.f >= 2 && pl->variant != 7 && !pl->no_flat) {
-        // what k_dec / k_decflat cannot take (spatial before chroma with f not dividing W or h not dividing Wo; tiny frames with a
-        // hold): the general flat kernel; variant 7 keeps the one-pixel-per-lane k_generic for A/B
-        pl->fam = FAM_DECFLAT;
-        pl->dec_hold = 1;
-        pl->fn = nt ? (KernelFn)k_flatgen<ROUND, FMT, DEC_K, true> : (KernelFn)k_flatgen<ROUND, FMT, DEC_K, false>;
-        pl->units_per_row = g.Wo;
-        pl->k_per_lane = DEC_K;
-        snprintf(pl->name, sizeof pl->name, "k_flatgen<%s,%s,K%d,%s>", rn, fn, DEC_K, ntn);
-    } else {
-        pl->fam = FAM_GENERIC;
-        pl->fn = ycc_in ? (KernelFn)k_generic<ROUND, FMT, F_YCC> : (KernelFn)k_generic<ROUND, FMT, F_ARGB>;
-        pl->units_per_row = g.Wo;
-        pl->k_per_lane = 1;
-        snprintf(pl->name, sizeof pl->name, "k_generic<%s,%s%s>", rn, fn, ycc_in ? ",ycc-in" : "");
-    }
+        return nullptr;
+    }); }); });
 }
 
+// plan->sel / plan->name for the plan's parameters and knobs
 static void select(csic_plan *pl)
 {
-    if (pl->p.out_format == CSIC_FMT_PLANAR) {           // csic_planar.hip picks and names its kernels
-        pl->fam = FAM_GENERIC; pl->fn = nullptr; pl->units_per_row = pl->g.Wo; pl->k_per_lane = 1;
-        planar_kernel_name(pl, pl->name, sizeof pl->name);
-        return;
-    }
-    if (pl->p.out_format == CSIC_FMT_PLANAR_BITS) {      // csic_planar_bits.hip picks and names its kernels
-        pl->fam = FAM_GENERIC; pl->fn = nullptr; pl->units_per_row = pl->g.Wo; pl->k_per_lane = 1;
-        planar_bits_kernel_name(pl, pl->name, sizeof pl->name);
-        return;
-    }
-    const int r = pl->p.rounding, f = pl->p.out_format;
-    if (r == R_FLOOR && f == F_ARGB) select_rf<R_FLOOR, F_ARGB>(pl);
-    else if (r == R_FLOOR) select_rf<R_FLOOR, F_YCC>(pl);
-    else if (f == F_ARGB) select_rf<R_TRUNC, F_ARGB>(pl);
-    else select_rf<R_TRUNC, F_YCC>(pl);
-}
-
-static int pow2_ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
-
-// The geometry half of the kernel arguments (what does not depend on the kernel family or the launch shape).
-void fill_base_args(const Geometry &g, int32_t ip, int32_t op, KArgs *pa)
-{
-    KArgs &a = *pa;
-    std::memset(&a, 0, sizeof a);
-    a.W = g.W; a.H = g.H; a.Wo = g.Wo; a.Ho = g.Ho;
-    a.last_sample_col = g.last_sample_col;
-    a.my = g.mask_y; a.mcb = g.mask_cb; a.mcr = g.mask_cr;
-    a.f = g.f; a.hmask = g.h - 1; a.vmask = g.v - 1; a.s_first = g.s_first;
-    a.ip = ip; a.op = op;
-    a.in_frame_px = (int64_t)ip * g.H;
-    a.out_frame_px = (int64_t)op * g.Ho;
-    a.sc_shift = (g.f == 8) ? 3 : (g.f == 4) ? 2 : (g.f == 2) ? 1 : 0;
-    a.bc_row_off = g.last_sample_col / g.Wo;             // only meaningful (and only used) when f | W
-    a.bc_col_in = (g.last_sample_col % g.Wo) * g.f;
-    magic_div((uint32_t)g.W, &a.mW, &a.kW);
-    magic_div((uint32_t)g.Wo, &a.mWo, &a.kWo);
+    pl->sel = select_kernel(pl->p, pl->g, pl->tune, Constraints{false, false});
+    if (pl->p.out_format == CSIC_FMT_PLANAR) planar_kernel_name(pl, pl->name, sizeof pl->name);
+    else if (pl->p.out_format == CSIC_FMT_PLANAR_BITS) planar_bits_kernel_name(pl, pl->name, sizeof pl->name);
+    else kernel_name(pl->sel.id, pl->g, pl->name, sizeof pl->name);
 }
 
 // Resolves kernel, grid and arguments for `nframes` frames (<= 65535, the grid z limit) whose base pointers OR to
 // `align_bits`; the callers below fill in where the frames are.
 static int prepare_common(const csic_plan *pl, uintptr_t align_bits, int nframes, int32_t in_pitch, int32_t out_pitch, LaunchDesc *d)
 {
-    if (nframes <= 0 || nframes > 65535)
-        return set_error(CSIC_EINVAL_SIZE, "nframes per launch must be in 1..65535. Got %d", nframes);
-    if (pl->p.out_format == CSIC_FMT_PLANAR_BITS)
-        return set_error(CSIC_EINVAL_FORMAT, "CSIC_FMT_PLANAR_BITS plans go through csic_process_device / csic_process_batch_device / "
-                                              "csic_process_host and csic_pipeline_* only (no row pitches, frame graphs, file pools or csic_multi)");
-    if (pl->p.out_format == CSIC_FMT_PLANAR)
-        return set_error(CSIC_EINVAL_FORMAT, "planar plans go through csic_process_device / csic_process_batch_device / csic_process_host, "
-                                              "csic_pipeline_* and fused frame graphs only (no row pitches, per-frame-launch graphs, file pools or csic_multi)");
-    const Geometry &g = pl->g;
-
-    Family fam = pl->fam;
-    KernelFn fn = pl->fn;
-    int units = pl->units_per_row, kpl = pl->k_per_lane, dec_hold = pl->dec_hold;
-    // The vector kernels need 16-byte aligned frame bases; otherwise take the 4-byte-access kernels.
-    const int32_t ip = in_pitch > 0 ? in_pitch : g.W, op = out_pitch > 0 ? out_pitch : g.Wo;
-    if (ip < g.W || op < g.Wo)
-        return set_error(CSIC_EINVAL_SIZE, "row pitch (%d, %d px) smaller than the frame width (%d, %d px)", ip, op, g.W, g.Wo);
-    // (k_avg takes any 4-byte alignment: gfx950 executes its 16-byte accesses at any dword address, tools/ubench_unaligned.hip;
-    // the others keep the rule because their 4-byte fallbacks are as fast as a misaligned vector access would be)
-    const bool vec = (fam == FAM_F1X4 || fam == FAM_DEC2V1 || fam == FAM_DEC2V2 || fam == FAM_F1FLAT);
-    // The flat kernels address a pixel by a 32-bit BYTE offset from its frame's base (decflat_body): frames whose extents -- pitch
-    // included -- pass 2^30 pixels (4 GiB) take the row kernels, which keep 64-bit offsets.
-    // (and whose rows and pitch -- times the factor -- fit 24 bits, for the full-rate 24-bit multiplies of the row offsets)
-    const int64_t flat_limit = 1ll << 30;
-    const bool too_wide = (fam == FAM_DECFLAT || fam == FAM_F1FLAT) &&
-                          ((int64_t)(g.H - 1) * ip + g.W > flat_limit || (int64_t)(g.Ho - 1) * op + g.Wo > flat_limit ||
-                           g.H >= (1 << 24) || (int64_t)ip * g.f >= (1 << 24) || op >= (1 << 24));
-    const bool misaligned = vec && ((align_bits & 15u) || ((ip | op) & 3));
-    if (too_wide || misaligned) {
-        csic_plan tmp = *pl;
-        if (too_wide) tmp.no_flat = 1;
-        if (misaligned) tmp.no_vec = 1;
-        select(&tmp);
-        fam = tmp.fam; fn = tmp.fn; units = tmp.units_per_row; kpl = tmp.k_per_lane; dec_hold = tmp.dec_hold;
-    }
-
-    KArgs &a = d->args;
-    fill_base_args(g, ip, op, &a);
-
-    // Threads per block.  256 by default; k_dec takes two-wave blocks (128 threads) for a single frame of >= 64 MB whose rows
-    // tile into full waves at that width: measured on one-frame-per-launch streams (profiles/r02_probe_block_shapes.log)
-    // 8192x8192 f=2 32.48 -> 31.89 us, 16384x4096 32.56 -> 31.98, 8192x4096 17.44 -> 17.27, 6144x6144 19.38 -> 19.18,
-    // 8192x8192 f=4 15.52 -> 15.37; no gain below ~64 MB (8192x2048: 9.88 / 9.88), none for batched launches, and a loss
-    // where 128 lanes do not divide the row into full waves (7680x4320: 17.29 -> 17.93).  CSIC_TUNE_BLOCK_THREADS overrides.
-    const int avg_th = g.f > g.v ? g.f : g.v;
-    const int rows = (fam == FAM_F1X4) ? g.H : (fam == FAM_AVG) ? (g.H + avg_th - 1) / avg_th : g.Ho;
-    const int lanes_x = (units + kpl - 1) / kpl;
-    int tpb = 256;
-    const bool forced = pl->block_threads == 64 || pl->block_threads == 128 || pl->block_threads == 256;
-    const int hold = (fam == FAM_DEC && dec_hold > 0) ? dec_hold : 1;
-    if (forced) tpb = pl->block_threads;
-    else if (fam == FAM_DEC && nframes == 1 && units % kpl == 0 && lanes_x % 128 == 0 &&
-             4ll * ((int64_t)g.W * g.Ho + (int64_t)g.Wo * g.Ho) >= (64ll << 20))
-        tpb = 128;
-    else if (fam == FAM_DEC && units % kpl == 0 && lanes_x >= 16 && lanes_x <= 128) {
-        // Narrow rows (a row needs at most two waves): one-wave blocks, when the row tiles into them, beat blocks that stack
-        // several rows -- batched launches, profiles/r02_probe_block_batched.log: 512x512 f=2 69.1 -> 73.5 %, f=8 69.3 -> 73.2,
-        // 1024x1024 f=8 66.8 -> 78.3, 1920x1080 f=4 74.1 -> 75.6, f=8 71.0 -> 73.5; rows that do not tile (1000x1000 f=2: 125
-        // lanes) lose (70.8 -> 63.4) and keep the default, as do rows of fewer than 16 lanes (128x128 f=4/8: -1 %).
-        // With f >= 4, rows of fewer than 64 lanes fit one wave whatever their width (640x480 f=4, 40 lanes: 74.1 -> 77.7 %;
-        // 352x288 f=4 s>c: 62.0 -> 72.4 %); at f = 2 that loses (352x288, 44 lanes: 70.5 -> 59.3 %) and only powers of two qualify.
-        if (dec_one_wave_blocks(lanes_x, g.f, hold)) tpb = 64;
-    }
-    int bx = pow2_ceil(lanes_x);
-    if (bx > tpb) bx = tpb;
-    if (bx < 1) bx = 1;
-    if (fam == FAM_DEC && units % kpl == 0) {
-        // Rows that do not tile into power-of-two chunks (1920/3840-wide video: Wo = 960, 1920, ...) would put
-        // their last chunk on the bounds-checked path.  A block width that divides the row exactly keeps
-        // every block on the straight-line path (4K f=2: 70 % -> 80 % of HBM peak).  The width only has to
-        // be a multiple of the lane-hold distance so that a DPP hold group never straddles two rows.
-        bx = dec_block_x(lanes_x, tpb, hold);
-    }
-    if (fam == FAM_F1FLAT) {
-        const int T = forced ? tpb : 64;
-        const int64_t ngroups = (int64_t)(g.W / 4) * g.H, per_block = (int64_t)T * 4;
-        d->block = dim3((unsigned)T, 1, 1);
-        a.bdx = T; a.bdy = 1; a.row_step = 1;
-        d->grid = dim3((unsigned)((ngroups + per_block - 1) / per_block), 1, (unsigned)nframes);
-        d->fn = fn;
-        return CSIC_OK;
-    }
-    if (fam == FAM_DECFLAT) {
-        // lanes over the flat decimated stream: blocks of whole waves, K indices per lane spaced by the block size
-        // Two-wave blocks at f = 2 (1000x1000 77.8 -> 78.6 %, 1366x768 77.1 -> 79.0, 352x288 80.5 -> 81.8, 8192x8192 80.0 -> 82.6)
-        // and for long rows at f = 4 / 8 (3840x2160 f = 4: 74.7 -> 76.7 %, 8192x8192 f = 8: 75.9 -> 77.0); four-wave blocks for
-        // short rows at f = 4 / 8 (1000x1000 f = 4: 72.3 % against 69.4 / 68.4 % with 128 / 64 threads; 1920x1080 f = 8: 75.7
-        // against 75.2 / 71.1).                                                      profiles/r03_probe_flat.log
-        const int T = forced ? tpb : ((g.f == 2 || g.Wo >= 512) ? 128 : 256);
-        const int64_t per_block = (int64_t)T * kpl, n = (int64_t)g.Wo * g.Ho;
-        d->block = dim3((unsigned)T, 1, 1);
-        a.bdx = T; a.bdy = 1; a.row_step = 1;
-        d->grid = dim3((unsigned)((n + per_block - 1) / per_block), 1, (unsigned)nframes);
-        d->fn = fn;
-        return CSIC_OK;
-    }
-    if (fam == FAM_F1X4 && !forced) {
-        // One 16-byte load and store per lane: this kernel lives on the wave launch rate, so waves that exit at once (the idle
-        // part of a block's last chunk) or run partly filled cost in proportion.  1280-wide rows are 320 lanes: [256][64 + 192
-        // idle] runs at 61 %, 5 x 64 lanes (four rows to a block) at 78 % (profiles/r02_probe_block_batched_video.log).
-        if (lanes_x % 64 == 0) {
-            for (int w : {256, 192, 128, 64}) if (lanes_x % w == 0) { bx = w; break; }
-        } else if (lanes_x <= 256) {
-            bx = lanes_x;                                      // one partly filled wave per row instead of idle ones
-        }
-    }
-    if (fam == FAM_AVG && !forced && lanes_x % 64 == 0 && lanes_x > 256 && lanes_x <= 512 && lanes_x % 256 != 0) {
-        // the same for k_avg on rows of at most two blocks: 1280-wide f = 4 / 8 (320 lanes) 64 / 61 % -> 80 % with blocks of whole
-        // waves that tile the row (profiles/r02_probe_block_avg.log)
-        for (int w : {192, 128, 64}) if (lanes_x % w == 0) { bx = w; break; }
-    } else if (fam == FAM_AVG && !forced && lanes_x > tpb && lanes_x % tpb != 0 && lanes_x <= 8 * tpb) {
-        // rows of a few blocks that do not tile (1368-wide f = 4: 342 lanes = [256][86 + 170 idle]): equal blocks instead of a
-        // nearly empty last one
-        // (a multiple of 4 lanes: at f = 8 the two tiles of an output are neighbouring lanes of one quad -- the DPP swap -- so a
-        // block must not start on an odd tile; tools/fuzz_gpu.py found 1032x8 with 129-lane blocks)
-        const int m = (lanes_x + tpb - 1) / tpb;
-        bx = ((lanes_x + m - 1) / m + 3) & ~3;
-        if (bx > tpb) bx = tpb;
-    }
-    const int by = tpb / bx > 0 ? tpb / bx : 1;
-    d->block = dim3(bx, by, 1);
-    unsigned gx = (unsigned)((lanes_x + bx - 1) / bx);
-    unsigned gy_edge = 0;
-    if (fam == FAM_AVG) {
-        // k_avg's edge blocks: one lane per output pixel that no whole tile produces (see k_avg), in rows of blocks below the grid
-        const int W4f = g.W / 4, ntrf = g.H / avg_th;
-        const int Cw = g.f == 8 ? W4f / 2 : W4f * (4 / g.f), Rw = g.f == 8 ? ntrf : ntrf * (avg_th / g.f);
-        const int64_t nedge = (int64_t)(g.Wo - Cw) * g.Ho + (int64_t)(g.Ho - Rw) * Cw;
-        const int64_t nblocks = (nedge + (int64_t)bx * by - 1) / ((int64_t)bx * by);
-        gy_edge = (unsigned)((nblocks + gx - 1) / gx);
-    }
-    unsigned gy = (unsigned)((rows + by - 1) / by);
-    if (gy > 65535u - gy_edge - 1u) gy = 65535u - gy_edge - 1u;  // kernels stride over rows
-    if (gy_edge > 0 && nframes > 1 && (gx * (gy + gy_edge)) % 8u == 0) {
-        // XCD-aware: workgroups go to the 8 XCDs round-robin in dispatch order, so with a multiple of 8 blocks per frame the
-        // few (slower, latency-bound) edge blocks of EVERY frame of a batch land on the same XCDs.  1922x1082 at f = 2 -- 541 + 3
-        // block rows -- ran at 66 % where 1922x1080 and 1922x1084 ran at 74 % (profiles/r04_avg_1922_sweep.log).  One more
-        // (empty) block row per frame rotates them.
-        gy_edge += 1;
-    }
-    a.bdx = bx; a.bdy = by; a.row_step = (int32_t)gy * by;
-    a.edge_y0 = (fam == FAM_AVG) ? (int32_t)gy : 0x7FFFFFFF;
-    d->grid = dim3(gx, gy + gy_edge, (unsigned)nframes);
-    d->fn = fn;
+    LaunchPlan lp;
+    const int st = plan_launch(pl->p, pl->g, pl->tune, align_bits, nframes, in_pitch, out_pitch, &lp);
+    if (st != CSIC_OK) return st;
+    d->fn = resolve(lp.id);
+    d->grid = dim3(lp.grid.x, lp.grid.y, lp.grid.z);
+    d->block = dim3(lp.block.x, lp.block.y, lp.block.z);
+    d->args = lp.args;
     return CSIC_OK;
-}
-
-// The launch geometry k_avg would take for a planar AVG plan -- its packed twin's grid, block and KArgs (edge blocks included) --
-// for the planar tile kernel, which runs k_avg's body (csic_avg_tile.h).  *tile = false: the tile kernel does not apply (no whole
-// tile in the frame, CSIC_TUNE_FORCE_GENERIC / NO_VECTOR, variant 8 on a ragged shape).
-int planar_avg_geometry(const csic_plan *pl, int nframes, LaunchDesc *d, bool *tile)
-{
-    csic_plan tmp = *pl;
-    tmp.p.out_format = CSIC_FMT_YCBCR888X;
-    select(&tmp);
-    *tile = tmp.fam == FAM_AVG;
-    if (!*tile) return CSIC_OK;
-    return prepare_common(&tmp, 0, nframes, 0, 0, d);
 }
 
 int prepare_launch(const csic_plan *pl, const void *d_in, void *d_out, int nframes, int32_t in_pitch, int32_t out_pitch,
@@ -1189,13 +770,6 @@ int launch_on_stream(csic_plan *pl, const void *d_in, void *d_out, int nframes, 
 {
     return launch(pl, d_in, d_out, nframes, stream);
 }
-int plan_device(const csic_plan *pl) { return pl->device; }
-const csic_params &plan_params(const csic_plan *pl) { return pl->p; }
-const Geometry &plan_geometry(const csic_plan *pl) { return pl->g; }
-int plan_variant(const csic_plan *pl) { return pl->variant; }
-bool plan_nontemporal(const csic_plan *pl) { return !pl->no_nt; }
-int plan_block_threads(const csic_plan *pl) { return pl->block_threads; }
-bool plan_force_generic(const csic_plan *pl) { return pl->force_generic != 0; }
 int64_t plan_algorithmic_bytes(const csic_plan *pl)
 {
     int64_t b = 0;
@@ -1215,12 +789,6 @@ void plan_sizes(const csic_plan *pl, size_t *in_px, size_t *out_px)
         planar_bits_layout(pl->g, &pl->p, &L);
         *out_px = (size_t)(L.frame_bytes / 4);
     }
-}
-int32_t plan_width(const csic_plan *pl) { return pl->g.W; }
-void plan_out_dims(const csic_plan *pl, int32_t *wo, int32_t *ho)
-{
-    *wo = pl->g.Wo;
-    *ho = pl->g.Ho;
 }
 
 } // namespace csic
@@ -1281,14 +849,15 @@ const char *csic_plan_kernel_name(const csic_plan *plan) { return plan ? plan->n
 int csic_plan_tune(csic_plan *plan, int32_t knob, int32_t value)
 {
     if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
-    if (knob == CSIC_TUNE_VARIANT) plan->variant = value;
-    else if (knob == CSIC_TUNE_FORCE_GENERIC) plan->force_generic = value ? 1 : 0;
-    else if (knob == CSIC_TUNE_NONTEMPORAL) plan->no_nt = value ? 0 : 1;
-    else if (knob == CSIC_TUNE_NO_VECTOR) plan->no_vec = value ? 1 : 0;
+    Tune &t = plan->tune;
+    if (knob == CSIC_TUNE_VARIANT) t.variant = value;
+    else if (knob == CSIC_TUNE_FORCE_GENERIC) t.force_generic = value ? 1 : 0;
+    else if (knob == CSIC_TUNE_NONTEMPORAL) t.no_nt = value ? 0 : 1;
+    else if (knob == CSIC_TUNE_NO_VECTOR) t.no_vec = value ? 1 : 0;
     else if (knob == CSIC_TUNE_BLOCK_THREADS) {
         if (value != 0 && value != 64 && value != 128 && value != 256)
             return set_error(CSIC_EINVAL_SIZE, "block threads must be 0 (default), 64, 128 or 256. Got %d", value);
-        plan->block_threads = value;
+        t.block_threads = value;
     }
     else return set_error(CSIC_EINVAL_SIZE, "unknown tuning knob %d", knob);
     select(plan);

@@ -60,7 +60,7 @@ int csic_pipeline_create(csic_plan *plan, int32_t depth, csic_pipeline **out)
     csic_pipeline *pp = new (std::nothrow) csic_pipeline();
     if (!pp) return set_error(CSIC_ENOMEM, "out of host memory");
     pp->plan = plan;
-    pp->device = plan_device(plan);
+    pp->device = plan->device;
     plan_sizes(plan, &pp->in_px, &pp->out_px);
     DeviceGuard guard(pp->device);
     if (guard.status() != 0) {

@@ -549,71 +549,73 @@ static void fill_extra(const csic_planar_layout &L, PExtra *e)
     magic_div((uint32_t)L.module_width, &e->mWm, &e->kWm);
 }
 
+// The packed-output plan whose k_avg the planar AVG tile kernel follows (same body, csic_avg_tile.h; same selection and geometry).
+static csic_params packed_twin(csic_params p)
+{
+    p.out_format = CSIC_FMT_YCBCR888X;
+    return p;
+}
+
 // which forward kernel a plan takes: 0 = flat MODE 0, 1 = strided, 2 = flat MODE 2, 3 = avg_f1, 4 = avg_gen, 5 = flat MODE 1, 6 = avg_tile
 static int forward_kind(const csic_plan *pl, const csic_planar_layout &L)
 {
-    const csic_params &p = plan_params(pl);
-    const Geometry &g = plan_geometry(pl);
-    const bool general = plan_variant(pl) == 9;                 // CSIC_TUNE_VARIANT 9: the general kernels (A/B, tests)
+    const csic_params &p = pl->p;
+    const Geometry &g = pl->g;
+    const bool general = pl->tune.variant == 9;                 // CSIC_TUNE_VARIANT 9: the general kernels (A/B, tests)
     if (p.sampling == CSIC_SAMPLING_AVG) {
         const bool f1_whole = g.f == 1 && g.W % 4 == 0 && g.H % g.v == 0;
         // factor 1 on frames of whole tiles: the dedicated kernel (Y bytes straight from the loaded pixels, no per-pixel write-back of
         // the block averages) is 3 points ahead of k_avg's body there -- 8192x8192 4:2:0: 77.5 against 74.1 % of the roofline,
         // profiles/r04_planar_avg_tile_ab.log; CSIC_TUNE_VARIANT 12 takes the tile body all the same (A/B, tests)
-        if (!general && f1_whole && (plan_variant(pl) != 12 || !plan_nontemporal(pl))) return 3;
-        if (!general && plan_nontemporal(pl)) {                  // k_avg's body wherever k_avg itself would run
-            LaunchDesc d;
-            bool tile = false;
-            if (planar_avg_geometry(pl, 1, &d, &tile) == CSIC_OK && tile) return 6;
+        if (!general && f1_whole && (pl->tune.variant != 12 || pl->tune.no_nt)) return 3;
+        if (!general && !pl->tune.no_nt) {                  // k_avg's body wherever k_avg itself would run
+            if (select_kernel(packed_twin(pl->p), g, pl->tune, Constraints{false, false}).id.fam == FAM_AVG) return 6;
         }
         return (!general && f1_whole) ? 3 : 4;
     }
     if (general || L.module_width % 4 != 0) return 0;
     if (g.f == 1 && g.W % 4 == 0) return 2;
-    return plan_variant(pl) == 10 ? 5 : 1;
+    return pl->tune.variant == 10 ? 5 : 1;
 }
 
-template <int ROUND, bool NT>
-static PlanarFn pick_forward(int kind, int he, int ve)
+// the kernel of a forward kind (he, ve: the layout's holds; g: the plan's geometry, for the tile kernel)
+static PlanarFn forward_kernel(int kind, int rounding, bool nontemporal, int he, int ve, const Geometry &g)
 {
-    switch (kind) {
-    case 0: return k_planar_flat<ROUND, 0, NT>;
-    case 1: return k_planar_strided<ROUND, NT>;
-    case 5: return k_planar_flat<ROUND, 1, NT>;           // the first form of kind 1 (4 consecutive positions per lane): A/B, CSIC_TUNE_VARIANT 10
-    case 2: return k_planar_flat<ROUND, 2, NT>;
-    case 3:
-        if (ve == 1) return he == 1 ? k_planar_avg_f1<ROUND, 1, 1, NT> : he == 2 ? k_planar_avg_f1<ROUND, 2, 1, NT> : k_planar_avg_f1<ROUND, 4, 1, NT>;
-        return he == 1 ? k_planar_avg_f1<ROUND, 1, 2, NT> : he == 2 ? k_planar_avg_f1<ROUND, 2, 2, NT> : k_planar_avg_f1<ROUND, 4, 2, NT>;
-    default: return k_planar_avg_gen<ROUND>;
-    }
-}
-
-template <int ROUND, int F>
-static PlanarFn pick_avg_tile_f(int h, int v)
-{
-    if (v == 1) return h == 1 ? k_planar_avg_tile<ROUND, F, 1, 1> : h == 2 ? k_planar_avg_tile<ROUND, F, 2, 1> : k_planar_avg_tile<ROUND, F, 4, 1>;
-    return h == 1 ? k_planar_avg_tile<ROUND, F, 1, 2> : h == 2 ? k_planar_avg_tile<ROUND, F, 2, 2> : k_planar_avg_tile<ROUND, F, 4, 2>;
-}
-template <int ROUND>
-static PlanarFn pick_avg_tile(int f, int h, int v)
-{
-    return f == 1 ? pick_avg_tile_f<ROUND, 1>(h, v) : f == 2 ? pick_avg_tile_f<ROUND, 2>(h, v)
-         : f == 4 ? pick_avg_tile_f<ROUND, 4>(h, v) : pick_avg_tile_f<ROUND, 8>(h, v);
+    return with_const<R_FLOOR, R_TRUNC>(rounding, [&](auto round) {
+    return with_const<true, false>(nontemporal, [&](auto nt) -> PlanarFn {
+        constexpr int ROUND = CSIC_CONST(round);
+        constexpr bool NT = CSIC_CONST(nt);
+        const auto hv = [](int h, int v, auto pick) {
+            return with_const<1, 2, 4>(h, [&](auto hc) { return with_const<1, 2>(v, [&](auto vc) { return pick(hc, vc); }); });
+        };
+        switch (kind) {
+        case 0: return k_planar_flat<ROUND, 0, NT>;
+        case 1: return k_planar_strided<ROUND, NT>;
+        case 5: return k_planar_flat<ROUND, 1, NT>;           // the first form of kind 1 (4 consecutive positions per lane): A/B, CSIC_TUNE_VARIANT 10
+        case 2: return k_planar_flat<ROUND, 2, NT>;
+        case 3: return hv(he, ve, [](auto h, auto v) -> PlanarFn { return k_planar_avg_f1<ROUND, CSIC_CONST(h), CSIC_CONST(v), NT>; });
+        case 6:
+            return with_const<1, 2, 4, 8>(g.f, [&](auto f) {
+                return hv(g.h, g.v, [](auto h, auto v) -> PlanarFn { return k_planar_avg_tile<ROUND, CSIC_CONST(f), CSIC_CONST(h), CSIC_CONST(v)>; });
+            });
+        default: return k_planar_avg_gen<ROUND>;
+        }
+    }); });
 }
 
 void planar_kernel_name(const csic_plan *pl, char *buf, size_t len)
 {
     csic_planar_layout L;
-    planar_layout(plan_geometry(pl), &plan_params(pl), &L);
-    const char *rn = plan_params(pl).rounding == CSIC_ROUND_FLOOR_HW ? "floor" : "trunc";
-    const char *nt = plan_nontemporal(pl) ? "nt" : "cached";
+    planar_layout(pl->g, &pl->p, &L);
+    const char *rn = pl->p.rounding == CSIC_ROUND_FLOOR_HW ? "floor" : "trunc";
+    const char *nt = !pl->tune.no_nt ? "nt" : "cached";
     switch (forward_kind(pl, L)) {
     case 0: snprintf(buf, len, "k_planar_flat<%s,general,h%d,v%d,%s>", rn, L.hold_h, L.hold_v, nt); break;
-    case 1: snprintf(buf, len, "k_planar_strided<%s,f%d,h%d,v%d,%s>", rn, plan_geometry(pl).f, L.hold_h, L.hold_v, nt); break;
-    case 5: snprintf(buf, len, "k_planar_flat<%s,f%d,h%d,v%d,%s>", rn, plan_geometry(pl).f, L.hold_h, L.hold_v, nt); break;
+    case 1: snprintf(buf, len, "k_planar_strided<%s,f%d,h%d,v%d,%s>", rn, pl->g.f, L.hold_h, L.hold_v, nt); break;
+    case 5: snprintf(buf, len, "k_planar_flat<%s,f%d,h%d,v%d,%s>", rn, pl->g.f, L.hold_h, L.hold_v, nt); break;
     case 2: snprintf(buf, len, "k_planar_flat<%s,f1x4,h%d,v%d,%s>", rn, L.hold_h, L.hold_v, nt); break;
     case 3: snprintf(buf, len, "k_planar_avg_f1<%s,h%d,v%d,%s>", rn, L.hold_h, L.hold_v, nt); break;
-    case 6: snprintf(buf, len, "k_planar_avg_tile<%s,f%d,h%d,v%d,nt>", rn, plan_geometry(pl).f, plan_geometry(pl).h, plan_geometry(pl).v); break;
+    case 6: snprintf(buf, len, "k_planar_avg_tile<%s,f%d,h%d,v%d,nt>", rn, pl->g.f, pl->g.h, pl->g.v); break;
     default: snprintf(buf, len, "k_planar_avg_gen<%s,h%d,v%d>", rn, L.hold_h, L.hold_v); break;
     }
 }
@@ -628,34 +630,29 @@ static int launch_pk(PlanarFn fn, dim3 grid, dim3 block, KArgs a, PExtra e, hipS
 // kernel, grid, block and both argument blocks of one forward launch over nz <= 65535 frames; the frame pointers stay unset
 static int planar_resolve(const csic_plan *pl, int nz, PlanarLaunchDesc *d)
 {
-    const csic_params &p = plan_params(pl);
-    const Geometry &g = plan_geometry(pl);
+    const csic_params &p = pl->p;
+    const Geometry &g = pl->g;
     csic_planar_layout L;
     planar_layout(g, &p, &L);
     const int kind = forward_kind(pl, L);
-    const bool nt = plan_nontemporal(pl);
-    const bool floor_r = p.rounding == CSIC_ROUND_FLOOR_HW;
-    PlanarFn fn = floor_r ? (nt ? pick_forward<R_FLOOR, true>(kind, L.hold_h, L.hold_v) : pick_forward<R_FLOOR, false>(kind, L.hold_h, L.hold_v))
-                          : (nt ? pick_forward<R_TRUNC, true>(kind, L.hold_h, L.hold_v) : pick_forward<R_TRUNC, false>(kind, L.hold_h, L.hold_v));
-    if (kind == 6) fn = floor_r ? pick_avg_tile<R_FLOOR>(g.f, g.h, g.v) : pick_avg_tile<R_TRUNC>(g.f, g.h, g.v);
+    const PlanarFn fn = forward_kernel(kind, p.rounding, !pl->tune.no_nt, L.hold_h, L.hold_v, g);
     KArgs &a = d->args;
     PExtra &e = d->extra;
     fill_base_args(g, g.W, g.Wo, &a);
     fill_extra(L, &e);
     dim3 grid, block;
     if (kind == 6) {
-        // k_avg's own geometry (block shape, edge blocks, XCD rotation): prepare_common through the plan's packed twin
-        LaunchDesc ld;
-        bool tile = false;
-        const int st = planar_avg_geometry(pl, nz, &ld, &tile);
+        // k_avg's own geometry (block shape, edge blocks, XCD rotation): plan_launch on the plan's packed twin
+        LaunchPlan lp;
+        const int st = plan_launch(packed_twin(p), g, pl->tune, 0, nz, 0, 0, &lp);
         if (st != CSIC_OK) return st;
-        if (!tile) return set_error(CSIC_EHIP, "internal: the planar AVG tile kernel was selected for a plan k_avg does not take");
-        a = ld.args;
-        grid = ld.grid; block = ld.block;
+        if (lp.id.fam != FAM_AVG) return set_error(CSIC_EHIP, "internal: the planar AVG tile kernel was selected for a plan k_avg does not take");
+        a = lp.args;
+        grid = dim3(lp.grid.x, lp.grid.y, lp.grid.z); block = dim3(lp.block.x, lp.block.y, lp.block.z);
         e.T = 256;
     } else if (kind == 1) {
         // k_planar_strided: 4 positions per lane, T * 4 positions per block
-        const int bt = plan_block_threads(pl);
+        const int bt = pl->tune.block_threads;
         const int T = (bt == 64 || bt == 128 || bt == 256) ? bt : 256;
         e.T = T;
         block = dim3((unsigned)T, 1, 1);
@@ -663,7 +660,7 @@ static int planar_resolve(const csic_plan *pl, int nz, PlanarLaunchDesc *d)
         a.bdx = T; a.bdy = 1; a.row_step = 1;
     } else if (kind <= 2 || kind == 5) {
         const int64_t ngroups = (e.n + 3) / 4;
-        const int bt = plan_block_threads(pl);
+        const int bt = pl->tune.block_threads;
         // one-wave blocks for the 16-byte-load kernel: a wave's four loads then cover 4 KiB of consecutive pixels
         // (8192x8192 4:2:0: 71.7 % of the roofline with 256-thread blocks, 77.6 % with 64; profiles/r04_planar_bt.log)
         const int T = (bt == 64 || bt == 128 || bt == 256) ? bt : (kind == 2 ? 64 : 256);
@@ -737,18 +734,17 @@ extern "C" int csic_reconstruct_device(csic_plan *plan, const void *d_planar, vo
         return set_error(CSIC_EINVAL_FORMAT, "csic_reconstruct_device writes ARGB8888(0) or YCBCR888X(1). Got %d", out_format);
     if (((uintptr_t)d_planar & 255u) || ((uintptr_t)d_out & 15u))
         return set_error(CSIC_EINVAL_SIZE, "a planar frame buffer must be 256-byte aligned and the packed output 16-byte aligned");
-    const csic_params &p = plan_params(plan);
-    const Geometry &g = plan_geometry(plan);
+    const csic_params &p = plan->p;
+    const Geometry &g = plan->g;
     csic_planar_layout L;
     planar_layout(g, &p, &L);
-    CSIC_DEVICE_SCOPE(plan_device(plan));
-    const bool fast = L.module_width % 4 == 0 && plan_variant(plan) != 9;
-    const bool nt = plan_nontemporal(plan);
-    PlanarFn fn;
-    if (out_format == CSIC_FMT_ARGB8888)
-        fn = fast ? (nt ? k_recon<F_ARGB, true, true> : k_recon<F_ARGB, true, false>) : (nt ? k_recon<F_ARGB, false, true> : k_recon<F_ARGB, false, false>);
-    else
-        fn = fast ? (nt ? k_recon<F_YCC, true, true> : k_recon<F_YCC, true, false>) : (nt ? k_recon<F_YCC, false, true> : k_recon<F_YCC, false, false>);
+    CSIC_DEVICE_SCOPE(plan->device);
+    const bool fast = L.module_width % 4 == 0 && plan->tune.variant != 9;
+    const PlanarFn fn = with_const<F_ARGB, F_YCC>(out_format, [&](auto fmt) {
+        return with_const<true, false>(fast, [&](auto fa) {
+            return with_const<true, false>(!plan->tune.no_nt, [](auto nt) -> PlanarFn { return k_recon<CSIC_CONST(fmt), CSIC_CONST(fa), CSIC_CONST(nt)>; });
+        });
+    });
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     for (int f0 = 0; f0 < nframes; f0 += 65535) {
         const int nz = nframes - f0 < 65535 ? nframes - f0 : 65535;
@@ -758,7 +754,7 @@ extern "C" int csic_reconstruct_device(csic_plan *plan, const void *d_planar, vo
         fill_extra(L, &e);
         e.planar = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_planar)) + (int64_t)f0 * L.frame_bytes;
         e.packed = static_cast<uint32_t *>(d_out) + (int64_t)f0 * e.n;
-        const int bt = plan_block_threads(plan);
+        const int bt = plan->tune.block_threads;
         const int T = (bt == 64 || bt == 128 || bt == 256) ? bt : 64;
         e.T = T;
         const int64_t ngroups = (e.n + 3) / 4, per_block = (int64_t)T * RECON_K;

@@ -465,9 +465,9 @@ static void fill_bits_extra(const csic_planar_bits_layout &L, BExtra *e)
 // 0 = general, 1 = factor 1 fast, 2 = chroma before spatial, factor >= 2, fast
 static int bits_kind(const csic_plan *pl, const csic_planar_bits_layout &L)
 {
-    const csic_params &p = plan_params(pl);
-    const Geometry &g = plan_geometry(pl);
-    if (plan_variant(pl) == 9 || p.sampling != CSIC_SAMPLING_HOLD_DECIMATE) return 0;
+    const csic_params &p = pl->p;
+    const Geometry &g = pl->g;
+    if (pl->tune.variant == 9 || p.sampling != CSIC_SAMPLING_HOLD_DECIMATE) return 0;
     // the fast kernels assemble dwords of 32 samples inside one row: every row a whole number of 128 positions (hold_h <= 4)
     if (L.geometry.module_width % 128 != 0) return 0;
     if (g.f == 1) return 1;
@@ -477,14 +477,14 @@ static int bits_kind(const csic_plan *pl, const csic_planar_bits_layout &L)
 void planar_bits_kernel_name(const csic_plan *pl, char *buf, size_t len)
 {
     csic_planar_bits_layout L;
-    planar_bits_layout(plan_geometry(pl), &plan_params(pl), &L);
-    const char *rn = plan_params(pl).rounding == CSIC_ROUND_FLOOR_HW ? "floor" : "trunc";
-    const char *nt = plan_nontemporal(pl) ? "nt" : "cached";
+    planar_bits_layout(pl->g, &pl->p, &L);
+    const char *rn = pl->p.rounding == CSIC_ROUND_FLOOR_HW ? "floor" : "trunc";
+    const char *nt = !pl->tune.no_nt ? "nt" : "cached";
     switch (bits_kind(pl, L)) {
     case 1: snprintf(buf, len, "k_pbits_f1<%s,h%d,v%d,%s>", rn, L.geometry.hold_h, L.geometry.hold_v, nt); break;
-    case 2: snprintf(buf, len, "k_pbits_strided<%s,f%d,h%d,%s>", rn, plan_geometry(pl).f, L.geometry.hold_h, nt); break;
+    case 2: snprintf(buf, len, "k_pbits_strided<%s,f%d,h%d,%s>", rn, pl->g.f, L.geometry.hold_h, nt); break;
     default:
-        snprintf(buf, len, "k_pbits_gen<%s,%s,h%d,v%d>", rn, plan_params(pl).sampling == CSIC_SAMPLING_AVG ? "avg" : "hold",
+        snprintf(buf, len, "k_pbits_gen<%s,%s,h%d,v%d>", rn, pl->p.sampling == CSIC_SAMPLING_AVG ? "avg" : "hold",
                  L.geometry.hold_h, L.geometry.hold_v);
         break;
     }
@@ -500,22 +500,24 @@ static int launch_bits(BitsFn fn, dim3 grid, dim3 block, KArgs a, BExtra e, hipS
 int planar_bits_forward(const csic_plan *pl, const void *d_in, void *d_bits, int nframes, hipStream_t stream)
 {
     if (!d_in || !d_bits) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
-    const csic_params &p = plan_params(pl);
-    const Geometry &g = plan_geometry(pl);
+    const csic_params &p = pl->p;
+    const Geometry &g = pl->g;
     csic_planar_bits_layout L;
     planar_bits_layout(g, &p, &L);
     int kind = bits_kind(pl, L);
     if ((uintptr_t)d_bits & 255u) return set_error(CSIC_EINVAL_SIZE, "a bit-packed planar frame buffer must be 256-byte aligned");
     if ((uintptr_t)d_in & 3u) return set_error(CSIC_EINVAL_SIZE, "the input must be 4-byte aligned");
     if (kind == 1 && ((uintptr_t)d_in & 15u)) kind = 0;                 // the 16-byte loads need a 16-byte aligned input
-    const bool nt = plan_nontemporal(pl), floor_r = p.rounding == CSIC_ROUND_FLOOR_HW;
+    const bool nt = !pl->tune.no_nt;
     const bool avg = p.sampling == CSIC_SAMPLING_AVG;
-    BitsFn fn;
-    if (kind == 1)      fn = floor_r ? (nt ? k_pbits_f1<R_FLOOR, true> : k_pbits_f1<R_FLOOR, false>) : (nt ? k_pbits_f1<R_TRUNC, true> : k_pbits_f1<R_TRUNC, false>);
-    else if (kind == 2) fn = floor_r ? (nt ? k_pbits_strided<R_FLOOR, true> : k_pbits_strided<R_FLOOR, false>)
-                                     : (nt ? k_pbits_strided<R_TRUNC, true> : k_pbits_strided<R_TRUNC, false>);
-    else                fn = floor_r ? (avg ? k_pbits_gen<R_FLOOR, true> : k_pbits_gen<R_FLOOR, false>) : (avg ? k_pbits_gen<R_TRUNC, true> : k_pbits_gen<R_TRUNC, false>);
-    const int bt = plan_block_threads(pl);
+    const BitsFn fn = with_const<R_FLOOR, R_TRUNC>(p.rounding, [&](auto round) {
+        return with_const<true, false>(kind == 0 ? avg : nt, [&](auto b) -> BitsFn {      // b: k_pbits_gen's AVG, the others' NT
+            if (kind == 1) return k_pbits_f1<CSIC_CONST(round), CSIC_CONST(b)>;
+            if (kind == 2) return k_pbits_strided<CSIC_CONST(round), CSIC_CONST(b)>;
+            return k_pbits_gen<CSIC_CONST(round), CSIC_CONST(b)>;
+        });
+    });
+    const int bt = pl->tune.block_threads;
     for (int f0 = 0; f0 < nframes; f0 += 65535) {                       // grid z limit
         const int nz = nframes - f0 < 65535 ? nframes - f0 : 65535;
         KArgs a;
@@ -553,18 +555,17 @@ extern "C" int csic_reconstruct_bits_device(csic_plan *plan, const void *d_bits,
         return set_error(CSIC_EINVAL_FORMAT, "csic_reconstruct_bits_device writes ARGB8888(0) or YCBCR888X(1). Got %d", out_format);
     if (((uintptr_t)d_bits & 255u) || ((uintptr_t)d_out & 15u))
         return set_error(CSIC_EINVAL_SIZE, "a bit-packed planar frame buffer must be 256-byte aligned and the packed output 16-byte aligned");
-    const csic_params &p = plan_params(plan);
-    const Geometry &g = plan_geometry(plan);
+    const csic_params &p = plan->p;
+    const Geometry &g = plan->g;
     csic_planar_bits_layout L;
     planar_bits_layout(g, &p, &L);
-    CSIC_DEVICE_SCOPE(plan_device(plan));
-    const bool fast = L.geometry.module_width % 4 == 0 && plan_variant(plan) != 9;
-    const bool nt = plan_nontemporal(plan);
-    BitsFn fn;
-    if (out_format == CSIC_FMT_ARGB8888)
-        fn = fast ? (nt ? k_rbits<F_ARGB, true, true> : k_rbits<F_ARGB, true, false>) : (nt ? k_rbits<F_ARGB, false, true> : k_rbits<F_ARGB, false, false>);
-    else
-        fn = fast ? (nt ? k_rbits<F_YCC, true, true> : k_rbits<F_YCC, true, false>) : (nt ? k_rbits<F_YCC, false, true> : k_rbits<F_YCC, false, false>);
+    CSIC_DEVICE_SCOPE(plan->device);
+    const bool fast = L.geometry.module_width % 4 == 0 && plan->tune.variant != 9;
+    const BitsFn fn = with_const<F_ARGB, F_YCC>(out_format, [&](auto fmt) {
+        return with_const<true, false>(fast, [&](auto fa) {
+            return with_const<true, false>(!plan->tune.no_nt, [](auto nt) -> BitsFn { return k_rbits<CSIC_CONST(fmt), CSIC_CONST(fa), CSIC_CONST(nt)>; });
+        });
+    });
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     for (int f0 = 0; f0 < nframes; f0 += 65535) {
         const int nz = nframes - f0 < 65535 ? nframes - f0 : 65535;
@@ -574,7 +575,7 @@ extern "C" int csic_reconstruct_bits_device(csic_plan *plan, const void *d_bits,
         fill_bits_extra(L, &e);
         e.bits = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_bits)) + (int64_t)f0 * L.frame_bytes;
         e.packed = static_cast<uint32_t *>(d_out) + (int64_t)f0 * e.n;
-        const int bt = plan_block_threads(plan);
+        const int bt = plan->tune.block_threads;
         const int T = (bt == 64 || bt == 128 || bt == 256) ? bt : 64;
         e.T = T;
         const int64_t ngroups = (e.n + 3) / 4, per_block = (int64_t)T * RBITS_K;

@@ -1,0 +1,385 @@
+// csic_select.cpp -- kernel selection, kernel names and launch geometry of the packed kernels (see csic_select.h).  Host only.
+// Every rule here is backed by a measurement under profiles/; tests/data/launch_table.txt records what the rules give.
+#include "csic_select.h"
+
+#include <cstdio>
+#include <cstring>
+#include <initializer_list>
+
+namespace csic {
+
+// Block width k_dec would take for `lanes_x` lanes per row in blocks of `tpb` threads (launch_dec): a width that divides
+// the row exactly when there is one between tpb / 2 and tpb lanes, else the power of two that leaves a partial chunk.
+static int dec_block_x(int lanes_x, int tpb, int hold)
+{
+    int bx = 1;
+    while (bx < lanes_x) bx <<= 1;
+    if (bx > tpb) bx = tpb;
+    if (lanes_x <= tpb) {
+        if (lanes_x % hold == 0) bx = lanes_x;
+    } else {
+        for (int m = (lanes_x + tpb - 1) / tpb; m <= lanes_x / (tpb / 2); ++m)
+            if (lanes_x % m == 0 && (lanes_x / m) % hold == 0) { bx = lanes_x / m; break; }
+    }
+    return bx;
+}
+
+// One-wave blocks for narrow rows (a row needs at most two waves and tiles into them): see launch_dec.
+static bool dec_one_wave_blocks(int lanes_x, int f, int hold)
+{
+    if (lanes_x < 16 || lanes_x > 128) return false;
+    bool tiles = (f >= 4 && lanes_x < 64) || (lanes_x & (lanes_x - 1)) == 0;       // 16, 32, 64, 128; any < 64 for f >= 4
+    for (int w = 64; !tiles && w >= 48; --w) tiles = lanes_x % w == 0 && w % hold == 0;
+    return tiles && (lanes_x >= 64 || lanes_x % hold == 0);
+}
+
+// Should a chroma-before-spatial, hold-free plan cover the flat decimated stream (k_decflat) instead of rows (k_dec)?
+// Measured over 22 shapes (tools/probe_flat.py, profiles/r03_probe_flat.log; batched launches, k_dec | flat):
+//  * rows k_dec cannot cut into whole blocks -- not a whole number of K-pixel lanes, or lanes without a usable divisor: every
+//    block of k_dec runs its bounds-checked path (1000x1000 f = 4 / 8: 66 / 63 | 73 / 71 %; 1366x768 f = 2: 68 | 79 %);
+//  * rows of a few partly filled waves that straddle two rows at odd offsets (1000x1000 f = 2: 70 | 78 %, 720x480 f = 2:
+//    70 | 78 %, 352x288 f = 2: 70 | 81 %, 1280x720 f = 2: 78.5 | 81.5 %);
+//  * rows of whole waves: level or slightly ahead (8192x8192 f = 2 / 4 / 8: 79.8 | 82.6, 76.3 | 76.9, 74.3 | 77.0 %; 3840x2160
+//    f = 4: 75.3 | 76.7 %; 1080p / 4K f = 2: 79.6 | 80.4 %), and on the headline -- ONE 8192x8192 frame per launch -- four
+//    interleaved repeats give 32.09 | 31.85 us = 78.4 | 79.0 % (profiles/r03_headline_flat_ab.jsonl);
+//  * the one exception: shapes that take k_dec's one-wave blocks (512x512 f = 2: 77 | 65-73 %; 1024x1024 f = 8: 79 | 70-78 %;
+//    640x480 f = 4 and 1920x1080 f = 4 level) stay with k_dec;
+//  * the same picture with a lane hold and with spatial before chroma (profiles/r03_probe_flat_{csq411,scq444,scq422,scq420}.log;
+//    4:2:0 spatial before chroma: 1000x1000 f = 2: 60 | 78 %, 352x288 f = 2: 61 | 80 %, 8192x8192 f = 2 / 4 / 8: 79.4 | 82.6,
+//    77.0 | 77.8, 75.2 | 77.5 % -- once the held-pixel load of the odd chroma rows is skipped wave-uniformly; loaded
+//    unconditionally it cost 8192x8192 f = 8 twenty points).
+static bool dec_prefers_flat(const Geometry &g, int hold)
+{
+    if (g.Wo % DEC_K != 0) return true;
+    return !dec_one_wave_blocks(g.Wo / DEC_K, g.f, hold);
+}
+
+// Can the k_dec family handle this geometry?  Chroma before spatial: always, except that a hold across
+// lanes (4:1:1 with f = 2) needs whole quads in a row.  Spatial before chroma: only when chroma rows
+// coincide with groups of decimated rows (f | W) and the in-row hold is lane-aligned (h | Wo).
+static bool dec_fast_ok(const Geometry &g)
+{
+    const int hold = (g.s_first || g.f == 1) ? g.h : (g.h > g.f ? g.h / g.f : 1);
+    const int lanes_x = (g.Wo + DEC_K - 1) / DEC_K;
+    if (hold > 1 && lanes_x < 3) return false;            // block width < 4 lanes: quads would span rows
+    if (!g.s_first) return true;
+    return (g.W % g.f == 0) && (g.Wo % g.h == 0);
+}
+
+Selection select_kernel(const csic_params &p, const Geometry &g, const Tune &t, const Constraints &c)
+{
+    Selection s{};
+    KernelId &id = s.id;
+    if (p.out_format == CSIC_FMT_PLANAR || p.out_format == CSIC_FMT_PLANAR_BITS) {
+        id.fam = FAM_PLANAR;
+        return s;
+    }
+    id.round = p.rounding; id.fmt = p.out_format;
+    const bool nt = !t.no_nt, no_vec = t.no_vec || c.no_vec;
+    // A YCbCr input stream (single-stage driving, the reference's spec style) is a test-oriented path:
+    // it is served by the run-time-parameter kernels only.
+    const bool ycc_in = p.in_format == CSIC_FMT_YCBCR888X;
+    if (p.sampling == CSIC_SAMPLING_AVG) {
+        const int th = g.f > g.v ? g.f : g.v;
+        const int tw = g.f == 8 ? 8 : 4;
+        // any shape with at least one whole tile (pair of tiles at f = 8) and tile row: the frame's cut tiles take the definition's
+        // clamped form inside k_avg; variant 8 keeps the rule of rounds 1-3 (whole tiles only, everything else generic) for A/B
+        const bool whole = g.W % tw == 0 && g.H % th == 0;
+        if (!t.force_generic && !ycc_in && !no_vec && g.W >= tw && g.H >= th && (whole || t.variant != 8)) {
+            id.fam = FAM_AVG; id.f = g.f; id.h = g.h; id.v = g.v; id.nt = nt;
+            id.tiles = (g.f <= 2) ? 2 : 1;               // TILES of k_avg
+            s.units_per_row = (g.W + 3) / 4;
+            s.k_per_lane = id.tiles;
+        } else {
+            id.fam = FAM_AVG_GENERIC; id.infmt = p.in_format;
+            s.units_per_row = g.Wo;
+            s.k_per_lane = 1;
+        }
+        return s;
+    }
+    // f = 1: the 16-byte kernel wins whenever it applies (8192^2: 4:4:4 84.0 vs 88.0 us, 4:2:0 84.5 vs 85.9 us for
+    // the 4-byte k_dec<f1>, which serves the other widths / alignments; variant 4 forces k_dec<f1> for A/B).
+    const bool f1x4_ok = !t.force_generic && !ycc_in && !no_vec && g.f == 1 && g.W % 4 == 0;
+    if (f1x4_ok && t.variant != 11 && t.variant != 4 && !c.no_flat) {
+        // the flat mapping (round 4): ahead of k_f1x4 at every chroma mode and on 10 of 12 frame sizes -- 8192x8192 4:2:0 77.0 ->
+        // 79.3 %, 4:2:2 77.5 -> 80.3 %, 4:4:4 78.8 -> 79.8 %, 4:1:0 76.5 -> 79.5 %, 4096x4096 76.5 -> 79.1 %, 1000x1000 76.6 -> 78.9 %;
+        // level (-0.5) on 3840x2160 and 1920x1080 (profiles/r04_f1flat_ab.log).  CSIC_TUNE_VARIANT 11 keeps k_f1x4 for A/B.
+        id.fam = FAM_F1FLAT; id.h = g.h; id.v = g.v; id.nt = nt;
+        s.units_per_row = g.W / 4;
+        s.k_per_lane = 1;
+    } else if (f1x4_ok && (t.variant != 4 || !dec_fast_ok(g))) {
+        id.fam = FAM_F1X4; id.h = g.h; id.v = g.v; id.nt = nt;
+        s.units_per_row = g.W / 4;
+        s.k_per_lane = 1;
+    } else if (!t.force_generic && !ycc_in && dec_fast_ok(g)) {
+        // in-row chroma hold distance in decimated lanes; srows = chroma rows follow the decimated stream
+        // (with f = 1 the decimated stream IS the image and both order classes coincide: any width, any
+        // 4-byte-aligned pointer, 4-byte accesses)
+        const bool srows = g.s_first != 0 || g.f == 1;
+        const int hold = srows ? g.h : (g.h > g.f ? g.h / g.f : 1);
+        if (g.f == 2 && hold == 1 && !srows && !no_vec && g.W % 8 == 0 && (t.variant == 1 || t.variant == 2)) {
+            id.fam = t.variant == 1 ? FAM_DEC2V1 : FAM_DEC2V2; id.nt = nt;
+            s.units_per_row = g.Wo / (t.variant == 1 ? 2 : 4);
+            s.k_per_lane = 1;
+        } else {
+            // lanes over the flat decimated stream (variant 5 keeps k_dec, variant 6 takes k_decflat wherever it applies: A/B);
+            // a hold group must not straddle two rows: hold | Wo (spatial before chroma has that from dec_fast_ok)
+            const bool flat = g.f >= 2 && g.Wo % hold == 0 && t.variant != 5 && !c.no_flat && (t.variant == 6 || dec_prefers_flat(g, hold));
+            id.fam = flat ? FAM_DECFLAT : FAM_DEC;
+            id.f = g.f; id.h = hold; id.srows = srows && g.v == 2; id.nt = nt;
+            s.units_per_row = g.Wo;
+            s.k_per_lane = DEC_K;
+        }
+    } else if (!t.force_generic && !ycc_in && g.f >= 2 && t.variant != 7 && !c.no_flat) {
+        // what k_dec / k_decflat cannot take (spatial before chroma with f not dividing W or h not dividing Wo; tiny frames with a
+        // hold): the general flat kernel; variant 7 keeps the one-pixel-per-lane k_generic for A/B
+        id.fam = FAM_FLATGEN; id.nt = nt;
+        s.units_per_row = g.Wo;
+        s.k_per_lane = DEC_K;
+    } else {
+        id.fam = FAM_GENERIC; id.infmt = p.in_format;
+        s.units_per_row = g.Wo;
+        s.k_per_lane = 1;
+    }
+    return s;
+}
+
+void kernel_name(const KernelId &id, const Geometry &g, char *buf, size_t len)
+{
+    const char *rn = id.round == CSIC_ROUND_FLOOR_HW ? "floor" : "trunc";
+    const char *fn = id.fmt == CSIC_FMT_ARGB8888 ? "argb" : "ycc";
+    const char *ntn = id.nt ? "nt" : "cached";
+    const char *ycc_in = id.infmt == CSIC_FMT_YCBCR888X ? ",ycc-in" : "";
+    const bool srows = g.s_first != 0 || g.f == 1;       // the order class as select_kernel sees it
+    const char *order = srows ? (g.v == 2 ? "s>c,v2" : "s>c") : "c>s";
+    switch (id.fam) {
+    case FAM_AVG: snprintf(buf, len, "k_avg<%s,%s,f%d,h%d,v%d,%s>", rn, fn, id.f, id.h, id.v, ntn); break;
+    case FAM_AVG_GENERIC: snprintf(buf, len, "k_avg_generic<%s,%s%s>", rn, fn, ycc_in); break;
+    case FAM_F1FLAT: snprintf(buf, len, "k_f1flat<%s,%s,h%d,v%d,%s>", rn, fn, id.h, id.v, ntn); break;
+    case FAM_F1X4: snprintf(buf, len, "k_f1x4<%s,%s,h%d,v%d,%s>", rn, fn, id.h, id.v, ntn); break;
+    case FAM_DEC2V1:
+    case FAM_DEC2V2: snprintf(buf, len, "k_dec2v<%s,%s,var%d,%s>", rn, fn, id.fam == FAM_DEC2V1 ? 1 : 2, ntn); break;
+    case FAM_DECFLAT:
+        if (id.h == 1 && !srows) snprintf(buf, len, "k_decflat<%s,%s,f%d,K%d,%s>", rn, fn, id.f, DEC_K, ntn);
+        else snprintf(buf, len, "k_decflat<%s,%s,f%d,hold%d,%s,K%d,%s>", rn, fn, id.f, id.h, order, DEC_K, ntn);
+        break;
+    case FAM_DEC:
+        snprintf(buf, len, "k_dec<%s,%s,f%d,hold%d,%s,K%d,%s>", rn, fn, id.f, id.h, id.f == 1 ? (g.v == 2 ? "v2" : "v1") : order, DEC_K, ntn);
+        break;
+    case FAM_FLATGEN: snprintf(buf, len, "k_flatgen<%s,%s,K%d,%s>", rn, fn, DEC_K, ntn); break;
+    case FAM_GENERIC: snprintf(buf, len, "k_generic<%s,%s%s>", rn, fn, ycc_in); break;
+    case FAM_PLANAR: snprintf(buf, len, "%s", ""); break;   // csic_planar.hip / csic_planar_bits.hip name their kernels
+    }
+}
+
+static int pow2_ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
+
+void fill_base_args(const Geometry &g, int32_t ip, int32_t op, KArgs *pa)
+{
+    KArgs &a = *pa;
+    std::memset(&a, 0, sizeof a);
+    a.W = g.W; a.H = g.H; a.Wo = g.Wo; a.Ho = g.Ho;
+    a.last_sample_col = g.last_sample_col;
+    a.my = g.mask_y; a.mcb = g.mask_cb; a.mcr = g.mask_cr;
+    a.f = g.f; a.hmask = g.h - 1; a.vmask = g.v - 1; a.s_first = g.s_first;
+    a.ip = ip; a.op = op;
+    a.in_frame_px = (int64_t)ip * g.H;
+    a.out_frame_px = (int64_t)op * g.Ho;
+    a.sc_shift = (g.f == 8) ? 3 : (g.f == 4) ? 2 : (g.f == 2) ? 1 : 0;
+    a.bc_row_off = g.last_sample_col / g.Wo;             // only meaningful (and only used) when f | W
+    a.bc_col_in = (g.last_sample_col % g.Wo) * g.f;
+    magic_div((uint32_t)g.W, &a.mW, &a.kW);
+    magic_div((uint32_t)g.Wo, &a.mWo, &a.kWo);
+}
+
+// ---- launch geometry, one function per mapping -------------------------------------------------------------------------
+static int forced_threads(const Tune &t)
+{
+    return (t.block_threads == 64 || t.block_threads == 128 || t.block_threads == 256) ? t.block_threads : 0;
+}
+
+// Lanes over a flat stream of `n` units, K per lane spaced by the block: one-dimensional blocks of T threads.
+static void launch_flat(int64_t n, int K, int T, int nframes, LaunchPlan *lp)
+{
+    const int64_t per_block = (int64_t)T * K;
+    lp->block = Dim3{(uint32_t)T, 1, 1};
+    lp->args.bdx = T; lp->args.bdy = 1; lp->args.row_step = 1;
+    lp->grid = Dim3{(uint32_t)((n + per_block - 1) / per_block), 1, (uint32_t)nframes};
+}
+
+// Blocks of bx lanes by tpb / bx rows over `lanes_x` lanes and `rows` rows; the kernels stride over rows past the grid y limit.
+// nedge >= 0: k_avg, whose edge blocks -- one lane per output pixel that no whole tile produces (see k_avg) -- lie in rows of
+// blocks below the grid.
+static void launch_rows(int lanes_x, int rows, int bx, int tpb, int64_t nedge, int nframes, LaunchPlan *lp)
+{
+    const int by = tpb / bx > 0 ? tpb / bx : 1;
+    const uint32_t gx = (uint32_t)((lanes_x + bx - 1) / bx);
+    uint32_t gy_edge = 0;
+    if (nedge >= 0) {
+        const int64_t nblocks = (nedge + (int64_t)bx * by - 1) / ((int64_t)bx * by);
+        gy_edge = (uint32_t)((nblocks + gx - 1) / gx);
+    }
+    uint32_t gy = (uint32_t)((rows + by - 1) / by);
+    if (gy > 65535u - gy_edge - 1u) gy = 65535u - gy_edge - 1u;  // kernels stride over rows
+    if (gy_edge > 0 && nframes > 1 && (gx * (gy + gy_edge)) % 8u == 0) {
+        // XCD-aware: workgroups go to the 8 XCDs round-robin in dispatch order, so with a multiple of 8 blocks per frame the
+        // few (slower, latency-bound) edge blocks of EVERY frame of a batch land on the same XCDs.  1922x1082 at f = 2 -- 541 + 3
+        // block rows -- ran at 66 % where 1922x1080 and 1922x1084 ran at 74 % (profiles/r04_avg_1922_sweep.log).  One more
+        // (empty) block row per frame rotates them.
+        gy_edge += 1;
+    }
+    lp->block = Dim3{(uint32_t)bx, (uint32_t)by, 1};
+    lp->args.bdx = bx; lp->args.bdy = by; lp->args.row_step = (int32_t)gy * by;
+    lp->args.edge_y0 = nedge >= 0 ? (int32_t)gy : 0x7FFFFFFF;
+    lp->grid = Dim3{gx, gy + gy_edge, (uint32_t)nframes};
+}
+
+static int pow2_block_x(int lanes_x, int tpb)
+{
+    int bx = pow2_ceil(lanes_x);
+    if (bx > tpb) bx = tpb;
+    return bx < 1 ? 1 : bx;
+}
+
+static void launch_f1flat(const Geometry &g, const Tune &t, int nframes, LaunchPlan *lp)
+{
+    const int forced = forced_threads(t);
+    launch_flat((int64_t)(g.W / 4) * g.H, 4, forced ? forced : 64, nframes, lp);
+}
+
+static void launch_decflat(const Geometry &g, const Tune &t, int nframes, LaunchPlan *lp)
+{
+    // lanes over the flat decimated stream: blocks of whole waves, K indices per lane spaced by the block size
+    // Two-wave blocks at f = 2 (1000x1000 77.8 -> 78.6 %, 1366x768 77.1 -> 79.0, 352x288 80.5 -> 81.8, 8192x8192 80.0 -> 82.6)
+    // and for long rows at f = 4 / 8 (3840x2160 f = 4: 74.7 -> 76.7 %, 8192x8192 f = 8: 75.9 -> 77.0); four-wave blocks for
+    // short rows at f = 4 / 8 (1000x1000 f = 4: 72.3 % against 69.4 / 68.4 % with 128 / 64 threads; 1920x1080 f = 8: 75.7
+    // against 75.2 / 71.1).                                                      profiles/r03_probe_flat.log
+    const int forced = forced_threads(t);
+    launch_flat((int64_t)g.Wo * g.Ho, DEC_K, forced ? forced : ((g.f == 2 || g.Wo >= 512) ? 128 : 256), nframes, lp);
+}
+
+static void launch_dec(const Geometry &g, const Tune &t, int hold, int nframes, LaunchPlan *lp)
+{
+    // Threads per block.  256 by default; k_dec takes two-wave blocks (128 threads) for a single frame of >= 64 MB whose rows
+    // tile into full waves at that width: measured on one-frame-per-launch streams (profiles/r02_probe_block_shapes.log)
+    // 8192x8192 f=2 32.48 -> 31.89 us, 16384x4096 32.56 -> 31.98, 8192x4096 17.44 -> 17.27, 6144x6144 19.38 -> 19.18,
+    // 8192x8192 f=4 15.52 -> 15.37; no gain below ~64 MB (8192x2048: 9.88 / 9.88), none for batched launches, and a loss
+    // where 128 lanes do not divide the row into full waves (7680x4320: 17.29 -> 17.93).  CSIC_TUNE_BLOCK_THREADS overrides.
+    const int lanes_x = (g.Wo + DEC_K - 1) / DEC_K;
+    const bool whole = g.Wo % DEC_K == 0;
+    int tpb = 256;
+    if (forced_threads(t)) tpb = forced_threads(t);
+    else if (nframes == 1 && whole && lanes_x % 128 == 0 && 4ll * ((int64_t)g.W * g.Ho + (int64_t)g.Wo * g.Ho) >= (64ll << 20))
+        tpb = 128;
+    else if (whole && lanes_x >= 16 && lanes_x <= 128) {
+        // Narrow rows (a row needs at most two waves): one-wave blocks, when the row tiles into them, beat blocks that stack
+        // several rows -- batched launches, profiles/r02_probe_block_batched.log: 512x512 f=2 69.1 -> 73.5 %, f=8 69.3 -> 73.2,
+        // 1024x1024 f=8 66.8 -> 78.3, 1920x1080 f=4 74.1 -> 75.6, f=8 71.0 -> 73.5; rows that do not tile (1000x1000 f=2: 125
+        // lanes) lose (70.8 -> 63.4) and keep the default, as do rows of fewer than 16 lanes (128x128 f=4/8: -1 %).
+        // With f >= 4, rows of fewer than 64 lanes fit one wave whatever their width (640x480 f=4, 40 lanes: 74.1 -> 77.7 %;
+        // 352x288 f=4 s>c: 62.0 -> 72.4 %); at f = 2 that loses (352x288, 44 lanes: 70.5 -> 59.3 %) and only powers of two qualify.
+        if (dec_one_wave_blocks(lanes_x, g.f, hold)) tpb = 64;
+    }
+    // Rows that do not tile into power-of-two chunks (1920/3840-wide video: Wo = 960, 1920, ...) would put
+    // their last chunk on the bounds-checked path.  A block width that divides the row exactly keeps
+    // every block on the straight-line path (4K f=2: 70 % -> 80 % of HBM peak).  The width only has to
+    // be a multiple of the lane-hold distance so that a DPP hold group never straddles two rows.
+    const int bx = whole ? dec_block_x(lanes_x, tpb, hold) : pow2_block_x(lanes_x, tpb);
+    launch_rows(lanes_x, g.Ho, bx, tpb, -1, nframes, lp);
+}
+
+static void launch_f1x4(const Geometry &g, const Tune &t, int nframes, LaunchPlan *lp)
+{
+    const int lanes_x = g.W / 4, forced = forced_threads(t), tpb = forced ? forced : 256;
+    int bx = pow2_block_x(lanes_x, tpb);
+    if (!forced) {
+        // One 16-byte load and store per lane: this kernel lives on the wave launch rate, so waves that exit at once (the idle
+        // part of a block's last chunk) or run partly filled cost in proportion.  1280-wide rows are 320 lanes: [256][64 + 192
+        // idle] runs at 61 %, 5 x 64 lanes (four rows to a block) at 78 % (profiles/r02_probe_block_batched_video.log).
+        if (lanes_x % 64 == 0) {
+            for (int w : {256, 192, 128, 64}) if (lanes_x % w == 0) { bx = w; break; }
+        } else if (lanes_x <= 256) {
+            bx = lanes_x;                                      // one partly filled wave per row instead of idle ones
+        }
+    }
+    launch_rows(lanes_x, g.H, bx, tpb, -1, nframes, lp);
+}
+
+static void launch_avg(const Geometry &g, const Tune &t, int tiles, int nframes, LaunchPlan *lp)
+{
+    const int units = (g.W + 3) / 4, lanes_x = (units + tiles - 1) / tiles, avg_th = g.f > g.v ? g.f : g.v;
+    const int forced = forced_threads(t), tpb = forced ? forced : 256;
+    int bx = pow2_block_x(lanes_x, tpb);
+    if (!forced && lanes_x % 64 == 0 && lanes_x > 256 && lanes_x <= 512 && lanes_x % 256 != 0) {
+        // the same as k_f1x4 on rows of at most two blocks: 1280-wide f = 4 / 8 (320 lanes) 64 / 61 % -> 80 % with blocks of whole
+        // waves that tile the row (profiles/r02_probe_block_avg.log)
+        for (int w : {192, 128, 64}) if (lanes_x % w == 0) { bx = w; break; }
+    } else if (!forced && lanes_x > tpb && lanes_x % tpb != 0 && lanes_x <= 8 * tpb) {
+        // rows of a few blocks that do not tile (1368-wide f = 4: 342 lanes = [256][86 + 170 idle]): equal blocks instead of a
+        // nearly empty last one
+        // (a multiple of 4 lanes: at f = 8 the two tiles of an output are neighbouring lanes of one quad -- the DPP swap -- so a
+        // block must not start on an odd tile; tools/fuzz_gpu.py found 1032x8 with 129-lane blocks)
+        const int m = (lanes_x + tpb - 1) / tpb;
+        bx = ((lanes_x + m - 1) / m + 3) & ~3;
+        if (bx > tpb) bx = tpb;
+    }
+    // the output pixels that no whole tile produces
+    const int W4f = g.W / 4, ntrf = g.H / avg_th;
+    const int Cw = g.f == 8 ? W4f / 2 : W4f * (4 / g.f), Rw = g.f == 8 ? ntrf : ntrf * (avg_th / g.f);
+    const int64_t nedge = (int64_t)(g.Wo - Cw) * g.Ho + (int64_t)(g.Ho - Rw) * Cw;
+    launch_rows(lanes_x, (g.H + avg_th - 1) / avg_th, bx, tpb, nedge, nframes, lp);
+}
+
+// k_dec2v, k_generic, k_avg_generic: one unit per lane along x, rows of the output along y
+static void launch_per_lane(const Geometry &g, const Tune &t, int units, int nframes, LaunchPlan *lp)
+{
+    const int tpb = forced_threads(t) ? forced_threads(t) : 256;
+    launch_rows(units, g.Ho, pow2_block_x(units, tpb), tpb, -1, nframes, lp);
+}
+
+int plan_launch(const csic_params &p, const Geometry &g, const Tune &t, uintptr_t align_bits, int nframes, int32_t in_pitch,
+                int32_t out_pitch, LaunchPlan *lp)
+{
+    if (nframes <= 0 || nframes > 65535)
+        return set_error(CSIC_EINVAL_SIZE, "nframes per launch must be in 1..65535. Got %d", nframes);
+    if (p.out_format == CSIC_FMT_PLANAR_BITS)
+        return set_error(CSIC_EINVAL_FORMAT, "CSIC_FMT_PLANAR_BITS plans go through csic_process_device / csic_process_batch_device / "
+                                              "csic_process_host and csic_pipeline_* only (no row pitches, frame graphs, file pools or csic_multi)");
+    if (p.out_format == CSIC_FMT_PLANAR)
+        return set_error(CSIC_EINVAL_FORMAT, "planar plans go through csic_process_device / csic_process_batch_device / csic_process_host, "
+                                              "csic_pipeline_* and fused frame graphs only (no row pitches, per-frame-launch graphs, file pools or csic_multi)");
+    const int32_t ip = in_pitch > 0 ? in_pitch : g.W, op = out_pitch > 0 ? out_pitch : g.Wo;
+    if (ip < g.W || op < g.Wo)
+        return set_error(CSIC_EINVAL_SIZE, "row pitch (%d, %d px) smaller than the frame width (%d, %d px)", ip, op, g.W, g.Wo);
+
+    Selection s = select_kernel(p, g, t, Constraints{false, false});
+    const Family fam = s.id.fam;
+    // The vector kernels need 16-byte aligned frame bases; otherwise take the 4-byte-access kernels.
+    // (k_avg takes any 4-byte alignment: gfx950 executes its 16-byte accesses at any dword address, tools/ubench_unaligned.hip;
+    // the others keep the rule because their 4-byte fallbacks are as fast as a misaligned vector access would be)
+    const bool vec = (fam == FAM_F1X4 || fam == FAM_DEC2V1 || fam == FAM_DEC2V2 || fam == FAM_F1FLAT);
+    // The flat kernels address a pixel by a 32-bit BYTE offset from its frame's base (decflat_body): frames whose extents -- pitch
+    // included -- pass 2^30 pixels (4 GiB) take the row kernels, which keep 64-bit offsets.
+    // (and whose rows and pitch -- times the factor -- fit 24 bits, for the full-rate 24-bit multiplies of the row offsets)
+    const int64_t flat_limit = 1ll << 30;
+    const bool too_wide = (fam == FAM_DECFLAT || fam == FAM_FLATGEN || fam == FAM_F1FLAT) &&
+                          ((int64_t)(g.H - 1) * ip + g.W > flat_limit || (int64_t)(g.Ho - 1) * op + g.Wo > flat_limit ||
+                           g.H >= (1 << 24) || (int64_t)ip * g.f >= (1 << 24) || op >= (1 << 24));
+    const bool misaligned = vec && ((align_bits & 15u) || ((ip | op) & 3));
+    if (too_wide || misaligned) s = select_kernel(p, g, t, Constraints{too_wide, misaligned});
+
+    lp->id = s.id;
+    fill_base_args(g, ip, op, &lp->args);
+    switch (s.id.fam) {
+    case FAM_F1FLAT: launch_f1flat(g, t, nframes, lp); break;
+    case FAM_DECFLAT:
+    case FAM_FLATGEN: launch_decflat(g, t, nframes, lp); break;
+    case FAM_DEC: launch_dec(g, t, s.id.h, nframes, lp); break;
+    case FAM_F1X4: launch_f1x4(g, t, nframes, lp); break;
+    case FAM_AVG: launch_avg(g, t, s.id.tiles, nframes, lp); break;
+    default: launch_per_lane(g, t, s.units_per_row, nframes, lp); break;
+    }
+    return CSIC_OK;
+}
+
+} // namespace csic

@@ -1,0 +1,89 @@
+// csic_select.h -- the host-only planner: which packed kernel a parameter set takes (select_kernel), what it is called
+// (kernel_name) and with what grid, block and kernel arguments it is launched (plan_launch).  Pure integer arithmetic on
+// csic_params, Geometry and the tuning knobs: no HIP header, no device; csic_kernels.hip turns a KernelId into a function
+// pointer (resolve) and tests/cpp/launch_table.cpp prints the whole table on a machine without a GPU.
+#pragma once
+#include "csic_internal.h"
+
+namespace csic {
+
+// ---- kernel arguments (kernarg segment -> SGPRs) ----------------------------------------------------
+struct KArgs {
+    const uint32_t *in;
+    uint32_t *out;
+    int32_t W, H, Wo, Ho;
+    int32_t last_sample_col;
+    uint32_t my, mcb, mcr;
+    int32_t f, hmask, vmask, s_first;   // hmask = h-1, vmask = v-1 (generic kernel; vmask also k_dec SROWS)
+    int32_t sc_shift, bc_row_off, bc_col_in;   // k_dec SROWS: log2 f; held-sample decimated row offset / input column
+    int32_t edge_y0;                    // k_avg: first row of edge blocks along grid y (in what used to be padding: the size stays 152)
+    int64_t in_frame_px, out_frame_px;  // batch strides (grid z = frame)
+    int32_t bdx, bdy, row_step;         // block width/height and gridDim.y * bdy, passed explicitly (see pin_args)
+    int32_t ip, op;                     // row pitch of the input / output frame in pixels (>= W / Wo; == when packed)
+    uint32_t mW, mWo, kW, kWo;          // k_generic: exact n / W and n / Wo for n < 2^31 as (n * m) >> k (see magic_div)
+    const uint32_t *const *in_tab;      // frame-table mode (CSIC_FRAME_GRAPH_FUSED): frame z reads in_tab[z] and writes out_tab[z];
+    uint32_t *const *out_tab;           //   null = frames lie back to back behind `in` / `out`
+};
+
+// The direct-dispatch engine copies sizeof(KArgs) bytes into raw kernarg memory (csic_graph.hip): every translation unit must
+// see this one layout -- there is exactly one copy of this header (tests/test_bench_contract.py checks that, too).
+static_assert(sizeof(KArgs) == 152 && alignof(KArgs) == 8, "KArgs layout changed: check the kernarg blocks built in csic_graph.hip");
+
+// The tuning knobs of csic_plan_tune.
+struct Tune {
+    int variant;         // CSIC_TUNE_VARIANT
+    int force_generic;   // CSIC_TUNE_FORCE_GENERIC
+    int no_vec;          // CSIC_TUNE_NO_VECTOR: 1 = no 16-byte vector kernels
+    int no_nt;           // 1 = plain (cached) loads/stores instead of non-temporal ones
+    int block_threads;   // 0 = default (256); 64 / 128 / 256 = that many (CSIC_TUNE_BLOCK_THREADS)
+};
+
+// What only a launch knows (its pointers, pitches and extents) and selection has to respect.
+struct Constraints {
+    bool no_flat;        // the frame's extents pass the 32-bit byte offsets / 24-bit row multiplies of the flat kernels
+    bool no_vec;         // pointers or pitches that are only 4-byte aligned: no 16-byte vector kernels
+};
+
+// FAM_PLANAR: out_format CSIC_FMT_PLANAR / CSIC_FMT_PLANAR_BITS -- no packed kernel; csic_planar.hip / csic_planar_bits.hip pick theirs.
+enum Family { FAM_F1X4, FAM_DEC, FAM_DEC2V1, FAM_DEC2V2, FAM_GENERIC, FAM_AVG, FAM_AVG_GENERIC, FAM_DECFLAT, FAM_FLATGEN, FAM_F1FLAT, FAM_PLANAR };
+
+constexpr int DEC_K = 4;     // output pixels per lane of k_dec / k_decflat / k_flatgen
+
+// One instantiation of a packed kernel: the family and exactly the values that become its template arguments (the others are 0).
+struct KernelId {
+    Family fam;
+    int round, fmt;      // csic_params.rounding / out_format: every family
+    int infmt;           // csic_params.in_format: k_generic, k_avg_generic
+    int f;               // k_dec, k_decflat, k_avg
+    int h;               // k_f1x4, k_f1flat, k_avg: chroma hold h; k_dec, k_decflat: lane-hold distance (1, 2 or 4)
+    int v;               // k_f1x4, k_f1flat, k_avg
+    bool srows;          // k_dec, k_decflat: chroma rows follow the decimated stream and v = 2
+    bool nt;             // non-temporal accesses (every family but the two generic ones)
+    int tiles;           // k_avg: tiles per lane
+};
+
+struct Selection {
+    KernelId id;
+    int units_per_row;   // units along x
+    int k_per_lane;      // x units consumed per lane
+};
+
+struct Dim3 { uint32_t x, y, z; };
+
+// One fully planned launch: csic_kernels.hip adds the function pointer and where the frames are.
+struct LaunchPlan {
+    KernelId id;
+    Dim3 grid, block;
+    KArgs args;
+};
+
+Selection select_kernel(const csic_params &p, const Geometry &g, const Tune &t, const Constraints &c);
+void kernel_name(const KernelId &id, const Geometry &g, char *buf, size_t len);
+// The geometry half of the kernel arguments (what does not depend on the kernel family or the launch shape).
+void fill_base_args(const Geometry &g, int32_t ip, int32_t op, KArgs *a);
+// Kernel, grid, block and arguments for `nframes` frames (<= 65535, the grid z limit) whose base pointers OR to `align_bits`,
+// rows `in_pitch` / `out_pitch` pixels apart (0 = packed); the pointers in lp->args stay null.  Returns a csic status.
+int plan_launch(const csic_params &p, const Geometry &g, const Tune &t, uintptr_t align_bits, int nframes, int32_t in_pitch,
+                int32_t out_pitch, LaunchPlan *lp);
+
+} // namespace csic

@@ -488,7 +488,7 @@ def test_flat_kernels_at_the_4gib_boundary(csic, oracle):
 @pytest.mark.parametrize("W,H", [(8, (1 << 24) + 64), ((1 << 24) + 64, 8), (1 << 23, 16), ((1 << 22) + 4, 16)])
 def test_flat_kernels_24_bit_rows_and_pitches(csic, oracle, W, H):
     """The flat kernels form row * pitch with 24-bit multiplies: frames with 2^24 rows or more, or whose pitch times the factor
-    reaches 2^24 pixels, take the row kernels at launch (prepare_common).  Very tall and very wide frames on both sides of that
+    reaches 2^24 pixels, take the row kernels at launch (plan_launch, csrc/csic_select.cpp).  Very tall and very wide frames on both sides of that
     rule, whole frames against the oracle (67-134 Mpixel each)."""
     import torch
     rng = np.random.default_rng(W ^ H)
@@ -743,7 +743,7 @@ def test_video_widths_tile_exactly(csic, oracle, W, H):
     (3840, 16, 1, (CSQ,)),               # k_f1x4, 960 lanes = 5 x 192
 ])
 def test_block_geometry_rules(csic, oracle, W, H, f, orders):
-    """The shapes that trigger each block-geometry rule of prepare_common (one-wave blocks for narrow rows, whole-wave
+    """The shapes that trigger each block-geometry rule of plan_launch (csrc/csic_select.cpp) (one-wave blocks for narrow rows, whole-wave
     blocks for k_f1x4), single frames and batches of three, every chroma mode: bit-exact against the oracle."""
     import torch
     n = 3

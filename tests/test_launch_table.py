@@ -1,0 +1,58 @@
+"""The launch table of the packed kernels, on the CPU: tests/cpp/launch_table.cpp (g++, host only) prints, for a structured sweep
+of parameter sets, knobs, batch sizes, alignments and pitches, which kernel csrc/csic_select.cpp picks and with what grid, block
+and KArgs; the output must equal tests/data/launch_table.txt.  A change of a selection or geometry rule therefore shows, in the
+diff of that file, exactly which shapes moved to which kernel and geometry:
+
+    python tests/test_launch_table.py --write      # regenerate the fixture after an intended change
+
+The program also asserts, for every case, what must hold whatever the rules are (see check_invariants there)."""
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "chroma-subsampling-image-compressor_amd", "csrc")
+SRC = os.path.join(ROOT, "tests", "cpp", "launch_table.cpp")
+FIXTURE = os.path.join(ROOT, "tests", "data", "launch_table.txt")
+
+
+def build(exe, extra=()):
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", *extra, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, SRC,
+                           os.path.join(CSRC, "csic_select.cpp"), os.path.join(CSRC, "csic_host.cpp"), "-o", exe])
+    return exe
+
+
+def table(exe):
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    return r.stdout
+
+
+def test_launch_table_matches_the_committed_fixture(tmp_path):
+    got = table(build(str(tmp_path / "launch_table"))).splitlines()
+    want = open(FIXTURE, encoding="utf-8").read().splitlines()
+    moved = [f"- {w}\n+ {g}" for w, g in zip(want, got) if w != g]
+    assert len(got) == len(want) and not moved, (
+        f"{len(moved)} of {len(want)} launches changed ({len(got)} printed); first ones:\n" + "\n".join(moved[:10]) +
+        "\nif intended: python tests/test_launch_table.py --write, and review the diff of tests/data/launch_table.txt")
+    assert os.path.getsize(FIXTURE) < 348 * 1024          # stays below the largest committed file
+    # the sweep reaches every packed family and both sides of the launch-time fall-backs
+    text = "\n".join(got)
+    for name in ("k_f1flat<", "k_f1x4<", "k_dec<", "k_decflat<", "k_dec2v<", "k_flatgen<", "k_generic<", "k_avg<", "k_avg_generic<"):
+        assert f" {name}" in text, name
+
+
+def test_whole_cross_product_keeps_the_invariants(tmp_path):
+    r = subprocess.run([build(str(tmp_path / "launch_table")), "--check"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and " 0 with a broken invariant" in r.stderr, r.stderr[-4000:]
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] != ["--write"]:
+        sys.exit("usage: python tests/test_launch_table.py --write")
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        text = table(build(os.path.join(tmp, "launch_table")))
+    with open(FIXTURE, "w", encoding="utf-8") as fh:
+        fh.write(text)
+    print(f"wrote {FIXTURE}: {len(text.splitlines())} launches")

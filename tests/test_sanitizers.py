@@ -25,6 +25,18 @@ def test_host_code_under_asan_ubsan(tmp_path):
     assert r.returncode == 0 and "sanitize ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
+def test_planner_under_asan_ubsan(tmp_path):
+    """Kernel selection and launch geometry (csrc/csic_select.cpp) over the whole cross product of tests/cpp/launch_table.cpp:
+    no fixture here, only the sanitizers and the program's own invariants."""
+    exe = str(tmp_path / "launch_table_sanitize")
+    subprocess.check_call(["g++", "-std=c++17", *SAN, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "launch_table.cpp"), os.path.join(PKG, "csrc", "csic_select.cpp"),
+                           os.path.join(PKG, "csrc", "csic_host.cpp"), "-o", exe])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe, "--check"], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and " 0 with a broken invariant" in r.stderr, r.stdout[-2000:] + r.stderr[-4000:]
+
+
 def test_oracle_under_asan_ubsan(tmp_path):
     """The oracle's C restatement built with sanitizers and driven from a tiny C main over random shapes
     (both forms, all orders, AVG, YCbCr input, threads)."""

@@ -285,5 +285,5 @@ def test_the_model_is_not_reachable_from_the_compute_path():
     for name in ("compressor.py", "pipeline.py", "distributed.py", "model.py", "stages.py"):
         src = open(os.path.join(pkg, name)).read()
         assert "csic_stream" not in src and "from .stream" not in src and "import stream" not in src, name
-    for name in ("csic_kernels.hip", "csic_pipeline.hip", "csic_multi.hip", "csic_graph.hip", "csic_png.cpp"):
+    for name in ("csic_kernels.hip", "csic_select.cpp", "csic_select.h", "csic_hip_common.h", "csic_pipeline.hip", "csic_multi.hip", "csic_graph.hip", "csic_png.cpp"):
         assert "csic_stream" not in open(os.path.join(pkg, "csrc", name)).read(), name

@@ -1,7 +1,7 @@
 // tools/ubench.hip -- developer micro-benchmark for the headline shape (8192x8192, f=2).
 // Not part of the product: it includes the product's device functions and times experimental
 // load/store/grid shapes next to the shipped kernels so that tuning decisions are measured.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -I<pkg>/csrc tools/ubench.hip <pkg>/csrc/csic_host.cpp -o tools/ubench
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -I<pkg>/csrc tools/ubench.hip <pkg>/csrc/csic_host.cpp <pkg>/csrc/csic_select.cpp -o tools/ubench
 #include "csic_kernels.hip"
 
 #include <cstdlib>

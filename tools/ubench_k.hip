@@ -1,7 +1,7 @@
 // tools/ubench_k.hip -- developer micro-benchmark (not part of the product): pixels per lane (K) x block size for the headline
 // kernel shape k_dec<floor, argb, f=2, hold 1, c>s, K, nt> on 8192x8192, one frame per launch over a ring of 16 frames,
 // serial launches on one stream after 400 ms of clock conditioning.  The library ships K = 4.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -I<pkg>/csrc tools/ubench_k.hip <pkg>/csrc/csic_host.cpp <pkg>/csrc/csic_png.cpp -lz -o tools/ubench_k
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -I<pkg>/csrc tools/ubench_k.hip <pkg>/csrc/csic_host.cpp <pkg>/csrc/csic_select.cpp <pkg>/csrc/csic_png.cpp -lz -o tools/ubench_k
 #include "csic_kernels.hip"
 
 #include <chrono>
