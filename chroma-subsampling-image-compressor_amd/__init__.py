@@ -13,13 +13,15 @@ from .model import Image, ImageProcessorModel
 from .pipeline import FramePipeline
 from .stages import (ChromaSubsampler, ColorQuantizer, PixelBundle, PixelYCbCrBundle, ReferenceModel, RGB2YCbCr,
                      SpatialDownsampler, YCbCrUtils, pack_ycc, unpack_ycc)
+from .container import container_info, read_container, write_container
 from .app import ImageCompressionApp
 from .distributed import MultiDeviceCompressor, Stripe, StripedImageCompressorTop, halo_stripe_for_rank, stripe_for_rank
-from . import app, compressor, distributed, model, params, pipeline, stages, stream
+from . import app, compressor, container, distributed, model, params, pipeline, stages, stream
 
 __all__ = [
     "CsicIOError", "CsicRuntimeError", "IllegalArgumentException", "ImageProcessorParams", "PixelFormat", "ProcessingStep",
     "Rounding", "Sampling", "make_c_params", "ImageCompressorTop", "ImageProcessor", "Plan", "FrameGraph", "Distortion", "Image", "ImageProcessorModel",
     "ImageCompressionApp", "FramePipeline", "ChromaSubsampler", "ColorQuantizer", "PixelBundle", "PixelYCbCrBundle", "ReferenceModel", "RGB2YCbCr",
     "SpatialDownsampler", "YCbCrUtils", "pack_ycc", "unpack_ycc", "Stripe", "StripedImageCompressorTop", "MultiDeviceCompressor", "halo_stripe_for_rank", "stripe_for_rank",
+    "container_info", "read_container", "write_container",
 ]

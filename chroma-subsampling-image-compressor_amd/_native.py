@@ -46,7 +46,7 @@ class CsicRuntimeError(RuntimeError):
 
 
 class CsicIOError(OSError):
-    """CSIC_EIO / CSIC_EFORMAT from the PNG codec."""
+    """CSIC_EIO / CSIC_EFORMAT from the PNG codec and the .csic container."""
 
     def __init__(self, status: int, message: str):
         super().__init__(message)
@@ -81,6 +81,11 @@ class CsicPlanarBitsLayout(C.Structure):
                 ("frame_bytes", C.c_int64), ("payload_bytes", C.c_int64)]
 
 
+class CsicContainerInfo(C.Structure):
+    _fields_ = [("params", CsicParams), ("version", C.c_int32), ("nframes", C.c_int32), ("payload_bytes", C.c_int64),
+                ("file_bytes", C.c_int64)]
+
+
 class CsicFilesStats(C.Structure):
     _fields_ = [("frames", C.c_int64), ("wall_s", C.c_double), ("decode_s", C.c_double), ("encode_s", C.c_double),
                 ("gpu_wait_s", C.c_double), ("slot_wait_s", C.c_double), ("decode_threads", C.c_int32), ("encode_threads", C.c_int32),
@@ -110,6 +115,12 @@ PROTOTYPES = {
     "csic_reconstruct_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "csic_planar_bits_layout_of": (C.c_int, [C.POINTER(CsicParams), C.POINTER(CsicPlanarBitsLayout)]),
     "csic_reconstruct_bits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "csic_decode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "csic_decode_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32]),
+    "csic_decode_kernel_name": (C.c_char_p, [C.c_void_p, C.c_int32, C.c_int32]),
+    "csic_container_info_of": (C.c_int, [C.c_char_p, C.POINTER(CsicContainerInfo)]),
+    "csic_container_write": (C.c_int, [C.c_char_p, C.POINTER(CsicParams), C.c_void_p, C.c_int32]),
+    "csic_container_read": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t]),
     "csic_distortion_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
     "csic_distortion_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "csic_distortion_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_uint64)]),

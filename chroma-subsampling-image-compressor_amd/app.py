@@ -7,6 +7,14 @@ Same flags (space-separated `--key value` pairs, :149-151), same defaults (:164-
 order spatial, color, chroma), same banner, same output naming including the literal `order-Pr-Pr-Pr`
 tag (:188; ChiselEnum.toString quirk).  The simulated-RTL run is replaced by one fused
 HIP launch.
+
+Two leading verbs go past what the reference's app does (it only ever writes the reconstructed pixels as a PNG):
+
+    python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ...
+    python -m csic_amd.app decompress --input x.csic --output x.png
+
+`compress` writes the bit-packed planes as a .csic container (include/csic.h), `decompress` decodes one back to a PNG of the
+original size.  The verb must be the first argument; with any other first argument main() behaves as described above.
 """
 from __future__ import annotations
 
@@ -16,9 +24,10 @@ from typing import Dict, List
 
 import numpy as np
 
-from .compressor import ImageCompressorTop
+from .compressor import ImageCompressorTop, Plan
+from .container import read_container, write_container
 from .model import Image, ImageProcessorModel
-from .params import ProcessingStep
+from .params import PixelFormat, ProcessingStep, Sampling
 
 
 class ImageCompressionApp:
@@ -66,6 +75,35 @@ class ImageCompressionApp:
             stream = np.concatenate([stream, pad])
         ImageProcessorModel.writeImage(Image(stream.reshape(finalH, finalW)), outputImagePath)
 
+
+    @staticmethod
+    def compressImage(inputImagePath: str, outputPath: str,
+                      chromaParamA: int, chromaParamB: int,
+                      yTargetBits: int, cbTargetBits: int, crTargetBits: int,
+                      spatialFactorToUse: int,
+                      op1: ProcessingStep, op2: ProcessingStep, op3: ProcessingStep,
+                      sampling: Sampling = Sampling.HOLD_DECIMATE, *, device: int = 0) -> int:
+        """PNG -> CSIC_FMT_PLANAR_BITS plan -> .csic container.  Returns the bytes written (80 + payload_bytes)."""
+        inputImage = ImageProcessorModel.readImage(inputImagePath)
+        top = ImageCompressorTop(inputImage.width, inputImage.height, chromaParamA, chromaParamB, yTargetBits, cbTargetBits,
+                                 crTargetBits, spatialFactorToUse, op1, op2, op3, device=device, sampling=sampling)
+        try:
+            plan = top.plan(PixelFormat.PLANAR_BITS)
+            bits = plan.process_host(inputImage.argb)
+            os.makedirs(os.path.dirname(os.path.abspath(outputPath)), exist_ok=True)
+            write_container(outputPath, plan.c_params, bits)
+        finally:
+            top.close()
+        return os.path.getsize(outputPath)
+
+    @staticmethod
+    def decompressImage(inputPath: str, outputImagePath: str, *, device: int = 0) -> None:
+        """.csic container -> plan from the stored parameters -> csic_decode_* -> PNG of width x height (the first frame of a
+        container that holds several)."""
+        c_params, _, frames = read_container(inputPath)
+        with Plan(c_params, device) as plan:
+            argb = plan.decode_host(frames[0])
+        ImageProcessorModel.writeImage(Image(argb), outputImagePath)
 
     @staticmethod
     def processImages(inputImagePaths, outputImagePaths, chromaParamA: int, chromaParamB: int,
@@ -142,12 +180,43 @@ def _order_tag(step: ProcessingStep) -> str:
     return f"ProcessingStep({int(step)}={step.name})".split(".")[-1][:2]
 
 
-def main(argv: List[str] = None) -> int:
-    args = list(sys.argv[1:] if argv is None else argv)
+def _args_map(args: List[str]) -> Dict[str, str]:
     argsMap: Dict[str, str] = {}
     for i in range(0, len(args) - 1, 2):                              # args.sliding(2, 2), :149-151
         if args[i].startswith("--"):
             argsMap[args[i]] = args[i + 1]
+    return argsMap
+
+
+def _main_container(verb: str, args: List[str]) -> int:
+    """`compress` / `decompress`: the keys of the verb-less CLI with its defaults, plus --output and (compress) --sampling avg."""
+    argsMap = _args_map(args)
+    if "--input" not in argsMap or "--output" not in argsMap:
+        print(f"[ERROR] {verb} needs --input and --output")
+        return 2
+    inputPath, outputPath = argsMap["--input"], argsMap["--output"]
+    if not os.path.exists(inputPath):
+        print(f"[ERROR] Input not found: {inputPath}")
+        return 1
+    if verb == "decompress":
+        ImageCompressionApp.decompressImage(inputPath, outputPath)
+        print(f"Decompression complete. Output saved to: {outputPath}")
+        return 0
+    sampling = Sampling.AVG if argsMap.get("--sampling", "hold").lower() == "avg" else Sampling.HOLD_DECIMATE
+    size = ImageCompressionApp.compressImage(
+        inputPath, outputPath, int(argsMap.get("--a", "4")), int(argsMap.get("--b", "4")), int(argsMap.get("--yq", "8")),
+        int(argsMap.get("--cbq", "8")), int(argsMap.get("--crq", "8")), int(argsMap.get("--sf", "8")),
+        ProcessingStep.parse(argsMap.get("--op1", "spatial")), ProcessingStep.parse(argsMap.get("--op2", "color")),
+        ProcessingStep.parse(argsMap.get("--op3", "chroma")), sampling)
+    print(f"Compression complete. {os.path.getsize(inputPath)} -> {size} bytes. Output saved to: {outputPath}")
+    return 0
+
+
+def main(argv: List[str] = None) -> int:
+    args = list(sys.argv[1:] if argv is None else argv)
+    if args and args[0] in ("compress", "decompress"):
+        return _main_container(args[0], args[1:])
+    argsMap = _args_map(args)
     inputPath = argsMap.get("--input", "test_images/in128x128.png")
     a = int(argsMap.get("--a", "4"))
     b = int(argsMap.get("--b", "4"))

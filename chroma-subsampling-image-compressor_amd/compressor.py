@@ -283,6 +283,56 @@ class Plan:
                                                      int(out_format), self._stream()))
         return d_out
 
+    # -- full-resolution decode (csic_decode_*) ---------------------------------------------------
+    def _decode_src_bytes(self, src_format: int) -> int:
+        """Bytes of one source frame of csic_decode_* in `src_format`."""
+        if src_format == N.FMT_PLANAR_BITS:
+            return self.planar_bits_layout.frame_bytes
+        if src_format == N.FMT_PLANAR:
+            return self.planar_layout.frame_bytes
+        return 4 * self.out_width * self.out_height
+
+    def decode_kernel_name(self, src_format: int, out_format: int = N.FMT_ARGB8888) -> str:
+        """The kernel decode_device takes for 16-byte aligned buffers (csic_decode_kernel_name); "" for a refused pair."""
+        return N.lib().csic_decode_kernel_name(self._h, int(src_format), int(out_format)).decode()
+
+    def decode_device(self, d_src, src_format=None, d_out=None, nframes: int = 1, out_format: int = N.FMT_ARGB8888):
+        """A compressed frame -> width x height packed pixels, decode(r, c) = o(r / f, c / f) (csic_decode_device).  d_src: a
+        contiguous CUDA tensor holding nframes sources in `src_format` -- PLANAR_BITS / PLANAR frame buffers, or out_width *
+        out_height packed YCBCR888X / ARGB8888 pixels per frame; None = the plan's own out_format.  Returns d_out shaped (H, W)
+        or (nframes, H, W), int32.  Asynchronous on torch's current stream."""
+        import torch
+        src_format = self.c_params.out_format if src_format is None else int(src_format)
+        if src_format not in (N.FMT_ARGB8888, N.FMT_YCBCR888X, N.FMT_PLANAR, N.FMT_PLANAR_BITS):
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: unknown source format {src_format}")
+        if not d_src.is_cuda or not d_src.is_contiguous() or d_src.numel() * d_src.element_size() != nframes * self._decode_src_bytes(src_format):
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_src must be a contiguous CUDA tensor of nframes source frames")
+        if d_src.device.index != self.device:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: tensor is on a different device than the plan")
+        shape = (self.height, self.width) if nframes == 1 else (nframes, self.height, self.width)
+        if d_out is None:
+            d_out = torch.empty(shape, dtype=torch.int32, device=d_src.device)
+        elif d_out.numel() != nframes * self.width * self.height or d_out.element_size() != 4 or not d_out.is_contiguous() \
+                or d_out.device != d_src.device:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_out has the wrong size/layout")
+        N.check(N.lib().csic_decode_device(self._h, C.c_void_p(d_src.data_ptr()), src_format, C.c_void_p(d_out.data_ptr()),
+                                           int(out_format), int(nframes), self._stream()))
+        return d_out
+
+    def decode_host(self, src: np.ndarray, src_format=None, nframes: int = 1, out_format: int = N.FMT_ARGB8888) -> np.ndarray:
+        """csic_decode_host: nframes source frames in host memory -> uint32 array (H, W) or (nframes, H, W)."""
+        src_format = self.c_params.out_format if src_format is None else int(src_format)
+        a = np.ascontiguousarray(src).reshape(-1).view(np.uint8)
+        out = np.empty(nframes * self.width * self.height, dtype=np.uint32)
+        N.check(N.lib().csic_decode_host(self._h, a.ctypes.data_as(C.c_void_p), a.size, src_format, out.ctypes.data_as(C.c_void_p),
+                                         out.size, int(out_format), int(nframes)))
+        return out.reshape((self.height, self.width) if nframes == 1 else (nframes, self.height, self.width))
+
+    def decode(self, src, src_format=None, nframes: int = 1, out_format: int = N.FMT_ARGB8888):
+        if _is_torch_tensor(src):
+            return self.decode_device(src, src_format, None, nframes, out_format)
+        return self.decode_host(src, src_format, nframes, out_format)
+
     def unpack_planar_bits(self, buf) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """One bit-packed planar frame buffer (bytes on the host) -> (Y (Ho, Wo), Cb, Cr) with the restored 8-bit values
         (code << (8 - q)): what split_planar gives for the PLANAR frame of the same parameters."""
@@ -464,6 +514,11 @@ class ImageCompressorTop:
         """ARGB frame in -> one bit-packed planar frame buffer (CSIC_FMT_PLANAR_BITS, uint8: planar_bits_layout.frame_bytes on the
         host, a CUDA uint8 tensor for a CUDA input); Plan.unpack_planar_bits cuts it into the three planes."""
         return self.plan(PixelFormat.PLANAR_BITS).process(argb)
+
+    def decode(self, buf):
+        """One bit-packed planar frame buffer (what processPlanarBits returns: host bytes or a CUDA uint8 tensor) -> the ARGB frame
+        of the ORIGINAL size, height x width: every reconstructed pixel replicated factor x factor times (csic_decode_*)."""
+        return self.plan(PixelFormat.PLANAR_BITS).decode(buf)
 
     def close(self) -> None:
         for p in self._plans.values():

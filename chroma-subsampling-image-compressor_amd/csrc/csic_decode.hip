@@ -1,0 +1,458 @@
+// csic_decode.hip -- csic_decode_*: a compressed frame (bit-packed planar, planar, or the packed output itself) back to a frame of
+// the ORIGINAL size, width x height packed pixels, by replication: decode(r, c) = o(r / f, c / f), o = the packed output of the
+// plan's parameters (definition in include/csic.h).  The pairing is the one csic_distortion_* measures, so
+// SSE(x, decode(compress(x))) == distortion(x).
+//
+// Kernels (wave64; a write stream of 4 W H bytes behind a small read; no LDS, no MFMA):
+//   k_decode<SRC, FMT, F, NT>   the fast kernel.  One lane owns one 16-byte PIECE of the output -- 4 consecutive pixels of an output row
+//                      -- and stores it to the F output rows that its source row expands to: F 16-byte non-temporal stores, and the
+//                      64 lanes of a wave write one contiguous 1 KiB run per store.  The piece comes from NP = 4 / 2 / 1 / 1 consecutive
+//                      source positions at F = 1 / 2 / 4 / 8 (planar sources: the two dwords that hold their codes in each plane,
+//                      k_rbits' replay rule, PLANAR being the bit-packed frame at 8 / 8 / 8; packed sources: one 16 / 8 / 4-byte load),
+//                      so the inverse transform runs once per source pixel up to F = 4 and twice at F = 8.  K = 4 / 2 / 1 pieces per
+//                      lane, spaced by the block size, all loads issued before any arithmetic.  Conditions (decode_kind): width % 4 == 0
+//                      (pieces tile the rows; the NP positions of a piece then start at a multiple of NP in a chroma row whose length
+//                      is a multiple of NP, whatever the order class), width * height <= 2^30 (32-bit byte offsets), output and packed source
+//                      16-byte aligned.  The height is free: a ragged last source row stores fewer rows.
+//                      (The first version had a lane decode 4 source pixels and store their whole F x F expansion, F 16-byte stores
+//                      per row at a lane stride of 16 F bytes: 27.8 % of 8 TB/s at factor 2 and 8.6 % at factor 4 on 8192 x 8192,
+//                      DESIGN.md 4.4 -- partial-line non-temporal stores do not combine.)
+//   k_decode_gen<SRC, FMT>      the general kernel: one output pixel per lane straight from the definition, 4-byte accesses.  Ragged
+//                      shapes, buffers that are only 4-byte aligned, CSIC_TUNE_VARIANT 9, CSIC_TUNE_NO_VECTOR, CSIC_TUNE_FORCE_GENERIC.
+//   At factor 1 a planar source IS a reconstruct: csic_reconstruct_bits_device / csic_reconstruct_device (k_rbits / k_recon) are
+//   called, and csic_decode_kernel_name says so.  (Not for a batch of frames whose W * H is not a multiple of 4: those kernels store
+//   16 bytes at a time from each frame's base, which only the first frame's alignment check covers.)
+// Every global access goes through the accessors below, which the CSIC_DEBUG build range-checks: loads against the source frame's
+// bytes, stores against the W * H pixels of the output frame.
+#include <cstdio>
+#include <cstring>
+
+#include "csic_kernel_ops.h"
+
+namespace csic {
+
+typedef const uint8_t CSIC_GLOBAL *gdsrc_t;
+
+enum { S_ARGB = CSIC_FMT_ARGB8888, S_YCC = CSIC_FMT_YCBCR888X, S_PLANAR = CSIC_FMT_PLANAR, S_BITS = CSIC_FMT_PLANAR_BITS };
+
+// the kernels' argument
+struct DecArgs {
+    const uint8_t *src;            // source frames, src_frame_bytes apart
+    uint32_t *dst;                 // W * H pixels per frame, back to back
+    int64_t off[3], nbytes[3];     // planar sources: plane offsets and the bytes each plane's samples occupy (Y, Cb, Cr)
+    int64_t src_frame_bytes;       // planar: frame_bytes; packed: 4 n
+    int64_t n, out_px;             // source positions (out_width * out_height); output pixels (W * H)
+    int32_t q[3];                  // bits per sample (8 for PLANAR)
+    int32_t Wm, Wc, lhe, lve, replay_last;
+    uint32_t mWm, kWm, mP, kP, mW, kW;     // exact j / Wm, t / P, t / W (magic_div)
+    int32_t W, H, Wo, lf, T;       // lf = log2 factor; T = threads per block
+    int32_t P;                     // fast kernel: pieces (4 output pixels) per row, W / 4
+    int64_t npieces, nwhole;       // fast kernel: P * out_height pieces; those of source rows that expand to F whole output rows
+};
+
+#if defined(CSIC_DEBUG) && CSIC_DEBUG
+#define CSIC_DCHECK(lim, off, cnt) CSIC_CHECK((int64_t)(off) >= 0 && (int64_t)(off) + (cnt) <= (lim))
+#else
+#define CSIC_DCHECK(lim, off, cnt) do { } while (0)
+#endif
+
+// source: a dword at a byte offset (4-byte aligned), 4 or 2 pixels at a pixel offset; output: 1 or 4 pixels at a pixel offset
+__device__ __forceinline__ uint32_t dsrc4(const DecArgs &e, gdsrc_t fb, int64_t off)
+{
+    CSIC_DCHECK(e.src_frame_bytes, off, 4); (void)e;
+    return *(gin_t)(fb + off);
+}
+template <bool NT> __device__ __forceinline__ u32x4 dsrc16(const DecArgs &e, gdsrc_t fb, uint32_t px)
+{
+    CSIC_DCHECK(e.src_frame_bytes, 4 * (int64_t)px, 16); (void)e;
+    return ld4<NT>((gin_t)(fb + (uint64_t)(px << 2)));
+}
+template <bool NT> __device__ __forceinline__ u32x2 dsrc8(const DecArgs &e, gdsrc_t fb, uint32_t px)
+{
+    CSIC_DCHECK(e.src_frame_bytes, 4 * (int64_t)px, 8); (void)e;
+    typedef const u32x2 CSIC_GLOBAL *vp;
+    const vp p = (vp)(fb + (uint64_t)(px << 2));
+    return NT ? __builtin_nontemporal_load(p) : *p;
+}
+__device__ __forceinline__ void dout1(const DecArgs &e, gout_t out, int64_t px, uint32_t v)
+{
+    CSIC_DCHECK(e.out_px, px, 1); (void)e;
+    out[px] = v;
+}
+template <bool NT> __device__ __forceinline__ void dout4(const DecArgs &e, gout_t out, uint32_t px, u32x4 v)
+{
+    CSIC_DCHECK(e.out_px, px, 4); (void)e;
+    st4<NT>((gout_t)((char CSIC_GLOBAL *)out + (uint64_t)(px << 2)), v);
+}
+
+__device__ __forceinline__ gdsrc_t dec_src(const DecArgs &e) { return (gdsrc_t)(uintptr_t)e.src + (int64_t)blockIdx.z * e.src_frame_bytes; }
+__device__ __forceinline__ gout_t dec_dst(const DecArgs &e) { return (gout_t)(uintptr_t)e.dst + (int64_t)blockIdx.z * e.out_px; }
+
+// ------------------------------------------------------------------------------------------------
+// planar sources: bit planes (csic_planar_bits_layout; PLANAR = the same at 8 bits per sample)
+// ------------------------------------------------------------------------------------------------
+// bits [bit, bit + 32) of plane p: the dword that holds `bit` and the next one, clamped to the plane's last dword (planes are padded
+// to 256 bytes, so that dword is inside the frame; what it cannot supply lies past the plane's end)
+__device__ __forceinline__ uint32_t dec_window(const DecArgs &e, gdsrc_t fb, int p, uint64_t bit)
+{
+    const int64_t dw = (int64_t)(bit >> 5), last = (e.nbytes[p] + 3) / 4 - 1;
+    const uint32_t lo = dsrc4(e, fb, e.off[p] + 4 * dw);
+    const uint32_t hi = dsrc4(e, fb, e.off[p] + 4 * min(dw + 1, last));
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (bit & 31u));
+}
+__device__ __forceinline__ uint32_t dec_code(uint32_t win, uint32_t i, uint32_t q) { return ((win >> (i * q)) & ((1u << q) - 1u)) << (8u - q); }
+
+// chroma sample of stream position (r, c): csic_reconstruct_device's rule
+__device__ __forceinline__ uint64_t dec_sample(const DecArgs &e, uint32_t r, uint32_t c)
+{
+    if ((r & ((1u << e.lve) - 1u)) == 0 || !e.replay_last) return (uint64_t)(r >> e.lve) * e.Wc + (c >> e.lhe);
+    return (uint64_t)((r - 1u) >> e.lve) * e.Wc + (e.Wc - 1);          // ChromaSubsampler.scala:52-65: the last sample of the row above
+}
+
+template <int SRC> __device__ __forceinline__ uint32_t dec_q(const DecArgs &e, int p) { return SRC == S_PLANAR ? 8u : (uint32_t)e.q[p]; }
+
+// source position j by the definition: the packed pixel o[j] in FMT
+template <int SRC, int FMT>
+__device__ __forceinline__ uint32_t dec_pixel(const DecArgs &e, gdsrc_t fb, uint32_t j)
+{
+    if (SRC == S_ARGB || SRC == S_YCC) {
+        const uint32_t v = dsrc4(e, fb, 4 * (int64_t)j);
+        if (SRC == S_YCC && FMT == F_ARGB) return finish_y<F_ARGB>(v & 0xFFu, chroma_term_q<F_ARGB>((v >> 8) & 0xFFu, (v >> 16) & 0xFFu));
+        return v;
+    }
+    const uint32_t qy = dec_q<SRC>(e, 0), qb = dec_q<SRC>(e, 1), qr = dec_q<SRC>(e, 2);
+    const uint32_t r = (uint32_t)(((uint64_t)j * e.mWm) >> e.kWm), c = j - r * (uint32_t)e.Wm;
+    const uint64_t k = dec_sample(e, r, c);
+    const uint32_t y = dec_code(dec_window(e, fb, 0, (uint64_t)j * qy), 0, qy);
+    const uint32_t cb = dec_code(dec_window(e, fb, 1, k * qb), 0, qb), cr = dec_code(dec_window(e, fb, 2, k * qr), 0, qr);
+    return finish_y<FMT>(y, chroma_term_q<FMT>(cb, cr));
+}
+
+// ------------------------------------------------------------------------------------------------
+// the fast kernel
+// ------------------------------------------------------------------------------------------------
+// A lane owns one PIECE: 4 consecutive output pixels of one output row, written to the F output rows of its source row.  Its NP
+// source positions (4 / F of them, at least 1) are consecutive and start at a multiple of NP.
+template <int F> constexpr int dec_np() { return F == 1 ? 4 : F == 2 ? 2 : 1; }
+template <int F> constexpr int dec_pieces_per_lane() { return F == 1 ? 4 : F == 2 ? 2 : 1; }
+
+// what a lane holds of its source positions once its loads are back
+struct DecGroup {
+    uint32_t px[4];             // packed sources: the NP pixels
+    uint32_t yw, bw, rw, sh;    // planar sources: the windows that start at the first Y / Cb / Cr code; position i takes chroma
+};                              // code i >> sh
+
+template <int SRC, int NP, bool NT>
+__device__ __forceinline__ DecGroup dec_load(const DecArgs &e, gdsrc_t fb, uint32_t j0)
+{
+    DecGroup g;
+    g.px[0] = g.px[1] = g.px[2] = g.px[3] = 0;
+    g.yw = g.bw = g.rw = g.sh = 0;
+    if (SRC == S_YCC) {
+        if (NP == 4) { const u32x4 v = dsrc16<NT>(e, fb, j0); g.px[0] = v.x; g.px[1] = v.y; g.px[2] = v.z; g.px[3] = v.w; }
+        else if (NP == 2) { const u32x2 v = dsrc8<NT>(e, fb, j0); g.px[0] = v.x; g.px[1] = v.y; }
+        else g.px[0] = dsrc4(e, fb, (int64_t)(uint64_t)(j0 << 2));
+        return g;
+    }
+    // module_width % NP == 0 and j0 % NP == 0: the positions lie in one chroma row at a column that is a multiple of NP -- their
+    // samples are consecutive codes, position i taking code i >> log2 hold_h, or ONE code on a row that replays the last sample of
+    // the row above
+    const uint32_t r = (uint32_t)(((uint64_t)j0 * e.mWm) >> e.kWm), c0 = j0 - r * (uint32_t)e.Wm;
+    const bool replay = (r & ((1u << e.lve) - 1u)) != 0 && e.replay_last;
+    const uint64_t k0 = dec_sample(e, r, c0);
+    g.sh = replay ? 2u : (uint32_t)e.lhe;
+    g.yw = dec_window(e, fb, 0, (uint64_t)j0 * dec_q<SRC>(e, 0));
+    g.bw = dec_window(e, fb, 1, k0 * dec_q<SRC>(e, 1));
+    g.rw = dec_window(e, fb, 2, k0 * dec_q<SRC>(e, 2));
+    return g;
+}
+
+// the NP packed pixels: the chroma half of the inverse transform once per DISTINCT sample
+template <int SRC, int FMT, int NP>
+__device__ __forceinline__ void dec_group_pixels(const DecArgs &e, const DecGroup &g, uint32_t o[4])
+{
+    if (SRC == S_YCC) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+            o[i] = FMT == F_ARGB ? finish_y<F_ARGB>(g.px[i] & 0xFFu, chroma_term_q<F_ARGB>((g.px[i] >> 8) & 0xFFu, (g.px[i] >> 16) & 0xFFu))
+                                 : g.px[i];
+        return;
+    }
+    const uint32_t qy = dec_q<SRC>(e, 0), qb = dec_q<SRC>(e, 1), qr = dec_q<SRC>(e, 2);
+    const ChromaTerm t0 = chroma_term_q<FMT>(dec_code(g.bw, 0, qb), dec_code(g.rw, 0, qr));
+    o[0] = finish_y<FMT>(dec_code(g.yw, 0, qy), t0);
+    if (NP == 1) return;
+    if (g.sh != 0u) {                                                     // positions 0 and 1 share a sample
+        o[1] = finish_y<FMT>(dec_code(g.yw, 1, qy), t0);
+        if (NP == 2) return;
+        const ChromaTerm t1 = g.sh == 2u ? t0 : chroma_term_q<FMT>(dec_code(g.bw, 1, qb), dec_code(g.rw, 1, qr));
+        o[2] = finish_y<FMT>(dec_code(g.yw, 2, qy), t1);
+        o[3] = finish_y<FMT>(dec_code(g.yw, 3, qy), t1);
+        return;
+    }
+#pragma unroll
+    for (int i = 1; i < NP; ++i)
+        o[i] = finish_y<FMT>(dec_code(g.yw, i, qy), chroma_term_q<FMT>(dec_code(g.bw, i, qb), dec_code(g.rw, i, qr)));
+}
+
+template <int SRC, int FMT, int F, bool NT, bool CHECK>
+__device__ __forceinline__ void decode_body(const DecArgs &e, gdsrc_t fb, gout_t out, uint32_t t0, uint32_t T, uint32_t npieces)
+{
+    constexpr int K = dec_pieces_per_lane<F>(), NP = dec_np<F>();
+    constexpr int LF = F == 1 ? 0 : F == 2 ? 1 : F == 4 ? 2 : 3;
+    DecGroup grp[K];
+    uint32_t ro[K], pc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const uint32_t t = t0 + (uint32_t)k * T, tc = CHECK ? min(t, npieces - 1u) : t;
+        // piece tc: source row ro, piece column pc (output columns 4 pc .. 4 pc + 3 <- source columns (4 pc) >> LF ..)
+        ro[k] = (uint32_t)(((uint64_t)tc * e.mP) >> e.kP);
+        pc[k] = tc - ro[k] * (uint32_t)e.P;
+        grp[k] = dec_load<SRC, NP, NT>(e, fb, ro[k] * (uint32_t)e.Wo + ((4u * pc[k]) >> LF));
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (CHECK && t0 + (uint32_t)k * T >= npieces) continue;
+        uint32_t o[4];
+        dec_group_pixels<SRC, FMT, NP>(e, grp[k], o);
+        const u32x4 piece = F == 1 ? u32x4{o[0], o[1], o[2], o[3]} : F == 2 ? u32x4{o[0], o[0], o[1], o[1]} : u32x4{o[0], o[0], o[0], o[0]};
+        // the same 16 bytes to the F output rows of the source row (fewer on a ragged last one): lanes of a wave store 1 KiB runs
+        const uint32_t row0 = ro[k] << LF, base = row0 * (uint32_t)e.W + 4u * pc[k];
+        const uint32_t rows = CHECK ? min((uint32_t)F, (uint32_t)e.H - row0) : (uint32_t)F;
+#pragma unroll
+        for (int i = 0; i < F; ++i)
+            if (!CHECK || (uint32_t)i < rows) dout4<NT>(e, out, base + (uint32_t)i * (uint32_t)e.W, piece);
+    }
+    if (!CHECK) keep_tail_apart();
+}
+
+template <int SRC, int FMT, int F, bool NT>
+__global__ void __launch_bounds__(256) k_decode(DecArgs e)
+{
+    const uint32_t T = (uint32_t)e.T;
+    const uint32_t npieces = (uint32_t)e.npieces;                      // (W / 4) * out_height
+    const uint32_t per_block = T * (uint32_t)dec_pieces_per_lane<F>();
+    const uint32_t b0 = blockIdx.x * per_block;
+    const gdsrc_t fb = dec_src(e);
+    const gout_t out = dec_dst(e);
+    // straight-line body: a whole block of pieces, none of them in a ragged last source row
+    if (b0 + per_block <= (uint32_t)e.nwhole) decode_body<SRC, FMT, F, NT, false>(e, fb, out, b0 + threadIdx.x, T, npieces);
+    else                                       decode_body<SRC, FMT, F, NT, true>(e, fb, out, b0 + threadIdx.x, T, npieces);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the general kernel: one output pixel per lane, from the definition
+// ------------------------------------------------------------------------------------------------
+template <int SRC, int FMT>
+__global__ void __launch_bounds__(256) k_decode_gen(DecArgs e)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;    // out_px < 2^31 (csic_decode_device)
+    if (t >= e.out_px) return;
+    const uint32_t r = (uint32_t)(((uint64_t)t * e.mW) >> e.kW), c = (uint32_t)t - r * (uint32_t)e.W;
+    const uint32_t j = (r >> e.lf) * (uint32_t)e.Wo + (c >> e.lf);
+    dout1(e, dec_dst(e), t, dec_pixel<SRC, FMT>(e, dec_src(e), j));
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+using DecFn = void (*)(DecArgs);
+
+static int dlog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
+
+static bool dec_is_planar(int src_format) { return src_format == CSIC_FMT_PLANAR || src_format == CSIC_FMT_PLANAR_BITS; }
+
+// bytes between the source frames of a batch
+static int64_t dec_src_frame_bytes(const csic_plan *pl, int src_format)
+{
+    if (src_format == CSIC_FMT_PLANAR_BITS) { csic_planar_bits_layout L; planar_bits_layout(pl->g, &pl->p, &L); return L.frame_bytes; }
+    if (src_format == CSIC_FMT_PLANAR) { csic_planar_layout L; planar_layout(pl->g, &pl->p, &L); return L.frame_bytes; }
+    return 4 * (int64_t)pl->g.Wo * pl->g.Ho;
+}
+
+static void fill_dec_args(const csic_plan *pl, int src_format, DecArgs *e)
+{
+    std::memset(e, 0, sizeof *e);
+    const Geometry &g = pl->g;
+    csic_planar_bits_layout B;
+    planar_bits_layout(g, &pl->p, &B);
+    const csic_planar_layout &G = B.geometry;
+    if (src_format == CSIC_FMT_PLANAR_BITS) {
+        e->off[0] = B.y_offset; e->off[1] = B.cb_offset; e->off[2] = B.cr_offset;
+        e->nbytes[0] = B.y_bytes; e->nbytes[1] = B.cb_bytes; e->nbytes[2] = B.cr_bytes;
+        e->q[0] = B.y_bits; e->q[1] = B.cb_bits; e->q[2] = B.cr_bits;
+    } else if (src_format == CSIC_FMT_PLANAR) {
+        e->off[0] = G.y_offset; e->off[1] = G.cb_offset; e->off[2] = G.cr_offset;
+        e->nbytes[0] = (int64_t)G.y_width * G.y_height; e->nbytes[1] = e->nbytes[2] = G.chroma_samples;
+        e->q[0] = e->q[1] = e->q[2] = 8;
+    }
+    e->src_frame_bytes = dec_src_frame_bytes(pl, src_format);
+    e->n = (int64_t)g.Wo * g.Ho;
+    e->out_px = (int64_t)g.W * g.H;
+    e->Wm = G.module_width; e->Wc = G.chroma_width; e->lhe = dlog2(G.hold_h); e->lve = dlog2(G.hold_v); e->replay_last = G.replay_last;
+    magic_div((uint32_t)G.module_width, &e->mWm, &e->kWm);
+    magic_div((uint32_t)g.W, &e->mW, &e->kW);
+    e->W = g.W; e->H = g.H; e->Wo = g.Wo; e->lf = dlog2(g.f);
+    e->P = g.W / 4 > 0 ? g.W / 4 : 1;
+    magic_div((uint32_t)e->P, &e->mP, &e->kP);
+    e->npieces = (int64_t)e->P * g.Ho;
+    e->nwhole = (int64_t)e->P * (g.H / g.f);
+}
+
+enum { DEC_GEN = 0, DEC_FAST = 1, DEC_RECON = 2 };
+
+// which kernel a call takes; align_bits: the output pointer, OR-ed with the source pointer for a packed source
+static int decode_kind(const csic_plan *pl, int src_format, uintptr_t align_bits, int nframes)
+{
+    const Geometry &g = pl->g;
+    if (pl->tune.variant == 9 || pl->tune.force_generic || pl->tune.no_vec || (align_bits & 15u)) return DEC_GEN;
+    // the reconstruct kernels store 16 bytes at a time from each frame's base: frames after the first start 4 W H bytes further on
+    if (g.f == 1 && dec_is_planar(src_format) && (nframes == 1 || ((int64_t)g.W * g.H) % 4 == 0)) return DEC_RECON;
+    // width % 4 == 0 is all a planar source needs too: the module width is W or out_width, a multiple of NP (4 at factor 1, 2 at 2, 1
+    // above), and so is every piece's first stream position
+    if (g.W % 4 != 0 || (int64_t)g.W * g.H > ((int64_t)1 << 30)) return DEC_GEN;
+    return DEC_FAST;
+}
+
+static DecFn decode_kernel(int kind, int src_format, int out_format, int f, bool nt)
+{
+    // an ARGB source is only ever replicated (ARGB -> YCbCr is refused): it takes the YCbCr -> YCbCr instantiations, a plain copy
+    if (src_format == S_ARGB) { src_format = S_YCC; out_format = F_YCC; }
+    return with_const<F_ARGB, F_YCC>(out_format, [&](auto fmt) {
+        return with_const<S_BITS, S_PLANAR, S_YCC>(src_format, [&](auto s) -> DecFn {
+            constexpr int SRC = CSIC_CONST(s), FMT = CSIC_CONST(fmt);
+            if (kind == DEC_GEN) return k_decode_gen<SRC, FMT>;
+            return with_const<true, false>(nt, [&](auto n) -> DecFn {
+                constexpr bool NT = CSIC_CONST(n);
+                if constexpr (SRC == S_YCC)
+                    return with_const<1, 2, 4, 8>(f, [](auto ff) -> DecFn { return k_decode<SRC, FMT, CSIC_CONST(ff), NT>; });
+                else                                                      // factor 1 from planes is k_rbits / k_recon
+                    return with_const<2, 4, 8>(f, [](auto ff) -> DecFn { return k_decode<SRC, FMT, CSIC_CONST(ff), NT>; });
+            });
+        });
+    });
+}
+
+static const char *dec_src_name(int src_format)
+{
+    switch (src_format) {
+    case CSIC_FMT_PLANAR_BITS: return "bits";
+    case CSIC_FMT_PLANAR: return "planar";
+    default: return "ycc";
+    }
+}
+
+static int decode_check_formats(int32_t src_format, int32_t out_format)
+{
+    if (src_format < CSIC_FMT_ARGB8888 || src_format > CSIC_FMT_PLANAR_BITS)
+        return set_error(CSIC_EINVAL_FORMAT, "csic_decode reads ARGB8888(0), YCBCR888X(1), PLANAR(2) or PLANAR_BITS(3). Got %d", src_format);
+    if (out_format != CSIC_FMT_ARGB8888 && out_format != CSIC_FMT_YCBCR888X)
+        return set_error(CSIC_EINVAL_FORMAT, "csic_decode writes ARGB8888(0) or YCBCR888X(1). Got %d", out_format);
+    if (src_format == CSIC_FMT_ARGB8888 && out_format == CSIC_FMT_YCBCR888X)
+        return set_error(CSIC_EINVAL_FORMAT, "csic_decode cannot turn an ARGB source into YCbCr: the inverse transform has no inverse");
+    return CSIC_OK;
+}
+
+} // namespace csic
+
+using namespace csic;
+
+extern "C" {
+
+const char *csic_decode_kernel_name(const csic_plan *plan, int32_t src_format, int32_t out_format)
+{
+    static thread_local char buf[96];
+    if (!plan || decode_check_formats(src_format, out_format) != CSIC_OK) return "";
+    // an ARGB source runs the YCbCr -> YCbCr instantiation (a copy): the name is the kernel's, as a profiler shows it
+    const char *fmt = out_format == CSIC_FMT_ARGB8888 && src_format != CSIC_FMT_ARGB8888 ? "argb" : "ycc";
+    const char *nt = !plan->tune.no_nt ? "nt" : "cached";
+    switch (decode_kind(plan, src_format, 0, 1)) {
+    case DEC_RECON: {
+        csic_planar_layout L;
+        planar_layout(plan->g, &plan->p, &L);
+        snprintf(buf, sizeof buf, "%s<%s,%s,%s>", src_format == CSIC_FMT_PLANAR_BITS ? "k_rbits" : "k_recon", fmt,
+                 L.module_width % 4 == 0 ? "fast" : "slow", nt);
+        break;
+    }
+    case DEC_FAST: snprintf(buf, sizeof buf, "k_decode<%s,%s,f%d,%s>", dec_src_name(src_format), fmt, plan->g.f, nt); break;
+    default: snprintf(buf, sizeof buf, "k_decode_gen<%s,%s>", dec_src_name(src_format), fmt); break;
+    }
+    return buf;
+}
+
+int csic_decode_device(csic_plan *plan, const void *d_src, int32_t src_format, void *d_out, int32_t out_format, int32_t nframes,
+                       void *hip_stream)
+{
+    if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
+    if (!d_src || !d_out) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
+    if (nframes <= 0) return set_error(CSIC_EINVAL_SIZE, "nframes must be positive. Got %d", nframes);
+    int st = decode_check_formats(src_format, out_format);
+    if (st != CSIC_OK) return st;
+    const bool planar = dec_is_planar(src_format);
+    if (planar && ((uintptr_t)d_src & 255u)) return set_error(CSIC_EINVAL_SIZE, "a planar frame buffer must be 256-byte aligned");
+    if (((uintptr_t)d_src & 3u) || ((uintptr_t)d_out & 3u)) return set_error(CSIC_EINVAL_SIZE, "source and output must be 4-byte aligned");
+    const Geometry &g = plan->g;
+    if ((int64_t)g.W * g.H >= ((int64_t)1 << 31)) return set_error(CSIC_EINVAL_SIZE, "frame too large for csic_decode_device");
+    const int kind = decode_kind(plan, src_format, (uintptr_t)d_out | (planar ? 0 : (uintptr_t)d_src), nframes);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (kind == DEC_RECON)
+        return src_format == CSIC_FMT_PLANAR_BITS ? csic_reconstruct_bits_device(plan, d_src, d_out, nframes, out_format, hip_stream)
+                                                  : csic_reconstruct_device(plan, d_src, d_out, nframes, out_format, hip_stream);
+    const DecFn fn = decode_kernel(kind, src_format, out_format, g.f, !plan->tune.no_nt);
+    CSIC_DEVICE_SCOPE(plan->device);
+    const int bt = plan->tune.block_threads;
+    const int T = (bt == 64 || bt == 128 || bt == 256) ? bt : 256;
+    for (int f0 = 0; f0 < nframes; f0 += 65535) {                       // grid z limit
+        const int nz = nframes - f0 < 65535 ? nframes - f0 : 65535;
+        DecArgs e;
+        fill_dec_args(plan, src_format, &e);
+        e.src = static_cast<const uint8_t *>(d_src) + (int64_t)f0 * e.src_frame_bytes;
+        e.dst = static_cast<uint32_t *>(d_out) + (int64_t)f0 * e.out_px;
+        e.T = T;
+        int64_t blocks;
+        if (kind == DEC_FAST) {
+            const int64_t per_block = (int64_t)T * (g.f == 1 ? 4 : g.f == 2 ? 2 : 1);
+            blocks = (e.npieces + per_block - 1) / per_block;
+        } else {
+            blocks = (e.out_px + T - 1) / T;
+        }
+        void *params[1] = {&e};
+        HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3((unsigned)blocks, 1, (unsigned)nz), dim3((unsigned)T, 1, 1), params, 0,
+                                stream));
+    }
+    clear_error();
+    return CSIC_OK;
+}
+
+int csic_decode_host(csic_plan *plan, const void *src, size_t src_bytes, int32_t src_format, uint32_t *out, size_t out_px,
+                     int32_t out_format, int32_t nframes)
+{
+    if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
+    if (!src || !out) return set_error(CSIC_EINVAL_NULL, "host buffer is NULL");
+    if (nframes <= 0) return set_error(CSIC_EINVAL_SIZE, "nframes must be positive. Got %d", nframes);
+    int st = decode_check_formats(src_format, out_format);
+    if (st != CSIC_OK) return st;
+    const Geometry &g = plan->g;
+    const size_t need_src = (size_t)nframes * (size_t)dec_src_frame_bytes(plan, src_format);
+    const size_t need_out = (size_t)nframes * (size_t)g.W * (size_t)g.H;
+    if (src_bytes != need_src) return set_error(CSIC_EINVAL_SIZE, "expected %zu source bytes (%d frames), got %zu", need_src, nframes, src_bytes);
+    if (out_px != need_out) return set_error(CSIC_EINVAL_SIZE, "expected room for %zu output pixels (%d frames), got %zu", need_out, nframes, out_px);
+    CSIC_DEVICE_SCOPE(plan->device);
+    void *d_src = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc(&d_src, need_src);
+    if (e == hipSuccess) e = hipMalloc(&d_out, need_out * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_src, src, need_src, hipMemcpyHostToDevice, nullptr);
+    if (e == hipSuccess) {
+        st = csic_decode_device(plan, d_src, src_format, d_out, out_format, nframes, nullptr);
+        if (st == CSIC_OK) e = hipMemcpyAsync(out, d_out, need_out * 4, hipMemcpyDeviceToHost, nullptr);
+        if (st == CSIC_OK && e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    }
+    if (d_src) (void)hipFree(d_src);
+    if (d_out) (void)hipFree(d_out);
+    if (st != CSIC_OK) return st;
+    if (e != hipSuccess) return set_error(CSIC_EHIP, "csic_decode_host: %s", hipGetErrorString(e));
+    clear_error();
+    return CSIC_OK;
+}
+
+} // extern "C"

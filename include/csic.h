@@ -62,7 +62,7 @@ typedef enum csic_status {
     CSIC_ENOMEM                 = -22,
     CSIC_ECAPTURE               = -23, /* the HIP stream is capturing and this operation cannot be captured */
     CSIC_EIO                    = -30, /* file cannot be opened / read / written                       */
-    CSIC_EFORMAT                = -31  /* not a PNG, corrupt, or an unsupported PNG feature            */
+    CSIC_EFORMAT                = -31  /* not a PNG / .csic file, corrupt, or an unsupported feature   */
 } csic_status;
 
 /* ---- enumerations -------------------------------------------------------------------------------*/
@@ -348,6 +348,40 @@ int  csic_reconstruct_device(csic_plan *plan, const void *d_planar, void *d_out,
 int  csic_reconstruct_bits_device(csic_plan *plan, const void *d_bits, void *d_out, int32_t nframes, int32_t out_format,
                                   void *hip_stream);
 
+/* ---- full-resolution decode: a compressed frame back to width x height pixels ----------------------------------------------
+ * csic_reconstruct*_device and csic_process_device stop at the decimated frame, out_width x out_height.  csic_decode_* produce the
+ * frame a viewer looks at, and the one csic_distortion_* measures.
+ *
+ * Definition.  Let o be the packed output of the plan's parameters in `out_format`, out_width x out_height (what
+ * csic_reconstruct*_device yields from a planar source and csic_process_device yields directly).  Then
+ *     decode(r, c) = o(r / f, c / f)        0 <= r < height, 0 <= c < width, integer division by the plan's factor f
+ * -- replication upsampling; ragged edges follow the same rule because out_width = ceil(width / f).  At f = 1 the decode equals the
+ * reconstruct output bit for bit.  Only the plan's parameters matter, as for reconstruct: any in_format, any out_format of the plan,
+ * HOLD_DECIMATE or AVG, all six orders.  It is the pairing of csic_distortion_*: the sums of squared differences between an input
+ * frame and decode(compress(input)) ARE that frame's distortion, channel by channel.
+ *
+ * src_format: CSIC_FMT_PLANAR_BITS / CSIC_FMT_PLANAR -- frames frame_bytes apart (csic_planar_bits_layout_of / csic_planar_layout_of),
+ *             256-byte aligned (CSIC_EINVAL_SIZE otherwise), the chroma replay rule of csic_reconstruct_device, replay_last rows included;
+ *             CSIC_FMT_YCBCR888X / CSIC_FMT_ARGB8888 -- out_width * out_height packed pixels per frame, back to back.
+ * out_format: CSIC_FMT_ARGB8888 (through YCbCrUtils.ycbcr2rgb, as every packed ARGB output) or CSIC_FMT_YCBCR888X; width * height
+ *             pixels per frame, back to back.  An ARGB source is replicated as it is; an ARGB source with a YCbCr output is refused
+ *             (CSIC_EINVAL_FORMAT: the inverse transform has no inverse).
+ * csic_decode_device : asynchronous on `hip_stream`, no allocation, no synchronisation, hipGraph-capturable; NULL arguments fail with
+ *             CSIC_EINVAL_NULL and nframes <= 0 with CSIC_EINVAL_SIZE before any device is touched.  A packed source or an output that
+ *             is only 4-byte aligned works (4-byte accesses).  More than 65535 frames go out as several launches.
+ * csic_decode_host   : the same from and to host memory, synchronous, allocates its staging; src_bytes = nframes * frame_bytes (planar
+ *             sources) or nframes * out_width * out_height * 4, out_px = nframes * width * height (CSIC_EINVAL_SIZE otherwise).
+ * csic_decode_kernel_name : the kernel csic_decode_device takes for one frame in 16-byte aligned buffers ("" for a refused format pair).  At f = 1 a
+ *             planar source is a reconstruct and the name is that kernel's (k_rbits / k_recon).  The string belongs to the calling
+ *             thread and is valid until its next call of this function.
+ * CSIC_TUNE_VARIANT 9, CSIC_TUNE_NO_VECTOR and CSIC_TUNE_FORCE_GENERIC select the general kernel (one output pixel per lane);
+ * CSIC_TUNE_NONTEMPORAL and CSIC_TUNE_BLOCK_THREADS apply as in csic_reconstruct_bits_device. */
+int  csic_decode_device(csic_plan *plan, const void *d_src, int32_t src_format, void *d_out, int32_t out_format, int32_t nframes,
+                        void *hip_stream);
+int  csic_decode_host(csic_plan *plan, const void *src, size_t src_bytes, int32_t src_format, uint32_t *out, size_t out_px,
+                      int32_t out_format, int32_t nframes);
+const char *csic_decode_kernel_name(const csic_plan *plan, int32_t src_format, int32_t out_format);
+
 /* Row pitches, in pixels, at which frames of this plan stream fastest when the CALLER lays them out
  * (csic_process_pitched_device).  Measured on 2048- to 16384-pixel rows x every factor x 13 (input pad, output pad) pairs
  * (tools/probe_pitch2.py, profiles/r04_probe_pitch.jsonl, r04_probe_pitch_f1flat.jsonl): on the round-4 kernels packed rows are
@@ -509,6 +543,40 @@ int  csic_frame_graph_destroy(csic_frame_graph *graph);
 int  csic_png_info(const char *path, int32_t *width, int32_t *height);
 int  csic_png_read_argb(const char *path, uint32_t *dst, size_t dst_px);
 int  csic_png_write_argb(const char *path, const uint32_t *src, int32_t width, int32_t height, int32_t level);
+
+/* ---- .csic files: the compressed frames on disk (host only, usable without a GPU) --------------------------------------------
+ * A container holds `nframes` CSIC_FMT_PLANAR_BITS frames of one parameter set: the only thing this library writes to a file that
+ * is smaller than its input (a 6/5/5 4:2:0 frame: 1.06 bytes per pixel at factor 1).  Version 1, every integer little endian:
+ *
+ *     offset  size                     content
+ *          0     4                     magic 43 53 49 43 ("CSIC")
+ *          4     4                     uint32 version = 1
+ *          8     4                     uint32 nframes, 1 .. 65535
+ *         12     4                     uint32 CRC-32 (zlib's crc32) of bytes [16, end of file)
+ *         16    64                     csic_params as 16 int32 in the struct's field order; out_format = CSIC_FMT_PLANAR_BITS,
+ *                                      in_format = CSIC_FMT_ARGB8888
+ *         80     nframes * payload     per frame: the Y plane's y_bytes, then cb_bytes, then cr_bytes, back to back
+ *                                      (csic_planar_bits_layout_of; payload = payload_bytes)
+ *
+ * `frames` is what csic_process_host and csic_pipeline_collect hand out for a PLANAR_BITS plan: nframes frame buffers, frame_bytes
+ * apart, in host memory.  Only the three payload ranges of each buffer are written -- its padding is undefined and never reaches
+ * the file -- and csic_container_read zeroes every byte of the buffers outside those ranges, so what it returns is deterministic.
+ *   csic_container_write   : stores out_format = CSIC_FMT_PLANAR_BITS whatever p->out_format says; fails with csic_validate's status
+ *                            when the parameters are invalid or p->in_format is not ARGB; nframes outside 1 .. 65535: CSIC_EINVAL_SIZE.
+ *   csic_container_info_of : header, parameters and length of a file (everything csic_container_read checks except the CRC).
+ *   csic_container_read    : frames_bytes must equal nframes * frame_bytes (CSIC_EINVAL_SIZE otherwise; ask csic_container_info_of).
+ * CSIC_EFORMAT: bad magic, version != 1, nframes out of range, parameters that fail csic_validate (or are not PLANAR_BITS), a length
+ * other than 80 + nframes * payload_bytes, a CRC mismatch.  CSIC_EIO: the file cannot be opened, read or written.  NULL arguments:
+ * CSIC_EINVAL_NULL. */
+typedef struct csic_container_info {
+    csic_params params;            /* out_format = CSIC_FMT_PLANAR_BITS, in_format = CSIC_FMT_ARGB8888 */
+    int32_t version, nframes;
+    int64_t payload_bytes;         /* per frame = csic_planar_bits_layout_of(params).payload_bytes */
+    int64_t file_bytes;
+} csic_container_info;
+int  csic_container_info_of(const char *path, csic_container_info *info);
+int  csic_container_write(const char *path, const csic_params *p, const void *frames, int32_t nframes);
+int  csic_container_read(const char *path, void *frames, size_t frames_bytes);
 
 /* ---- host-frame pipeline (the step either side of the hot path) -----------------------------------
  * Replaces the reference's per-image  readImage -> per-pixel poke ... peek -> writeImage  flow

@@ -109,6 +109,38 @@ struct PlanarBitsFrame {
     std::vector<uint8_t> bytes;                                   // layout.frame_bytes long
 };
 
+// A .csic file (csic.h: csic_container_*): `nframes` bit-packed planar frame buffers of one parameter set, layout.frame_bytes apart
+// in `bytes`.  Host only -- none of the three functions needs a GPU.  File and format errors surface as csic::RuntimeError with
+// status CSIC_EIO / CSIC_EFORMAT.
+struct Container {
+    csic_params params{};
+    int nframes = 0;
+    csic_planar_bits_layout layout{};
+    std::vector<uint8_t> bytes;                                   // nframes * layout.frame_bytes, zero outside the planes' payload
+};
+inline csic_container_info containerInfo(const std::string &file)
+{
+    csic_container_info info;
+    check(csic_container_info_of(file.c_str(), &info));
+    return info;
+}
+// frames: nframes PLANAR_BITS frame buffers of `p`, frame_bytes apart (p.out_format does not matter)
+inline void writeContainer(const std::string &file, const csic_params &p, const void *frames, int nframes)
+{
+    check(csic_container_write(file.c_str(), &p, frames, nframes));
+}
+inline Container readContainer(const std::string &file)
+{
+    Container c;
+    const csic_container_info info = containerInfo(file);
+    c.params = info.params;
+    c.nframes = info.nframes;
+    check(csic_planar_bits_layout_of(&c.params, &c.layout));
+    c.bytes.resize((size_t)c.nframes * (size_t)c.layout.frame_bytes);
+    check(csic_container_read(file.c_str(), c.bytes.data(), c.bytes.size()));
+    return c;
+}
+
 // The six sums of squared errors of one frame (csic.h: csic_distortion_*), in the order R, G, B, Y, Cb, Cr, over `pixels` input
 // pixels, with the PSNR helpers (+inf at zero error).
 struct Distortion {
@@ -210,6 +242,29 @@ public:
     {
         check(csic_reconstruct_bits_device(plan(PixelFormat::PLANAR_BITS), d_bits, d_out, nframes, (int32_t)f, hip_stream));
     }
+    // Full-resolution decode (csic_decode_*): a compressed frame -> width x height packed pixels, every pixel of the packed output
+    // replicated factor x factor times.  decode() moves `nframes` host frames in `src` format (PLANAR_BITS / PLANAR frame buffers,
+    // or the packed YCBCR888X / ARGB8888 output); decodeDevice() is device-resident and asynchronous on `hip_stream`.
+    std::vector<uint32_t> decode(const void *src, size_t src_bytes, PixelFormat src_format = PixelFormat::PLANAR_BITS,
+                                 PixelFormat f = PixelFormat::ARGB8888, int nframes = 1)
+    {
+        std::vector<uint32_t> out((size_t)params_.width * (size_t)params_.height * (size_t)(nframes > 0 ? nframes : 0));
+        check(csic_decode_host(plan(PixelFormat::ARGB8888), src, src_bytes, (int32_t)src_format, out.data(), out.size(), (int32_t)f, nframes));
+        return out;
+    }
+    std::vector<uint32_t> decode(const PlanarBitsFrame &fr, PixelFormat f = PixelFormat::ARGB8888)
+    {
+        return decode(fr.bytes.data(), fr.bytes.size(), PixelFormat::PLANAR_BITS, f, 1);
+    }
+    void decodeDevice(const void *d_src, PixelFormat src_format, void *d_out, int nframes, void *hip_stream, PixelFormat f = PixelFormat::ARGB8888)
+    {
+        check(csic_decode_device(plan(PixelFormat::ARGB8888), d_src, (int32_t)src_format, d_out, (int32_t)f, nframes, hip_stream));
+    }
+    const char *decodeKernelName(PixelFormat src_format, PixelFormat f = PixelFormat::ARGB8888)
+    {
+        return csic_decode_kernel_name(plan(PixelFormat::ARGB8888), (int32_t)src_format, (int32_t)f);
+    }
+    const csic_params &params() const { return params_; }
     // what row pitch (pixels, input / output) a caller that owns its surfaces should allocate for csic_process_pitched_device
     std::pair<int, int> preferredPitch(PixelFormat f = PixelFormat::ARGB8888)
     {
