@@ -25,7 +25,8 @@ TUNE_VARIANT, TUNE_FORCE_GENERIC, TUNE_NONTEMPORAL, TUNE_NO_VECTOR, TUNE_BLOCK_T
 FRAME_GRAPH_HIP, FRAME_GRAPH_DIRECT, FRAME_GRAPH_FUSED, FRAME_GRAPH_AUTO = 0, 1, 2, 3
 FRAME_GRAPH_DEFAULT_BRANCHES, FRAME_GRAPH_DEFAULT_QUEUES = 4, 3
 PIPELINE_STAGED, PIPELINE_ZERO_COPY = 0, 1
-DIST_CHANNELS = 6                       # R, G, B, Y, Cb, Cr (csic_distortion_*)
+DIST_CHANNELS = 6                       # R, G, B, Y, Cb, Cr (csic_distortion_*, csic_ssim_*)
+SSIM_WINDOW, SSIM_ONE = 8, 65536        # csic_ssim_*: window edge in pixels, SSIM 1.0 in 16.16 fixed point
 
 
 class IllegalArgumentException(ValueError):
@@ -125,6 +126,10 @@ PROTOTYPES = {
     "csic_distortion_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "csic_distortion_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_uint64)]),
     "csic_distortion_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "csic_ssim_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
+    "csic_ssim_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "csic_ssim_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_int64), C.c_void_p]),
+    "csic_ssim_kernel_name": (C.c_char_p, [C.c_void_p]),
     "csic_plan_preferred_pitch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "csic_debug_build": (C.c_int, []),
     "csic_debug_probe_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),

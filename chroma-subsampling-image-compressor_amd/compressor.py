@@ -61,6 +61,36 @@ class Distortion:
         return f"Distortion(sse={self.sse}, pixels={self.pixels})"
 
 
+class Ssim:
+    """The six sums of the 8 x 8 block SSIM of one frame (csic_ssim_*; definition in include/csic.h), in the order
+    R, G, B, Y, Cb, Cr: each the sum of the windows' 16.16 fixed-point quotients over `windows` windows.  mean(ch) is the
+    channel's mean SSIM (index or name), mean_rgb the mean of the R, G and B means; 1.0 exactly for an output equal to the input."""
+
+    CHANNELS = Distortion.CHANNELS
+
+    def __init__(self, sums, windows: int):
+        self.sums = tuple(int(v) for v in sums)
+        if len(self.sums) != N.DIST_CHANNELS:
+            raise ValueError(f"need {N.DIST_CHANNELS} sums (R, G, B, Y, Cb, Cr), got {len(self.sums)}")
+        self.windows = int(windows)
+
+    def _index(self, ch) -> int:
+        return self.CHANNELS.index(ch) if isinstance(ch, str) else int(ch)
+
+    def mean(self, ch) -> float:
+        return self.sums[self._index(ch)] / (N.SSIM_ONE * self.windows)
+
+    @property
+    def mean_rgb(self) -> float:
+        return (self.mean(0) + self.mean(1) + self.mean(2)) / 3.0
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Ssim) and (self.sums, self.windows) == (other.sums, other.windows)
+
+    def __repr__(self) -> str:
+        return f"Ssim(sums={self.sums}, windows={self.windows})"
+
+
 class Plan:
     """One validated parameter set bound to one HIP device (csic_plan_create / csic_plan_destroy)."""
 
@@ -196,6 +226,72 @@ class Plan:
             sse = self.distortion_host(a, n)
             single = a.ndim != 3
         out = [Distortion(row, px) for row in sse]
+        return out[0] if single and n == 1 else out
+
+    # -- structural similarity (csic_ssim_*) -----------------------------------------------------
+    @property
+    def ssim_kernel_name(self) -> str:
+        return N.lib().csic_ssim_kernel_name(self._h).decode()
+
+    @property
+    def ssim_windows(self) -> Tuple[int, int]:
+        """(rows, columns) of 8 x 8 windows in a frame."""
+        return self.height // N.SSIM_WINDOW, self.width // N.SSIM_WINDOW
+
+    def ssim_workspace_bytes(self, nframes: int = 1) -> int:
+        b = C.c_size_t()
+        N.check(N.lib().csic_ssim_workspace_bytes(self._h, int(nframes), C.byref(b)))
+        return b.value
+
+    def ssim_device(self, d_in, nframes: int = 1, want_map: bool = False):
+        """d_in: contiguous 4-byte CUDA tensor of nframes * W * H input pixels.  Returns an int64 tensor (nframes, 6) on the
+        device: the sums of the windows' quotients for R, G, B, Y, Cb, Cr of each frame; with want_map, (sums, map), the map an
+        int32 tensor (nframes, 6, H / 8, W / 8) of the quotients themselves.  Asynchronous on torch's current stream; the plan
+        keeps its workspace between calls (allocate it with a first call before capturing the call into a graph)."""
+        import torch
+        if not d_in.is_cuda or d_in.element_size() != 4 or not d_in.is_contiguous():
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_in must be a contiguous 4-byte CUDA tensor")
+        if d_in.device.index != self.device:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: tensor is on a different device than the plan")
+        if d_in.numel() != nframes * self.width * self.height:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: expected {nframes * self.width * self.height} input pixels, got {d_in.numel()}")
+        need = self.ssim_workspace_bytes(nframes)
+        ws = getattr(self, "_ssim_ws", None)
+        if ws is None or ws.numel() * 8 < need or ws.device != d_in.device:
+            ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=d_in.device)
+            self._ssim_ws = ws
+        d_ssim = torch.empty((nframes, N.DIST_CHANNELS), dtype=torch.int64, device=d_in.device)
+        d_map = torch.empty((nframes, N.DIST_CHANNELS) + self.ssim_windows, dtype=torch.int32, device=d_in.device) if want_map else None
+        N.check(N.lib().csic_ssim_device(self._h, C.c_void_p(d_in.data_ptr()), int(nframes), C.c_void_p(d_ssim.data_ptr()),
+                                         C.c_void_p(d_map.data_ptr()) if want_map else None, C.c_void_p(ws.data_ptr()),
+                                         ws.numel() * 8, self._stream()))
+        return (d_ssim, d_map) if want_map else d_ssim
+
+    def ssim_host(self, frames: np.ndarray, nframes: int = 1, want_map: bool = False):
+        """csic_ssim_host: nframes * W * H host pixels -> int64 array (nframes, 6); with want_map, (sums, map), the map an int32
+        array (nframes, 6, H / 8, W / 8)."""
+        a = np.ascontiguousarray(frames, dtype=np.uint32).reshape(-1)
+        sums = np.zeros((nframes, N.DIST_CHANNELS), dtype=np.int64)
+        smap = np.zeros((nframes, N.DIST_CHANNELS) + self.ssim_windows, dtype=np.int32) if want_map else None
+        N.check(N.lib().csic_ssim_host(self._h, a.ctypes.data_as(C.c_void_p), a.size, int(nframes),
+                                       sums.ctypes.data_as(C.POINTER(C.c_int64)), smap.ctypes.data_as(C.c_void_p) if want_map else None))
+        return (sums, smap) if want_map else sums
+
+    def ssim(self, frames):
+        """One frame ((H, W), or flat W * H) -> Ssim; a stack (n, H, W) -> list of Ssim.  numpy input goes through csic_ssim_host,
+        a CUDA tensor through ssim_device (synchronised here)."""
+        px = self.width * self.height
+        if _is_torch_tensor(frames):
+            n = frames.numel() // px if px else 0
+            sums = self.ssim_device(frames.contiguous(), n).cpu().numpy()
+            single = frames.dim() != 3
+        else:
+            a = np.asarray(frames)
+            n = a.size // px if px else 0
+            sums = self.ssim_host(a, n)
+            single = a.ndim != 3
+        wy, wx = self.ssim_windows
+        out = [Ssim(row, wy * wx) for row in sums]
         return out[0] if single and n == 1 else out
 
     # -- compute ----------------------------------------------------------------------------------
@@ -509,6 +605,11 @@ class ImageCompressorTop:
         """What these parameters cost in image quality on `argb` (one frame, or a stack (n, H, W)): Distortion (list of them for a
         stack) -- the per-channel sums of squared errors against the packed ARGB / YCbCr outputs and their PSNR."""
         return self.plan(PixelFormat.ARGB8888).distortion(argb)
+
+    def ssim(self, argb):
+        """How much of the structure of `argb` (one frame, or a stack (n, H, W)) these parameters keep: Ssim (list of them for a
+        stack) -- the per-channel 8 x 8 block SSIM against the packed ARGB / YCbCr outputs."""
+        return self.plan(PixelFormat.ARGB8888).ssim(argb)
 
     def processPlanarBits(self, argb):
         """ARGB frame in -> one bit-packed planar frame buffer (CSIC_FMT_PLANAR_BITS, uint8: planar_bits_layout.frame_bytes on the

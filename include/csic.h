@@ -276,6 +276,55 @@ int  csic_distortion_device(csic_plan *plan, const void *d_in, int32_t nframes, 
 int  csic_distortion_host(csic_plan *plan, const uint32_t *in, size_t in_px, int32_t nframes, uint64_t *sse);
 const char *csic_distortion_kernel_name(const csic_plan *plan);
 
+/* ---- structural similarity: 8 x 8 block SSIM, in integers ---------------------------------------------------------------------
+ * Channels and pairing are exactly those of csic_distortion_*: the reference value of an input pixel in R, G, B, Y, Cb, Cr against
+ * the paired output pixel (r / f, c / f) of o_rgb (R, G, B) and of o_ycc (Y, Cb, Cr); any in_format, every order, HOLD_DECIMATE
+ * and AVG; the plan's own out_format does not matter.
+ *
+ * Windows: non-overlapping 8 x 8 blocks of input pixels with their top-left corner at (8 wy, 8 wx), wy < height / 8, wx < width / 8
+ * (integer division).  Pixels beyond the last whole window are not measured; a frame with width < 8 or height < 8 has no window and
+ * is refused with CSIC_EINVAL_DIMS.  f divides 8, so a window covers whole f x f replication cells.
+ *
+ * Per window and channel, with x the 64 reference values and y the 64 paired output values:
+ *     s1 = sum x    s2 = sum y    ss = sum x^2 + sum y^2    s12 = sum xy
+ *     vars  = 64 ss  - s1^2 - s2^2
+ *     covar = 64 s12 - s1 s2
+ *     c1 = 416      (= floor(0.01^2 255^2 64 + 0.5))
+ *     c2 = 235963   (= floor(0.03^2 255^2 64 63 + 0.5))
+ *     N = (2 s1 s2 + c1) (2 covar + c2)          signed 64-bit; |N| <= 7.2e16
+ *     D = (s1^2 + s2^2 + c1) (vars + c2)         98 160 608 <= D <= 7.2e16
+ *     q = sign(N) floor(64 |N| / floor(D / 1024))      SSIM in 16.16 fixed point, rounded toward zero
+ * The constants and the 64 sum - s^2 form are the customary integer 8 x 8 SSIM; only the final quotient is pinned to integers here,
+ * so that the GPU, numpy and any other host agree bit for bit.  Properties: 64 |N| < 2^63; |N| <= D, hence |q| <= 65536; q = 65536
+ * exactly when x = y; |q / 65536 - N / D| < 2.6e-5 (1 / 65536 from the floor plus at most 1.05e-5 relative from truncating D, since
+ * floor(D / 1024) >= 95 859).
+ *
+ * Outputs: d_ssim[nframes * 6], int64, the sum of q over the frame's windows in the order R, G, B, Y, Cb, Cr.  The mean SSIM of a
+ * channel is sum / (65536 (width / 8) (height / 8)) and the combined RGB figure the mean of the three channel means (host layers).
+ * d_map, which may be NULL: int32 [frame][channel][height / 8][width / 8], each entry that window's q -- where the loss is.
+ *
+ * csic_ssim_workspace_bytes : the workspace csic_ssim_device needs for `nframes` (1..65535) frames of this plan (one 48-byte partial
+ *                             per block of 32 windows).  Needs no device.  CSIC_EINVAL_DIMS for a frame without a window.
+ * csic_ssim_device          : d_in -> d_ssim[nframes * 6] (8-byte aligned) and, unless NULL, d_map (4-byte aligned), through
+ *                             d_workspace (8-byte aligned, at least the queried size); a short workspace, a misaligned pointer or
+ *                             nframes outside 1..65535 fail with CSIC_EINVAL_SIZE.  Asynchronous on `hip_stream`, no allocation, no
+ *                             synchronisation, hipGraph-capturable; NULL plan, d_in, d_ssim or workspace fail with CSIC_EINVAL_NULL
+ *                             before any device is touched.  16-byte loads when d_in is 16-byte aligned, 4-byte loads otherwise.
+ * csic_ssim_host            : the same from host memory (in_px = nframes * width * height) into ssim[nframes * 6] and, unless NULL,
+ *                             map; synchronous, allocates its staging.
+ * csic_ssim_kernel_name     : the kernel csic_ssim_device takes (static string): k_ssim_fast<f1> / <f2> for the plans
+ *                             k_dist_fast serves whose width and height are multiples of 8, k_ssim_gen<hold> / <avg> otherwise,
+ *                             with ",ycc-in" for a YCbCr input.
+ * CSIC_TUNE_FORCE_GENERIC selects k_ssim_gen, CSIC_TUNE_NONTEMPORAL = 0 cached loads and CSIC_TUNE_NO_VECTOR the 4-byte loads of
+ * k_ssim_fast. */
+#define CSIC_SSIM_WINDOW 8
+#define CSIC_SSIM_ONE    65536
+int  csic_ssim_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes);
+int  csic_ssim_device(csic_plan *plan, const void *d_in, int32_t nframes, int64_t *d_ssim, int32_t *d_map,
+                      void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int  csic_ssim_host(csic_plan *plan, const uint32_t *in, size_t in_px, int32_t nframes, int64_t *ssim, int32_t *map);
+const char *csic_ssim_kernel_name(const csic_plan *plan);
+
 const char *csic_strerror(int status);
 const char *csic_last_error(void);       /* thread-local; "" when the last call succeeded */
 
@@ -301,7 +350,8 @@ const char *csic_plan_kernel_name(const csic_plan *plan);
  *                       11 = factor 1: k_f1x4 (rounds 1-3's kernel) instead of k_f1flat,
  *                       12 = planar AVG at factor 1 on frames of whole tiles: k_avg's body with the planar sink instead of k_planar_avg_f1)
  *   CSIC_TUNE_FORCE_GENERIC : 1 = always use the one-thread-per-pixel generic kernel
- *                             (csic_distortion_device: its general kernel k_dist_gen; nothing else changes for the other entry points)
+ *                             (csic_distortion_device: its general kernel k_dist_gen; csic_ssim_device: its general kernel
+ *                             k_ssim_gen; nothing else changes for the other entry points)
  *   CSIC_TUNE_NONTEMPORAL   : 1 (default) = non-temporal loads/stores for the frame stream, 0 = cached
  *   CSIC_TUNE_NO_VECTOR     : 1 = never use the 16-byte-per-lane kernels
  *   CSIC_TUNE_BLOCK_THREADS : threads per block, 64 / 128 / 256 (0 = the library's choice) */

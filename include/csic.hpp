@@ -159,6 +159,17 @@ private:
     }
 };
 
+// The six sums of the 8 x 8 block SSIM of one frame (csic.h: csic_ssim_*), in the order R, G, B, Y, Cb, Cr: each the sum of the
+// windows' 16.16 fixed-point quotients over `windows` windows; `map`, when asked for, holds the quotients [channel][wy][wx].
+struct Ssim {
+    enum Channel { R = 0, G = 1, B = 2, Y = 3, Cb = 4, Cr = 5 };
+    int64_t sums[CSIC_DIST_CHANNELS] = {0, 0, 0, 0, 0, 0};
+    int64_t windows = 0;
+    std::vector<int32_t> map;
+    double mean(int ch) const { return (double)sums[ch] / ((double)CSIC_SSIM_ONE * (double)windows); }
+    double meanRgb() const { return (mean(R) + mean(G) + mean(B)) / 3.0; }
+};
+
 class ImageCompressorTop {
 public:
     ImageCompressorTop(int width, int height, int chroma_param_a_config, int chroma_param_b_config,
@@ -303,6 +314,36 @@ public:
         }
         return out;
     }
+    // How much of the structure of `nframes` ARGB frames back to back (host memory) these parameters keep: one Ssim per frame,
+    // with the per-window map if `want_map`.
+    std::vector<Ssim> ssim(const uint32_t *argb, int nframes = 1, bool want_map = false)
+    {
+        const size_t n = (size_t)(nframes > 0 ? nframes : 0), px = (size_t)params_.width * (size_t)params_.height;
+        const size_t windows = (size_t)(params_.width / CSIC_SSIM_WINDOW) * (size_t)(params_.height / CSIC_SSIM_WINDOW);
+        std::vector<int64_t> sums(n * CSIC_DIST_CHANNELS);
+        std::vector<int32_t> map(want_map ? n * CSIC_DIST_CHANNELS * windows : 0);
+        check(csic_ssim_host(plan(PixelFormat::ARGB8888), argb, px * n, nframes, sums.data(), want_map ? map.data() : nullptr));
+        std::vector<Ssim> out(n);
+        for (size_t k = 0; k < n; ++k) {
+            for (int c = 0; c < CSIC_DIST_CHANNELS; ++c) out[k].sums[c] = sums[k * CSIC_DIST_CHANNELS + (size_t)c];
+            out[k].windows = (int64_t)windows;
+            if (want_map) out[k].map.assign(map.begin() + (ptrdiff_t)(k * CSIC_DIST_CHANNELS * windows), map.begin() + (ptrdiff_t)((k + 1) * CSIC_DIST_CHANNELS * windows));
+        }
+        return out;
+    }
+    // device-resident: d_in holds `nframes` frames, d_ssim receives nframes * 6 sums (8-byte aligned), d_map (or NULL) the
+    // quotients, d_workspace at least ssimWorkspaceBytes(nframes) bytes; asynchronous on `hip_stream`, no allocation, capturable.
+    size_t ssimWorkspaceBytes(int nframes = 1)
+    {
+        size_t b = 0;
+        check(csic_ssim_workspace_bytes(plan(PixelFormat::ARGB8888), nframes, &b));
+        return b;
+    }
+    void ssimDevice(const void *d_in, int nframes, int64_t *d_ssim, int32_t *d_map, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+    {
+        check(csic_ssim_device(plan(PixelFormat::ARGB8888), d_in, nframes, d_ssim, d_map, d_workspace, workspace_bytes, hip_stream));
+    }
+    const char *ssimKernelName() { return csic_ssim_kernel_name(plan(PixelFormat::ARGB8888)); }
     // the plan behind process(): what FrameGraph records launches of (owned by this object)
     csic_plan *nativePlan(PixelFormat f = PixelFormat::ARGB8888) { return plan(f); }
 

@@ -2,8 +2,9 @@
 """tools/rd_sweep.py [OUT_PREFIX] -- the rate-distortion table of the committed golden inputs (tests/golden/inputs/in128.png and
 in512.png) on the GPU: chroma 4:4:4 / 4:2:2 / 4:2:0 / 4:1:1 x bits 8/8/8, 6/5/5, 4/4/4, 3/3/2 x factor 1, 2 x HOLD / AVG (order
 chroma, spatial, quant).  Rate: bits per input pixel of the bit-packed planar frame, 8 * csic_planar_bits_layout_of(...).payload_bytes
-/ (W * H).  Distortion: csic_distortion_host -> PSNR-RGB and PSNR-Y / Cb / Cr (dB, inf when lossless).  Writes OUT_PREFIX.jsonl and
-OUT_PREFIX.md (default profiles/r06_rd_sweep)."""
+/ (W * H).  Distortion: csic_distortion_host -> PSNR-RGB and PSNR-Y / Cb / Cr (dB, inf when lossless); csic_ssim_host -> the mean
+8 x 8 block SSIM of Y, Cb, Cr and of R, G, B together.  Writes OUT_PREFIX.jsonl and OUT_PREFIX.md (default profiles/r09_rd_sweep;
+profiles/r06_rd_sweep.* is the table from before the SSIM columns)."""
 import ctypes as C
 import json
 import math
@@ -16,7 +17,7 @@ import numpy as np  # noqa: E402
 import csic_amd as csic  # noqa: E402
 
 N = csic._native
-PREFIX = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r06_rd_sweep")
+PREFIX = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r09_rd_sweep")
 CSQ = (3, 1, 2)
 CHROMA = (("4:4:4", 4, 4), ("4:2:2", 2, 2), ("4:2:0", 2, 0), ("4:1:1", 1, 1))
 BITS = ((8, 8, 8), (6, 5, 5), (4, 4, 4), (3, 3, 2))
@@ -48,11 +49,14 @@ def main():
                         N.check(N.lib().csic_planar_bits_layout_of(C.byref(cp), C.byref(lay)))
                         with csic.Plan(cp, 0) as pl:
                             d = pl.distortion(img)
-                            kernel = pl.distortion_kernel_name
+                            q = pl.ssim(img)
+                            kernel, ssim_kernel = pl.distortion_kernel_name, pl.ssim_kernel_name
                         r = {"image": name, "shape": f"{W}x{H}", "chroma": cname, "bits": list(bits), "factor": f, "sampling": sampling,
                              "bpp": round(8 * lay.payload_bytes / (W * H), 4), "psnr_rgb": round(d.psnr_rgb, 3),
                              "psnr_y": round(d.psnr("Y"), 3), "psnr_cb": round(d.psnr("Cb"), 3), "psnr_cr": round(d.psnr("Cr"), 3),
-                             "sse": list(d.sse), "kernel": kernel}
+                             "sse": list(d.sse), "kernel": kernel, "ssim_rgb": round(q.mean_rgb, 5), "ssim_y": round(q.mean("Y"), 5),
+                             "ssim_cb": round(q.mean("Cb"), 5), "ssim_cr": round(q.mean("Cr"), 5), "ssim_sums": list(q.sums),
+                             "ssim_windows": q.windows, "ssim_kernel": ssim_kernel}
                         rows.append(r)
                         print(json.dumps(r), flush=True)
     os.makedirs(os.path.dirname(PREFIX) or ".", exist_ok=True)
@@ -63,12 +67,14 @@ def main():
         fh.write("# Rate-distortion of the golden inputs (tools/rd_sweep.py)\n\n"
                  "Order chroma, spatial, quant; floor rounding.  bpp = bits per input pixel of the bit-packed planar frame "
                  "(csic_planar_bits_layout_of payload); PSNR in dB against the input, every input pixel paired with its output "
-                 "pixel by replication (csic_distortion_*).\n\n")
-        fh.write("| image | chroma | bits | f | sampling | bpp | PSNR-RGB | PSNR-Y | PSNR-Cb | PSNR-Cr |\n"
-                 "|---|---|---|---|---|---:|---:|---:|---:|---:|\n")
+                 "pixel by replication (csic_distortion_*); SSIM is the mean 8 x 8 block SSIM of the same pairing (csic_ssim_*), "
+                 "SSIM-RGB the mean of the R, G and B means.\n\n")
+        fh.write("| image | chroma | bits | f | sampling | bpp | PSNR-RGB | PSNR-Y | PSNR-Cb | PSNR-Cr | SSIM-RGB | SSIM-Y | SSIM-Cb | SSIM-Cr |\n"
+                 "|---|---|---|---|---|---:|---:|---:|---:|---:|---:|---:|---:|---:|\n")
         for r in rows:
             fh.write(f"| {r['image']} | {r['chroma']} | {'/'.join(map(str, r['bits']))} | {r['factor']} | {r['sampling']} | {r['bpp']:.3f} | "
-                     f"{fmt_db(r['psnr_rgb'])} | {fmt_db(r['psnr_y'])} | {fmt_db(r['psnr_cb'])} | {fmt_db(r['psnr_cr'])} |\n")
+                     f"{fmt_db(r['psnr_rgb'])} | {fmt_db(r['psnr_y'])} | {fmt_db(r['psnr_cb'])} | {fmt_db(r['psnr_cr'])} | "
+                     f"{r['ssim_rgb']:.4f} | {r['ssim_y']:.4f} | {r['ssim_cb']:.4f} | {r['ssim_cr']:.4f} |\n")
 
 
 if __name__ == "__main__":
