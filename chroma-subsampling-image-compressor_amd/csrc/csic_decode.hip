@@ -438,19 +438,15 @@ int csic_decode_host(csic_plan *plan, const void *src, size_t src_bytes, int32_t
     if (src_bytes != need_src) return set_error(CSIC_EINVAL_SIZE, "expected %zu source bytes (%d frames), got %zu", need_src, nframes, src_bytes);
     if (out_px != need_out) return set_error(CSIC_EINVAL_SIZE, "expected room for %zu output pixels (%d frames), got %zu", need_out, nframes, out_px);
     CSIC_DEVICE_SCOPE(plan->device);
-    void *d_src = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc(&d_src, need_src);
-    if (e == hipSuccess) e = hipMalloc(&d_out, need_out * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_src, src, need_src, hipMemcpyHostToDevice, nullptr);
-    if (e == hipSuccess) {
+    DeviceStaging dev;
+    void *d_src = dev.alloc(need_src), *d_out = dev.alloc(need_out * 4);
+    dev.to_device(d_src, src, need_src);
+    if (dev.ok()) {
         st = csic_decode_device(plan, d_src, src_format, d_out, out_format, nframes, nullptr);
-        if (st == CSIC_OK) e = hipMemcpyAsync(out, d_out, need_out * 4, hipMemcpyDeviceToHost, nullptr);
-        if (st == CSIC_OK && e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (st == CSIC_OK) { dev.to_host(out, d_out, need_out * 4); dev.sync(); }
     }
-    if (d_src) (void)hipFree(d_src);
-    if (d_out) (void)hipFree(d_out);
     if (st != CSIC_OK) return st;
-    if (e != hipSuccess) return set_error(CSIC_EHIP, "csic_decode_host: %s", hipGetErrorString(e));
+    if (!dev.ok()) return set_error(CSIC_EHIP, "csic_decode_host: %s", hipGetErrorString(dev.error()));
     clear_error();
     return CSIC_OK;
 }

@@ -12,21 +12,21 @@
 //                      is inside the unit too), and only a 4:x:0 odd row at F = 1 needs one more pixel -- the last sample of the row
 //                      above, one row-uniform load issued only by waves that sit on such a row (as k_f1flat).  K = 4 / F units per
 //                      lane spaced by the block: 16 input pixels per lane, 4096 per block, all loads issued before any arithmetic.
-//   k_dist_gen<ROUND, AVG, INFMT>   anything csic_validate accepts: one output pixel per lane, computed as k_generic (HOLD) or
-//                      avg_pixel_generic (AVG) compute it, then its f x f input block, clamped at the frame edge.
-//   k_dist_reduce      one block per frame: the frame's partials, summed in a fixed order, -> d_sse[frame * 6 + channel].
+//   k_dist_gen<ROUND, AVG, INFMT>   anything csic_validate accepts: one output pixel per lane (measure_out_pixel: hold_pixel_generic
+//                      for HOLD, avg_pixel_generic for AVG), then its f x f input block, clamped at the frame edge.
+//   k_sum_partials     (csic_measure.h) one block per frame: the frame's partials, summed in a fixed order, -> d_sse[frame * 6 + channel].
+// Which of the two a plan takes is measure_kind (csic_select.cpp); what this unit shares with csic_ssim.hip is csic_measure.h.
 // Accumulation widths: a lane sums squared 8-bit errors in 32 bits (it sees at most 64 input pixels -- 16 in k_dist_fast, f * f <= 64
 // in k_dist_gen), and so does the wave reduction (at most 64 * 64 = 4096 pixels; 2^32 / 255^2 = 66 051).  The block sum, the partials
 // and the per-frame sums are 64-bit.  No atomics: each block writes its own partial with plain vector stores.
 #include <cstdio>
-#include <cstring>
 
-#include "csic_kernel_ops.h"
+#include "csic_measure.h"
 
 namespace csic {
 
-constexpr int DIST_T = 256;          // threads per block, every kernel here
-constexpr int DIST_CH = CSIC_DIST_CHANNELS;
+constexpr int DIST_T = MEAS_T;
+constexpr int DIST_CH = MEAS_CH;
 
 struct DExtra {
     uint64_t *part;                  // workspace: nblk partials of DIST_CH uint64 per frame, frames back to back
@@ -40,8 +40,8 @@ typedef uint64_t CSIC_GLOBAL *gpart_t;
 struct DRgb { int r, g, b; };
 __device__ __forceinline__ DRgb rgb_of(uint32_t y, const ChromaTerm &t)
 {
-    const int yy = __mul24((int)y, 298);
-    return DRgb{min(max(yy + t.kr, 0), 65535) >> 8, min(max(yy + t.kg, 0), 65535) >> 8, min(max(yy + t.kb, 0), 65535) >> 8};
+    const Rgb16 o = rgb16_of<8>(y, t);
+    return DRgb{(int)o.r, (int)o.g, (int)o.b};
 }
 
 __device__ __forceinline__ void sq_add(uint32_t &s, int e) { s += (uint32_t)__mul24(e, e); }
@@ -88,14 +88,6 @@ __device__ __forceinline__ void block_partial(const DExtra &e, uint32_t (&s)[DIS
 // ------------------------------------------------------------------------------------------------
 // k_dist_fast
 // ------------------------------------------------------------------------------------------------
-template <bool VEC, bool NT>
-__device__ __forceinline__ u32x4 dld4(const KArgs &a, gin_t in, uint32_t off)
-{
-    if (VEC) return in4n<NT>(a, in, off);
-    const u32x4 v = {in1n<NT>(a, in, off), in1n<NT>(a, in, off + 1u), in1n<NT>(a, in, off + 2u), in1n<NT>(a, in, off + 3u)};
-    return v;
-}
-
 template <int ROUND, int F, int HH, int VV, bool VEC, bool NT, bool CHECK>
 __device__ __forceinline__ void dist_fast_body(const KArgs &a, gin_t in, uint32_t u0, uint32_t nunits, uint32_t (&s)[DIST_CH])
 {
@@ -108,7 +100,7 @@ __device__ __forceinline__ void dist_fast_body(const KArgs &a, gin_t in, uint32_
     for (int k = 0; k < K; ++k) {
         // the frame's last block: clamp instead of branching, so that every load still issues ahead of the arithmetic
         const uint32_t u = CHECK ? min(u0 + (uint32_t)(k * DIST_T), nunits - 1u) : u0 + (uint32_t)(k * DIST_T);
-        const uint32_t j0 = 4u * u;                                         // < 2^30 (dist_kind)
+        const uint32_t j0 = 4u * u;                                         // < 2^30 (measure_kind)
         const uint32_t ur = (uint32_t)(((uint64_t)j0 * a.mW) >> a.kW);      // unit row = j0 / W, exact
         off[k] = F == 1 ? j0 : j0 + __umul24(ur, W);                        // rows F * ur .. : (F * ur) * W + (j0 - ur * W)
         odd[k] = F == 1 && VV == 2 && (ur & 1u);
@@ -122,7 +114,7 @@ __device__ __forceinline__ void dist_fast_body(const KArgs &a, gin_t in, uint32_
 #pragma unroll
     for (int k = 0; k < K; ++k)
 #pragma unroll
-        for (int i = 0; i < F; ++i) p[k][i] = dld4<VEC, NT>(a, in, off[k] + (uint32_t)i * W);
+        for (int i = 0; i < F; ++i) p[k][i] = in4n_or_1n<VEC, NT>(a, in, off[k] + (uint32_t)i * W);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         if (CHECK && u0 + (uint32_t)(k * DIST_T) >= nunits) continue;
@@ -189,42 +181,15 @@ __global__ void __launch_bounds__(DIST_T) k_dist_gen(KArgs a, DExtra e)
     uint32_t s[DIST_CH] = {0, 0, 0, 0, 0, 0};
     if (j < e.nunits) {
         const int ro = (int)(((uint64_t)j * a.mWo) >> a.kWo), co = (int)j - ro * a.Wo;      // j / Wo, exact for j < 2^31
-        uint32_t y, cb, cr;                                                                 // the output pixel, packed-YCbCr values
-        if (AVG) {
-            const uint32_t o = avg_pixel_generic<ROUND, F_YCC, INFMT>(a, in, ro, co);
-            y = o & 0xFFu; cb = (o >> 8) & 0xFFu; cr = (o >> 16) & 0xFFu;
-        } else {
-            // k_generic's sources
-            const int64_t y_idx = (int64_t)(ro * a.f) * a.ip + co * a.f;
-            int64_t c_idx;
-            if (!a.s_first) {
-                const int r = ro * a.f, c = co * a.f;
-                c_idx = ((r & a.vmask) == 0) ? (int64_t)r * a.ip + (c & ~a.hmask) : (int64_t)(r - 1) * a.ip + a.last_sample_col;
-            } else {
-                const int jj = ro * a.Wo + co;
-                const int r = (int)(((uint64_t)(uint32_t)jj * a.mW) >> a.kW), c = jj - r * a.W;
-                const int src = ((r & a.vmask) == 0) ? (jj - (c & a.hmask)) : ((r - 1) * a.W + a.last_sample_col);
-                const int sro = (int)(((uint64_t)(uint32_t)src * a.mWo) >> a.kWo), sco = src - sro * a.Wo;
-                c_idx = (int64_t)(sro * a.f) * a.ip + sco * a.f;
-            }
-            in_c<ROUND, INFMT>(in1<false>(a, in, c_idx), cb, cr);
-            cb &= a.mcb; cr &= a.mcr;
-            y = in_y<ROUND, INFMT>(in1<false>(a, in, y_idx)) & a.my;
-        }
+        const Ycc o = measure_out_pixel<ROUND, AVG, INFMT>(a, in, ro, co);                  // the output pixel, packed-YCbCr values
+        const uint32_t y = o.y, cb = o.cb, cr = o.cr;
         const DRgb rgb = rgb_of(y, chroma_term_q<F_ARGB>(cb, cr));
         const int r0 = ro * a.f, c0 = co * a.f, r1 = min(r0 + a.f, a.H), c1 = min(c0 + a.f, a.W);
         for (int r = r0; r < r1; ++r) {
             for (int c = c0; c < c1; ++c) {
-                const uint32_t px = in1<false>(a, in, (int64_t)r * a.ip + c);
-                if (INFMT == F_YCC) {
-                    const uint32_t py = px & 0xFFu, pb = (px >> 8) & 0xFFu, pr = (px >> 16) & 0xFFu;
-                    const DRgb ref = rgb_of(py, chroma_term_q<F_ARGB>(pb, pr));
-                    acc_px(s, ref.r, ref.g, ref.b, py, pb, pr, rgb, y, cb, cr);
-                } else {
-                    uint32_t pb, pr;
-                    fwd_c<ROUND>(px, pb, pr);
-                    acc_argb(s, px, fwd_y(px), pb, pr, rgb, y, cb, cr);
-                }
+                uint32_t ref[DIST_CH];
+                ref_channels<ROUND, INFMT>(in1<false>(a, in, (int64_t)r * a.ip + c), ref);
+                acc_px(s, (int)ref[0], (int)ref[1], (int)ref[2], ref[3], ref[4], ref[5], rgb, y, cb, cr);
             }
         }
     }
@@ -232,89 +197,37 @@ __global__ void __launch_bounds__(DIST_T) k_dist_gen(KArgs a, DExtra e)
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_dist_reduce: frame blockIdx.x's partials -> its DIST_CH sums
+// host side: what csic_measure.h asks of a unit
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(DIST_T) k_dist_reduce(const uint64_t *part, uint32_t nblk, uint64_t *sse)
-{
-    typedef const uint64_t CSIC_GLOBAL *gcpart_t;
-    const gcpart_t p = (gcpart_t)(uintptr_t)part + (uint64_t)blockIdx.x * nblk * DIST_CH;
-    uint64_t t[DIST_CH] = {0, 0, 0, 0, 0, 0};
-    for (uint32_t b = threadIdx.x; b < nblk; b += DIST_T)
-#pragma unroll
-        for (int ch = 0; ch < DIST_CH; ++ch) t[ch] += p[(uint64_t)b * DIST_CH + ch];
-    __shared__ uint64_t red[DIST_T][DIST_CH];
-#pragma unroll
-    for (int ch = 0; ch < DIST_CH; ++ch) red[threadIdx.x][ch] = t[ch];
-    __syncthreads();
-    for (int w = DIST_T / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w)
-#pragma unroll
-            for (int ch = 0; ch < DIST_CH; ++ch) red[threadIdx.x][ch] += red[threadIdx.x + w][ch];
-        __syncthreads();
+struct DistUnit {
+    typedef DExtra Extra;
+    static constexpr MeasureFamily family = MEASURE_DIST;
+    static constexpr const char *result_name = "d_sse", *workspace_fn = "csic_distortion_workspace_bytes";
+    static int check_plan(const csic_plan *) { return CSIC_OK; }
+    static int check_extra(const DExtra &) { return CSIC_OK; }
+    // k_dist_fast: units per frame; k_dist_gen: output pixels per frame
+    static uint32_t units(const csic_plan *pl, int kind)
+    {
+        const Geometry &g = pl->g;
+        if (kind == 0) return (uint32_t)((int64_t)g.Wo * g.Ho);
+        return (uint32_t)((int64_t)(g.W / 4) * (g.H / kind));
     }
-    if (threadIdx.x < (unsigned)DIST_CH) ((gpart_t)(uintptr_t)sse)[(uint64_t)blockIdx.x * DIST_CH + threadIdx.x] = red[0][threadIdx.x];
-}
-
-// ------------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------------
-using DistFn = void (*)(KArgs, DExtra);
-
-// 0 = k_dist_gen, 1 / 2 = k_dist_fast at factor 1 / 2
-static int dist_kind(const csic_plan *pl)
-{
-    const csic_params &p = pl->p;
-    const Geometry &g = pl->g;
-    if (pl->tune.force_generic || p.sampling != CSIC_SAMPLING_HOLD_DECIMATE || p.in_format != CSIC_FMT_ARGB8888) return 0;
-    if (g.f > 2 || (g.f == 2 && g.s_first)) return 0;
-    if (g.W % 4 != 0 || g.H % g.f != 0) return 0;
-    // 32-bit offsets (in1n / in4n) and 24-bit row multiplies
-    if ((int64_t)g.W * g.H > (1ll << 30) || g.W >= (1 << 24) || g.H >= (1 << 24)) return 0;
-    return g.f;
-}
-
-static uint32_t dist_units(const csic_plan *pl, int kind)
-{
-    const Geometry &g = pl->g;
-    if (kind == 0) return (uint32_t)((int64_t)g.Wo * g.Ho);
-    return (uint32_t)((int64_t)(g.W / 4) * (g.H / kind));
-}
-
-static uint32_t dist_blocks(const csic_plan *pl, int kind)
-{
-    const int64_t per_block = kind == 0 ? DIST_T : (int64_t)DIST_T * (4 / kind);
-    return (uint32_t)((dist_units(pl, kind) + per_block - 1) / per_block);
-}
-
-// the kernel of a plan: `kind` from dist_kind, `vec` = 16-byte loads
-static DistFn dist_kernel(const csic_plan *pl, int kind, bool vec)
-{
-    const csic_params &p = pl->p;
-    const Geometry &g = pl->g;
-    return with_const<R_FLOOR, R_TRUNC>(p.rounding, [&](auto round) -> DistFn {
-        constexpr int ROUND = CSIC_CONST(round);
-        if (kind == 0)
-            return with_const<true, false>(p.sampling == CSIC_SAMPLING_AVG, [&](auto avg) {
-                return with_const<F_YCC, F_ARGB>(p.in_format, [](auto in) -> DistFn { return k_dist_gen<ROUND, CSIC_CONST(avg), CSIC_CONST(in)>; });
+    static uint32_t blocks(const csic_plan *pl, int kind)
+    {
+        const int64_t per_block = kind == 0 ? DIST_T : (int64_t)DIST_T * (4 / kind);
+        return (uint32_t)((units(pl, kind) + per_block - 1) / per_block);
+    }
+    static void fill_extra(const csic_plan *pl, int kind, DExtra *e) { e->nunits = units(pl, kind); }
+    static MeasureFn<DExtra> kernel(const csic_plan *pl, int kind, bool vec)
+    {
+        return measure_kernel<MeasureFn<DExtra>>(
+            pl, kind, vec,
+            [](auto round, auto avg, auto in) { return k_dist_gen<CSIC_CONST(round), CSIC_CONST(avg), CSIC_CONST(in)>; },
+            [](auto round, auto f, auto h, auto v, auto v16, auto nt) {
+                return k_dist_fast<CSIC_CONST(round), CSIC_CONST(f), CSIC_CONST(h), CSIC_CONST(v), CSIC_CONST(v16), CSIC_CONST(nt)>;
             });
-        return with_const<true, false>(vec, [&](auto v16) {
-        return with_const<true, false>(!pl->tune.no_nt, [&](auto nt) {
-        return with_const<1, 2>(kind, [&](auto f) {
-        return with_const<1, 2, 4>(g.h, [&](auto h) {
-        // at F = 2 the output rows are sample rows: v does not matter
-        return with_const<2, 1>(CSIC_CONST(f) == 1 ? g.v : 1, [](auto v) -> DistFn {
-            return k_dist_fast<ROUND, CSIC_CONST(f), CSIC_CONST(h), CSIC_CONST(v), CSIC_CONST(v16), CSIC_CONST(nt)>;
-        }); }); }); }); });
-    });
-}
-
-static int dist_workspace(const csic_plan *pl, int32_t nframes, size_t *bytes)
-{
-    if (nframes <= 0 || nframes > 65535)
-        return set_error(CSIC_EINVAL_SIZE, "nframes must be in 1..65535. Got %d", nframes);
-    *bytes = (size_t)nframes * dist_blocks(pl, dist_kind(pl)) * DIST_CH * sizeof(uint64_t);
-    return CSIC_OK;
-}
+    }
+};
 
 } // namespace csic
 
@@ -324,65 +237,19 @@ extern "C" {
 
 int csic_distortion_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes)
 {
-    if (!plan || !bytes) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    const int st = dist_workspace(plan, nframes, bytes);
-    if (st == CSIC_OK) clear_error();
-    return st;
+    return measure_workspace_bytes<DistUnit>(plan, nframes, bytes);
 }
 
 const char *csic_distortion_kernel_name(const csic_plan *plan)
 {
-    if (!plan) return "";
-    const csic_params &p = plan->p;
-    const bool ycc = p.in_format == CSIC_FMT_YCBCR888X;
-    switch (dist_kind(plan)) {
-    case 1: return "k_dist_fast<f1>";
-    case 2: return "k_dist_fast<f2>";
-    default:
-        if (p.sampling == CSIC_SAMPLING_AVG) return ycc ? "k_dist_gen<avg,ycc-in>" : "k_dist_gen<avg>";
-        return ycc ? "k_dist_gen<hold,ycc-in>" : "k_dist_gen<hold>";
-    }
+    return plan ? measure_kernel_name(MEASURE_DIST, measure_kind_of<DistUnit>(plan), plan->p) : "";
 }
 
 int csic_distortion_device(csic_plan *plan, const void *d_in, int32_t nframes, uint64_t *d_sse, void *d_workspace,
                            size_t workspace_bytes, void *hip_stream)
 {
     if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
-    if (!d_in || !d_sse || !d_workspace) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
-    size_t need = 0;
-    int st = dist_workspace(plan, nframes, &need);
-    if (st != CSIC_OK) return st;
-    if (workspace_bytes < need)
-        return set_error(CSIC_EINVAL_SIZE, "workspace of %zu bytes is smaller than the %zu bytes csic_distortion_workspace_bytes asks for",
-                         workspace_bytes, need);
-    if ((uintptr_t)d_sse & 7u) return set_error(CSIC_EINVAL_SIZE, "d_sse must be 8-byte aligned");
-    if ((uintptr_t)d_workspace & 7u) return set_error(CSIC_EINVAL_SIZE, "the workspace must be 8-byte aligned");
-    if ((uintptr_t)d_in & 3u) return set_error(CSIC_EINVAL_SIZE, "the input must be 4-byte aligned");
-    const Geometry &g = plan->g;
-    const int kind = dist_kind(plan);
-    // 16-byte loads only for a 16-byte aligned d_in (the frame stride W * H * 4 is a multiple of 16 whenever width % 4 == 0)
-    const bool vec = ((uintptr_t)d_in & 15u) == 0;
-    const DistFn fn = dist_kernel(plan, kind, vec);
-    CSIC_DEVICE_SCOPE(plan->device);
-    KArgs a;
-    fill_base_args(g, g.W, g.Wo, &a);
-    a.in = static_cast<const uint32_t *>(d_in);
-    a.bdx = DIST_T; a.bdy = 1; a.row_step = 1;
-    DExtra e;
-    std::memset(&e, 0, sizeof e);
-    e.part = static_cast<uint64_t *>(d_workspace);
-    e.nblk = dist_blocks(plan, kind);
-    e.nunits = dist_units(plan, kind);
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    void *params[2] = {&a, &e};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3(e.nblk, 1, (unsigned)nframes), dim3(DIST_T, 1, 1), params, 0, stream));
-    const uint64_t *part = e.part;
-    uint32_t nblk = e.nblk;
-    void *rparams[3] = {&part, &nblk, &d_sse};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(k_dist_reduce), dim3((unsigned)nframes, 1, 1), dim3(DIST_T, 1, 1), rparams, 0,
-                            stream));
-    clear_error();
-    return CSIC_OK;
+    return measure_device<DistUnit>(plan, d_in, nframes, d_sse, d_workspace, workspace_bytes, DExtra{}, hip_stream);
 }
 
 int csic_distortion_host(csic_plan *plan, const uint32_t *in, size_t in_px, int32_t nframes, uint64_t *sse)
@@ -390,28 +257,22 @@ int csic_distortion_host(csic_plan *plan, const uint32_t *in, size_t in_px, int3
     if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
     if (!in || !sse) return set_error(CSIC_EINVAL_NULL, "host buffer is NULL");
     size_t ws = 0;
-    int st = dist_workspace(plan, nframes, &ws);
+    int st = measure_workspace<DistUnit>(plan, nframes, &ws);
     if (st != CSIC_OK) return st;
     const Geometry &g = plan->g;
     const size_t need = (size_t)nframes * (size_t)g.W * (size_t)g.H;
     if (in_px != need) return set_error(CSIC_EINVAL_SIZE, "expected %zu input pixels (%d frames), got %zu", need, nframes, in_px);
     CSIC_DEVICE_SCOPE(plan->device);
-    void *d_in = nullptr, *d_ws = nullptr, *d_sse = nullptr;
     const size_t sse_bytes = (size_t)nframes * DIST_CH * sizeof(uint64_t);
-    hipError_t e = hipMalloc(&d_in, need * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_ws, ws);
-    if (e == hipSuccess) e = hipMalloc(&d_sse, sse_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, need * 4, hipMemcpyHostToDevice, nullptr);
-    if (e == hipSuccess) {
+    DeviceStaging dev;
+    void *d_in = dev.alloc(need * 4), *d_ws = dev.alloc(ws), *d_sse = dev.alloc(sse_bytes);
+    dev.to_device(d_in, in, need * 4);
+    if (dev.ok()) {
         st = csic_distortion_device(plan, d_in, nframes, static_cast<uint64_t *>(d_sse), d_ws, ws, nullptr);
-        if (st == CSIC_OK) e = hipMemcpyAsync(sse, d_sse, sse_bytes, hipMemcpyDeviceToHost, nullptr);
-        if (st == CSIC_OK && e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (st == CSIC_OK) { dev.to_host(sse, d_sse, sse_bytes); dev.sync(); }
     }
-    if (d_in) (void)hipFree(d_in);
-    if (d_ws) (void)hipFree(d_ws);
-    if (d_sse) (void)hipFree(d_sse);
     if (st != CSIC_OK) return st;
-    if (e != hipSuccess) return set_error(CSIC_EHIP, "csic_distortion_host: %s", hipGetErrorString(e));
+    if (!dev.ok()) return set_error(CSIC_EHIP, "csic_distortion_host: %s", hipGetErrorString(dev.error()));
     clear_error();
     return CSIC_OK;
 }

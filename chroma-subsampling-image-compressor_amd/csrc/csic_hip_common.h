@@ -1,6 +1,7 @@
-// csic_hip_common.h -- shared by the HIP translation units (csic_kernels.hip, csic_pipeline.hip,
-// csic_multi.hip, csic_graph.hip): error macro, the HIP instantiation of the device guard, the plan, the launch
-// descriptor that csic_kernels.hip prepares for the other units and the run-time-value -> template-argument helper.
+// csic_hip_common.h -- shared by the HIP translation units (csic_kernels.hip, csic_planar.hip, csic_planar_bits.hip,
+// csic_decode.hip, csic_distortion.hip, csic_ssim.hip, csic_pipeline.hip, csic_files.hip, csic_multi.hip, csic_graph.hip): error
+// macro, the HIP instantiation of the device guard, the plan, the launch descriptor that csic_kernels.hip prepares for the other
+// units, the device staging of the synchronous *_host wrappers and the run-time-value -> template-argument helper.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,6 +47,35 @@ using DeviceGuard = BasicDeviceGuard<HipDeviceApi>;
     if (csic_device_guard_.status() != 0)                                                                   \
         return ::csic::set_error(CSIC_EHIP, "cannot make device %d current: %s", (int)(dev),                \
                                  hipGetErrorString((hipError_t)csic_device_guard_.status()))
+
+// Device staging of a synchronous *_host wrapper (csic_decode_host, csic_distortion_host, csic_ssim_host): buffers that live
+// until the scope ends and copies on the null stream.  The first HIP error is kept and turns every later call into a no-op, so a
+// wrapper runs its sequence straight through and looks at error() once.
+class DeviceStaging {
+public:
+    DeviceStaging() = default;
+    DeviceStaging(const DeviceStaging &) = delete;
+    DeviceStaging &operator=(const DeviceStaging &) = delete;
+    ~DeviceStaging() { for (int i = 0; i < n_; ++i) (void)hipFree(buf_[i]); }
+    void *alloc(size_t bytes)                       // nullptr after an error
+    {
+        void *p = nullptr;
+        if (ok()) keep(n_ < MAX_BUFFERS ? hipMalloc(&p, bytes) : hipErrorInvalidValue);   // (more than MAX_BUFFERS: a bug here, not a full device)
+        if (p) buf_[n_++] = p;
+        return p;
+    }
+    void to_device(void *dst, const void *src, size_t bytes) { if (ok()) keep(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, nullptr)); }
+    void to_host(void *dst, const void *src, size_t bytes) { if (ok()) keep(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, nullptr)); }
+    void sync() { if (ok()) keep(hipStreamSynchronize(nullptr)); }
+    bool ok() const { return err_ == hipSuccess; }
+    hipError_t error() const { return err_; }
+private:
+    static constexpr int MAX_BUFFERS = 4;           // csic_ssim_host takes all four: raise it with the next buffer
+    void keep(hipError_t e) { if (err_ == hipSuccess) err_ = e; }
+    void *buf_[MAX_BUFFERS] = {};
+    int n_ = 0;
+    hipError_t err_ = hipSuccess;
+};
 
 using KernelFn = void (*)(KArgs);
 

@@ -1,6 +1,8 @@
-// csic_kernel_ops.h -- device-side building blocks shared by the kernel translation units (csic_kernels.hip, csic_planar.hip):
+// csic_kernel_ops.h -- device-side building blocks shared by the kernel translation units (csic_kernels.hip, csic_planar.hip,
+// csic_planar_bits.hip, csic_decode.hip and, through csic_measure.h, csic_distortion.hip and csic_ssim.hip):
 // the wave prologue, address-space-qualified pixel pointers, streaming (non-temporal) accesses, the per-pixel arithmetic of
-// the forward / inverse transforms and the quantiser, and -- in the CSIC_DEBUG build -- the range checks of every global access.
+// the forward / inverse transforms and the quantiser, one output pixel by the definition for both samplings (avg_pixel_generic,
+// hold_pixel_generic), and -- in the CSIC_DEBUG build -- the range checks of every global access.
 // Citations are relative to /root/reference/.
 #pragma once
 #include "csic_hip_common.h"
@@ -296,6 +298,40 @@ __device__ __forceinline__ uint32_t avg_pixel_generic(const KArgs &a, gin_t in, 
     sb = ((sb + ((f * f) >> 1)) >> flog2) & a.mcb;
     sr = ((sr + ((f * f) >> 1)) >> flog2) & a.mcr;
     return finish_y<FMT>(sy, chroma_term_q<FMT>(sb, sr));
+}
+
+// ------------------------------------------------------------------------------------------------
+// HOLD_DECIMATE, any parameters: the one-pixel-per-lane kernels (k_generic, k_dist_gen, k_ssim_gen)
+// ------------------------------------------------------------------------------------------------
+struct Ycc { uint32_t y, cb, cr; };      // one output pixel, quantised
+
+// The quantised (Y, Cb, Cr) of output pixel (ro, co): SURVEY.md App. A.3 / A.4 verbatim, both order classes and the 4:x:0 replay
+// row.  The single statement of that rule for the kernels that compute one output pixel at a time (k_ssim_gen carries a copy
+// of this body for its schedule's sake and says so).
+template <int ROUND, int INFMT>
+__device__ __forceinline__ Ycc hold_pixel_generic(const KArgs &a, gin_t in, int ro, int co)
+{
+    const int64_t y_idx = (int64_t)(ro * a.f) * a.ip + co * a.f;
+    int64_t c_idx;
+    if (!a.s_first) {
+        const int r = ro * a.f, c = co * a.f;       // chroma counters == image coordinates
+        c_idx = ((r & a.vmask) == 0) ? (int64_t)r * a.ip + (c & ~a.hmask)
+                                     : (int64_t)(r - 1) * a.ip + a.last_sample_col;
+    } else {
+        // chroma sits behind the decimator but was built with the full width
+        // (ImageCompressorTop.scala:52-58): its column counter wraps every W decimated pixels.
+        // The two divisions by run-time constants are exact multiply-shifts (magic_div, host side).
+        const int j = ro * a.Wo + co;               // < 2^31 (validated)
+        const int r = (int)(((uint64_t)(uint32_t)j * a.mW) >> a.kW), c = j - r * a.W;
+        const int src = ((r & a.vmask) == 0) ? (j - (c & a.hmask)) : ((r - 1) * a.W + a.last_sample_col);
+        const int sro = (int)(((uint64_t)(uint32_t)src * a.mWo) >> a.kWo), sco = src - sro * a.Wo;
+        c_idx = (int64_t)(sro * a.f) * a.ip + sco * a.f;       // (counters above use the semantic W, addresses the pitch)
+    }
+    uint32_t cb, cr;
+    in_c<ROUND, INFMT>(in1<false>(a, in, c_idx), cb, cr);
+    cb &= a.mcb; cr &= a.mcr;
+    const uint32_t y = in_y<ROUND, INFMT>(in1<false>(a, in, y_idx)) & a.my;
+    return Ycc{y, cb, cr};
 }
 
 } // namespace csic

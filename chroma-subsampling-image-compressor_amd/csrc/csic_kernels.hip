@@ -460,7 +460,7 @@ __global__ void __launch_bounds__(256) k_avg_generic(KArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_generic: any parameters, one output pixel per lane (SURVEY.md App. A.3 / A.4 verbatim)
+// k_generic: any parameters, one output pixel per lane (hold_pixel_generic: SURVEY.md App. A.3 / A.4 verbatim)
 // ------------------------------------------------------------------------------------------------
 template <int ROUND, int FMT, int INFMT>
 __global__ void __launch_bounds__(256) k_generic(KArgs a)
@@ -472,26 +472,8 @@ __global__ void __launch_bounds__(256) k_generic(KArgs a)
     const gout_t out = frame_out(a);
     const int row_step = a.row_step;
     for (int ro = blockIdx.y * a.bdy + threadIdx.y; ro < a.Ho; ro += row_step) {
-        const int64_t y_idx = (int64_t)(ro * a.f) * a.ip + co * a.f;
-        int64_t c_idx;
-        if (!a.s_first) {
-            const int r = ro * a.f, c = co * a.f;       // chroma counters == image coordinates
-            c_idx = ((r & a.vmask) == 0) ? (int64_t)r * a.ip + (c & ~a.hmask)
-                                         : (int64_t)(r - 1) * a.ip + a.last_sample_col;
-        } else {
-            // chroma sits behind the decimator but was built with the full width
-            // (ImageCompressorTop.scala:52-58): its column counter wraps every W decimated pixels.
-            // The two divisions by run-time constants are exact multiply-shifts (magic_div, host side).
-            const int j = ro * a.Wo + co;               // < 2^31 (validated)
-            const int r = (int)(((uint64_t)(uint32_t)j * a.mW) >> a.kW), c = j - r * a.W;
-            const int src = ((r & a.vmask) == 0) ? (j - (c & a.hmask)) : ((r - 1) * a.W + a.last_sample_col);
-            const int sro = (int)(((uint64_t)(uint32_t)src * a.mWo) >> a.kWo), sco = src - sro * a.Wo;
-            c_idx = (int64_t)(sro * a.f) * a.ip + sco * a.f;       // (counters above use the semantic W, addresses the pitch)
-        }
-        uint32_t cb, cr;
-        in_c<ROUND, INFMT>(in1<false>(a, in, c_idx), cb, cr);
-        const uint32_t y = in_y<ROUND, INFMT>(in1<false>(a, in, y_idx)) & a.my;
-        out1<false>(a, out, (int64_t)ro * a.op + co, finish_y<FMT>(y, chroma_term_q<FMT>(cb & a.mcb, cr & a.mcr)));
+        const Ycc o = hold_pixel_generic<ROUND, INFMT>(a, in, ro, co);
+        out1<false>(a, out, (int64_t)ro * a.op + co, finish_y<FMT>(o.y, chroma_term_q<FMT>(o.cb, o.cr)));
     }
 }
 

@@ -1,4 +1,5 @@
-// csic_select.cpp -- kernel selection, kernel names and launch geometry of the packed kernels (see csic_select.h).  Host only.
+// csic_select.cpp -- kernel selection, kernel names and launch geometry of the packed kernels, kernel selection and names of the
+// measurement units (see csic_select.h).  Host only.
 // Every rule here is backed by a measurement under profiles/; tests/data/launch_table.txt records what the rules give.
 #include "csic_select.h"
 
@@ -380,6 +381,31 @@ int plan_launch(const csic_params &p, const Geometry &g, const Tune &t, uintptr_
     default: launch_per_lane(g, t, s.units_per_row, nframes, lp); break;
     }
     return CSIC_OK;
+}
+
+// ---- the measurement units ----------------------------------------------------------------------------------------------
+// The fast kernels serve the reference's sampling on ARGB input at factor 1 and, chroma before spatial, at factor 2 (spatial
+// before chroma at factor 2 is excluded: the chroma counters then run over the decimated stream modulo the full width, and a
+// lane's held sample need not lie among the pixels it loads), on frames that its units tile: 4 columns x f rows for
+// k_dist_fast, the 8 x 8 window for k_ssim_fast.
+int measure_kind(const csic_params &p, const Geometry &g, const Tune &t, MeasureFamily fam)
+{
+    const int tile_w = fam == MEASURE_DIST ? 4 : CSIC_SSIM_WINDOW, tile_h = fam == MEASURE_DIST ? g.f : CSIC_SSIM_WINDOW;
+    if (t.force_generic || p.sampling != CSIC_SAMPLING_HOLD_DECIMATE || p.in_format != CSIC_FMT_ARGB8888) return 0;
+    if (g.f > 2 || (g.f == 2 && g.s_first)) return 0;
+    if (g.W % tile_w != 0 || g.H % tile_h != 0) return 0;
+    // 32-bit offsets (in1n / in4n) and 24-bit row multiplies
+    if ((int64_t)g.W * g.H > (1ll << 30) || g.W >= (1 << 24) || g.H >= (1 << 24)) return 0;
+    return g.f;
+}
+
+const char *measure_kernel_name(MeasureFamily fam, int kind, const csic_params &p)
+{
+#define CSIC_MEASURE_NAMES(k) {k "_gen<hold>", k "_gen<hold,ycc-in>", k "_gen<avg>", k "_gen<avg,ycc-in>", k "_fast<f1>", k "_fast<f2>"}
+    static const char *const names[2][6] = {CSIC_MEASURE_NAMES("k_dist"), CSIC_MEASURE_NAMES("k_ssim")};
+#undef CSIC_MEASURE_NAMES
+    const int gen = (p.sampling == CSIC_SAMPLING_AVG ? 2 : 0) + (p.in_format == CSIC_FMT_YCBCR888X ? 1 : 0);
+    return names[fam == MEASURE_DIST ? 0 : 1][kind == 0 ? gen : 3 + kind];
 }
 
 } // namespace csic

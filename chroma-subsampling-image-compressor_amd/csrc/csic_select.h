@@ -1,7 +1,8 @@
 // csic_select.h -- the host-only planner: which packed kernel a parameter set takes (select_kernel), what it is called
-// (kernel_name) and with what grid, block and kernel arguments it is launched (plan_launch).  Pure integer arithmetic on
-// csic_params, Geometry and the tuning knobs: no HIP header, no device; csic_kernels.hip turns a KernelId into a function
-// pointer (resolve) and tests/cpp/launch_table.cpp prints the whole table on a machine without a GPU.
+// (kernel_name) and with what grid, block and kernel arguments it is launched (plan_launch); which kernel the measurement units
+// take (measure_kind, measure_kernel_name).  Pure integer arithmetic on csic_params, Geometry and the tuning knobs: no HIP header,
+// no device; csic_kernels.hip turns a KernelId into a function pointer (resolve), csic_measure.h a kind into one
+// (measure_kernel), and tests/cpp/launch_table.cpp prints the whole table on a machine without a GPU.
 #pragma once
 #include "csic_internal.h"
 
@@ -85,5 +86,12 @@ void fill_base_args(const Geometry &g, int32_t ip, int32_t op, KArgs *a);
 // rows `in_pitch` / `out_pitch` pixels apart (0 = packed); the pointers in lp->args stay null.  Returns a csic status.
 int plan_launch(const csic_params &p, const Geometry &g, const Tune &t, uintptr_t align_bits, int nframes, int32_t in_pitch,
                 int32_t out_pitch, LaunchPlan *lp);
+
+// ---- the measurement units (csic_distortion.hip, csic_ssim.hip) -----------------------------------------
+enum MeasureFamily { MEASURE_DIST, MEASURE_SSIM };
+// 0 = the unit's general kernel (k_dist_gen / k_ssim_gen), 1 / 2 = its fast kernel (k_dist_fast / k_ssim_fast) at factor 1 / 2
+int measure_kind(const csic_params &p, const Geometry &g, const Tune &t, MeasureFamily fam);
+// "k_dist_fast<f1>", "k_ssim_gen<avg,ycc-in>", ...: a static string
+const char *measure_kernel_name(MeasureFamily fam, int kind, const csic_params &p);
 
 } // namespace csic

@@ -16,11 +16,12 @@
 //                      v_dot4_u32_u8: sum x = dot4(x, 0x01010101), sum x^2 = dot4(x, x), sum xy = dot4(x, y) -- five per channel per
 //                      four pixels.  The quantiser is one AND on the transposed dword.
 //   k_ssim_gen<ROUND, AVG, INFMT>   anything csic_validate accepts: lane l of a window takes its row l.  The output pixel of each
-//                      f-wide run of the row is computed as k_dist_gen computes it (k_generic's HOLD sources for both order classes,
-//                      4:x:0 replay row included; avg_pixel_generic for AVG), the sums are scalar multiply-adds.  The lanes of a
+//                      f-wide run of the row is hold_pixel_generic's (both order classes, 4:x:0 replay row included; written out
+//                      in the kernel, see there) or avg_pixel_generic's for AVG, the sums are scalar multiply-adds.  The lanes of a
 //                      window that share an output row each compute it: f-fold redundant arithmetic on cached loads, the price of a
 //                      kernel without a second mapping.
-//   k_ssim_reduce      one block per frame: the frame's partials, summed in a fixed order, -> d_ssim[frame * 6 + channel].
+//   k_sum_partials     (csic_measure.h) one block per frame: the frame's partials, summed in a fixed order, -> d_ssim[frame * 6 + channel].
+// Which of the two a plan takes is measure_kind (csic_select.cpp); what this unit shares with csic_distortion.hip is csic_measure.h.
 // Both pixel kernels end in ssim_finish: the 8 lanes' sums are added with three DPP steps (quad_perm xor 1, xor 2, row_half_mirror),
 // lane l < 6 of the window then takes channel l, so that N, D and the 64-bit quotient are evaluated once per wave for all 8 windows
 // x 6 channels instead of six times with an eighth of the lanes live.
@@ -29,14 +30,13 @@
 // 64 times either of the last two is below 2^30.  N and D are 64-bit products of two 32-bit factors.  q fits 18 bits, a wave's sum of
 // 8 of them 21; the block sum, the partials and the per-frame sums are int64.  No atomics: each block writes its own partial.
 #include <cstdio>
-#include <cstring>
 
-#include "csic_kernel_ops.h"
+#include "csic_measure.h"
 
 namespace csic {
 
-constexpr int SSIM_T = 256;                     // threads per block, every kernel here
-constexpr int SSIM_CH = CSIC_DIST_CHANNELS;
+constexpr int SSIM_T = MEAS_T;
+constexpr int SSIM_CH = MEAS_CH;
 constexpr int SSIM_WPB = SSIM_T / 8;            // windows per block
 constexpr uint32_t SSIM_C1 = 416u, SSIM_C2 = 235963u;
 static_assert(CSIC_SSIM_WINDOW == 8 && CSIC_SSIM_ONE == 65536, "the kernels are written for 8 x 8 windows and 16.16 quotients");
@@ -54,14 +54,6 @@ typedef int32_t CSIC_GLOBAL *gsmap_t;
 
 // what a lane knows of its window: sum x | sum y << 16, sum x^2 + sum y^2, sum xy, per channel
 struct WSums { uint32_t s12[SSIM_CH], ss[SSIM_CH], sxy[SSIM_CH]; };
-
-// the clamped 16-bit (R, G, B) << 8 of (Y, chroma): byte 1 of each is the packed ARGB output's channel (finish_y)
-struct SRgb16 { uint32_t r, g, b; };
-__device__ __forceinline__ SRgb16 ssim_rgb16(uint32_t y, const ChromaTerm &t)
-{
-    const int yy = __mul24((int)y, 298);
-    return SRgb16{(uint32_t)min(max(yy + t.kr, 0), 65535), (uint32_t)min(max(yy + t.kg, 0), 65535), (uint32_t)min(max(yy + t.kb, 0), 65535)};
-}
 
 __device__ __forceinline__ uint32_t group8_sum(uint32_t v)
 {
@@ -142,14 +134,6 @@ __device__ __forceinline__ uint32_t window_of_lane(const SExtra &e, bool &valid,
 // ------------------------------------------------------------------------------------------------
 // k_ssim_fast
 // ------------------------------------------------------------------------------------------------
-template <bool VEC, bool NT>
-__device__ __forceinline__ u32x4 sld4(const KArgs &a, gin_t in, uint32_t off)
-{
-    if (VEC) return in4n<NT>(a, in, off);
-    const u32x4 v = {in1n<NT>(a, in, off), in1n<NT>(a, in, off + 1u), in1n<NT>(a, in, off + 2u), in1n<NT>(a, in, off + 3u)};
-    return v;
-}
-
 __device__ __forceinline__ uint32_t pack4(uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3) { return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24); }
 // byte 1 of four clamped 16-bit values -> one dword
 __device__ __forceinline__ uint32_t pack4_b1(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3)
@@ -205,12 +189,12 @@ __global__ void __launch_bounds__(SSIM_T) k_ssim_fast(KArgs a, SExtra e)
     uint32_t wy, wx;
     const uint32_t wi = window_of_lane(e, valid, wy, wx);
     const uint32_t gl = threadIdx.x & 7u, W = (uint32_t)a.W;
-    const uint32_t r0 = 8u * wy + 2u * (gl >> 1);                               // even; < 2^24 (ssim_kind)
+    const uint32_t r0 = 8u * wy + 2u * (gl >> 1);                               // even; < 2^24 (measure_kind)
     const uint32_t off = __umul24(r0, W) + 8u * wx + 4u * (gl & 1u);            // < 2^30
     uint32_t cpx = 0;
     // 4:x:0 at F = 1: the odd row holds the chroma latched at the last sample of the row above (ChromaSubsampler.scala:52-65)
     if (F == 1 && VV == 2) cpx = in1n<false>(a, in, __umul24(r0, W) + (uint32_t)a.last_sample_col);
-    const u32x4 p0 = sld4<VEC, NT>(a, in, off), p1 = sld4<VEC, NT>(a, in, off + W);
+    const u32x4 p0 = in4n_or_1n<VEC, NT>(a, in, off), p1 = in4n_or_1n<VEC, NT>(a, in, off + W);
 
     const uint32_t my4 = (a.my & 0xFFu) * 0x01010101u, mcb4 = (a.mcb & 0xFFu) * 0x01010101u, mcr4 = (a.mcr & 0xFFu) * 0x01010101u;
     uint32_t s1[SSIM_CH] = {0, 0, 0, 0, 0, 0}, s2[SSIM_CH] = {0, 0, 0, 0, 0, 0};
@@ -226,12 +210,12 @@ __global__ void __launch_bounds__(SSIM_T) k_ssim_fast(KArgs a, SExtra e)
             const bool held_row = VV == 2 && row == 1;
             uint32_t ocb = 0, ocr = 0;
             if (held_row) fwd_c<ROUND>(cpx, ocb, ocr);
-            SRgb16 o[4];
+            Rgb16 o[4];
 #pragma unroll
             for (int g = 0; g < 4; g += HH) {
                 const ChromaTerm t = chroma_term_q<F_ARGB>((held_row ? ocb : rcb[g]) & a.mcb, (held_row ? ocr : rcr[g]) & a.mcr);
 #pragma unroll
-                for (int i = g; i < g + HH; ++i) o[i] = ssim_rgb16(ry[i] & a.my, t);
+                for (int i = g; i < g + HH; ++i) o[i] = rgb16_of(ry[i] & a.my, t);
             }
             y[0] = pack4_b1(o[0].r, o[1].r, o[2].r, o[3].r);
             y[1] = pack4_b1(o[0].g, o[1].g, o[2].g, o[3].g);
@@ -244,11 +228,11 @@ __global__ void __launch_bounds__(SSIM_T) k_ssim_fast(KArgs a, SExtra e)
     } else {
         // outputs (r0 / 2, 4 wx + 2 (gl & 1) + o), o = 0, 1: Y of this lane's column 2 o of the even row, chroma held from column
         // 2 o & ~(h - 1) of it; both rows of the lane are measured against them
-        SRgb16 o[2];
+        Rgb16 o[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int src = HH == 4 ? 0 : 2 * k;
-            o[k] = ssim_rgb16(ry[2 * k] & a.my, chroma_term_q<F_ARGB>(rcb[src] & a.mcb, rcr[src] & a.mcr));
+            o[k] = rgb16_of(ry[2 * k] & a.my, chroma_term_q<F_ARGB>(rcb[src] & a.mcb, rcr[src] & a.mcr));
         }
         y[0] = __builtin_amdgcn_perm(o[1].r, o[0].r, 0x05050101u);
         y[1] = __builtin_amdgcn_perm(o[1].g, o[0].g, 0x05050101u);
@@ -293,7 +277,9 @@ __global__ void __launch_bounds__(SSIM_T) k_ssim_gen(KArgs a, SExtra e)
                 const uint32_t o = avg_pixel_generic<ROUND, F_YCC, INFMT>(a, in, ro, co);
                 y = o & 0xFFu; cb = (o >> 8) & 0xFFu; cr = (o >> 16) & 0xFFu;
             } else {
-                // k_generic's sources, as k_dist_gen takes them
+                // hold_pixel_generic (csic_kernel_ops.h) written out: inside this 8-fold unrolled loop the call compiles to a
+                // longer schedule (12 instructions more, 0.5-0.7 % slower on 8192 x 8192: profiles/r10_measure_refactor.md).
+                // The rule is stated THERE; change it there first and keep this copy equal to it.
                 const int64_t y_idx = (int64_t)(ro * a.f) * a.ip + co * a.f;
                 int64_t c_idx;
                 if (!a.s_first) {
@@ -310,20 +296,11 @@ __global__ void __launch_bounds__(SSIM_T) k_ssim_gen(KArgs a, SExtra e)
                 cb &= a.mcb; cr &= a.mcr;
                 y = in_y<ROUND, INFMT>(in1<false>(a, in, y_idx)) & a.my;
             }
-            const SRgb16 o = ssim_rgb16(y, chroma_term_q<F_ARGB>(cb, cr));
+            const Rgb16 o = rgb16_of(y, chroma_term_q<F_ARGB>(cb, cr));
             out[0] = o.r >> 8; out[1] = o.g >> 8; out[2] = o.b >> 8; out[3] = y; out[4] = cb; out[5] = cr;
         }
-        const uint32_t px = in1<false>(a, in, (int64_t)r * a.ip + c);
         uint32_t ref[SSIM_CH];
-        if (INFMT == F_YCC) {
-            ref[3] = px & 0xFFu; ref[4] = (px >> 8) & 0xFFu; ref[5] = (px >> 16) & 0xFFu;
-            const SRgb16 o = ssim_rgb16(ref[3], chroma_term_q<F_ARGB>(ref[4], ref[5]));
-            ref[0] = o.r >> 8; ref[1] = o.g >> 8; ref[2] = o.b >> 8;
-        } else {
-            ref[0] = (px >> 16) & 0xFFu; ref[1] = (px >> 8) & 0xFFu; ref[2] = px & 0xFFu;
-            ref[3] = fwd_y(px);
-            fwd_c<ROUND>(px, ref[4], ref[5]);
-        }
+        ref_channels<ROUND, INFMT, true>(in1<false>(a, in, (int64_t)r * a.ip + c), ref);
 #pragma unroll
         for (int ch = 0; ch < SSIM_CH; ++ch) {
             w.s12[ch] += ref[ch] | (out[ch] << 16);
@@ -335,81 +312,41 @@ __global__ void __launch_bounds__(SSIM_T) k_ssim_gen(KArgs a, SExtra e)
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_ssim_reduce: frame blockIdx.x's partials -> its SSIM_CH sums
+// host side: what csic_measure.h asks of a unit
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(SSIM_T) k_ssim_reduce(const int64_t *part, uint32_t nblk, int64_t *ssim)
-{
-    typedef const int64_t CSIC_GLOBAL *gcpart_t;
-    const gcpart_t p = (gcpart_t)(uintptr_t)part + (uint64_t)blockIdx.x * nblk * SSIM_CH;
-    int64_t t[SSIM_CH] = {0, 0, 0, 0, 0, 0};
-    for (uint32_t b = threadIdx.x; b < nblk; b += SSIM_T)
-#pragma unroll
-        for (int ch = 0; ch < SSIM_CH; ++ch) t[ch] += p[(uint64_t)b * SSIM_CH + ch];
-    __shared__ int64_t red[SSIM_T][SSIM_CH];
-#pragma unroll
-    for (int ch = 0; ch < SSIM_CH; ++ch) red[threadIdx.x][ch] = t[ch];
-    __syncthreads();
-    for (int k = SSIM_T / 2; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k)
-#pragma unroll
-            for (int ch = 0; ch < SSIM_CH; ++ch) red[threadIdx.x][ch] += red[threadIdx.x + k][ch];
-        __syncthreads();
+struct SsimUnit {
+    typedef SExtra Extra;
+    static constexpr MeasureFamily family = MEASURE_SSIM;
+    static constexpr const char *result_name = "d_ssim", *workspace_fn = "csic_ssim_workspace_bytes";
+    static int check_plan(const csic_plan *pl)
+    {
+        if (pl->g.W < CSIC_SSIM_WINDOW || pl->g.H < CSIC_SSIM_WINDOW)
+            return set_error(CSIC_EINVAL_DIMS, "a %dx%d frame has no %dx%d window", pl->g.W, pl->g.H, CSIC_SSIM_WINDOW, CSIC_SSIM_WINDOW);
+        return CSIC_OK;
     }
-    if (threadIdx.x < (unsigned)SSIM_CH) ((gspart_t)(uintptr_t)ssim)[(uint64_t)blockIdx.x * SSIM_CH + threadIdx.x] = red[0][threadIdx.x];
-}
-
-// ------------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------------
-using SsimFn = void (*)(KArgs, SExtra);
-
-// 0 = k_ssim_gen, 1 / 2 = k_ssim_fast at factor 1 / 2
-static int ssim_kind(const csic_plan *pl)
-{
-    const csic_params &p = pl->p;
-    const Geometry &g = pl->g;
-    if (pl->tune.force_generic || p.sampling != CSIC_SAMPLING_HOLD_DECIMATE || p.in_format != CSIC_FMT_ARGB8888) return 0;
-    if (g.f > 2 || (g.f == 2 && g.s_first)) return 0;
-    if (g.W % CSIC_SSIM_WINDOW != 0 || g.H % CSIC_SSIM_WINDOW != 0) return 0;
-    // 32-bit offsets (in1n / in4n) and 24-bit row multiplies
-    if ((int64_t)g.W * g.H > (1ll << 30) || g.W >= (1 << 24) || g.H >= (1 << 24)) return 0;
-    return g.f;
-}
-
-static uint32_t ssim_windows(const csic_plan *pl) { return (uint32_t)(pl->g.W / CSIC_SSIM_WINDOW) * (uint32_t)(pl->g.H / CSIC_SSIM_WINDOW); }
-static uint32_t ssim_blocks(const csic_plan *pl) { return (ssim_windows(pl) + SSIM_WPB - 1) / SSIM_WPB; }
-
-// the kernel of a plan: `kind` from ssim_kind, `vec` = 16-byte loads
-static SsimFn ssim_kernel(const csic_plan *pl, int kind, bool vec)
-{
-    const csic_params &p = pl->p;
-    const Geometry &g = pl->g;
-    return with_const<R_FLOOR, R_TRUNC>(p.rounding, [&](auto round) -> SsimFn {
-        constexpr int ROUND = CSIC_CONST(round);
-        if (kind == 0)
-            return with_const<true, false>(p.sampling == CSIC_SAMPLING_AVG, [&](auto avg) {
-                return with_const<F_YCC, F_ARGB>(p.in_format, [](auto in) -> SsimFn { return k_ssim_gen<ROUND, CSIC_CONST(avg), CSIC_CONST(in)>; });
+    static int check_extra(const SExtra &e)
+    {
+        if ((uintptr_t)e.map & 3u) return set_error(CSIC_EINVAL_SIZE, "d_map must be 4-byte aligned");
+        return CSIC_OK;
+    }
+    static uint32_t windows(const csic_plan *pl) { return (uint32_t)(pl->g.W / CSIC_SSIM_WINDOW) * (uint32_t)(pl->g.H / CSIC_SSIM_WINDOW); }
+    static uint32_t blocks(const csic_plan *pl, int) { return (windows(pl) + SSIM_WPB - 1) / SSIM_WPB; }
+    static void fill_extra(const csic_plan *pl, int, SExtra *e)
+    {
+        e->nwin = windows(pl);
+        e->nwx = (uint32_t)(pl->g.W / CSIC_SSIM_WINDOW);
+        magic_div(e->nwx, &e->mNwx, &e->kNwx);
+    }
+    static MeasureFn<SExtra> kernel(const csic_plan *pl, int kind, bool vec)
+    {
+        return measure_kernel<MeasureFn<SExtra>>(
+            pl, kind, vec,
+            [](auto round, auto avg, auto in) { return k_ssim_gen<CSIC_CONST(round), CSIC_CONST(avg), CSIC_CONST(in)>; },
+            [](auto round, auto f, auto h, auto v, auto v16, auto nt) {
+                return k_ssim_fast<CSIC_CONST(round), CSIC_CONST(f), CSIC_CONST(h), CSIC_CONST(v), CSIC_CONST(v16), CSIC_CONST(nt)>;
             });
-        return with_const<true, false>(vec, [&](auto v16) {
-        return with_const<true, false>(!pl->tune.no_nt, [&](auto nt) {
-        return with_const<1, 2>(kind, [&](auto f) {
-        return with_const<1, 2, 4>(g.h, [&](auto h) {
-        // at F = 2 the output rows are sample rows: v does not matter
-        return with_const<2, 1>(CSIC_CONST(f) == 1 ? g.v : 1, [](auto v) -> SsimFn {
-            return k_ssim_fast<ROUND, CSIC_CONST(f), CSIC_CONST(h), CSIC_CONST(v), CSIC_CONST(v16), CSIC_CONST(nt)>;
-        }); }); }); }); });
-    });
-}
-
-static int ssim_workspace(const csic_plan *pl, int32_t nframes, size_t *bytes)
-{
-    if (nframes <= 0 || nframes > 65535)
-        return set_error(CSIC_EINVAL_SIZE, "nframes must be in 1..65535. Got %d", nframes);
-    if (pl->g.W < CSIC_SSIM_WINDOW || pl->g.H < CSIC_SSIM_WINDOW)
-        return set_error(CSIC_EINVAL_DIMS, "a %dx%d frame has no %dx%d window", pl->g.W, pl->g.H, CSIC_SSIM_WINDOW, CSIC_SSIM_WINDOW);
-    *bytes = (size_t)nframes * ssim_blocks(pl) * SSIM_CH * sizeof(int64_t);
-    return CSIC_OK;
-}
+    }
+};
 
 } // namespace csic
 
@@ -419,69 +356,21 @@ extern "C" {
 
 int csic_ssim_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes)
 {
-    if (!plan || !bytes) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    const int st = ssim_workspace(plan, nframes, bytes);
-    if (st == CSIC_OK) clear_error();
-    return st;
+    return measure_workspace_bytes<SsimUnit>(plan, nframes, bytes);
 }
 
 const char *csic_ssim_kernel_name(const csic_plan *plan)
 {
-    if (!plan) return "";
-    const csic_params &p = plan->p;
-    const bool ycc = p.in_format == CSIC_FMT_YCBCR888X;
-    switch (ssim_kind(plan)) {
-    case 1: return "k_ssim_fast<f1>";
-    case 2: return "k_ssim_fast<f2>";
-    default:
-        if (p.sampling == CSIC_SAMPLING_AVG) return ycc ? "k_ssim_gen<avg,ycc-in>" : "k_ssim_gen<avg>";
-        return ycc ? "k_ssim_gen<hold,ycc-in>" : "k_ssim_gen<hold>";
-    }
+    return plan ? measure_kernel_name(MEASURE_SSIM, measure_kind_of<SsimUnit>(plan), plan->p) : "";
 }
 
 int csic_ssim_device(csic_plan *plan, const void *d_in, int32_t nframes, int64_t *d_ssim, int32_t *d_map, void *d_workspace,
                      size_t workspace_bytes, void *hip_stream)
 {
     if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
-    if (!d_in || !d_ssim || !d_workspace) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
-    size_t need = 0;
-    int st = ssim_workspace(plan, nframes, &need);
-    if (st != CSIC_OK) return st;
-    if (workspace_bytes < need)
-        return set_error(CSIC_EINVAL_SIZE, "workspace of %zu bytes is smaller than the %zu bytes csic_ssim_workspace_bytes asks for",
-                         workspace_bytes, need);
-    if ((uintptr_t)d_ssim & 7u) return set_error(CSIC_EINVAL_SIZE, "d_ssim must be 8-byte aligned");
-    if ((uintptr_t)d_workspace & 7u) return set_error(CSIC_EINVAL_SIZE, "the workspace must be 8-byte aligned");
-    if ((uintptr_t)d_map & 3u) return set_error(CSIC_EINVAL_SIZE, "d_map must be 4-byte aligned");
-    if ((uintptr_t)d_in & 3u) return set_error(CSIC_EINVAL_SIZE, "the input must be 4-byte aligned");
-    const Geometry &g = plan->g;
-    const int kind = ssim_kind(plan);
-    // 16-byte loads only for a 16-byte aligned d_in (the frame stride W * H * 4 is a multiple of 16 whenever width % 4 == 0)
-    const bool vec = ((uintptr_t)d_in & 15u) == 0 && !plan->tune.no_vec;
-    const SsimFn fn = ssim_kernel(plan, kind, vec);
-    CSIC_DEVICE_SCOPE(plan->device);
-    KArgs a;
-    fill_base_args(g, g.W, g.Wo, &a);
-    a.in = static_cast<const uint32_t *>(d_in);
-    a.bdx = SSIM_T; a.bdy = 1; a.row_step = 1;
-    SExtra e;
-    std::memset(&e, 0, sizeof e);
-    e.part = static_cast<int64_t *>(d_workspace);
+    SExtra e{};
     e.map = d_map;
-    e.nblk = ssim_blocks(plan);
-    e.nwin = ssim_windows(plan);
-    e.nwx = (uint32_t)(g.W / CSIC_SSIM_WINDOW);
-    magic_div(e.nwx, &e.mNwx, &e.kNwx);
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    void *params[2] = {&a, &e};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3(e.nblk, 1, (unsigned)nframes), dim3(SSIM_T, 1, 1), params, 0, stream));
-    const int64_t *part = e.part;
-    uint32_t nblk = e.nblk;
-    void *rparams[3] = {&part, &nblk, &d_ssim};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(k_ssim_reduce), dim3((unsigned)nframes, 1, 1), dim3(SSIM_T, 1, 1), rparams, 0,
-                            stream));
-    clear_error();
-    return CSIC_OK;
+    return measure_device<SsimUnit>(plan, d_in, nframes, d_ssim, d_workspace, workspace_bytes, e, hip_stream);
 }
 
 int csic_ssim_host(csic_plan *plan, const uint32_t *in, size_t in_px, int32_t nframes, int64_t *ssim, int32_t *map)
@@ -489,32 +378,27 @@ int csic_ssim_host(csic_plan *plan, const uint32_t *in, size_t in_px, int32_t nf
     if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
     if (!in || !ssim) return set_error(CSIC_EINVAL_NULL, "host buffer is NULL");
     size_t ws = 0;
-    int st = ssim_workspace(plan, nframes, &ws);
+    int st = measure_workspace<SsimUnit>(plan, nframes, &ws);
     if (st != CSIC_OK) return st;
     const Geometry &g = plan->g;
     const size_t need = (size_t)nframes * (size_t)g.W * (size_t)g.H;
     if (in_px != need) return set_error(CSIC_EINVAL_SIZE, "expected %zu input pixels (%d frames), got %zu", need, nframes, in_px);
     CSIC_DEVICE_SCOPE(plan->device);
-    void *d_in = nullptr, *d_ws = nullptr, *d_ssim = nullptr, *d_map = nullptr;
     const size_t ssim_bytes = (size_t)nframes * SSIM_CH * sizeof(int64_t);
-    const size_t map_bytes = (size_t)nframes * SSIM_CH * ssim_windows(plan) * sizeof(int32_t);
-    hipError_t e = hipMalloc(&d_in, need * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_ws, ws);
-    if (e == hipSuccess) e = hipMalloc(&d_ssim, ssim_bytes);
-    if (e == hipSuccess && map) e = hipMalloc(&d_map, map_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, need * 4, hipMemcpyHostToDevice, nullptr);
-    if (e == hipSuccess) {
+    const size_t map_bytes = (size_t)nframes * SSIM_CH * SsimUnit::windows(plan) * sizeof(int32_t);
+    DeviceStaging dev;
+    void *d_in = dev.alloc(need * 4), *d_ws = dev.alloc(ws), *d_ssim = dev.alloc(ssim_bytes), *d_map = map ? dev.alloc(map_bytes) : nullptr;
+    dev.to_device(d_in, in, need * 4);
+    if (dev.ok()) {
         st = csic_ssim_device(plan, d_in, nframes, static_cast<int64_t *>(d_ssim), static_cast<int32_t *>(d_map), d_ws, ws, nullptr);
-        if (st == CSIC_OK) e = hipMemcpyAsync(ssim, d_ssim, ssim_bytes, hipMemcpyDeviceToHost, nullptr);
-        if (st == CSIC_OK && e == hipSuccess && map) e = hipMemcpyAsync(map, d_map, map_bytes, hipMemcpyDeviceToHost, nullptr);
-        if (st == CSIC_OK && e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (st == CSIC_OK) {
+            dev.to_host(ssim, d_ssim, ssim_bytes);
+            if (map) dev.to_host(map, d_map, map_bytes);
+            dev.sync();
+        }
     }
-    if (d_in) (void)hipFree(d_in);
-    if (d_ws) (void)hipFree(d_ws);
-    if (d_ssim) (void)hipFree(d_ssim);
-    if (d_map) (void)hipFree(d_map);
     if (st != CSIC_OK) return st;
-    if (e != hipSuccess) return set_error(CSIC_EHIP, "csic_ssim_host: %s", hipGetErrorString(e));
+    if (!dev.ok()) return set_error(CSIC_EHIP, "csic_ssim_host: %s", hipGetErrorString(dev.error()));
     clear_error();
     return CSIC_OK;
 }

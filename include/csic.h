@@ -265,7 +265,8 @@ int  csic_planar_bits_layout_of(const csic_params *p, csic_planar_bits_layout *l
  * csic_distortion_device          : d_in -> d_sse[nframes * 6] (8-byte aligned), through d_workspace (8-byte aligned, at least the
  *                                   queried size, else CSIC_EINVAL_SIZE).  Asynchronous on `hip_stream`, no allocation, no
  *                                   synchronisation, hipGraph-capturable; NULL arguments fail with CSIC_EINVAL_NULL before any
- *                                   device is touched.  16-byte loads when d_in is 16-byte aligned, 4-byte loads otherwise.
+ *                                   device is touched.  16-byte loads when d_in is 16-byte aligned, 4-byte loads otherwise
+ *                                   (and under CSIC_TUNE_NO_VECTOR).
  * csic_distortion_host            : the same from host memory (in_px = nframes * width * height) into sse[nframes * 6];
  *                                   synchronous, allocates its staging.
  * csic_distortion_kernel_name     : the kernel csic_distortion_device takes for a 16-byte aligned d_in (static string). */
@@ -353,7 +354,8 @@ const char *csic_plan_kernel_name(const csic_plan *plan);
  *                             (csic_distortion_device: its general kernel k_dist_gen; csic_ssim_device: its general kernel
  *                             k_ssim_gen; nothing else changes for the other entry points)
  *   CSIC_TUNE_NONTEMPORAL   : 1 (default) = non-temporal loads/stores for the frame stream, 0 = cached
- *   CSIC_TUNE_NO_VECTOR     : 1 = never use the 16-byte-per-lane kernels
+ *   CSIC_TUNE_NO_VECTOR     : 1 = never use the 16-byte-per-lane kernels (csic_decode_device: its general kernel;
+ *                             csic_distortion_device and csic_ssim_device: the 4-byte loads of their fast kernels, same sums)
  *   CSIC_TUNE_BLOCK_THREADS : threads per block, 64 / 128 / 256 (0 = the library's choice) */
 #define CSIC_TUNE_VARIANT        1
 #define CSIC_TUNE_FORCE_GENERIC  2

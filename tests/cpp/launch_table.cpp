@@ -11,11 +11,18 @@
 // Line (3 / 3 / 2 bits kept throughout): WxH a:b f order sampling out in rounding [| variant force_generic no_vec no_nt block_threads]
 //       [| nframes align in_pitch,out_pitch] -> status name t=template arguments g=grid b=block a=bdx,bdy,row_step,edge_y0 h=hash
 // (the bracketed groups only where they differ from no knob / one frame, 16-byte-aligned pointers, packed rows)
+// After the launches, the committed sweep prints what the measurement units take (measure_kind, measure_kernel_name) for each of
+// its distinct parameter sets, one line per unit:
+//       measure WxH a:b f order sampling in rounding [| g1] -> dist|ssim kind name
+// (neither the output format nor, of the knobs, anything but force_generic enters that choice)
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <set>
+#include <string>
+#include <vector>
 
 #include "csic.h"
 #include "csic_select.h"
@@ -65,6 +72,8 @@ static Result run_case(const Case &c, const Geometry &g)
 }
 
 static bool g_print = true, g_fields = false;
+static std::vector<std::string> g_measure;      // the measurement section, in the order of the cases' first appearance
+static std::set<std::string> g_measure_seen;
 static long g_cases = 0, g_failed = 0;
 
 static uint32_t fnv(uint32_t h, uint64_t v)
@@ -139,10 +148,28 @@ static bool check_invariants(const Case &c, const Geometry &g, const LaunchPlan 
     return ok;
 }
 
+// the measurement units' lines of one parameter set, once
+static void note_measure(const Case &c, const Geometry &g)
+{
+    const csic_params &p = c.p;
+    char head[192];
+    std::snprintf(head, sizeof head, "measure %dx%d %d:%d f%d o%d%d%d %s %s %s%s", p.width, p.height, p.chroma_a, p.chroma_b, p.factor, p.op[0], p.op[1],
+                  p.op[2], p.sampling == CSIC_SAMPLING_AVG ? "avg" : "hold", p.in_format == CSIC_FMT_ARGB8888 ? "argb" : "ycc",
+                  p.rounding == CSIC_ROUND_FLOOR_HW ? "floor" : "trunc", c.t.force_generic ? " | g1" : "");
+    if (!g_measure_seen.insert(head).second) return;
+    for (MeasureFamily fam : {MEASURE_DIST, MEASURE_SSIM}) {
+        const int kind = measure_kind(p, g, c.t, fam);
+        char line[256];
+        std::snprintf(line, sizeof line, "%s -> %s %d %s", head, fam == MEASURE_DIST ? "dist" : "ssim", kind, measure_kernel_name(fam, kind, p));
+        g_measure.push_back(line);
+    }
+}
+
 static void emit(const Case &c)
 {
     Geometry g;
     if (derive_geometry(&c.p, &g) != CSIC_OK) { std::fprintf(stderr, "bad case: %s\n", csic_last_error()); std::exit(2); }
+    if (g_print && !g_fields) note_measure(c, g);
     const Result r = run_case(c, g);
     ++g_cases;
     const csic_params &p = c.p;
@@ -420,6 +447,7 @@ int main(int argc, char **argv)
     sweep_rules();
     sweep_limits();
     sweep_errors();
+    for (const std::string &line : g_measure) std::printf("%s\n", line.c_str());
     std::fprintf(stderr, "launch_table: %ld cases, %ld with a broken invariant\n", g_cases, g_failed);
     return g_failed ? 1 : 0;
 }

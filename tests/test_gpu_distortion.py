@@ -80,7 +80,9 @@ def test_random_shapes_vs_numpy(csic, oracle, seed):
 @pytest.mark.parametrize("a,b", CHROMA)
 @pytest.mark.parametrize("f", [1, 2])
 def test_fast_kernel_every_chroma_mode(csic, oracle, a, b, f):
-    """Both roundings, every order, the fast kernels' own shapes (rows of whole units, several blocks, a partial last block)."""
+    """Both roundings, every order, the fast kernels' own shapes (rows of whole units, several blocks, a partial last block); then
+    the same plan under TUNE_NO_VECTOR: the sums must not move.  (The kernel name is defined for an aligned d_in and the sums are
+    equal whichever load width ran, so this does not show that the 4-byte loads were taken -- only that the knob is harmless.)"""
     rng = np.random.default_rng(a * 10 + b + f)
     W, H = 136, 62
     frame = rng.integers(0, 1 << 32, W * H, dtype=np.uint32)
@@ -90,7 +92,12 @@ def test_fast_kernel_every_chroma_mode(csic, oracle, a, b, f):
         with _plan(csic, W, H, a, b, (6, 5, 5), f, op, rounding) as pl:
             s_first = op.index(1) < op.index(3)
             assert pl.distortion_kernel_name == ("k_dist_gen<hold>" if f == 2 and s_first else f"k_dist_fast<f{f}>")
-            assert _device_sse(csic, pl, frame)[0].tolist() == want
+            got = _device_sse(csic, pl, frame)[0].tolist()
+            assert got == want
+            name = pl.distortion_kernel_name
+            pl.tune(csic._native.TUNE_NO_VECTOR, 1)
+            assert pl.distortion_kernel_name == name
+            assert _device_sse(csic, pl, frame)[0].tolist() == got == want
 
 
 def test_headline_plans_take_the_fast_kernel(csic):
