@@ -27,6 +27,7 @@ FRAME_GRAPH_DEFAULT_BRANCHES, FRAME_GRAPH_DEFAULT_QUEUES = 4, 3
 PIPELINE_STAGED, PIPELINE_ZERO_COPY = 0, 1
 DIST_CHANNELS = 6                       # R, G, B, Y, Cb, Cr (csic_distortion_*, csic_ssim_*)
 SSIM_WINDOW, SSIM_ONE = 8, 65536        # csic_ssim_*: window edge in pixels, SSIM 1.0 in 16.16 fixed point
+STATS_KINDS, STATS_PLANES, STATS_BINS = 2, 3, 256     # csic_code_stats_*: codes / residuals; Y, Cb, Cr; bins per histogram
 
 
 class IllegalArgumentException(ValueError):
@@ -130,6 +131,10 @@ PROTOTYPES = {
     "csic_ssim_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "csic_ssim_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_int64), C.c_void_p]),
     "csic_ssim_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "csic_code_stats_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "csic_code_stats_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p]),
+    "csic_code_stats_kernel_name": (C.c_char_p, [C.c_void_p, C.c_int32]),
+    "csic_code_stats_block_samples": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "csic_plan_preferred_pitch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "csic_debug_build": (C.c_int, []),
     "csic_debug_probe_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),

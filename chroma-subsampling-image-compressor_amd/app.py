@@ -13,8 +13,12 @@ Two leading verbs go past what the reference's app does (it only ever writes the
     python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ...
     python -m csic_amd.app decompress --input x.csic --output x.png
 
+    python -m csic_amd.app inspect    --input x.csic
+
 `compress` writes the bit-packed planes as a .csic container (include/csic.h), `decompress` decodes one back to a PNG of the
-original size.  The verb must be the first argument; with any other first argument main() behaves as described above.
+original size, `inspect` prints a container's header and, per frame, what its samples carry: the entropies of the codes and of
+their left-predicted residuals and the sizes an entropy coder could reach (csic_code_stats_*).  The verb must be the first
+argument; with any other first argument main() behaves as described above.
 """
 from __future__ import annotations
 
@@ -25,7 +29,8 @@ from typing import Dict, List
 import numpy as np
 
 from .compressor import ImageCompressorTop, Plan
-from .container import read_container, write_container
+from . import _native as N
+from .container import container_info, read_container, write_container
 from .model import Image, ImageProcessorModel
 from .params import PixelFormat, ProcessingStep, Sampling
 
@@ -212,8 +217,47 @@ def _main_container(verb: str, args: List[str]) -> int:
     return 0
 
 
+def _main_inspect(args: List[str]) -> int:
+    """`inspect`: the header needs no GPU, the statistics do; without a device the header is printed, then the library's message."""
+    argsMap = _args_map(args)
+    if "--input" not in argsMap:
+        print("[ERROR] inspect needs --input")
+        return 2
+    inputPath = argsMap["--input"]
+    if not os.path.exists(inputPath):
+        print(f"[ERROR] Input not found: {inputPath}")
+        return 1
+    info = container_info(inputPath)
+    p = info.params
+    ops = " -> ".join(ProcessingStep(int(o)).name for o in p.op)
+    print(f"Container: {inputPath} (version {info.version}, {info.file_bytes} bytes)")
+    print(f"Image: {p.width}x{p.height}, chroma 4:{p.chroma_a}:{p.chroma_b}, bits Y/Cb/Cr {p.y_bits}/{p.cb_bits}/{p.cr_bits}, "
+          f"factor {p.factor}, order {ops}, rounding {p.rounding}, sampling {p.sampling}")
+    print(f"Frames: {info.nframes}, payload bytes per frame: {info.payload_bytes}")
+    try:
+        c_params, nframes, frames = read_container(inputPath)
+        with Plan(c_params, 0) as plan:
+            stats = plan.code_stats(frames, N.FMT_PLANAR_BITS, nframes)
+    except N.CsicRuntimeError as e:
+        if e.status != N.ENODEVICE:
+            raise
+        print(f"[ERROR] No code statistics: {e}")
+        return 0
+    for k, st in enumerate(stats if nframes > 1 else [stats]):
+        print(f"Frame {k}:")
+        for i, name in enumerate(st.PLANES):
+            print(f"  {name:<2}: {st.samples[i]} samples, q = {st.bits[i]}, H0 = {st.entropy(0, i):.4f}, H1 = {st.entropy(1, i):.4f} bits / sample")
+        raw_bytes = (sum(n * q for n, q in zip(st.samples, st.bits)) + 7) // 8
+        print(f"  raw            : {st.raw_bits_per_pixel:.4f} bits / px, {raw_bytes} bytes")
+        for label, kind in (("order-0", 0), ("left-predicted", 1), ("best", "best")):
+            print(f"  {label:<15}: {st.bits_per_pixel(kind):.4f} bits / px, {st.ideal_bytes(kind)} bytes")
+    return 0
+
+
 def main(argv: List[str] = None) -> int:
     args = list(sys.argv[1:] if argv is None else argv)
+    if args and args[0] == "inspect":
+        return _main_inspect(args[1:])
     if args and args[0] in ("compress", "decompress"):
         return _main_container(args[0], args[1:])
     argsMap = _args_map(args)

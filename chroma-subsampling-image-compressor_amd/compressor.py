@@ -91,6 +91,68 @@ class Ssim:
         return f"Ssim(sums={self.sums}, windows={self.windows})"
 
 
+class CodeStats:
+    """The histograms of one compressed frame (csic_code_stats_*; definition in include/csic.h): hist[kind][plane] is a uint64
+    array of 256 counts, kind 0 = the sample codes, 1 = their left-predicted residuals, planes Y, Cb, Cr (index or name) with
+    bits[plane] bits per code and samples[plane] samples.  entropy(kind, plane) is the zero-order entropy in bits per sample,
+    bits_per_pixel(kind) / ideal_bytes(kind) what an ideal order-0 coder of that kind spends on the frame per input pixel / in
+    bytes; kind "best" takes per plane the cheapest of raw, codes and residuals.  All in double precision from the counts."""
+
+    KINDS = ("codes", "residuals")
+    PLANES = ("Y", "Cb", "Cr")
+
+    def __init__(self, hist, bits, pixels: int):
+        self.hist = np.array(hist, dtype=np.uint64).reshape(N.STATS_KINDS, N.STATS_PLANES, N.STATS_BINS)
+        self.bits = tuple(int(v) for v in bits)
+        if len(self.bits) != N.STATS_PLANES:
+            raise ValueError(f"need {N.STATS_PLANES} bit widths (Y, Cb, Cr), got {len(self.bits)}")
+        self.pixels = int(pixels)
+        self.samples = tuple(int(self.hist[0, p].sum()) for p in range(N.STATS_PLANES))
+
+    def _kind(self, kind) -> int:
+        return self.KINDS.index(kind) if isinstance(kind, str) else int(kind)
+
+    def _plane(self, plane) -> int:
+        return self.PLANES.index(plane) if isinstance(plane, str) else int(plane)
+
+    def entropy(self, kind, plane) -> float:
+        h = self.hist[self._kind(kind), self._plane(plane)].astype(np.float64)
+        total = h.sum()
+        if total == 0:
+            return 0.0
+        p = h[h > 0] / total
+        return max(0.0, float(-(p * np.log2(p)).sum()))
+
+    def _plane_bits(self, kind, p: int) -> float:
+        """Bits plane p takes under `kind` (0, 1 or "best")."""
+        if kind == "best":
+            return self.samples[p] * min(float(self.bits[p]), self.entropy(0, p), self.entropy(1, p))
+        return self.samples[p] * self.entropy(kind, p)
+
+    def total_bits(self, kind) -> float:
+        return sum(self._plane_bits(kind, p) for p in range(N.STATS_PLANES))
+
+    def bits_per_pixel(self, kind) -> float:
+        return self.total_bits(kind) / self.pixels
+
+    def ideal_bytes(self, kind) -> int:
+        return int(math.ceil(self.total_bits(kind) / 8.0))
+
+    @property
+    def raw_bits_per_pixel(self) -> float:
+        return sum(n * q for n, q in zip(self.samples, self.bits)) / self.pixels
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, CodeStats) and (self.bits, self.pixels) == (other.bits, other.pixels) \
+            and np.array_equal(self.hist, other.hist)
+
+    __hash__ = None
+
+    def __repr__(self) -> str:
+        return (f"CodeStats(samples={self.samples}, bits={self.bits}, pixels={self.pixels}, raw={self.raw_bits_per_pixel:.4f}, "
+                f"H0={self.bits_per_pixel(0):.4f}, H1={self.bits_per_pixel(1):.4f}, best={self.bits_per_pixel('best'):.4f} bits/px)")
+
+
 class Plan:
     """One validated parameter set bound to one HIP device (csic_plan_create / csic_plan_destroy)."""
 
@@ -293,6 +355,57 @@ class Plan:
         wy, wx = self.ssim_windows
         out = [Ssim(row, wy * wx) for row in sums]
         return out[0] if single and n == 1 else out
+
+    # -- code statistics (csic_code_stats_*) ------------------------------------------------------
+    def _stats_format(self, src_format) -> int:
+        src_format = self.c_params.out_format if src_format is None else int(src_format)
+        if src_format not in (N.FMT_PLANAR, N.FMT_PLANAR_BITS):
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: code statistics read PLANAR or PLANAR_BITS frames, not format {src_format}")
+        return src_format
+
+    def code_stats_kernel_name(self, src_format=None) -> str:
+        return N.lib().csic_code_stats_kernel_name(self._h, self._stats_format(src_format)).decode()
+
+    def code_stats_block_samples(self, src_format=None) -> int:
+        """Consecutive samples of a plane that one block counts (csic_code_stats_block_samples)."""
+        b = C.c_int64()
+        N.check(N.lib().csic_code_stats_block_samples(self._h, self._stats_format(src_format), C.byref(b)))
+        return b.value
+
+    def code_stats_device(self, d_src, src_format=None, nframes: int = 1):
+        """d_src: contiguous CUDA tensor of nframes PLANAR / PLANAR_BITS frame buffers (None = the plan's own out_format).  Returns
+        an int64 tensor (nframes, 2, 3, 256) on the device: the counts [kind][plane][bin] of each frame (never above 2^63).
+        Asynchronous on torch's current stream; no workspace."""
+        import torch
+        src_format = self._stats_format(src_format)
+        if not d_src.is_cuda or not d_src.is_contiguous() or d_src.numel() * d_src.element_size() != nframes * self._decode_src_bytes(src_format):
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_src must be a contiguous CUDA tensor of nframes source frames")
+        if d_src.device.index != self.device:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: tensor is on a different device than the plan")
+        d_hist = torch.empty((nframes, N.STATS_KINDS, N.STATS_PLANES, N.STATS_BINS), dtype=torch.int64, device=d_src.device)
+        N.check(N.lib().csic_code_stats_device(self._h, C.c_void_p(d_src.data_ptr()), src_format, int(nframes),
+                                               C.c_void_p(d_hist.data_ptr()), self._stream()))
+        return d_hist
+
+    def code_stats_host(self, buf, src_format=None, nframes: int = 1) -> np.ndarray:
+        """csic_code_stats_host: nframes frame buffers in host memory -> uint64 array (nframes, 2, 3, 256)."""
+        src_format = self._stats_format(src_format)
+        a = np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
+        hist = np.zeros((nframes, N.STATS_KINDS, N.STATS_PLANES, N.STATS_BINS), dtype=np.uint64)
+        N.check(N.lib().csic_code_stats_host(self._h, a.ctypes.data_as(C.c_void_p), a.size, src_format, int(nframes),
+                                             hist.ctypes.data_as(C.c_void_p)))
+        return hist
+
+    def code_stats(self, src, src_format=None, nframes: int = 1):
+        """One compressed frame -> CodeStats; nframes > 1 -> a list of them.  Host bytes go through csic_code_stats_host, a CUDA
+        tensor through code_stats_device (synchronised here)."""
+        if _is_torch_tensor(src):
+            hist = self.code_stats_device(src.contiguous(), src_format, nframes).cpu().numpy().view(np.uint64)
+        else:
+            hist = self.code_stats_host(src, src_format, nframes)
+        bits = (self.c_params.y_bits, self.c_params.cb_bits, self.c_params.cr_bits)
+        out = [CodeStats(h, bits, self.width * self.height) for h in hist]
+        return out[0] if nframes == 1 else out
 
     # -- compute ----------------------------------------------------------------------------------
     def _stream(self):
@@ -610,6 +723,13 @@ class ImageCompressorTop:
         """How much of the structure of `argb` (one frame, or a stack (n, H, W)) these parameters keep: Ssim (list of them for a
         stack) -- the per-channel 8 x 8 block SSIM against the packed ARGB / YCbCr outputs."""
         return self.plan(PixelFormat.ARGB8888).ssim(argb)
+
+    def codeStats(self, argb):
+        """What the samples of `argb`'s compressed frame really carry: CodeStats of its bit-packed planes (csic_code_stats_*).  A
+        CUDA frame is compressed and measured on the device with no host round trip in between; a numpy frame goes through the
+        two host entry points."""
+        pl = self.plan(PixelFormat.PLANAR_BITS)
+        return pl.code_stats(pl.process(argb))
 
     def processPlanarBits(self, argb):
         """ARGB frame in -> one bit-packed planar frame buffer (CSIC_FMT_PLANAR_BITS, uint8: planar_bits_layout.frame_bytes on the

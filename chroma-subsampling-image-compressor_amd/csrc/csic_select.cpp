@@ -408,4 +408,21 @@ const char *measure_kernel_name(MeasureFamily fam, int kind, const csic_params &
     return names[fam == MEASURE_DIST ? 0 : 1][kind == 0 ? gen : 3 + kind];
 }
 
+CodeStatsKind code_stats_kind(int src_format, const Tune &t)
+{
+    if (t.force_generic || t.variant == 9) return CSTAT_GEN;
+    if (src_format == CSIC_FMT_PLANAR_BITS) return CSTAT_BITS;
+    return t.no_vec ? CSTAT_GEN : CSTAT_BYTES;         // k_cstat_bytes is 16-byte loads throughout
+}
+
+void code_stats_kernel_name(CodeStatsKind kind, int src_format, const csic_params &p, const Tune &t, char *buf, size_t len)
+{
+    const char *nt = t.no_nt ? "cached" : "nt";
+    switch (kind) {
+    case CSTAT_BYTES: snprintf(buf, len, "k_cstat_bytes<%s>", nt); break;
+    case CSTAT_BITS: snprintf(buf, len, "k_cstat_bits<q%d,%d,%d,%s>", p.y_bits, p.cb_bits, p.cr_bits, nt); break;
+    default: snprintf(buf, len, "k_cstat_gen<%s>", src_format == CSIC_FMT_PLANAR_BITS ? "bits" : "planar"); break;
+    }
+}
+
 } // namespace csic

@@ -94,4 +94,14 @@ int measure_kind(const csic_params &p, const Geometry &g, const Tune &t, Measure
 // "k_dist_fast<f1>", "k_ssim_gen<avg,ycc-in>", ...: a static string
 const char *measure_kernel_name(MeasureFamily fam, int kind, const csic_params &p);
 
+// ---- code statistics (csic_code_stats.hip) ----------------------------------------------------------------
+// CSTAT_GEN = k_cstat_gen (either source format), CSTAT_BYTES = k_cstat_bytes (CSIC_FMT_PLANAR), CSTAT_BITS = k_cstat_bits (CSIC_FMT_PLANAR_BITS)
+enum CodeStatsKind { CSTAT_GEN, CSTAT_BYTES, CSTAT_BITS };
+constexpr int CSTAT_T = 256;                    // threads per block
+constexpr int64_t CSTAT_BLOCK_SAMPLES = 65536;  // consecutive samples of one plane that one block counts, whichever kernel
+// src_format: CSIC_FMT_PLANAR or CSIC_FMT_PLANAR_BITS (validated by the caller)
+CodeStatsKind code_stats_kind(int src_format, const Tune &t);
+// "k_cstat_bytes<nt>", "k_cstat_bits<q6,5,5,nt>" (the Q of the Y, Cb and Cr launches), "k_cstat_gen<planar>" / "<bits>"
+void code_stats_kernel_name(CodeStatsKind kind, int src_format, const csic_params &p, const Tune &t, char *buf, size_t len);
+
 } // namespace csic

@@ -326,6 +326,57 @@ int  csic_ssim_device(csic_plan *plan, const void *d_in, int32_t nframes, int64_
 int  csic_ssim_host(csic_plan *plan, const uint32_t *in, size_t in_px, int32_t nframes, int64_t *ssim, int32_t *map);
 const char *csic_ssim_kernel_name(const csic_plan *plan);
 
+/* ---- code statistics: what the samples of a compressed frame really carry --------------------------------------------------------
+ * csic_distortion_* and csic_ssim_* measure what a parameter set costs in quality; this is the rate side.  The raw size of the
+ * bit-packed planes depends on the parameters alone.  These entry points return exact histograms of the sample codes of a compressed
+ * frame and of their left-predicted residuals, from which the host layers compute zero-order entropies and the size an entropy coder
+ * could reach.  No entropy coder is part of the library.
+ *
+ * Source: a compressed frame of the plan's parameters, as for csic_decode_device.  src_format is CSIC_FMT_PLANAR or
+ * CSIC_FMT_PLANAR_BITS (anything else: CSIC_EINVAL_FORMAT); frames lie frame_bytes apart (csic_planar_layout_of /
+ * csic_planar_bits_layout_of) and are 256-byte aligned; every parameter set csic_decode_device accepts for that format is accepted.
+ *
+ * Planes p = 0, 1, 2 are Y, Cb, Cr with q_p = y_bits, cb_bits, cr_bits.  Plane 0 has n_0 = y_width * y_height samples, planes 1 and
+ * 2 chroma_samples each.  Bytes or bits of a plane beyond its samples are never read into a count, the unwritten tail of a partial
+ * last chroma row included.  The code c_i of sample i:
+ *     PLANAR      : byte i of the plane >> (8 - q)    (the low bits are ignored, not checked)
+ *     PLANAR_BITS : the q bits at [i q, i q + q), LSB first, as stated above for csic_planar_bits_layout
+ * Two histograms per plane, over the plane's samples in storage order:
+ *     kind 0, codes     : h0[c_i] += 1
+ *     kind 1, residuals : e_0 = c_0,  e_i = (c_i - c_(i-1)) mod 2^q for i >= 1,  h1[e_i] += 1
+ * Storage order is the order a coder walking the plane meets the samples: the predecessor of a row's first sample is the previous
+ * row's last, with no special case per row.  Worked vectors (the ones of the bit layout above):
+ *     q = 3, codes 1,2,3,4,5,6,7,0 -> h1[1] = 8          q = 5, codes 0x1f, 0, 0x15 -> h1[0x1f] = h1[1] = h1[0x15] = 1
+ *
+ * Result per frame: uint64_t [CSIC_STATS_KINDS][CSIC_STATS_PLANES][CSIC_STATS_BINS], 12 288 bytes, frames back to back.  Bins >= 2^q
+ * are 0; a plane without samples gives all zeros.  Every count is exact, so the result does not depend on scheduling.
+ *
+ * Derived figures (host layers only, double precision, from the counts; N = a histogram's total, n_i its bins):
+ *     H_k,p = -sum (n_i / N) log2(n_i / N)   bits per sample; 0 for an empty or single-valued plane
+ *     bits_per_pixel(k) = sum_p N_p H_k,p / (width * height)          ideal_bytes(k) = ceil(sum_p N_p H_k,p / 8)
+ *     "best" takes, per plane, min(q_p, H_0,p, H_1,p): raw, order-0 or left-predicted, whichever a coder would choose
+ *
+ * csic_code_stats_device : d_src -> d_hist[nframes * 2 * 3 * 256] (8-byte aligned).  Asynchronous on `hip_stream`, no allocation, no
+ *             workspace, no synchronisation, hipGraph-capturable: d_hist is cleared by a memset on the stream, blocks count in LDS and
+ *             add their non-zero bins with 64-bit atomics.  NULL plan, d_src or d_hist fail with CSIC_EINVAL_NULL, a bad src_format
+ *             with CSIC_EINVAL_FORMAT, nframes outside 1..65535, a d_src that is not 256-byte aligned or a d_hist that is not 8-byte
+ *             aligned with CSIC_EINVAL_SIZE -- all before any device is touched.
+ * csic_code_stats_host   : the same from and to host memory, synchronous, allocates its staging; src_bytes = nframes * frame_bytes
+ *             (CSIC_EINVAL_SIZE otherwise).
+ * csic_code_stats_kernel_name : the kernel(s) csic_code_stats_device takes: k_cstat_bytes<nt> for PLANAR, k_cstat_bits<q6,5,5,nt> for
+ *             PLANAR_BITS (one instantiation per bit width: the widths of Y, Cb, Cr), k_cstat_gen<planar> / <bits> under
+ *             CSIC_TUNE_FORCE_GENERIC or CSIC_TUNE_VARIANT 9 (and, for PLANAR, CSIC_TUNE_NO_VECTOR); "" for a NULL plan or another
+ *             format.  The string belongs to the calling thread and is valid until its next call of this function.
+ * csic_code_stats_block_samples : consecutive samples of a plane that one block counts (the predecessor crosses lanes, waves and
+ *             blocks: tests build frames around this number).  Needs no device. */
+#define CSIC_STATS_KINDS  2    /* 0 = codes, 1 = residuals of the left predictor */
+#define CSIC_STATS_PLANES 3    /* Y, Cb, Cr */
+#define CSIC_STATS_BINS   256
+int  csic_code_stats_device(csic_plan *plan, const void *d_src, int32_t src_format, int32_t nframes, uint64_t *d_hist, void *hip_stream);
+int  csic_code_stats_host(csic_plan *plan, const void *src, size_t src_bytes, int32_t src_format, int32_t nframes, uint64_t *hist);
+const char *csic_code_stats_kernel_name(const csic_plan *plan, int32_t src_format);
+int  csic_code_stats_block_samples(const csic_plan *plan, int32_t src_format, int64_t *samples);   /* samples one block covers; needs no device */
+
 const char *csic_strerror(int status);
 const char *csic_last_error(void);       /* thread-local; "" when the last call succeeded */
 
@@ -352,10 +403,12 @@ const char *csic_plan_kernel_name(const csic_plan *plan);
  *                       12 = planar AVG at factor 1 on frames of whole tiles: k_avg's body with the planar sink instead of k_planar_avg_f1)
  *   CSIC_TUNE_FORCE_GENERIC : 1 = always use the one-thread-per-pixel generic kernel
  *                             (csic_distortion_device: its general kernel k_dist_gen; csic_ssim_device: its general kernel
- *                             k_ssim_gen; nothing else changes for the other entry points)
+ *                             k_ssim_gen; csic_code_stats_device: its general kernel k_cstat_gen; nothing else changes for the
+ *                             other entry points)
  *   CSIC_TUNE_NONTEMPORAL   : 1 (default) = non-temporal loads/stores for the frame stream, 0 = cached
  *   CSIC_TUNE_NO_VECTOR     : 1 = never use the 16-byte-per-lane kernels (csic_decode_device: its general kernel;
- *                             csic_distortion_device and csic_ssim_device: the 4-byte loads of their fast kernels, same sums)
+ *                             csic_distortion_device and csic_ssim_device: the 4-byte loads of their fast kernels, same sums;
+ *                             csic_code_stats_device on a PLANAR source: its general kernel)
  *   CSIC_TUNE_BLOCK_THREADS : threads per block, 64 / 128 / 256 (0 = the library's choice) */
 #define CSIC_TUNE_VARIANT        1
 #define CSIC_TUNE_FORCE_GENERIC  2

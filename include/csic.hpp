@@ -170,6 +170,103 @@ struct Ssim {
     double meanRgb() const { return (mean(R) + mean(G) + mean(B)) / 3.0; }
 };
 
+// The histograms of one compressed frame (csic.h: csic_code_stats_*): hist[kind][plane][bin], kind 0 = the sample codes, 1 = their
+// left-predicted residuals, planes Y, Cb, Cr with bits[plane] bits per code; `pixels` = width * height of the image.  entropy() is
+// the zero-order entropy in bits per sample, bitsPerPixel() / idealBytes() what an ideal coder of that kind spends on the frame;
+// Best takes per plane the cheapest of raw, codes and residuals.  Double precision, from the counts.
+struct CodeStats {
+    enum Kind { Codes = 0, Residuals = 1, Best = 2 };
+    enum Plane { Y = 0, Cb = 1, Cr = 2 };
+    uint64_t hist[CSIC_STATS_KINDS][CSIC_STATS_PLANES][CSIC_STATS_BINS] = {};
+    int bits[CSIC_STATS_PLANES] = {0, 0, 0};
+    int64_t pixels = 0;
+    uint64_t samples(int plane) const
+    {
+        uint64_t n = 0;
+        for (int i = 0; i < CSIC_STATS_BINS; ++i) n += hist[0][plane][i];
+        return n;
+    }
+    double entropy(int kind, int plane) const
+    {
+        uint64_t total = 0;
+        for (int i = 0; i < CSIC_STATS_BINS; ++i) total += hist[kind][plane][i];
+        double h = 0.0;
+        for (int i = 0; i < CSIC_STATS_BINS; ++i) {
+            if (hist[kind][plane][i] == 0) continue;
+            const double p = (double)hist[kind][plane][i] / (double)total;
+            h -= p * std::log2(p);
+        }
+        return h > 0.0 ? h : 0.0;
+    }
+    double totalBits(int kind) const
+    {
+        double t = 0.0;
+        for (int p = 0; p < CSIC_STATS_PLANES; ++p) {
+            double b = kind == Best ? std::fmin((double)bits[p], std::fmin(entropy(Codes, p), entropy(Residuals, p))) : entropy(kind, p);
+            t += (double)samples(p) * b;
+        }
+        return t;
+    }
+    double bitsPerPixel(int kind) const { return totalBits(kind) / (double)pixels; }
+    int64_t idealBytes(int kind) const { return (int64_t)std::ceil(totalBits(kind) / 8.0); }
+    double rawBitsPerPixel() const
+    {
+        double t = 0.0;
+        for (int p = 0; p < CSIC_STATS_PLANES; ++p) t += (double)samples(p) * (double)bits[p];
+        return t / (double)pixels;
+    }
+    bool operator==(const CodeStats &o) const
+    {
+        return std::memcmp(hist, o.hist, sizeof hist) == 0 && std::memcmp(bits, o.bits, sizeof bits) == 0 && pixels == o.pixels;
+    }
+};
+
+// One validated parameter set bound to one device (csic_plan_create / csic_plan_destroy), for what works on compressed frames of
+// known parameters -- a container's, for instance -- rather than on an image.
+class Plan {
+public:
+    explicit Plan(const csic_params &p, int device = 0) : params_(p) { check(csic_plan_create(&params_, device, &plan_)); }
+    Plan(const Plan &) = delete;
+    Plan &operator=(const Plan &) = delete;
+    ~Plan() { csic_plan_destroy(plan_); }
+    csic_plan *native() { return plan_; }
+    const csic_params &params() const { return params_; }
+    // `nframes` compressed frames in host memory (PLANAR_BITS / PLANAR frame buffers, frame_bytes apart) -> one CodeStats per frame
+    std::vector<CodeStats> codeStats(const void *src, size_t src_bytes, PixelFormat src_format = PixelFormat::PLANAR_BITS, int nframes = 1)
+    {
+        const size_t n = (size_t)(nframes > 0 ? nframes : 0);
+        std::vector<uint64_t> hist(n * CSIC_STATS_KINDS * CSIC_STATS_PLANES * CSIC_STATS_BINS);
+        check(csic_code_stats_host(plan_, src, src_bytes, (int32_t)src_format, nframes, hist.data()));
+        std::vector<CodeStats> out(n);
+        for (size_t k = 0; k < n; ++k) {
+            std::memcpy(out[k].hist, hist.data() + k * CSIC_STATS_KINDS * CSIC_STATS_PLANES * CSIC_STATS_BINS, sizeof out[k].hist);
+            out[k].bits[0] = params_.y_bits; out[k].bits[1] = params_.cb_bits; out[k].bits[2] = params_.cr_bits;
+            out[k].pixels = (int64_t)params_.width * params_.height;
+        }
+        return out;
+    }
+    // device-resident: d_hist receives nframes * 2 * 3 * 256 counts (8-byte aligned); asynchronous on `hip_stream`, no workspace,
+    // no allocation, capturable
+    void codeStatsDevice(const void *d_src, PixelFormat src_format, int nframes, uint64_t *d_hist, void *hip_stream)
+    {
+        check(csic_code_stats_device(plan_, d_src, (int32_t)src_format, nframes, d_hist, hip_stream));
+    }
+    const char *codeStatsKernelName(PixelFormat src_format = PixelFormat::PLANAR_BITS)
+    {
+        return csic_code_stats_kernel_name(plan_, (int32_t)src_format);
+    }
+    int64_t codeStatsBlockSamples(PixelFormat src_format = PixelFormat::PLANAR_BITS)
+    {
+        int64_t n = 0;
+        check(csic_code_stats_block_samples(plan_, (int32_t)src_format, &n));
+        return n;
+    }
+
+private:
+    csic_params params_;
+    csic_plan *plan_ = nullptr;
+};
+
 class ImageCompressorTop {
 public:
     ImageCompressorTop(int width, int height, int chroma_param_a_config, int chroma_param_b_config,
@@ -344,6 +441,21 @@ public:
         check(csic_ssim_device(plan(PixelFormat::ARGB8888), d_in, nframes, d_ssim, d_map, d_workspace, workspace_bytes, hip_stream));
     }
     const char *ssimKernelName() { return csic_ssim_kernel_name(plan(PixelFormat::ARGB8888)); }
+    // What the samples of an ARGB frame's compressed form really carry: compresses to bit-packed planes, then measures them
+    // (csic_code_stats_*), host memory in, CodeStats out.
+    CodeStats codeStats(const std::vector<uint32_t> &argb)
+    {
+        const PlanarBitsFrame fr = processPlanarBits(argb);
+        CodeStats out;
+        check(csic_code_stats_host(plan(PixelFormat::PLANAR_BITS), fr.bytes.data(), fr.bytes.size(), CSIC_FMT_PLANAR_BITS, 1, &out.hist[0][0][0]));
+        out.bits[0] = params_.y_bits; out.bits[1] = params_.cb_bits; out.bits[2] = params_.cr_bits;
+        out.pixels = (int64_t)params_.width * params_.height;
+        return out;
+    }
+    const char *codeStatsKernelName(PixelFormat src_format = PixelFormat::PLANAR_BITS)
+    {
+        return csic_code_stats_kernel_name(plan(PixelFormat::PLANAR_BITS), (int32_t)src_format);
+    }
     // the plan behind process(): what FrameGraph records launches of (owned by this object)
     csic_plan *nativePlan(PixelFormat f = PixelFormat::ARGB8888) { return plan(f); }
 

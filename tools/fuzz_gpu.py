@@ -2,6 +2,7 @@
 """Randomised differential run: the HIP path (through the C ABI) against the CPU oracle on fresh seeds.
     python tools/fuzz_gpu.py [seconds] [seed]
 Covers every kernel family, both samplings, both input formats, planar output with its reconstruct kernel (one case in three),
+code statistics of the PLANAR and PLANAR_BITS frames (one case in four: planar against bits, fast against general, both against numpy),
 tuning knobs, odd shapes and batches, and -- for one
 case in three -- the pre-recorded launch paths: the same frames through a frame graph (csic_frame_graph_*), HIP chains or
 direct dispatch, ordered by the host (submit/wait) or with a stream (launch), random branch/queue counts.
@@ -102,6 +103,31 @@ while time.time() < t_end:
                         if not (np.array_equal(y, y_w) and np.array_equal(cb, cb_w) and np.array_equal(cr, cr_w)):
                             print(f"MISMATCH (planar, fused frame graph of {nf}) seed={seed} case={n} {pp.kernel_name} W={W} H={H} a={a} b={b} bits={bits} f={f} "
                                   f"op={op} rounding={rounding} avg={avg}")
+                            sys.exit(1)
+        if rng.random() < 0.25 and not ycc_in:
+            # code statistics (csic_code_stats_*) of the library's own PLANAR and PLANAR_BITS frames of these parameters: the fast
+            # kernel of each format and the general one must give the same counts, and those of np.bincount on the oracle's planes
+            _, y_o, cb_o, cr_o = orc.planar(op_, frame, avg=avg)
+            want_h = np.zeros((2, 3, 256), dtype=np.uint64)
+            for p_, (v, q) in enumerate(zip((y_o, cb_o, cr_o), bits)):
+                c = np.asarray(v, dtype=np.uint8).reshape(-1).astype(np.int64) >> (8 - q)
+                want_h[0, p_] = np.bincount(c, minlength=256)
+                want_h[1, p_] = np.bincount(np.concatenate([c[:1], np.diff(c) % (1 << q)]), minlength=256)
+            d_in = torch.from_numpy(frame.view(np.int32)).cuda()
+            for sfmt in (N.FMT_PLANAR, N.FMT_PLANAR_BITS):
+                cps = csic.make_c_params(W, H, a, b, *bits, f, op, rounding=rounding, out_format=sfmt, sampling=1 if avg else 0)
+                with csic.Plan(cps, 0) as ps:
+                    buf = ps.process_device(d_in)
+                    for knob, val in ((None, None), (N.TUNE_NONTEMPORAL, 0), (N.TUNE_FORCE_GENERIC, 1)):
+                        if knob is not None:
+                            ps.tune(knob, val)
+                        got_h = ps.code_stats_device(buf).cpu().numpy().view(np.uint64)[0]
+                        fam = ps.code_stats_kernel_name().split("<")[0]
+                        families[fam] = families.get(fam, 0) + 1
+                        if not np.array_equal(got_h, want_h):
+                            kd, pn, bn = np.argwhere(got_h != want_h)[0].tolist()
+                            print(f"MISMATCH (code stats) seed={seed} case={n} {ps.code_stats_kernel_name()} W={W} H={H} a={a} b={b} bits={bits} f={f} "
+                                  f"op={op} rounding={rounding} avg={avg} first_bad=kind {kd} plane {pn} bin {bn}: {got_h[kd, pn, bn]} != {want_h[kd, pn, bn]}")
                             sys.exit(1)
         if rng.random() < 0.34 and not ycc_in:
             # the same frame, 1-5 copies with different contents, through a pre-recorded frame graph
