@@ -13,7 +13,8 @@ from .model import Image, ImageProcessorModel
 from .pipeline import FramePipeline
 from .stages import (ChromaSubsampler, ColorQuantizer, PixelBundle, PixelYCbCrBundle, ReferenceModel, RGB2YCbCr,
                      SpatialDownsampler, YCbCrUtils, pack_ycc, unpack_ycc)
-from .container import container_info, read_container, write_container
+from .container import (container_coded_sizes, container_info, pack_frame_host, pack_layout, read_container, unpack_frame_host,
+                        write_container, write_container_coded)
 from .app import ImageCompressionApp
 from .distributed import MultiDeviceCompressor, Stripe, StripedImageCompressorTop, halo_stripe_for_rank, stripe_for_rank
 from . import app, compressor, container, distributed, model, params, pipeline, stages, stream
@@ -23,5 +24,6 @@ __all__ = [
     "Rounding", "Sampling", "make_c_params", "ImageCompressorTop", "ImageProcessor", "Plan", "FrameGraph", "Distortion", "Ssim", "CodeStats", "Image", "ImageProcessorModel",
     "ImageCompressionApp", "FramePipeline", "ChromaSubsampler", "ColorQuantizer", "PixelBundle", "PixelYCbCrBundle", "ReferenceModel", "RGB2YCbCr",
     "SpatialDownsampler", "YCbCrUtils", "pack_ycc", "unpack_ycc", "Stripe", "StripedImageCompressorTop", "MultiDeviceCompressor", "halo_stripe_for_rank", "stripe_for_rank",
-    "container_info", "read_container", "write_container",
+    "container_info", "read_container", "write_container", "write_container_coded", "container_coded_sizes", "pack_layout", "pack_frame_host",
+    "unpack_frame_host",
 ]

@@ -10,13 +10,14 @@ HIP launch.
 
 Two leading verbs go past what the reference's app does (it only ever writes the reconstructed pixels as a PNG):
 
-    python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ...
+    python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ... [--coding raw|groups]
     python -m csic_amd.app decompress --input x.csic --output x.png
 
     python -m csic_amd.app inspect    --input x.csic
 
-`compress` writes the bit-packed planes as a .csic container (include/csic.h), `decompress` decodes one back to a PNG of the
-original size, `inspect` prints a container's header and, per frame, what its samples carry: the entropies of the codes and of
+`compress` writes the bit-packed planes as a .csic container (include/csic.h) -- as they are (`--coding raw`, the default: version 1)
+or group-coded on the GPU (`--coding groups`: csic_pack_device, version 3, lossless and smaller) --, `decompress` decodes either back
+to a PNG of the original size, `inspect` prints a container's header, its coding and stored bytes per frame and, per frame, what its samples carry: the entropies of the codes and of
 their left-predicted residuals and the sizes an entropy coder could reach (csic_code_stats_*).  The verb must be the first
 argument; with any other first argument main() behaves as described above.
 """
@@ -30,7 +31,7 @@ import numpy as np
 
 from .compressor import ImageCompressorTop, Plan
 from . import _native as N
-from .container import container_info, read_container, write_container
+from .container import container_coded_sizes, container_info, read_container, write_container, write_container_coded
 from .model import Image, ImageProcessorModel
 from .params import PixelFormat, ProcessingStep, Sampling
 
@@ -87,16 +88,25 @@ class ImageCompressionApp:
                       yTargetBits: int, cbTargetBits: int, crTargetBits: int,
                       spatialFactorToUse: int,
                       op1: ProcessingStep, op2: ProcessingStep, op3: ProcessingStep,
-                      sampling: Sampling = Sampling.HOLD_DECIMATE, *, device: int = 0) -> int:
-        """PNG -> CSIC_FMT_PLANAR_BITS plan -> .csic container.  Returns the bytes written (80 + payload_bytes)."""
+                      sampling: Sampling = Sampling.HOLD_DECIMATE, *, device: int = 0, coding: str = "raw") -> int:
+        """PNG -> CSIC_FMT_PLANAR_BITS plan -> .csic container.  Returns the bytes written (coding "raw": 80 + payload_bytes;
+        "groups": the frame is group-coded on the device and goes out through csic_container_write_coded)."""
+        if coding not in ("raw", "groups"):
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: --coding must be raw or groups, got {coding!r}")
         inputImage = ImageProcessorModel.readImage(inputImagePath)
         top = ImageCompressorTop(inputImage.width, inputImage.height, chromaParamA, chromaParamB, yTargetBits, cbTargetBits,
                                  crTargetBits, spatialFactorToUse, op1, op2, op3, device=device, sampling=sampling)
         try:
             plan = top.plan(PixelFormat.PLANAR_BITS)
-            bits = plan.process_host(inputImage.argb)
             os.makedirs(os.path.dirname(os.path.abspath(outputPath)), exist_ok=True)
-            write_container(outputPath, plan.c_params, bits)
+            if coding == "groups":
+                import torch
+                d_in = torch.from_numpy(np.ascontiguousarray(inputImage.argb, dtype=np.uint32).reshape(-1).view(np.int32)).to(f"cuda:{device}")
+                coded, sizes = plan.pack_device(plan.process_device(d_in))
+                write_container_coded(outputPath, plan.c_params, coded.cpu().numpy(), sizes.cpu().numpy())
+            else:
+                bits = plan.process_host(inputImage.argb)
+                write_container(outputPath, plan.c_params, bits)
         finally:
             top.close()
         return os.path.getsize(outputPath)
@@ -194,7 +204,8 @@ def _args_map(args: List[str]) -> Dict[str, str]:
 
 
 def _main_container(verb: str, args: List[str]) -> int:
-    """`compress` / `decompress`: the keys of the verb-less CLI with its defaults, plus --output and (compress) --sampling avg."""
+    """`compress` / `decompress`: the keys of the verb-less CLI with its defaults, plus --output and (compress) --sampling avg and
+    --coding raw|groups."""
     argsMap = _args_map(args)
     if "--input" not in argsMap or "--output" not in argsMap:
         print(f"[ERROR] {verb} needs --input and --output")
@@ -208,11 +219,15 @@ def _main_container(verb: str, args: List[str]) -> int:
         print(f"Decompression complete. Output saved to: {outputPath}")
         return 0
     sampling = Sampling.AVG if argsMap.get("--sampling", "hold").lower() == "avg" else Sampling.HOLD_DECIMATE
+    coding = argsMap.get("--coding", "raw").lower()
+    if coding not in ("raw", "groups"):
+        print(f"[ERROR] --coding must be raw or groups, got {coding}")
+        return 2
     size = ImageCompressionApp.compressImage(
         inputPath, outputPath, int(argsMap.get("--a", "4")), int(argsMap.get("--b", "4")), int(argsMap.get("--yq", "8")),
         int(argsMap.get("--cbq", "8")), int(argsMap.get("--crq", "8")), int(argsMap.get("--sf", "8")),
         ProcessingStep.parse(argsMap.get("--op1", "spatial")), ProcessingStep.parse(argsMap.get("--op2", "color")),
-        ProcessingStep.parse(argsMap.get("--op3", "chroma")), sampling)
+        ProcessingStep.parse(argsMap.get("--op3", "chroma")), sampling, coding=coding)
     print(f"Compression complete. {os.path.getsize(inputPath)} -> {size} bytes. Output saved to: {outputPath}")
     return 0
 
@@ -234,6 +249,9 @@ def _main_inspect(args: List[str]) -> int:
     print(f"Image: {p.width}x{p.height}, chroma 4:{p.chroma_a}:{p.chroma_b}, bits Y/Cb/Cr {p.y_bits}/{p.cb_bits}/{p.cr_bits}, "
           f"factor {p.factor}, order {ops}, rounding {p.rounding}, sampling {p.sampling}")
     print(f"Frames: {info.nframes}, payload bytes per frame: {info.payload_bytes}")
+    print(f"Frame coding: {'groups' if info.version == 3 else 'raw'}")
+    for k, stored in enumerate(container_coded_sizes(inputPath)):
+        print(f"  frame {k}: stored in {int(stored)} bytes, {int(stored) / info.payload_bytes:.4f} of raw")
     try:
         c_params, nframes, frames = read_container(inputPath)
         with Plan(c_params, 0) as plan:

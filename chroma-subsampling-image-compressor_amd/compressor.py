@@ -19,6 +19,7 @@ from typing import Tuple
 import numpy as np
 
 from . import _native as N
+from .container import pack_frame_host, unpack_frame_host
 from .params import (ImageProcessorParams, PixelFormat, ProcessingStep, Rounding, Sampling, make_c_params)
 
 
@@ -406,6 +407,72 @@ class Plan:
         bits = (self.c_params.y_bits, self.c_params.cb_bits, self.c_params.cr_bits)
         out = [CodeStats(h, bits, self.width * self.height) for h in hist]
         return out[0] if nframes == 1 else out
+
+    # -- lossless group coding of PLANAR_BITS frames (csic_pack_*) -------------------------------------
+    @property
+    def pack_layout(self) -> N.CsicPackLayout:
+        """csic_pack_layout of these parameters: groups, section offsets, fixed_bytes, bound_bytes."""
+        lay = N.CsicPackLayout()
+        N.check(N.lib().csic_pack_layout_of(C.byref(self.c_params), C.byref(lay)))
+        return lay
+
+    @property
+    def pack_kernel_name(self) -> str:
+        return N.lib().csic_pack_kernel_name(self._h).decode()
+
+    def pack_workspace_bytes(self, nframes: int = 1) -> int:
+        b = C.c_size_t()
+        N.check(N.lib().csic_pack_workspace_bytes(self._h, int(nframes), C.byref(b)))
+        return b.value
+
+    def _pack_check(self, t, nbytes: int, what: str) -> None:
+        if not t.is_cuda or not t.is_contiguous() or t.numel() * t.element_size() != nbytes:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: {what} must be a contiguous CUDA tensor of {nbytes} bytes")
+        if t.device.index != self.device:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: tensor is on a different device than the plan")
+
+    def pack_device(self, d_bits, nframes: int = 1, d_coded=None):
+        """d_bits: nframes PLANAR_BITS frame buffers on the device (frame_bytes each).  Returns (coded, sizes): a uint8 tensor
+        (nframes, bound_bytes) whose row k holds frame k's coded bytes in [0, sizes[k]) -- the rest of a row is not written -- and an
+        int64 tensor (nframes,) of the coded sizes.  Asynchronous on torch's current stream."""
+        import torch
+        fb, bound = self.planar_bits_layout.frame_bytes, self.pack_layout.bound_bytes
+        self._pack_check(d_bits, nframes * fb, "d_bits")
+        if d_coded is None:
+            d_coded = torch.empty((nframes, bound), dtype=torch.uint8, device=d_bits.device)
+        else:
+            self._pack_check(d_coded, nframes * bound, "d_coded")
+        sizes = torch.empty((nframes,), dtype=torch.int64, device=d_bits.device)
+        wsb = self.pack_workspace_bytes(nframes)
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=d_bits.device)
+        N.check(N.lib().csic_pack_device(self._h, C.c_void_p(d_bits.data_ptr()), int(nframes), C.c_void_p(d_coded.data_ptr()),
+                                         C.c_void_p(sizes.data_ptr()), C.c_void_p(ws.data_ptr()), wsb, self._stream()))
+        return d_coded, sizes
+
+    def unpack_device(self, d_coded, nframes: int = 1, d_bits=None):
+        """The inverse of pack_device: d_coded holds nframes coded frames bound_bytes apart.  Returns the PLANAR_BITS frame buffers,
+        a uint8 tensor (nframes, frame_bytes) (one frame: (frame_bytes,)); only their payload ranges are written.  The device does
+        not validate: check untrusted bytes with unpack() first."""
+        import torch
+        fb, bound = self.planar_bits_layout.frame_bytes, self.pack_layout.bound_bytes
+        self._pack_check(d_coded, nframes * bound, "d_coded")
+        if d_bits is None:
+            d_bits = torch.empty((nframes, fb) if nframes > 1 else (fb,), dtype=torch.uint8, device=d_coded.device)
+        else:
+            self._pack_check(d_bits, nframes * fb, "d_bits")
+        wsb = self.pack_workspace_bytes(nframes)
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=d_coded.device)
+        N.check(N.lib().csic_unpack_device(self._h, C.c_void_p(d_coded.data_ptr()), int(nframes), C.c_void_p(d_bits.data_ptr()),
+                                           C.c_void_p(ws.data_ptr()), wsb, self._stream()))
+        return d_bits
+
+    def pack(self, bits_frame) -> np.ndarray:
+        """csic_pack_host: one PLANAR_BITS frame buffer in host memory -> its coded bytes (uint8 array).  Needs no GPU."""
+        return pack_frame_host(self.c_params, bits_frame)
+
+    def unpack(self, coded, out=None) -> np.ndarray:
+        """csic_unpack_host: coded bytes -> a PLANAR_BITS frame buffer (zero outside the payload ranges unless `out` is given)."""
+        return unpack_frame_host(self.c_params, coded, out)
 
     # -- compute ----------------------------------------------------------------------------------
     def _stream(self):

@@ -1,5 +1,5 @@
-""".csic files: CSIC_FMT_PLANAR_BITS frames on disk (csic_container_*; byte layout in include/csic.h).  Host only: nothing here
-needs a GPU."""
+""".csic files: CSIC_FMT_PLANAR_BITS frames on disk (csic_container_*; byte layout in include/csic.h), raw (version 1) or group-coded
+(version 3), and the host codec of the group coding (csic_pack_host / csic_unpack_host).  Host only: nothing here needs a GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,20 +18,101 @@ def container_info(path: str) -> N.CsicContainerInfo:
     return info
 
 
-def write_container(path: str, c_params: N.CsicParams, frames) -> None:
-    """frames: the PLANAR_BITS frame buffers of `c_params` (its out_format does not matter), frame_bytes each -- one buffer, an
-    array (nframes, frame_bytes), or a list of buffers.  Only the planes' payload bytes reach the file."""
+def _bits_params(c_params: N.CsicParams):
+    """-> (the parameters a container stores, their PLANAR_BITS layout); raises what csic_validate refuses."""
     lay = N.CsicPlanarBitsLayout()
     q = N.CsicParams.from_buffer_copy(c_params)
     q.out_format = N.FMT_PLANAR_BITS
     N.check(N.lib().csic_validate(C.byref(q)))
     N.check(N.lib().csic_planar_bits_layout_of(C.byref(q), C.byref(lay)))
+    return q, lay
+
+
+def _coding(coding) -> int:
+    if isinstance(coding, str):
+        names = {"raw": N.CODING_RAW, "groups": N.CODING_GROUPS}
+        if coding.lower() not in names:
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: coding must be 'raw' or 'groups', got {coding!r}")
+        return names[coding.lower()]
+    return int(coding)
+
+
+def pack_layout(c_params: N.CsicParams) -> N.CsicPackLayout:
+    """csic_pack_layout_of: groups, section offsets, fixed_bytes and bound_bytes of a coded frame of these parameters."""
+    lay = N.CsicPackLayout()
+    N.check(N.lib().csic_pack_layout_of(C.byref(c_params), C.byref(lay)))
+    return lay
+
+
+def pack_frame_host(c_params: N.CsicParams, bits_frame) -> np.ndarray:
+    """csic_pack_host: one PLANAR_BITS frame buffer (frame_bytes) -> its coded bytes, a uint8 array of coded_bytes."""
+    q, lay = _bits_params(c_params)
+    a = np.ascontiguousarray(bits_frame).reshape(-1).view(np.uint8)
+    if a.size != lay.frame_bytes:
+        raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: a frame buffer of these parameters has {lay.frame_bytes} bytes, got {a.size}")
+    coded = np.empty(pack_layout(q).bound_bytes, dtype=np.uint8)
+    n = C.c_uint64()
+    N.check(N.lib().csic_pack_host(C.byref(q), a.ctypes.data_as(C.c_void_p), coded.ctypes.data_as(C.c_void_p), coded.size, C.byref(n)))
+    return coded[:n.value].copy()
+
+
+def unpack_frame_host(c_params: N.CsicParams, coded, out=None) -> np.ndarray:
+    """csic_unpack_host: coded bytes -> a PLANAR_BITS frame buffer.  `out` (uint8, frame_bytes) keeps its bytes outside the three
+    payload ranges; without it the buffer is zero there.  Damaged input raises CsicIOError (CSIC_EFORMAT)."""
+    q, lay = _bits_params(c_params)
+    a = np.ascontiguousarray(coded).reshape(-1).view(np.uint8)
+    if out is None:
+        out = np.zeros(lay.frame_bytes, dtype=np.uint8)
+    elif out.dtype != np.uint8 or out.size != lay.frame_bytes or not out.flags.c_contiguous:
+        raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: out must be a contiguous uint8 buffer of {lay.frame_bytes} bytes")
+    N.check(N.lib().csic_unpack_host(C.byref(q), a.ctypes.data_as(C.c_void_p), a.size, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def write_container(path: str, c_params: N.CsicParams, frames, coding="raw") -> None:
+    """frames: the PLANAR_BITS frame buffers of `c_params` (its out_format does not matter), frame_bytes each -- one buffer, an
+    array (nframes, frame_bytes), or a list of buffers.  Only the planes' payload bytes reach the file.  coding = "raw" (version 1,
+    the bytes as they are) or "groups" (version 3, every frame group-coded on the host: csic_container_write_ex)."""
+    q, lay = _bits_params(c_params)
+    coding = _coding(coding)
     if isinstance(frames, (list, tuple)):
         frames = np.stack([np.ascontiguousarray(f).reshape(-1).view(np.uint8) for f in frames])
     a = np.ascontiguousarray(frames).reshape(-1).view(np.uint8)
     if a.size == 0 or a.size % lay.frame_bytes != 0:
         raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: frames must hold whole frame buffers of {lay.frame_bytes} bytes, got {a.size}")
-    N.check(N.lib().csic_container_write(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.size // lay.frame_bytes))
+    if coding == N.CODING_RAW:
+        N.check(N.lib().csic_container_write(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.size // lay.frame_bytes))
+    else:
+        N.check(N.lib().csic_container_write_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.size // lay.frame_bytes, coding))
+
+
+def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes) -> None:
+    """Version 3 from frames that are packed already (csic_container_write_coded): `coded` is an array (nframes, stride) -- what
+    Plan.pack_device returns, copied to the host -- or a list of coded frames; sizes[k] is frame k's coded_bytes.  Every frame is
+    validated before anything is written."""
+    q, _ = _bits_params(c_params)
+    sz = np.ascontiguousarray(np.asarray(sizes).reshape(-1), dtype=np.uint64)
+    if isinstance(coded, (list, tuple)):
+        rows = [np.ascontiguousarray(f).reshape(-1).view(np.uint8) for f in coded]
+        stride = max([r.size for r in rows] + [1])
+        a = np.zeros((len(rows), stride), dtype=np.uint8)
+        for k, r in enumerate(rows):
+            a[k, :r.size] = r
+    else:
+        a = np.ascontiguousarray(coded).view(np.uint8)
+        a = a.reshape(sz.size, -1) if sz.size and a.size % sz.size == 0 else a.reshape(1, -1)
+    if sz.size == 0 or a.shape[0] != sz.size:
+        raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: {a.shape[0]} coded frames but {sz.size} sizes")
+    N.check(N.lib().csic_container_write_coded(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1],
+                                               sz.ctypes.data_as(C.POINTER(C.c_uint64)), int(sz.size)))
+
+
+def container_coded_sizes(path: str) -> np.ndarray:
+    """The stored bytes of each frame (csic_container_coded_sizes): a version-3 file's table, payload_bytes per frame for version 1."""
+    info = container_info(path)
+    sizes = np.zeros(info.nframes, dtype=np.uint64)
+    N.check(N.lib().csic_container_coded_sizes(os.fsencode(path), sizes.ctypes.data_as(C.POINTER(C.c_uint64)), info.nframes))
+    return sizes
 
 
 def read_container(path: str) -> Tuple[N.CsicParams, int, np.ndarray]:

@@ -1,21 +1,37 @@
 // csic_container.cpp -- .csic files: CSIC_FMT_PLANAR_BITS frames on disk (host only, no device; byte layout in include/csic.h).
 // A file is an 80-byte header -- magic, version, frame count, CRC-32 of everything behind the CRC field, the parameters -- and per
 // frame the three planes' payload bytes back to back: the padding of a frame buffer never reaches the file, and reading zeroes it.
+// Version 3 holds the frames group-coded instead (csic_pack_host.cpp): a coding word, a table of the frames' coded sizes, the coded frames.
 #include <zlib.h>
 
 #include <cstdio>
 #include <cstring>
+#include <new>
+#include <vector>
 
 #include "csic_internal.h"
 
 namespace csic {
 
 constexpr size_t CONTAINER_HEADER = 80, CONTAINER_CRC_FROM = 16;
-constexpr uint32_t CONTAINER_VERSION = 1;
+constexpr uint32_t CONTAINER_VERSION = 1, CONTAINER_VERSION_CODED = 3;
+constexpr size_t CODED_BODY = 8;                  // version 3: coding, reserved; then the table of sizes
 static const unsigned char CONTAINER_MAGIC[4] = {0x43, 0x53, 0x49, 0x43};   // "CSIC"
 
 static void put_u32(unsigned char *p, uint32_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24); }
 static uint32_t get_u32(const unsigned char *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+static void put_u64(unsigned char *p, uint64_t v) { put_u32(p, (uint32_t)v); put_u32(p + 4, (uint32_t)(v >> 32)); }
+static uint64_t get_u64(const unsigned char *p) { return (uint64_t)get_u32(p) | ((uint64_t)get_u32(p + 4) << 32); }
+
+static uLong crc_long(uLong crc, const unsigned char *s, int64_t n)     // zlib's length is 32 bits
+{
+    for (int64_t done = 0; done < n;) {
+        const int64_t part = n - done < (1 << 30) ? n - done : (1 << 30);
+        crc = crc32(crc, s + done, (uInt)part);
+        done += part;
+    }
+    return crc;
+}
 
 // csic_params <-> 16 little-endian int32 in the struct's field order
 static_assert(sizeof(csic_params) == 64, "csic_params is 16 int32: the container stores it field by field");
@@ -39,8 +55,10 @@ struct FileCloser {
     ~FileCloser() { if (f) fclose(f); }
 };
 
-// Reads and checks everything but the CRC: header fields, parameters, the file's length.  *stored_crc may be NULL.
-static int read_header(FILE *f, const char *path, csic_container_info *info, csic_planar_bits_layout *L, uint32_t *stored_crc)
+// Reads and checks everything but the CRC (and, version 3, the coded frames themselves): header fields, parameters, the table of
+// sizes, the file's length.  `sizes` (may be NULL) receives the stored bytes of each frame; the file pointer is left behind the
+// header (version 1) or the table (version 3).  *stored_crc may be NULL.
+static int read_header(FILE *f, const char *path, csic_container_info *info, PackGeometry *G, uint32_t *stored_crc, std::vector<uint64_t> *sizes)
 {
     unsigned char h[CONTAINER_HEADER];
     if (fseek(f, 0, SEEK_END) != 0) return set_error(CSIC_EIO, "cannot seek in %s", path);
@@ -50,21 +68,92 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, csi
     if (fread(h, 1, sizeof h, f) != sizeof h) return set_error(CSIC_EIO, "cannot read %s", path);
     if (std::memcmp(h, CONTAINER_MAGIC, 4) != 0) return set_error(CSIC_EFORMAT, "%s is not a .csic file (bad magic)", path);
     const uint32_t version = get_u32(h + 4), nframes = get_u32(h + 8);
-    if (version != CONTAINER_VERSION) return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1 is)", path, version);
+    if (version != CONTAINER_VERSION && version != CONTAINER_VERSION_CODED)
+        return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1 and 3 are)", path, version);
     if (nframes < 1 || nframes > 65535) return set_error(CSIC_EFORMAT, "%s: nframes must be in 1..65535. Got %u", path, nframes);
     int32_t fields[16];
     for (int i = 0; i < 16; ++i) fields[i] = (int32_t)get_u32(h + 16 + 4 * i);
     const csic_params p = params_of_fields(fields);
-    if (p.out_format != CSIC_FMT_PLANAR_BITS || csic_validate(&p) != CSIC_OK || csic_planar_bits_layout_of(&p, L) != CSIC_OK)
+    if (p.out_format != CSIC_FMT_PLANAR_BITS || pack_geometry(&p, G) != CSIC_OK)
         return set_error(CSIC_EFORMAT, "%s: the stored parameters are not a valid PLANAR_BITS parameter set", path);
-    const long long want = (long long)CONTAINER_HEADER + (long long)nframes * L->payload_bytes;
-    if (size != want) return set_error(CSIC_EFORMAT, "%s: %lld bytes, but %u frames of these parameters make %lld", path, size, nframes, want);
+    const csic_planar_bits_layout &L = G->bits;
+    if (version == CONTAINER_VERSION) {
+        const long long want = (long long)CONTAINER_HEADER + (long long)nframes * L.payload_bytes;
+        if (size != want) return set_error(CSIC_EFORMAT, "%s: %lld bytes, but %u frames of these parameters make %lld", path, size, nframes, want);
+        if (sizes) sizes->assign(nframes, (uint64_t)L.payload_bytes);
+    } else {
+        const long long front = (long long)(CONTAINER_HEADER + CODED_BODY) + 8ll * nframes;
+        if (size < front) return set_error(CSIC_EFORMAT, "%s: %lld bytes is shorter than the size table of %u frames", path, size, nframes);
+        std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
+        if (fread(t.data(), 1, t.size(), f) != t.size()) return set_error(CSIC_EIO, "cannot read %s", path);
+        if (get_u32(t.data()) != CSIC_CODING_GROUPS || get_u32(t.data() + 4) != 0)
+            return set_error(CSIC_EFORMAT, "%s: coding %u (reserved word %u) is not supported (1, 0 is)", path, get_u32(t.data()), get_u32(t.data() + 4));
+        const uint64_t lo = (uint64_t)G->layout.fixed_bytes, hi = lo + 4 * (uint64_t)G->max_payload_dwords;
+        long long want = front;
+        if (sizes) sizes->resize(nframes);
+        for (uint32_t k = 0; k < nframes; ++k) {
+            const uint64_t sz = get_u64(t.data() + CODED_BODY + 8 * (size_t)k);
+            if (sz < lo || sz > hi || sz % 4 != 0)
+                return set_error(CSIC_EFORMAT, "%s: frame %u is stored in %llu bytes; these parameters code to %llu .. %llu, in dwords", path, k,
+                                 (unsigned long long)sz, (unsigned long long)lo, (unsigned long long)hi);
+            want += (long long)sz;
+            if (sizes) (*sizes)[k] = sz;
+        }
+        if (size != want) return set_error(CSIC_EFORMAT, "%s: %lld bytes, but the header and the frames' sizes make %lld", path, size, want);
+    }
     info->params = p;
     info->version = (int32_t)version;
     info->nframes = (int32_t)nframes;
-    info->payload_bytes = L->payload_bytes;
+    info->payload_bytes = L.payload_bytes;
     info->file_bytes = size;
     if (stored_crc) *stored_crc = get_u32(h + 12);
+    return CSIC_OK;
+}
+
+static void fill_header(unsigned char h[CONTAINER_HEADER], uint32_t version, const csic_params &q, int32_t nframes)
+{
+    std::memcpy(h, CONTAINER_MAGIC, 4);
+    put_u32(h + 4, version);
+    put_u32(h + 8, (uint32_t)nframes);
+    put_u32(h + 12, 0);
+    int32_t fields[16];
+    params_fields(q, fields);
+    for (int i = 0; i < 16; ++i) put_u32(h + 16 + 4 * i, (uint32_t)fields[i]);
+}
+
+// the parameters a file stores, and their geometry; nframes checked
+static int writer_params(const csic_params *p, int32_t nframes, csic_params *q, PackGeometry *G)
+{
+    *q = *p;
+    q->out_format = CSIC_FMT_PLANAR_BITS;
+    const int st = pack_geometry(q, G);               // csic_validate first: refuses in_format != ARGB for PLANAR_BITS
+    if (st != CSIC_OK) return st;
+    if (nframes < 1 || nframes > 65535) return set_error(CSIC_EINVAL_SIZE, "nframes must be in 1..65535. Got %d", nframes);
+    return CSIC_OK;
+}
+
+// A version-3 file from coded frames in memory: frame k is frames[k][0, sizes[k]).
+static int write_coded_file(const char *path, const csic_params &q, const unsigned char *const *frames, const uint64_t *sizes, int32_t nframes)
+{
+    unsigned char h[CONTAINER_HEADER];
+    fill_header(h, CONTAINER_VERSION_CODED, q, nframes);
+    std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
+    put_u32(t.data(), CSIC_CODING_GROUPS);
+    put_u32(t.data() + 4, 0);
+    for (int32_t k = 0; k < nframes; ++k) put_u64(t.data() + CODED_BODY + 8 * (size_t)k, sizes[k]);
+    uLong crc = crc32(0L, h + CONTAINER_CRC_FROM, (uInt)(CONTAINER_HEADER - CONTAINER_CRC_FROM));
+    crc = crc_long(crc, t.data(), (int64_t)t.size());
+    for (int32_t k = 0; k < nframes; ++k) crc = crc_long(crc, frames[k], (int64_t)sizes[k]);
+    put_u32(h + 12, (uint32_t)crc);
+
+    FileCloser fc{fopen(path, "wb")};
+    if (!fc.f) return set_error(CSIC_EIO, "cannot open %s for writing", path);
+    bool ok = fwrite(h, 1, sizeof h, fc.f) == sizeof h && fwrite(t.data(), 1, t.size(), fc.f) == t.size();
+    for (int32_t k = 0; ok && k < nframes; ++k) ok = fwrite(frames[k], 1, (size_t)sizes[k], fc.f) == (size_t)sizes[k];
+    FILE *f = fc.f;
+    fc.f = nullptr;
+    if (fclose(f) != 0) ok = false;
+    if (!ok) return set_error(CSIC_EIO, "cannot write %s", path);
     return CSIC_OK;
 }
 
@@ -79,11 +168,35 @@ int csic_container_info_of(const char *path, csic_container_info *info)
     if (!path || !info) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
-    csic_planar_bits_layout L;
-    csic_container_info ci;
-    const int st = read_header(fc.f, path, &ci, &L, nullptr);
-    if (st != CSIC_OK) return st;
-    *info = ci;
+    try {
+        PackGeometry G;
+        csic_container_info ci;
+        const int st = read_header(fc.f, path, &ci, &G, nullptr, nullptr);
+        if (st != CSIC_OK) return st;
+        *info = ci;
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
+    }
+    clear_error();
+    return CSIC_OK;
+}
+
+int csic_container_coded_sizes(const char *path, uint64_t *sizes, int32_t n)
+{
+    if (!path || !sizes) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    FileCloser fc{fopen(path, "rb")};
+    if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
+    try {
+        PackGeometry G;
+        csic_container_info ci;
+        std::vector<uint64_t> table;
+        const int st = read_header(fc.f, path, &ci, &G, nullptr, &table);
+        if (st != CSIC_OK) return st;
+        if (n != ci.nframes) return set_error(CSIC_EINVAL_SIZE, "expected room for %d sizes, got %d", ci.nframes, n);
+        std::memcpy(sizes, table.data(), table.size() * sizeof(uint64_t));
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
+    }
     clear_error();
     return CSIC_OK;
 }
@@ -91,34 +204,18 @@ int csic_container_info_of(const char *path, csic_container_info *info)
 int csic_container_write(const char *path, const csic_params *p, const void *frames, int32_t nframes)
 {
     if (!path || !p || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    csic_params q = *p;
-    q.out_format = CSIC_FMT_PLANAR_BITS;
-    int st = csic_validate(&q);                       // refuses in_format != ARGB for PLANAR_BITS
+    csic_params q;
+    PackGeometry G;
+    const int st = writer_params(p, nframes, &q, &G);
     if (st != CSIC_OK) return st;
-    if (nframes < 1 || nframes > 65535) return set_error(CSIC_EINVAL_SIZE, "nframes must be in 1..65535. Got %d", nframes);
-    csic_planar_bits_layout L;
-    st = csic_planar_bits_layout_of(&q, &L);
-    if (st != CSIC_OK) return st;
+    const csic_planar_bits_layout &L = G.bits;
 
     unsigned char h[CONTAINER_HEADER];
-    std::memcpy(h, CONTAINER_MAGIC, 4);
-    put_u32(h + 4, CONTAINER_VERSION);
-    put_u32(h + 8, (uint32_t)nframes);
-    int32_t fields[16];
-    params_fields(q, fields);
-    for (int i = 0; i < 16; ++i) put_u32(h + 16 + 4 * i, (uint32_t)fields[i]);
-    const int64_t plane_off[3] = {L.y_offset, L.cb_offset, L.cr_offset}, plane_bytes[3] = {L.y_bytes, L.cb_bytes, L.cr_bytes};
+    fill_header(h, CONTAINER_VERSION, q, nframes);
     const unsigned char *base = static_cast<const unsigned char *>(frames);
     uLong crc = crc32(0L, h + CONTAINER_CRC_FROM, (uInt)(CONTAINER_HEADER - CONTAINER_CRC_FROM));
     for (int32_t k = 0; k < nframes; ++k)
-        for (int pl = 0; pl < 3; ++pl) {
-            const unsigned char *s = base + (int64_t)k * L.frame_bytes + plane_off[pl];
-            for (int64_t done = 0; done < plane_bytes[pl];) {              // zlib's length is 32 bits
-                const int64_t part = plane_bytes[pl] - done < (1 << 30) ? plane_bytes[pl] - done : (1 << 30);
-                crc = crc32(crc, s + done, (uInt)part);
-                done += part;
-            }
-        }
+        for (int pl = 0; pl < 3; ++pl) crc = crc_long(crc, base + (int64_t)k * L.frame_bytes + G.src_offset[pl], G.src_bytes[pl]);
     put_u32(h + 12, (uint32_t)crc);
 
     FileCloser fc{fopen(path, "wb")};
@@ -126,7 +223,7 @@ int csic_container_write(const char *path, const csic_params *p, const void *fra
     bool ok = fwrite(h, 1, sizeof h, fc.f) == sizeof h;
     for (int32_t k = 0; ok && k < nframes; ++k)
         for (int pl = 0; ok && pl < 3; ++pl)
-            ok = fwrite(base + (int64_t)k * L.frame_bytes + plane_off[pl], 1, (size_t)plane_bytes[pl], fc.f) == (size_t)plane_bytes[pl];
+            ok = fwrite(base + (int64_t)k * L.frame_bytes + G.src_offset[pl], 1, (size_t)G.src_bytes[pl], fc.f) == (size_t)G.src_bytes[pl];
     FILE *f = fc.f;
     fc.f = nullptr;
     if (fclose(f) != 0) ok = false;
@@ -135,41 +232,122 @@ int csic_container_write(const char *path, const csic_params *p, const void *fra
     return CSIC_OK;
 }
 
-int csic_container_read(const char *path, void *frames, size_t frames_bytes)
+int csic_container_write_ex(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding)
 {
-    if (!path || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    if (coding == CSIC_CODING_RAW) return csic_container_write(path, p, frames, nframes);
+    if (!path || !p || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    if (coding != CSIC_CODING_GROUPS) return set_error(CSIC_EINVAL_FORMAT, "coding must be CSIC_CODING_RAW(0) or CSIC_CODING_GROUPS(1). Got %d", coding);
+    csic_params q;
+    PackGeometry G;
+    int st = writer_params(p, nframes, &q, &G);
+    if (st != CSIC_OK) return st;
+    try {
+        // the table of sizes stands in front of the frames: every frame is coded before the first byte is written
+        std::vector<unsigned char> all;
+        std::vector<uint64_t> sizes((size_t)nframes);
+        for (int32_t k = 0; k < nframes; ++k) {
+            const size_t at = all.size();
+            all.resize(at + (size_t)G.layout.bound_bytes);
+            st = pack_frame(G, static_cast<const unsigned char *>(frames) + (int64_t)k * G.bits.frame_bytes, all.data() + at, (size_t)G.layout.bound_bytes, &sizes[k]);
+            if (st != CSIC_OK) return st;
+            all.resize(at + (size_t)sizes[k]);
+        }
+        std::vector<const unsigned char *> ptrs((size_t)nframes);
+        size_t at = 0;
+        for (int32_t k = 0; k < nframes; ++k) { ptrs[k] = all.data() + at; at += (size_t)sizes[k]; }
+        st = write_coded_file(path, q, ptrs.data(), sizes.data(), nframes);
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory coding %d frames for %s", nframes, path);
+    }
+    if (st != CSIC_OK) return st;
+    clear_error();
+    return CSIC_OK;
+}
+
+int csic_container_write_coded(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
+                               int32_t nframes)
+{
+    if (!path || !p || !coded || !sizes) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    csic_params q;
+    PackGeometry G;
+    int st = writer_params(p, nframes, &q, &G);
+    if (st != CSIC_OK) return st;
+    try {
+        std::vector<const unsigned char *> ptrs((size_t)nframes);
+        for (int32_t k = 0; k < nframes; ++k) {
+            if (sizes[k] > stride_bytes)
+                return set_error(CSIC_EINVAL_SIZE, "frame %d: %llu coded bytes do not fit the stride of %zu", k, (unsigned long long)sizes[k], stride_bytes);
+            ptrs[k] = static_cast<const unsigned char *>(coded) + (size_t)k * stride_bytes;
+            st = pack_check_coded(G, ptrs[k], (size_t)sizes[k]);
+            if (st != CSIC_OK) return st;
+        }
+        st = write_coded_file(path, q, ptrs.data(), sizes, nframes);
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory writing %s", path);
+    }
+    if (st != CSIC_OK) return st;
+    clear_error();
+    return CSIC_OK;
+}
+
+static int container_read(const char *path, void *frames, size_t frames_bytes)
+{
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
-    csic_planar_bits_layout L;
+    PackGeometry G;
     csic_container_info ci;
     uint32_t stored = 0;
-    const int st = read_header(fc.f, path, &ci, &L, &stored);
+    std::vector<uint64_t> sizes;
+    int st = read_header(fc.f, path, &ci, &G, &stored, &sizes);
     if (st != CSIC_OK) return st;
+    const csic_planar_bits_layout &L = G.bits;
     const size_t need = (size_t)ci.nframes * (size_t)L.frame_bytes;
     if (frames_bytes != need)
         return set_error(CSIC_EINVAL_SIZE, "expected room for %zu bytes (%d frames of %lld), got %zu", need, ci.nframes, (long long)L.frame_bytes,
                          frames_bytes);
-    // the file pointer stands behind the header; bytes [16, 80) of it take part in the CRC
-    unsigned char h[CONTAINER_HEADER];
-    if (fseek(fc.f, 0, SEEK_SET) != 0 || fread(h, 1, sizeof h, fc.f) != sizeof h) return set_error(CSIC_EIO, "cannot read %s", path);
-    uLong crc = crc32(0L, h + CONTAINER_CRC_FROM, (uInt)(CONTAINER_HEADER - CONTAINER_CRC_FROM));
-    const int64_t plane_off[3] = {L.y_offset, L.cb_offset, L.cr_offset}, plane_bytes[3] = {L.y_bytes, L.cb_bytes, L.cr_bytes};
+    // bytes [16, here) of the file take part in the CRC; the file pointer stands where the frames begin
+    const long long front = ftello(fc.f);
+    if (front < (long long)CONTAINER_HEADER) return set_error(CSIC_EIO, "cannot read %s", path);
+    std::vector<unsigned char> h((size_t)front);
+    if (fseek(fc.f, 0, SEEK_SET) != 0 || fread(h.data(), 1, h.size(), fc.f) != h.size()) return set_error(CSIC_EIO, "cannot read %s", path);
+    uLong crc = crc_long(0L, h.data() + CONTAINER_CRC_FROM, (int64_t)(h.size() - CONTAINER_CRC_FROM));
     unsigned char *base = static_cast<unsigned char *>(frames);
     std::memset(base, 0, need);
-    for (int32_t k = 0; k < ci.nframes; ++k)
-        for (int pl = 0; pl < 3; ++pl) {
-            unsigned char *d = base + (int64_t)k * L.frame_bytes + plane_off[pl];
-            if (fread(d, 1, (size_t)plane_bytes[pl], fc.f) != (size_t)plane_bytes[pl]) return set_error(CSIC_EIO, "cannot read %s", path);
-            for (int64_t done = 0; done < plane_bytes[pl];) {
-                const int64_t part = plane_bytes[pl] - done < (1 << 30) ? plane_bytes[pl] - done : (1 << 30);
-                crc = crc32(crc, d + done, (uInt)part);
-                done += part;
+    std::vector<unsigned char> coded;
+    for (int32_t k = 0; k < ci.nframes && st == CSIC_OK; ++k) {
+        unsigned char *fr = base + (int64_t)k * L.frame_bytes;
+        if (ci.version == (int32_t)CONTAINER_VERSION) {
+            for (int pl = 0; pl < 3; ++pl) {
+                unsigned char *d = fr + G.src_offset[pl];
+                if (fread(d, 1, (size_t)G.src_bytes[pl], fc.f) != (size_t)G.src_bytes[pl]) return set_error(CSIC_EIO, "cannot read %s", path);
+                crc = crc_long(crc, d, G.src_bytes[pl]);
             }
+        } else {
+            coded.resize((size_t)sizes[k]);            // <= fixed_bytes + 4 sum G_p q_p: read_header checked the table
+            if (fread(coded.data(), 1, coded.size(), fc.f) != coded.size()) return set_error(CSIC_EIO, "cannot read %s", path);
+            crc = crc_long(crc, coded.data(), (int64_t)coded.size());
+            st = unpack_frame(G, coded.data(), coded.size(), fr);
         }
-    if ((uint32_t)crc != stored) {
-        std::memset(base, 0, need);
-        return set_error(CSIC_EFORMAT, "%s: CRC mismatch (stored %08x, computed %08x)", path, stored, (uint32_t)crc);
     }
+    if (st == CSIC_OK && (uint32_t)crc != stored)
+        st = set_error(CSIC_EFORMAT, "%s: CRC mismatch (stored %08x, computed %08x)", path, stored, (uint32_t)crc);
+    if (st != CSIC_OK) {
+        std::memset(base, 0, need);
+        return st;
+    }
+    return CSIC_OK;
+}
+
+int csic_container_read(const char *path, void *frames, size_t frames_bytes)
+{
+    if (!path || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    int st;
+    try {
+        st = container_read(path, frames, frames_bytes);
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
+    }
+    if (st != CSIC_OK) return st;
     clear_error();
     return CSIC_OK;
 }

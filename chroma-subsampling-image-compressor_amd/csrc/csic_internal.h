@@ -25,6 +25,21 @@ int  derive_geometry(const csic_params *p, Geometry *g);   // validates first
 void planar_layout(const Geometry &g, const csic_params *p, csic_planar_layout *layout);   // csic.h: CSIC_FMT_PLANAR
 void planar_bits_layout(const Geometry &g, const csic_params *p, csic_planar_bits_layout *layout);   // csic.h: CSIC_FMT_PLANAR_BITS
 
+// csic_pack_host.cpp: the group coding (csic.h: csic_pack_*).  Everything both codecs and the container derive from the parameters, the
+// host codec on one frame, and the checks csic_unpack_host makes on their own (csic_container_write_coded).
+struct PackGeometry {
+    csic_planar_bits_layout bits;             // the PLANAR_BITS frame the coding reads and restores
+    csic_pack_layout layout;
+    int64_t n[3];                             // samples per plane
+    int32_t q[3];                             // bits per code
+    int64_t src_offset[3], src_bytes[3];      // the planes' payload ranges inside a frame buffer
+    int64_t max_payload_dwords;               // sum of G_p q_p: no frame's payload is longer
+};
+int pack_geometry(const csic_params *p, PackGeometry *G);     // validates first (out_format ignored)
+int pack_frame(const PackGeometry &G, const unsigned char *frame, unsigned char *coded, size_t capacity, uint64_t *coded_bytes);
+int unpack_frame(const PackGeometry &G, const unsigned char *coded, size_t coded_bytes, unsigned char *frame);
+int pack_check_coded(const PackGeometry &G, const unsigned char *coded, size_t coded_bytes);
+
 // Exact unsigned division by a run-time constant without a divide (k_generic's stream-index arithmetic): for
 // 1 <= d < 2^31 and every n < 2^31,  n / d == (uint64(n) * m) >> k  with  k = 31 + ceil(log2 d),  m = ceil(2^k / d) < 2^32.
 // (Error term e = m*d - 2^k < d <= 2^ceil(log2 d), and n * e < 2^31 * 2^ceil(log2 d) = 2^k.)  Host side, csic_host.cpp;

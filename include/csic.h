@@ -330,7 +330,7 @@ const char *csic_ssim_kernel_name(const csic_plan *plan);
  * csic_distortion_* and csic_ssim_* measure what a parameter set costs in quality; this is the rate side.  The raw size of the
  * bit-packed planes depends on the parameters alone.  These entry points return exact histograms of the sample codes of a compressed
  * frame and of their left-predicted residuals, from which the host layers compute zero-order entropies and the size an entropy coder
- * could reach.  No entropy coder is part of the library.
+ * could reach.  The coder the library has is csic_pack_* below; these counts are what sizes it, and any better one.
  *
  * Source: a compressed frame of the plan's parameters, as for csic_decode_device.  src_format is CSIC_FMT_PLANAR or
  * CSIC_FMT_PLANAR_BITS (anything else: CSIC_EINVAL_FORMAT); frames lie frame_bytes apart (csic_planar_layout_of /
@@ -649,9 +649,89 @@ int  csic_png_info(const char *path, int32_t *width, int32_t *height);
 int  csic_png_read_argb(const char *path, uint32_t *dst, size_t dst_px);
 int  csic_png_write_argb(const char *path, const uint32_t *src, int32_t width, int32_t height, int32_t level);
 
+/* ---- lossless group coding of the bit planes (csic_pack_*) ----------------------------------------------------------------------
+ * csic_code_stats_* say what an entropy coder could reach; this is the library's first coder, chosen so that encode and decode are
+ * data-parallel per group of 32 samples and need no serial bit stream.  It is lossless: unpack(pack(x)) gives back the three payload
+ * ranges of x.  (A per-sample variable-length coder would come closer to the entropy bound and is not part of the library.)
+ *
+ * Input: one CSIC_FMT_PLANAR_BITS frame of the parameters.  Planes p = 0, 1, 2 are Y, Cb, Cr with q_p = y_bits, cb_bits, cr_bits bits
+ * per code and n_0 = y_width * y_height, n_1 = n_2 = chroma_samples samples (as for csic_code_stats_*); c_i is the code of sample i in
+ * storage order.
+ *
+ * Groups.  A plane is cut into G_p = ceil(n_p / 32) groups of 32 consecutive samples: one group is exactly q dwords of the source, no
+ * sample straddles a group.  The last group is completed by repeating the plane's last real code.  Source bits and bytes beyond sample
+ * n_p - 1 are never read into a value (they are undefined in a PLANAR_BITS buffer).  Per group g, with slots j = 0 .. 31:
+ *     anchor_g = c_(32 g)                                        the group's first code
+ *     e_0 = 0,   e_j = (c_(32 g + j) - c_(32 g + j - 1)) mod 2^q    for j >= 1
+ *     s_j = e_j if e_j < 2^(q - 1), else e_j - 2^q               the centred residual
+ *     u_j = 2 s_j if s_j >= 0, else -2 s_j - 1                   folded: 0 <= u_j < 2^q
+ *     w_g = the number of significant bits of max_j u_j          0 when every u_j is 0; 0 <= w_g <= q
+ * Groups do not depend on each other: the predictor restarts at every group, so decode needs no scan over samples.
+ *
+ * The coded frame (CSIC_CODING_GROUPS) is a byte string.  Every section starts at a multiple of 4, every padding bit is 0 (the string
+ * is deterministic), bit order is LSB first as in PLANAR_BITS.  Sections, in this order:
+ *     1. widths of Y, Cb, Cr   nibble g at bits [4 g, 4 g + 4) holds w_g; each section 4 * ceil(G_p / 8) bytes
+ *     2. anchors of Y, Cb, Cr  a PLANAR_BITS-style plane of G_p codes at q_p bits; each section 4 * ceil(G_p q_p / 32) bytes
+ *     3. payload               all groups of Y, then of Cb, then of Cr: group g occupies w_g dwords, slot j's u_j at bits
+ *                              [j w_g, j w_g + w_g) of those dwords; a group with w_g = 0 occupies nothing
+ *     fixed_bytes = the sum of sections 1 and 2         coded_bytes = fixed_bytes + 4 * sum of w_g over all groups
+ *     bound_bytes = the next multiple of 256 at or above fixed_bytes + 4 * sum_p G_p q_p          (no frame codes to more)
+ * Worked vectors, one plane alone (the ones of the bit layout):
+ *     q = 3, codes 1,2,3,4,5,6,7,0 -> w = 2, widths 02 00 00 00, anchors 01 00 00 00, payload a8 aa 00 00 00 00 00 00
+ *     q = 5, codes 0x1f, 0, 0x15   -> anchor 0x1f, u = 0, 2, 21, 0, ..., w = 5
+ * Decode: c_(32 g) = anchor_g, c_(32 g + j) = (c_(32 g + j - 1) + e_j) mod 2^q with e_j unfolded from u_j.  It writes exactly the
+ * y_bytes / cb_bytes / cr_bytes of the PLANAR_BITS frame (the unused high bits of a plane's last byte 0) and nothing outside them.
+ *
+ * Host codec (no GPU; the parameters are those csic_container_write accepts, with its statuses; p->out_format is ignored):
+ *   csic_pack_layout_of : groups, section offsets and sizes of a coded frame of these parameters.
+ *   csic_pack_host      : one frame (frame_bytes of csic_planar_bits_layout_of) -> coded[0, *coded_bytes).  A `capacity` below the
+ *                         frame's coded size fails with CSIC_EINVAL_SIZE (bound_bytes always suffices); *coded_bytes then holds the
+ *                         size that was needed.
+ *   csic_unpack_host    : coded[0, coded_bytes) -> the three payload ranges of one frame buffer; the rest of the buffer is not touched.
+ *                         The input is untrusted: a nibble greater than q_p, a padding bit that is not 0 (widths or anchors) or a
+ *                         coded_bytes other than what the widths imply give CSIC_EFORMAT and write nothing; whatever the bytes, nothing
+ *                         outside coded[0, coded_bytes) is read and nothing outside the payload ranges written.
+ *
+ * Device codec (gfx950), asynchronous on `hip_stream`, no allocation, no synchronisation, hipGraph-capturable; three launches per
+ * direction in stream order (widths / sums, a scan of the blocks' totals, emit), no block ever waits for another:
+ *   csic_pack_workspace_bytes : the workspace both directions need for `nframes` (1..65535) frames: one uint32 per block of 256
+ *                         groups and frame.  Needs no device.
+ *   csic_pack_device    : d_bits (frames frame_bytes apart, 256-byte aligned) -> d_coded (frames bound_bytes apart, 256-byte aligned)
+ *                         and d_sizes[k] (8-byte aligned) = frame k's coded_bytes.  Bytes of a coded frame beyond its coded_bytes are
+ *                         not written.
+ *   csic_unpack_device  : the inverse.  Bytes of a PLANAR_BITS frame outside the three payload ranges are not written.  It does NOT
+ *                         validate: a nibble takes part as min(nibble, q_p), so that no access can leave a frame's bound_bytes, and
+ *                         a coded frame csic_unpack_host would refuse decodes to some valid codes.  Validate untrusted input on the host.
+ *   csic_pack_kernel_name : the kernels of both directions, "k_pack<q6,5,5,nt>" (one instantiation per bit width, as k_cstat_bits);
+ *                         "" for a NULL plan.  The string belongs to the calling thread until its next call of this function.
+ * NULL plan / buffers fail with CSIC_EINVAL_NULL; nframes outside 1..65535, a misaligned pointer (d_workspace: 8 bytes) or a short
+ * workspace with CSIC_EINVAL_SIZE -- all before any device is touched.  CSIC_TUNE_NONTEMPORAL applies to the accesses of the
+ * PLANAR_BITS frames; CSIC_TUNE_BLOCK_THREADS is ignored (a block is 256 lanes = 256 groups: the workspace is laid out by it), and so
+ * are the other knobs. */
+#define CSIC_CODING_RAW    0   /* the planes' payload bytes as they are (.csic version 1) */
+#define CSIC_CODING_GROUPS 1   /* the group coding above (.csic version 3)                */
+typedef struct csic_pack_layout {
+    int64_t groups[3];             /* G_p                                                              */
+    int64_t widths_offset[3];      /* byte offsets of the sections inside a coded frame               */
+    int64_t anchors_offset[3];
+    int64_t payload_offset;        /* = fixed_bytes                                                    */
+    int64_t fixed_bytes;
+    int64_t bound_bytes;           /* multiple of 256: the distance of coded frames in device memory   */
+} csic_pack_layout;
+int  csic_pack_layout_of(const csic_params *p, csic_pack_layout *layout);
+int  csic_pack_host(const csic_params *p, const void *bits_frame, void *coded, size_t capacity, uint64_t *coded_bytes);
+int  csic_unpack_host(const csic_params *p, const void *coded, size_t coded_bytes, void *bits_frame);
+int  csic_pack_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes);
+int  csic_pack_device(csic_plan *plan, const void *d_bits, int32_t nframes, void *d_coded, uint64_t *d_sizes,
+                      void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int  csic_unpack_device(csic_plan *plan, const void *d_coded, int32_t nframes, void *d_bits,
+                        void *d_workspace, size_t workspace_bytes, void *hip_stream);
+const char *csic_pack_kernel_name(const csic_plan *plan);
+
 /* ---- .csic files: the compressed frames on disk (host only, usable without a GPU) --------------------------------------------
  * A container holds `nframes` CSIC_FMT_PLANAR_BITS frames of one parameter set: the only thing this library writes to a file that
- * is smaller than its input (a 6/5/5 4:2:0 frame: 1.06 bytes per pixel at factor 1).  Version 1, every integer little endian:
+ * is smaller than its input (a 6/5/5 4:2:0 frame: 1.06 bytes per pixel at factor 1; group-coded, version 3 below, less).  Version 1,
+ * every integer little endian:
  *
  *     offset  size                     content
  *          0     4                     magic 43 53 49 43 ("CSIC")
@@ -670,9 +750,29 @@ int  csic_png_write_argb(const char *path, const uint32_t *src, int32_t width, i
  *                            when the parameters are invalid or p->in_format is not ARGB; nframes outside 1 .. 65535: CSIC_EINVAL_SIZE.
  *   csic_container_info_of : header, parameters and length of a file (everything csic_container_read checks except the CRC).
  *   csic_container_read    : frames_bytes must equal nframes * frame_bytes (CSIC_EINVAL_SIZE otherwise; ask csic_container_info_of).
- * CSIC_EFORMAT: bad magic, version != 1, nframes out of range, parameters that fail csic_validate (or are not PLANAR_BITS), a length
- * other than 80 + nframes * payload_bytes, a CRC mismatch.  CSIC_EIO: the file cannot be opened, read or written.  NULL arguments:
- * CSIC_EINVAL_NULL. */
+ * CSIC_EFORMAT: bad magic, a version other than 1 or 3, nframes out of range, parameters that fail csic_validate (or are not
+ * PLANAR_BITS), a length other than 80 + nframes * payload_bytes, a CRC mismatch.  CSIC_EIO: the file cannot be opened, read or
+ * written.  NULL arguments: CSIC_EINVAL_NULL.
+ *
+ * Version 3 holds the frames group-coded (csic_pack_*, CSIC_CODING_GROUPS); version 2 was never written and stays refused.  Bytes
+ * 0 .. 79 are as in version 1 with version = 3, the CRC covers [16, end of file) as well, and the body is
+ *
+ *         80     4                     uint32 coding = 1 (CSIC_CODING_GROUPS)
+ *         84     4                     uint32 reserved = 0
+ *         88     8 * nframes           uint64 coded_bytes of each frame
+ *         88 + 8 * nframes             the coded frames back to back, each exactly its coded_bytes
+ *
+ *   csic_container_write_ex    : coding = CSIC_CODING_RAW writes what csic_container_write writes, byte for byte; CSIC_CODING_GROUPS
+ *                                packs every frame on the host (csic_pack_host) and writes version 3; another coding: CSIC_EINVAL_FORMAT.
+ *   csic_container_write_coded : version 3 from frames that are packed already (csic_pack_device's output copied to the host, say):
+ *                                frame k is coded[k * stride_bytes, + sizes[k]).  Every frame is validated as csic_unpack_host would
+ *                                before anything is written (CSIC_EFORMAT); sizes[k] > stride_bytes: CSIC_EINVAL_SIZE.
+ *   csic_container_read        : reads both versions into PLANAR_BITS frame buffers, padding zeroed.
+ *   csic_container_info_of     : reports version 3; payload_bytes keeps its meaning, the raw payload per frame.
+ *   csic_container_coded_sizes : the stored bytes of each frame into sizes[0, n), n = the file's nframes (CSIC_EINVAL_SIZE otherwise):
+ *                                the table of a version-3 file, payload_bytes for every frame of a version-1 file.
+ * CSIC_EFORMAT for a version-3 file, beyond the above: coding != 1, reserved != 0, a coded_bytes below fixed_bytes, above fixed_bytes +
+ * 4 sum_p G_p q_p or not a multiple of 4, a length other than 88 + 8 nframes + the sum of the table, any frame csic_unpack_host refuses. */
 typedef struct csic_container_info {
     csic_params params;            /* out_format = CSIC_FMT_PLANAR_BITS, in_format = CSIC_FMT_ARGB8888 */
     int32_t version, nframes;
@@ -682,6 +782,10 @@ typedef struct csic_container_info {
 int  csic_container_info_of(const char *path, csic_container_info *info);
 int  csic_container_write(const char *path, const csic_params *p, const void *frames, int32_t nframes);
 int  csic_container_read(const char *path, void *frames, size_t frames_bytes);
+int  csic_container_write_ex(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding);
+int  csic_container_write_coded(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
+                                int32_t nframes);
+int  csic_container_coded_sizes(const char *path, uint64_t *sizes, int32_t n);
 
 /* ---- host-frame pipeline (the step either side of the hot path) -----------------------------------
  * Replaces the reference's per-image  readImage -> per-pixel poke ... peek -> writeImage  flow

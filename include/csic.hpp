@@ -124,10 +124,24 @@ inline csic_container_info containerInfo(const std::string &file)
     check(csic_container_info_of(file.c_str(), &info));
     return info;
 }
-// frames: nframes PLANAR_BITS frame buffers of `p`, frame_bytes apart (p.out_format does not matter)
-inline void writeContainer(const std::string &file, const csic_params &p, const void *frames, int nframes)
+// frames: nframes PLANAR_BITS frame buffers of `p`, frame_bytes apart (p.out_format does not matter); coding = CSIC_CODING_RAW writes
+// version 1, CSIC_CODING_GROUPS packs every frame on the host and writes version 3.  readContainer reads both.
+inline void writeContainer(const std::string &file, const csic_params &p, const void *frames, int nframes, int coding = CSIC_CODING_RAW)
 {
-    check(csic_container_write(file.c_str(), &p, frames, nframes));
+    check(csic_container_write_ex(file.c_str(), &p, frames, nframes, coding));
+}
+// version 3 from frames that are packed already (csic_pack_device's output on the host): frame k at coded + k * stride_bytes
+inline void writeContainerCoded(const std::string &file, const csic_params &p, const void *coded, size_t stride_bytes,
+                                const std::vector<uint64_t> &sizes)
+{
+    check(csic_container_write_coded(file.c_str(), &p, coded, stride_bytes, sizes.data(), (int32_t)sizes.size()));
+}
+// the stored bytes of each frame: a version-3 file's table, payload_bytes per frame for version 1
+inline std::vector<uint64_t> containerCodedSizes(const std::string &file)
+{
+    std::vector<uint64_t> sizes((size_t)containerInfo(file).nframes);
+    check(csic_container_coded_sizes(file.c_str(), sizes.data(), (int32_t)sizes.size()));
+    return sizes;
 }
 inline Container readContainer(const std::string &file)
 {
@@ -139,6 +153,34 @@ inline Container readContainer(const std::string &file)
     c.bytes.resize((size_t)c.nframes * (size_t)c.layout.frame_bytes);
     check(csic_container_read(file.c_str(), c.bytes.data(), c.bytes.size()));
     return c;
+}
+
+// The lossless group coding of PLANAR_BITS frames (csic.h: csic_pack_*), host codec: needs no GPU.  pack: one frame buffer
+// (frame_bytes) -> its coded bytes; unpack: coded bytes -> a frame buffer, zero outside the planes' payload.  Damaged input surfaces as
+// csic::RuntimeError with status CSIC_EFORMAT.
+inline csic_pack_layout packLayout(const csic_params &p)
+{
+    csic_pack_layout layout;
+    check(csic_pack_layout_of(&p, &layout));
+    return layout;
+}
+inline std::vector<uint8_t> pack(const csic_params &p, const void *bitsFrame)
+{
+    std::vector<uint8_t> coded((size_t)packLayout(p).bound_bytes);
+    uint64_t size = 0;
+    check(csic_pack_host(&p, bitsFrame, coded.data(), coded.size(), &size));
+    coded.resize((size_t)size);
+    return coded;
+}
+inline std::vector<uint8_t> unpack(const csic_params &p, const void *coded, size_t codedBytes)
+{
+    csic_params q = p;
+    q.out_format = CSIC_FMT_PLANAR_BITS;
+    csic_planar_bits_layout layout;
+    check(csic_planar_bits_layout_of(&q, &layout));
+    std::vector<uint8_t> frame((size_t)layout.frame_bytes, 0);
+    check(csic_unpack_host(&p, coded, codedBytes, frame.data()));
+    return frame;
 }
 
 // The six sums of squared errors of one frame (csic.h: csic_distortion_*), in the order R, G, B, Y, Cb, Cr, over `pixels` input
@@ -261,6 +303,27 @@ public:
         check(csic_code_stats_block_samples(plan_, (int32_t)src_format, &n));
         return n;
     }
+    // the group coding of this plan's PLANAR_BITS frames: on the host (csic::pack / csic::unpack of the plan's parameters) ...
+    csic_pack_layout packLayout() const { return csic::packLayout(params_); }
+    std::vector<uint8_t> pack(const void *bitsFrame) const { return csic::pack(params_, bitsFrame); }
+    std::vector<uint8_t> unpack(const void *coded, size_t codedBytes) const { return csic::unpack(params_, coded, codedBytes); }
+    // ... and device-resident: frames frame_bytes / bound_bytes apart, 256-byte aligned, through a workspace of packWorkspaceBytes;
+    // asynchronous on `hip_stream`, no allocation, capturable.  unpackDevice does not validate (csic.h).
+    size_t packWorkspaceBytes(int nframes = 1)
+    {
+        size_t bytes = 0;
+        check(csic_pack_workspace_bytes(plan_, nframes, &bytes));
+        return bytes;
+    }
+    void packDevice(const void *d_bits, int nframes, void *d_coded, uint64_t *d_sizes, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+    {
+        check(csic_pack_device(plan_, d_bits, nframes, d_coded, d_sizes, d_workspace, workspace_bytes, hip_stream));
+    }
+    void unpackDevice(const void *d_coded, int nframes, void *d_bits, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+    {
+        check(csic_unpack_device(plan_, d_coded, nframes, d_bits, d_workspace, workspace_bytes, hip_stream));
+    }
+    const char *packKernelName() { return csic_pack_kernel_name(plan_); }
 
 private:
     csic_params params_;
