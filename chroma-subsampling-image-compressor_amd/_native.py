@@ -29,6 +29,7 @@ DIST_CHANNELS = 6                       # R, G, B, Y, Cb, Cr (csic_distortion_*,
 SSIM_WINDOW, SSIM_ONE = 8, 65536        # csic_ssim_*: window edge in pixels, SSIM 1.0 in 16.16 fixed point
 STATS_KINDS, STATS_PLANES, STATS_BINS = 2, 3, 256     # csic_code_stats_*: codes / residuals; Y, Cb, Cr; bins per histogram
 CODING_RAW, CODING_GROUPS = 0, 1        # csic_pack_* / .csic: the planes as they are (version 1), group-coded (version 3)
+CODING_RICE = 3                         # csic_rice_* / .csic version 4: Rice-coded (id 2 was never written)
 
 
 class IllegalArgumentException(ValueError):
@@ -89,6 +90,11 @@ class CsicPackLayout(C.Structure):
                 ("payload_offset", C.c_int64), ("fixed_bytes", C.c_int64), ("bound_bytes", C.c_int64)]
 
 
+class CsicRiceLayout(C.Structure):
+    _fields_ = [("groups", C.c_int64 * 3), ("blocks", C.c_int64 * 3), ("modes_offset", C.c_int64 * 3), ("anchors_offset", C.c_int64 * 3),
+                ("directory_offset", C.c_int64), ("payload_offset", C.c_int64), ("fixed_bytes", C.c_int64), ("bound_bytes", C.c_int64)]
+
+
 class CsicContainerInfo(C.Structure):
     _fields_ = [("params", CsicParams), ("version", C.c_int32), ("nframes", C.c_int32), ("payload_bytes", C.c_int64),
                 ("file_bytes", C.c_int64)]
@@ -131,6 +137,7 @@ PROTOTYPES = {
     "csic_container_read": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t]),
     "csic_container_write_ex": (C.c_int, [C.c_char_p, C.POINTER(CsicParams), C.c_void_p, C.c_int32, C.c_int32]),
     "csic_container_write_coded": (C.c_int, [C.c_char_p, C.POINTER(CsicParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_int32]),
+    "csic_container_write_coded_ex": (C.c_int, [C.c_char_p, C.POINTER(CsicParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "csic_container_coded_sizes": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.c_int32]),
     "csic_pack_layout_of": (C.c_int, [C.POINTER(CsicParams), C.POINTER(CsicPackLayout)]),
     "csic_pack_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
@@ -139,6 +146,13 @@ PROTOTYPES = {
     "csic_pack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "csic_unpack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "csic_pack_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "csic_rice_layout_of": (C.c_int, [C.POINTER(CsicParams), C.POINTER(CsicRiceLayout)]),
+    "csic_rice_pack_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "csic_rice_unpack_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "csic_rice_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
+    "csic_rice_pack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "csic_rice_unpack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "csic_rice_kernel_name": (C.c_char_p, [C.c_void_p]),
     "csic_distortion_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
     "csic_distortion_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "csic_distortion_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_uint64)]),

@@ -10,13 +10,14 @@ HIP launch.
 
 Two leading verbs go past what the reference's app does (it only ever writes the reconstructed pixels as a PNG):
 
-    python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ... [--coding raw|groups]
+    python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ... [--coding raw|groups|rice]
     python -m csic_amd.app decompress --input x.csic --output x.png
 
     python -m csic_amd.app inspect    --input x.csic
 
 `compress` writes the bit-packed planes as a .csic container (include/csic.h) -- as they are (`--coding raw`, the default: version 1)
-or group-coded on the GPU (`--coding groups`: csic_pack_device, version 3, lossless and smaller) --, `decompress` decodes either back
+or coded on the GPU (`--coding groups`: csic_pack_device, version 3; `--coding rice`: csic_rice_pack_device, version 4; both lossless, the
+second smaller) --, `decompress` decodes any of them back
 to a PNG of the original size, `inspect` prints a container's header, its coding and stored bytes per frame and, per frame, what its samples carry: the entropies of the codes and of
 their left-predicted residuals and the sizes an entropy coder could reach (csic_code_stats_*).  The verb must be the first
 argument; with any other first argument main() behaves as described above.
@@ -90,20 +91,21 @@ class ImageCompressionApp:
                       op1: ProcessingStep, op2: ProcessingStep, op3: ProcessingStep,
                       sampling: Sampling = Sampling.HOLD_DECIMATE, *, device: int = 0, coding: str = "raw") -> int:
         """PNG -> CSIC_FMT_PLANAR_BITS plan -> .csic container.  Returns the bytes written (coding "raw": 80 + payload_bytes;
-        "groups": the frame is group-coded on the device and goes out through csic_container_write_coded)."""
-        if coding not in ("raw", "groups"):
-            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: --coding must be raw or groups, got {coding!r}")
+        "groups" / "rice": the frame is coded on the device and goes out through csic_container_write_coded_ex)."""
+        if coding not in ("raw", "groups", "rice"):
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: --coding must be raw, groups or rice, got {coding!r}")
         inputImage = ImageProcessorModel.readImage(inputImagePath)
         top = ImageCompressorTop(inputImage.width, inputImage.height, chromaParamA, chromaParamB, yTargetBits, cbTargetBits,
                                  crTargetBits, spatialFactorToUse, op1, op2, op3, device=device, sampling=sampling)
         try:
             plan = top.plan(PixelFormat.PLANAR_BITS)
             os.makedirs(os.path.dirname(os.path.abspath(outputPath)), exist_ok=True)
-            if coding == "groups":
+            if coding != "raw":
                 import torch
                 d_in = torch.from_numpy(np.ascontiguousarray(inputImage.argb, dtype=np.uint32).reshape(-1).view(np.int32)).to(f"cuda:{device}")
-                coded, sizes = plan.pack_device(plan.process_device(d_in))
-                write_container_coded(outputPath, plan.c_params, coded.cpu().numpy(), sizes.cpu().numpy())
+                pack = plan.pack_device if coding == "groups" else plan.rice_pack_device
+                coded, sizes = pack(plan.process_device(d_in))
+                write_container_coded(outputPath, plan.c_params, coded.cpu().numpy(), sizes.cpu().numpy(), coding=coding)
             else:
                 bits = plan.process_host(inputImage.argb)
                 write_container(outputPath, plan.c_params, bits)
@@ -205,7 +207,7 @@ def _args_map(args: List[str]) -> Dict[str, str]:
 
 def _main_container(verb: str, args: List[str]) -> int:
     """`compress` / `decompress`: the keys of the verb-less CLI with its defaults, plus --output and (compress) --sampling avg and
-    --coding raw|groups."""
+    --coding raw|groups|rice."""
     argsMap = _args_map(args)
     if "--input" not in argsMap or "--output" not in argsMap:
         print(f"[ERROR] {verb} needs --input and --output")
@@ -220,8 +222,8 @@ def _main_container(verb: str, args: List[str]) -> int:
         return 0
     sampling = Sampling.AVG if argsMap.get("--sampling", "hold").lower() == "avg" else Sampling.HOLD_DECIMATE
     coding = argsMap.get("--coding", "raw").lower()
-    if coding not in ("raw", "groups"):
-        print(f"[ERROR] --coding must be raw or groups, got {coding}")
+    if coding not in ("raw", "groups", "rice"):
+        print(f"[ERROR] --coding must be raw, groups or rice, got {coding}")
         return 2
     size = ImageCompressionApp.compressImage(
         inputPath, outputPath, int(argsMap.get("--a", "4")), int(argsMap.get("--b", "4")), int(argsMap.get("--yq", "8")),
@@ -249,7 +251,7 @@ def _main_inspect(args: List[str]) -> int:
     print(f"Image: {p.width}x{p.height}, chroma 4:{p.chroma_a}:{p.chroma_b}, bits Y/Cb/Cr {p.y_bits}/{p.cb_bits}/{p.cr_bits}, "
           f"factor {p.factor}, order {ops}, rounding {p.rounding}, sampling {p.sampling}")
     print(f"Frames: {info.nframes}, payload bytes per frame: {info.payload_bytes}")
-    print(f"Frame coding: {'groups' if info.version == 3 else 'raw'}")
+    print(f"Frame coding: {({3: 'groups', 4: 'rice'}).get(info.version, 'raw')}")
     for k, stored in enumerate(container_coded_sizes(inputPath)):
         print(f"  frame {k}: stored in {int(stored)} bytes, {int(stored) / info.payload_bytes:.4f} of raw")
     try:

@@ -19,7 +19,7 @@ from typing import Tuple
 import numpy as np
 
 from . import _native as N
-from .container import pack_frame_host, unpack_frame_host
+from .container import pack_frame_host, rice_pack_host, rice_unpack_host, unpack_frame_host
 from .params import (ImageProcessorParams, PixelFormat, ProcessingStep, Rounding, Sampling, make_c_params)
 
 
@@ -473,6 +473,62 @@ class Plan:
     def unpack(self, coded, out=None) -> np.ndarray:
         """csic_unpack_host: coded bytes -> a PLANAR_BITS frame buffer (zero outside the payload ranges unless `out` is given)."""
         return unpack_frame_host(self.c_params, coded, out)
+
+    # -- lossless Rice coding of PLANAR_BITS frames (csic_rice_*) ---------------------------------------
+    @property
+    def rice_layout(self) -> N.CsicRiceLayout:
+        """csic_rice_layout of these parameters: groups, blocks, section offsets, fixed_bytes, bound_bytes."""
+        lay = N.CsicRiceLayout()
+        N.check(N.lib().csic_rice_layout_of(C.byref(self.c_params), C.byref(lay)))
+        return lay
+
+    @property
+    def rice_kernel_name(self) -> str:
+        return N.lib().csic_rice_kernel_name(self._h).decode()
+
+    def rice_workspace_bytes(self, nframes: int = 1) -> int:
+        b = C.c_size_t()
+        N.check(N.lib().csic_rice_workspace_bytes(self._h, int(nframes), C.byref(b)))
+        return b.value
+
+    def rice_pack_device(self, d_bits, nframes: int = 1, d_coded=None):
+        """As pack_device, in the Rice coding: returns (coded, sizes), a uint8 tensor (nframes, rice_layout.bound_bytes) whose row k
+        holds frame k's coded bytes in [0, sizes[k]), and an int64 tensor of the sizes.  Asynchronous on torch's current stream."""
+        import torch
+        fb, bound = self.planar_bits_layout.frame_bytes, self.rice_layout.bound_bytes
+        self._pack_check(d_bits, nframes * fb, "d_bits")
+        if d_coded is None:
+            d_coded = torch.empty((nframes, bound), dtype=torch.uint8, device=d_bits.device)
+        else:
+            self._pack_check(d_coded, nframes * bound, "d_coded")
+        sizes = torch.empty((nframes,), dtype=torch.int64, device=d_bits.device)
+        wsb = self.rice_workspace_bytes(nframes)
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=d_bits.device)
+        N.check(N.lib().csic_rice_pack_device(self._h, C.c_void_p(d_bits.data_ptr()), int(nframes), C.c_void_p(d_coded.data_ptr()),
+                                              C.c_void_p(sizes.data_ptr()), C.c_void_p(ws.data_ptr()), wsb, self._stream()))
+        return d_coded, sizes
+
+    def rice_unpack_device(self, d_coded, nframes: int = 1, d_bits=None):
+        """The inverse of rice_pack_device, one pass without a workspace.  The device does not validate: check untrusted bytes with
+        rice_unpack() first."""
+        import torch
+        fb, bound = self.planar_bits_layout.frame_bytes, self.rice_layout.bound_bytes
+        self._pack_check(d_coded, nframes * bound, "d_coded")
+        if d_bits is None:
+            d_bits = torch.empty((nframes, fb) if nframes > 1 else (fb,), dtype=torch.uint8, device=d_coded.device)
+        else:
+            self._pack_check(d_bits, nframes * fb, "d_bits")
+        N.check(N.lib().csic_rice_unpack_device(self._h, C.c_void_p(d_coded.data_ptr()), int(nframes), C.c_void_p(d_bits.data_ptr()),
+                                                self._stream()))
+        return d_bits
+
+    def rice_pack(self, bits_frame) -> np.ndarray:
+        """csic_rice_pack_host: one PLANAR_BITS frame buffer in host memory -> its Rice-coded bytes.  Needs no GPU."""
+        return rice_pack_host(self.c_params, bits_frame)
+
+    def rice_unpack(self, coded, out=None) -> np.ndarray:
+        """csic_rice_unpack_host: Rice-coded bytes -> a PLANAR_BITS frame buffer."""
+        return rice_unpack_host(self.c_params, coded, out)
 
     # -- compute ----------------------------------------------------------------------------------
     def _stream(self):

@@ -1,5 +1,6 @@
-""".csic files: CSIC_FMT_PLANAR_BITS frames on disk (csic_container_*; byte layout in include/csic.h), raw (version 1) or group-coded
-(version 3), and the host codec of the group coding (csic_pack_host / csic_unpack_host).  Host only: nothing here needs a GPU."""
+""".csic files: CSIC_FMT_PLANAR_BITS frames on disk (csic_container_*; byte layout in include/csic.h), raw (version 1), group-coded
+(version 3) or Rice-coded (version 4), and the host codecs of both codings (csic_pack_host / csic_unpack_host, csic_rice_pack_host /
+csic_rice_unpack_host).  Host only: nothing here needs a GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -30,9 +31,9 @@ def _bits_params(c_params: N.CsicParams):
 
 def _coding(coding) -> int:
     if isinstance(coding, str):
-        names = {"raw": N.CODING_RAW, "groups": N.CODING_GROUPS}
+        names = {"raw": N.CODING_RAW, "groups": N.CODING_GROUPS, "rice": N.CODING_RICE}
         if coding.lower() not in names:
-            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: coding must be 'raw' or 'groups', got {coding!r}")
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: coding must be 'raw', 'groups' or 'rice', got {coding!r}")
         return names[coding.lower()]
     return int(coding)
 
@@ -69,10 +70,43 @@ def unpack_frame_host(c_params: N.CsicParams, coded, out=None) -> np.ndarray:
     return out
 
 
+def rice_layout(c_params: N.CsicParams) -> N.CsicRiceLayout:
+    """csic_rice_layout_of: groups, blocks, section offsets, fixed_bytes and bound_bytes of a Rice-coded frame of these parameters."""
+    lay = N.CsicRiceLayout()
+    N.check(N.lib().csic_rice_layout_of(C.byref(c_params), C.byref(lay)))
+    return lay
+
+
+def rice_pack_host(c_params: N.CsicParams, bits_frame) -> np.ndarray:
+    """csic_rice_pack_host: one PLANAR_BITS frame buffer (frame_bytes) -> its Rice-coded bytes, a uint8 array of coded_bytes."""
+    q, lay = _bits_params(c_params)
+    a = np.ascontiguousarray(bits_frame).reshape(-1).view(np.uint8)
+    if a.size != lay.frame_bytes:
+        raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: a frame buffer of these parameters has {lay.frame_bytes} bytes, got {a.size}")
+    coded = np.empty(rice_layout(q).bound_bytes, dtype=np.uint8)
+    n = C.c_uint64()
+    N.check(N.lib().csic_rice_pack_host(C.byref(q), a.ctypes.data_as(C.c_void_p), coded.ctypes.data_as(C.c_void_p), coded.size, C.byref(n)))
+    return coded[:n.value].copy()
+
+
+def rice_unpack_host(c_params: N.CsicParams, coded, out=None) -> np.ndarray:
+    """csic_rice_unpack_host: Rice-coded bytes -> a PLANAR_BITS frame buffer, as unpack_frame_host.  Damaged input raises CsicIOError."""
+    q, lay = _bits_params(c_params)
+    a = np.ascontiguousarray(coded).reshape(-1).view(np.uint8)
+    if out is None:
+        out = np.zeros(lay.frame_bytes, dtype=np.uint8)
+    elif out.dtype != np.uint8 or out.size != lay.frame_bytes or not out.flags.c_contiguous:
+        raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: out must be a contiguous uint8 buffer of {lay.frame_bytes} bytes")
+    src = a if a.size else np.zeros(1, dtype=np.uint8)
+    N.check(N.lib().csic_rice_unpack_host(C.byref(q), src.ctypes.data_as(C.c_void_p), a.size, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 def write_container(path: str, c_params: N.CsicParams, frames, coding="raw") -> None:
     """frames: the PLANAR_BITS frame buffers of `c_params` (its out_format does not matter), frame_bytes each -- one buffer, an
     array (nframes, frame_bytes), or a list of buffers.  Only the planes' payload bytes reach the file.  coding = "raw" (version 1,
-    the bytes as they are) or "groups" (version 3, every frame group-coded on the host: csic_container_write_ex)."""
+    the bytes as they are), "groups" (version 3, every frame group-coded on the host: csic_container_write_ex) or "rice" (version 4,
+    every frame Rice-coded on the host)."""
     q, lay = _bits_params(c_params)
     coding = _coding(coding)
     if isinstance(frames, (list, tuple)):
@@ -86,11 +120,12 @@ def write_container(path: str, c_params: N.CsicParams, frames, coding="raw") -> 
         N.check(N.lib().csic_container_write_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.size // lay.frame_bytes, coding))
 
 
-def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes) -> None:
-    """Version 3 from frames that are packed already (csic_container_write_coded): `coded` is an array (nframes, stride) -- what
-    Plan.pack_device returns, copied to the host -- or a list of coded frames; sizes[k] is frame k's coded_bytes.  Every frame is
-    validated before anything is written."""
+def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, coding="groups") -> None:
+    """Version 3 (coding "groups") or 4 ("rice") from frames that are packed already (csic_container_write_coded_ex): `coded` is an
+    array (nframes, stride) -- what Plan.pack_device / Plan.rice_pack_device returns, copied to the host -- or a list of coded frames;
+    sizes[k] is frame k's coded_bytes.  Every frame is validated before anything is written."""
     q, _ = _bits_params(c_params)
+    coding = _coding(coding)
     sz = np.ascontiguousarray(np.asarray(sizes).reshape(-1), dtype=np.uint64)
     if isinstance(coded, (list, tuple)):
         rows = [np.ascontiguousarray(f).reshape(-1).view(np.uint8) for f in coded]
@@ -103,12 +138,13 @@ def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes) -> No
         a = a.reshape(sz.size, -1) if sz.size and a.size % sz.size == 0 else a.reshape(1, -1)
     if sz.size == 0 or a.shape[0] != sz.size:
         raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: {a.shape[0]} coded frames but {sz.size} sizes")
-    N.check(N.lib().csic_container_write_coded(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1],
-                                               sz.ctypes.data_as(C.POINTER(C.c_uint64)), int(sz.size)))
+    N.check(N.lib().csic_container_write_coded_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1],
+                                                  sz.ctypes.data_as(C.POINTER(C.c_uint64)), int(sz.size), coding))
 
 
 def container_coded_sizes(path: str) -> np.ndarray:
-    """The stored bytes of each frame (csic_container_coded_sizes): a version-3 file's table, payload_bytes per frame for version 1."""
+    """The stored bytes of each frame (csic_container_coded_sizes): a version-3 or version-4 file's table, payload_bytes per frame for
+    version 1."""
     info = container_info(path)
     sizes = np.zeros(info.nframes, dtype=np.uint64)
     N.check(N.lib().csic_container_coded_sizes(os.fsencode(path), sizes.ctypes.data_as(C.POINTER(C.c_uint64)), info.nframes))

@@ -1,7 +1,8 @@
 // csic_container.cpp -- .csic files: CSIC_FMT_PLANAR_BITS frames on disk (host only, no device; byte layout in include/csic.h).
 // A file is an 80-byte header -- magic, version, frame count, CRC-32 of everything behind the CRC field, the parameters -- and per
 // frame the three planes' payload bytes back to back: the padding of a frame buffer never reaches the file, and reading zeroes it.
-// Version 3 holds the frames group-coded instead (csic_pack_host.cpp): a coding word, a table of the frames' coded sizes, the coded frames.
+// Version 3 holds the frames group-coded instead (csic_pack_host.cpp): a coding word, a table of the frames' coded sizes, the coded frames;
+// version 4 is the same layout with the frames Rice-coded (csic_rice_host.cpp).
 #include <zlib.h>
 
 #include <cstdio>
@@ -14,8 +15,8 @@
 namespace csic {
 
 constexpr size_t CONTAINER_HEADER = 80, CONTAINER_CRC_FROM = 16;
-constexpr uint32_t CONTAINER_VERSION = 1, CONTAINER_VERSION_CODED = 3;
-constexpr size_t CODED_BODY = 8;                  // version 3: coding, reserved; then the table of sizes
+constexpr uint32_t CONTAINER_VERSION = 1, CONTAINER_VERSION_CODED = 3, CONTAINER_VERSION_RICE = 4;
+constexpr size_t CODED_BODY = 8;                  // versions 3 and 4: coding, reserved; then the table of sizes
 static const unsigned char CONTAINER_MAGIC[4] = {0x43, 0x53, 0x49, 0x43};   // "CSIC"
 
 static void put_u32(unsigned char *p, uint32_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24); }
@@ -50,6 +51,25 @@ static csic_params params_of_fields(const int32_t f[16])
     return p;
 }
 
+// the geometry of both codings of one parameter set (R.pk is the group coding's), and what depends on the coding
+struct Codings {
+    RiceGeometry R;
+    const PackGeometry &pk() const { return R.pk; }
+    uint64_t lo(int coding) const { return (uint64_t)(coding == CSIC_CODING_RICE ? R.layout.fixed_bytes : R.pk.layout.fixed_bytes); }
+    uint64_t hi(int coding) const { return lo(coding) + 4 * (uint64_t)(coding == CSIC_CODING_RICE ? R.max_payload_dwords : R.pk.max_payload_dwords); }
+    size_t bound(int coding) const { return (size_t)(coding == CSIC_CODING_RICE ? R.layout.bound_bytes : R.pk.layout.bound_bytes); }
+    int check(int coding, const unsigned char *c, size_t n) const { return coding == CSIC_CODING_RICE ? rice_check_coded(R, c, n) : pack_check_coded(R.pk, c, n); }
+    int pack(int coding, const unsigned char *frame, unsigned char *c, size_t cap, uint64_t *n) const
+    {
+        return coding == CSIC_CODING_RICE ? rice_pack_frame(R, frame, c, cap, n) : pack_frame(R.pk, frame, c, cap, n);
+    }
+    int unpack(int coding, const unsigned char *c, size_t n, unsigned char *frame) const
+    {
+        return coding == CSIC_CODING_RICE ? rice_unpack_frame(R, c, n, frame) : unpack_frame(R.pk, c, n, frame);
+    }
+};
+static uint32_t version_of(int coding) { return coding == CSIC_CODING_RICE ? CONTAINER_VERSION_RICE : CONTAINER_VERSION_CODED; }
+
 struct FileCloser {
     FILE *f;
     ~FileCloser() { if (f) fclose(f); }
@@ -58,7 +78,7 @@ struct FileCloser {
 // Reads and checks everything but the CRC (and, version 3, the coded frames themselves): header fields, parameters, the table of
 // sizes, the file's length.  `sizes` (may be NULL) receives the stored bytes of each frame; the file pointer is left behind the
 // header (version 1) or the table (version 3).  *stored_crc may be NULL.
-static int read_header(FILE *f, const char *path, csic_container_info *info, PackGeometry *G, uint32_t *stored_crc, std::vector<uint64_t> *sizes)
+static int read_header(FILE *f, const char *path, csic_container_info *info, Codings *G, uint32_t *stored_crc, std::vector<uint64_t> *sizes)
 {
     unsigned char h[CONTAINER_HEADER];
     if (fseek(f, 0, SEEK_END) != 0) return set_error(CSIC_EIO, "cannot seek in %s", path);
@@ -68,15 +88,15 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Pac
     if (fread(h, 1, sizeof h, f) != sizeof h) return set_error(CSIC_EIO, "cannot read %s", path);
     if (std::memcmp(h, CONTAINER_MAGIC, 4) != 0) return set_error(CSIC_EFORMAT, "%s is not a .csic file (bad magic)", path);
     const uint32_t version = get_u32(h + 4), nframes = get_u32(h + 8);
-    if (version != CONTAINER_VERSION && version != CONTAINER_VERSION_CODED)
-        return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1 and 3 are)", path, version);
+    if (version != CONTAINER_VERSION && version != CONTAINER_VERSION_CODED && version != CONTAINER_VERSION_RICE)
+        return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1, 3 and 4 are)", path, version);
     if (nframes < 1 || nframes > 65535) return set_error(CSIC_EFORMAT, "%s: nframes must be in 1..65535. Got %u", path, nframes);
     int32_t fields[16];
     for (int i = 0; i < 16; ++i) fields[i] = (int32_t)get_u32(h + 16 + 4 * i);
     const csic_params p = params_of_fields(fields);
-    if (p.out_format != CSIC_FMT_PLANAR_BITS || pack_geometry(&p, G) != CSIC_OK)
+    if (p.out_format != CSIC_FMT_PLANAR_BITS || rice_geometry(&p, &G->R) != CSIC_OK)
         return set_error(CSIC_EFORMAT, "%s: the stored parameters are not a valid PLANAR_BITS parameter set", path);
-    const csic_planar_bits_layout &L = G->bits;
+    const csic_planar_bits_layout &L = G->pk().bits;
     if (version == CONTAINER_VERSION) {
         const long long want = (long long)CONTAINER_HEADER + (long long)nframes * L.payload_bytes;
         if (size != want) return set_error(CSIC_EFORMAT, "%s: %lld bytes, but %u frames of these parameters make %lld", path, size, nframes, want);
@@ -86,9 +106,11 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Pac
         if (size < front) return set_error(CSIC_EFORMAT, "%s: %lld bytes is shorter than the size table of %u frames", path, size, nframes);
         std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
         if (fread(t.data(), 1, t.size(), f) != t.size()) return set_error(CSIC_EIO, "cannot read %s", path);
-        if (get_u32(t.data()) != CSIC_CODING_GROUPS || get_u32(t.data() + 4) != 0)
-            return set_error(CSIC_EFORMAT, "%s: coding %u (reserved word %u) is not supported (1, 0 is)", path, get_u32(t.data()), get_u32(t.data() + 4));
-        const uint64_t lo = (uint64_t)G->layout.fixed_bytes, hi = lo + 4 * (uint64_t)G->max_payload_dwords;
+        const int coding = version == CONTAINER_VERSION_RICE ? CSIC_CODING_RICE : CSIC_CODING_GROUPS;
+        if (get_u32(t.data()) != (uint32_t)coding || get_u32(t.data() + 4) != 0)
+            return set_error(CSIC_EFORMAT, "%s: coding %u (reserved word %u) is not what version %u holds (%d, 0)", path, get_u32(t.data()), get_u32(t.data() + 4),
+                             version, coding);
+        const uint64_t lo = G->lo(coding), hi = G->hi(coding);
         long long want = front;
         if (sizes) sizes->resize(nframes);
         for (uint32_t k = 0; k < nframes; ++k) {
@@ -122,23 +144,23 @@ static void fill_header(unsigned char h[CONTAINER_HEADER], uint32_t version, con
 }
 
 // the parameters a file stores, and their geometry; nframes checked
-static int writer_params(const csic_params *p, int32_t nframes, csic_params *q, PackGeometry *G)
+static int writer_params(const csic_params *p, int32_t nframes, csic_params *q, Codings *G)
 {
     *q = *p;
     q->out_format = CSIC_FMT_PLANAR_BITS;
-    const int st = pack_geometry(q, G);               // csic_validate first: refuses in_format != ARGB for PLANAR_BITS
+    const int st = rice_geometry(q, &G->R);           // csic_validate first: refuses in_format != ARGB for PLANAR_BITS
     if (st != CSIC_OK) return st;
     if (nframes < 1 || nframes > 65535) return set_error(CSIC_EINVAL_SIZE, "nframes must be in 1..65535. Got %d", nframes);
     return CSIC_OK;
 }
 
-// A version-3 file from coded frames in memory: frame k is frames[k][0, sizes[k]).
-static int write_coded_file(const char *path, const csic_params &q, const unsigned char *const *frames, const uint64_t *sizes, int32_t nframes)
+// A version-3 or version-4 file from coded frames in memory: frame k is frames[k][0, sizes[k]).
+static int write_coded_file(const char *path, const csic_params &q, const unsigned char *const *frames, const uint64_t *sizes, int32_t nframes, int coding)
 {
     unsigned char h[CONTAINER_HEADER];
-    fill_header(h, CONTAINER_VERSION_CODED, q, nframes);
+    fill_header(h, version_of(coding), q, nframes);
     std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
-    put_u32(t.data(), CSIC_CODING_GROUPS);
+    put_u32(t.data(), (uint32_t)coding);
     put_u32(t.data() + 4, 0);
     for (int32_t k = 0; k < nframes; ++k) put_u64(t.data() + CODED_BODY + 8 * (size_t)k, sizes[k]);
     uLong crc = crc32(0L, h + CONTAINER_CRC_FROM, (uInt)(CONTAINER_HEADER - CONTAINER_CRC_FROM));
@@ -169,7 +191,7 @@ int csic_container_info_of(const char *path, csic_container_info *info)
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
     try {
-        PackGeometry G;
+        Codings G;
         csic_container_info ci;
         const int st = read_header(fc.f, path, &ci, &G, nullptr, nullptr);
         if (st != CSIC_OK) return st;
@@ -187,7 +209,7 @@ int csic_container_coded_sizes(const char *path, uint64_t *sizes, int32_t n)
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
     try {
-        PackGeometry G;
+        Codings G;
         csic_container_info ci;
         std::vector<uint64_t> table;
         const int st = read_header(fc.f, path, &ci, &G, nullptr, &table);
@@ -205,9 +227,10 @@ int csic_container_write(const char *path, const csic_params *p, const void *fra
 {
     if (!path || !p || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
     csic_params q;
-    PackGeometry G;
-    const int st = writer_params(p, nframes, &q, &G);
+    Codings C;
+    const int st = writer_params(p, nframes, &q, &C);
     if (st != CSIC_OK) return st;
+    const PackGeometry &G = C.pk();
     const csic_planar_bits_layout &L = G.bits;
 
     unsigned char h[CONTAINER_HEADER];
@@ -236,9 +259,10 @@ int csic_container_write_ex(const char *path, const csic_params *p, const void *
 {
     if (coding == CSIC_CODING_RAW) return csic_container_write(path, p, frames, nframes);
     if (!path || !p || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    if (coding != CSIC_CODING_GROUPS) return set_error(CSIC_EINVAL_FORMAT, "coding must be CSIC_CODING_RAW(0) or CSIC_CODING_GROUPS(1). Got %d", coding);
+    if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE)
+        return set_error(CSIC_EINVAL_FORMAT, "coding must be CSIC_CODING_RAW(0), CSIC_CODING_GROUPS(1) or CSIC_CODING_RICE(3). Got %d", coding);
     csic_params q;
-    PackGeometry G;
+    Codings G;
     int st = writer_params(p, nframes, &q, &G);
     if (st != CSIC_OK) return st;
     try {
@@ -247,17 +271,45 @@ int csic_container_write_ex(const char *path, const csic_params *p, const void *
         std::vector<uint64_t> sizes((size_t)nframes);
         for (int32_t k = 0; k < nframes; ++k) {
             const size_t at = all.size();
-            all.resize(at + (size_t)G.layout.bound_bytes);
-            st = pack_frame(G, static_cast<const unsigned char *>(frames) + (int64_t)k * G.bits.frame_bytes, all.data() + at, (size_t)G.layout.bound_bytes, &sizes[k]);
+            all.resize(at + G.bound(coding));
+            st = G.pack(coding, static_cast<const unsigned char *>(frames) + (int64_t)k * G.pk().bits.frame_bytes, all.data() + at, G.bound(coding), &sizes[k]);
             if (st != CSIC_OK) return st;
             all.resize(at + (size_t)sizes[k]);
         }
         std::vector<const unsigned char *> ptrs((size_t)nframes);
         size_t at = 0;
         for (int32_t k = 0; k < nframes; ++k) { ptrs[k] = all.data() + at; at += (size_t)sizes[k]; }
-        st = write_coded_file(path, q, ptrs.data(), sizes.data(), nframes);
+        st = write_coded_file(path, q, ptrs.data(), sizes.data(), nframes, coding);
     } catch (const std::bad_alloc &) {
         return set_error(CSIC_ENOMEM, "out of host memory coding %d frames for %s", nframes, path);
+    }
+    if (st != CSIC_OK) return st;
+    clear_error();
+    return CSIC_OK;
+}
+
+int csic_container_write_coded_ex(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
+                                  int32_t nframes, int32_t coding)
+{
+    if (!path || !p || !coded || !sizes) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE)
+        return set_error(CSIC_EINVAL_FORMAT, "coded frames are CSIC_CODING_GROUPS(1) or CSIC_CODING_RICE(3). Got %d", coding);
+    csic_params q;
+    Codings G;
+    int st = writer_params(p, nframes, &q, &G);
+    if (st != CSIC_OK) return st;
+    try {
+        std::vector<const unsigned char *> ptrs((size_t)nframes);
+        for (int32_t k = 0; k < nframes; ++k) {
+            if (sizes[k] > stride_bytes)
+                return set_error(CSIC_EINVAL_SIZE, "frame %d: %llu coded bytes do not fit the stride of %zu", k, (unsigned long long)sizes[k], stride_bytes);
+            ptrs[k] = static_cast<const unsigned char *>(coded) + (size_t)k * stride_bytes;
+            st = G.check(coding, ptrs[k], (size_t)sizes[k]);
+            if (st != CSIC_OK) return st;
+        }
+        st = write_coded_file(path, q, ptrs.data(), sizes, nframes, coding);
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory writing %s", path);
     }
     if (st != CSIC_OK) return st;
     clear_error();
@@ -267,39 +319,20 @@ int csic_container_write_ex(const char *path, const csic_params *p, const void *
 int csic_container_write_coded(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
                                int32_t nframes)
 {
-    if (!path || !p || !coded || !sizes) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    csic_params q;
-    PackGeometry G;
-    int st = writer_params(p, nframes, &q, &G);
-    if (st != CSIC_OK) return st;
-    try {
-        std::vector<const unsigned char *> ptrs((size_t)nframes);
-        for (int32_t k = 0; k < nframes; ++k) {
-            if (sizes[k] > stride_bytes)
-                return set_error(CSIC_EINVAL_SIZE, "frame %d: %llu coded bytes do not fit the stride of %zu", k, (unsigned long long)sizes[k], stride_bytes);
-            ptrs[k] = static_cast<const unsigned char *>(coded) + (size_t)k * stride_bytes;
-            st = pack_check_coded(G, ptrs[k], (size_t)sizes[k]);
-            if (st != CSIC_OK) return st;
-        }
-        st = write_coded_file(path, q, ptrs.data(), sizes, nframes);
-    } catch (const std::bad_alloc &) {
-        return set_error(CSIC_ENOMEM, "out of host memory writing %s", path);
-    }
-    if (st != CSIC_OK) return st;
-    clear_error();
-    return CSIC_OK;
+    return csic_container_write_coded_ex(path, p, coded, stride_bytes, sizes, nframes, CSIC_CODING_GROUPS);
 }
 
 static int container_read(const char *path, void *frames, size_t frames_bytes)
 {
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
-    PackGeometry G;
+    Codings C;
     csic_container_info ci;
     uint32_t stored = 0;
     std::vector<uint64_t> sizes;
-    int st = read_header(fc.f, path, &ci, &G, &stored, &sizes);
+    int st = read_header(fc.f, path, &ci, &C, &stored, &sizes);
     if (st != CSIC_OK) return st;
+    const PackGeometry &G = C.pk();
     const csic_planar_bits_layout &L = G.bits;
     const size_t need = (size_t)ci.nframes * (size_t)L.frame_bytes;
     if (frames_bytes != need)
@@ -323,10 +356,10 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
                 crc = crc_long(crc, d, G.src_bytes[pl]);
             }
         } else {
-            coded.resize((size_t)sizes[k]);            // <= fixed_bytes + 4 sum G_p q_p: read_header checked the table
+            coded.resize((size_t)sizes[k]);            // within the coding's sizes: read_header checked the table
             if (fread(coded.data(), 1, coded.size(), fc.f) != coded.size()) return set_error(CSIC_EIO, "cannot read %s", path);
             crc = crc_long(crc, coded.data(), (int64_t)coded.size());
-            st = unpack_frame(G, coded.data(), coded.size(), fr);
+            st = C.unpack(ci.version == (int32_t)CONTAINER_VERSION_RICE ? CSIC_CODING_RICE : CSIC_CODING_GROUPS, coded.data(), coded.size(), fr);
         }
     }
     if (st == CSIC_OK && (uint32_t)crc != stored)

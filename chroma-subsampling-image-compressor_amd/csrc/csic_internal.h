@@ -40,6 +40,21 @@ int pack_frame(const PackGeometry &G, const unsigned char *frame, unsigned char 
 int unpack_frame(const PackGeometry &G, const unsigned char *coded, size_t coded_bytes, unsigned char *frame);
 int pack_check_coded(const PackGeometry &G, const unsigned char *coded, size_t coded_bytes);
 
+// csic_rice_host.cpp: the Rice coding (csic.h: csic_rice_*), the same three for it.  `pk` is the group coding's geometry of the same
+// parameters: the PLANAR_BITS frame, n, q and the payload ranges are shared, pk.layout is not used.
+constexpr int64_t RICE_BLOCK = 256;                       // groups per block
+inline int64_t rice_chunk_cap(int q) { return 248 * (int64_t)q + 1; }     // dwords: no chunk of a plane of q bits per code is longer
+struct RiceGeometry {
+    PackGeometry pk;
+    csic_rice_layout layout;
+    int64_t block0[3], nblocks;               // a plane's first block number; NB
+    int64_t max_payload_dwords;               // sum of B_p (248 q_p + 1)
+};
+int rice_geometry(const csic_params *p, RiceGeometry *G);
+int rice_pack_frame(const RiceGeometry &G, const unsigned char *frame, unsigned char *coded, size_t capacity, uint64_t *coded_bytes);
+int rice_unpack_frame(const RiceGeometry &G, const unsigned char *coded, size_t coded_bytes, unsigned char *frame);
+int rice_check_coded(const RiceGeometry &G, const unsigned char *coded, size_t coded_bytes);
+
 // Exact unsigned division by a run-time constant without a divide (k_generic's stream-index arithmetic): for
 // 1 <= d < 2^31 and every n < 2^31,  n / d == (uint64(n) * m) >> k  with  k = 31 + ceil(log2 d),  m = ceil(2^k / d) < 2^32.
 // (Error term e = m*d - 2^k < d <= 2^ceil(log2 d), and n * e < 2^31 * 2^ceil(log2 d) = 2^k.)  Host side, csic_host.cpp;

@@ -652,7 +652,7 @@ int  csic_png_write_argb(const char *path, const uint32_t *src, int32_t width, i
 /* ---- lossless group coding of the bit planes (csic_pack_*) ----------------------------------------------------------------------
  * csic_code_stats_* say what an entropy coder could reach; this is the library's first coder, chosen so that encode and decode are
  * data-parallel per group of 32 samples and need no serial bit stream.  It is lossless: unpack(pack(x)) gives back the three payload
- * ranges of x.  (A per-sample variable-length coder would come closer to the entropy bound and is not part of the library.)
+ * ranges of x.  (The per-sample variable-length coder that comes closer to the entropy bound is csic_rice_* below.)
  *
  * Input: one CSIC_FMT_PLANAR_BITS frame of the parameters.  Planes p = 0, 1, 2 are Y, Cb, Cr with q_p = y_bits, cb_bits, cr_bits bits
  * per code and n_0 = y_width * y_height, n_1 = n_2 = chroma_samples samples (as for csic_code_stats_*); c_i is the code of sample i in
@@ -728,6 +728,84 @@ int  csic_unpack_device(csic_plan *plan, const void *d_coded, int32_t nframes, v
                         void *d_workspace, size_t workspace_bytes, void *hip_stream);
 const char *csic_pack_kernel_name(const csic_plan *plan);
 
+/* ---- lossless Rice coding of the bit planes (csic_rice_*) -------------------------------------------------------------------------
+ * The group coding stores every group at the width of its largest residual: one edge pixel sets the cost of its 31 neighbours.  This
+ * coding (CSIC_CODING_RICE) gives each sample a Golomb-Rice code with a parameter chosen per group, and stays as data-parallel: one
+ * lane per group, no serial bit stream across groups, no stored lengths.  Coding id 2 was never written and stays refused.
+ *
+ * Carried over from the group coding, word for word: the input is one CSIC_FMT_PLANAR_BITS frame; planes, q_p, n_p, the groups of 32
+ * (G_p of them), anchor_g, e_j, s_j and the folded u_j (slots j = 1 .. 31) are as above; the last group is completed with the plane's
+ * last real code; bits beyond sample n_p - 1 are never read into a value; bit order is LSB first, every section starts at a multiple
+ * of 4 and every padding bit is 0.
+ *
+ * Mode of a group, a nibble m_g:
+ *     m = 15        zero: every u_j is 0, the group stores nothing
+ *     m = k < q     Rice (a "unary group"): slot j stores the k low bits of u_j and (u_j >> k) in unary; 31 k + sum_j ((u_j >> k) + 1) bits
+ *     m = q         raw: 31 q bits; k = q with the unary part omitted
+ * The encoder takes zero mode when it applies, otherwise the cheapest of k = 0 .. q and on a tie the smallest k: no group costs more
+ * than 31 q bits.
+ *
+ * Blocks.  Plane p has B_p = ceil(G_p / 256) blocks of 256 consecutive groups; a frame's blocks are numbered Y, then Cb, then Cr;
+ * NB = sum_p B_p.
+ *
+ * Sections, in this order:
+ *     1. modes of Y, Cb, Cr     nibble g at bits [4 g, 4 g + 4); each section 4 * ceil(G_p / 8) bytes, padding nibbles 0
+ *     2. anchors of Y, Cb, Cr   exactly as in the group coding
+ *     3. directory              NB + 1 uint32: dir[i] = the dword offset of block i's chunk from payload_offset, dir[0] = 0,
+ *                               dir[NB] = the number of payload dwords
+ *     4. payload                one chunk per block, back to back; a chunk is R then U:
+ *          R   for each group of the block in order 31 k_g bits, slot j's u_j & (2^k - 1) at bits [(j - 1) k, j k) of the group's run
+ *              (zero groups and k = 0 groups contribute nothing); runs bit-contiguous, R zero-padded to a dword
+ *          U   for each unary group in order and j = 1 .. 31: (u_j >> k) zero bits, then a one bit (the terminator);
+ *              bit-contiguous, zero-padded to a dword
+ *     fixed_bytes = the sum of sections 1 to 3              coded_bytes = fixed_bytes + 4 * dir[NB]
+ *     a chunk is at most 248 q_p + 1 dwords (R + U <= 256 * 31 q bits); a longer one is not a coded frame
+ *     bound_bytes = the next multiple of 256 at or above fixed_bytes + 4 * sum_p B_p (248 q_p + 1)
+ * Decode of group g in block b: R starts at dir[b]; the group's run in R starts at sum 31 k over the earlier groups of the block; U
+ * starts ceil(R bits / 32) dwords behind R's start; the group's unary run starts right behind terminator number 31 z of U, z = the
+ * unary groups before g in the block (z = 0: bit 0 of U).  u_j = (zeros << k) | remainder, then unfold and prefix-sum as above.
+ * Worked vector, one plane alone: q = 3, codes 1,2,3,4,5,6,7,0 -> u_1 .. u_7 = 2, the rest 0; k = 0 costs 45 bits;
+ *     modes 00 00 00 00, anchors 01 00 00 00, directory 00 00 00 00 02 00 00 00, payload 24 49 f2 ff ff 1f 00 00
+ *
+ * Host codec (no GPU; parameters and statuses as for csic_pack_*):
+ *   csic_rice_layout_of   : groups, blocks, section offsets and sizes of a coded frame of these parameters.
+ *   csic_rice_pack_host   : as csic_pack_host, capacity rule included.
+ *   csic_rice_unpack_host : as csic_unpack_host.  The input is untrusted; CSIC_EFORMAT, nothing written, for: a nibble outside
+ *                         {0 .. q_p, 15}; a padding nibble, anchor padding bit or R / U padding bit that is not 0; dir[0] != 0 or a chunk
+ *                         that is not ceil(R / 32) + ceil(U / 32) dwords (or longer than 248 q_p + 1); coded_bytes != fixed_bytes +
+ *                         4 dir[NB]; a U that does not hold exactly 31 terminators per unary group; a decoded u_j >= 2^q.  Whether the
+ *                         encoder's k was the cheapest is not checked.
+ * Device codec (gfx950), with the argument lists, alignment rules, refusals before any device is touched, asynchrony and
+ * capturability of csic_pack_*:
+ *   csic_rice_workspace_bytes : what csic_rice_pack_device needs: one uint32 per block and frame.
+ *   csic_rice_pack_device : three launches per run of planes of one width (modes and sums; the scan of the group coding; emit, which
+ *                         assembles each chunk in LDS and stores it and its directory entry as whole dwords).
+ *   csic_rice_unpack_device : ONE pass, no workspace: a block reads its directory entry, takes its chunk into LDS, counts terminators
+ *                         per dword and selects each group's start.  It does NOT validate: a nibble takes part as min(m, q_p) (15:
+ *                         zero mode), chunk extents are clamped to bound_bytes and to 248 q_p + 1 dwords, a unary run ends with its
+ *                         chunk at the latest, u is masked to q bits.  Whatever the bytes, nothing outside a frame's bound_bytes is
+ *                         read and nothing outside the three payload ranges written.  Validate untrusted input on the host.
+ *   csic_rice_kernel_name : "k_rice<q6,5,5,nt>". */
+#define CSIC_CODING_RICE   3   /* the Rice coding above (.csic version 4)                 */
+typedef struct csic_rice_layout {
+    int64_t groups[3];             /* G_p                                                              */
+    int64_t blocks[3];             /* B_p                                                              */
+    int64_t modes_offset[3];       /* byte offsets of the sections inside a coded frame               */
+    int64_t anchors_offset[3];
+    int64_t directory_offset;      /* sum_p B_p + 1 uint32                                             */
+    int64_t payload_offset;        /* = fixed_bytes                                                    */
+    int64_t fixed_bytes;
+    int64_t bound_bytes;           /* multiple of 256: the distance of coded frames in device memory   */
+} csic_rice_layout;
+int  csic_rice_layout_of(const csic_params *p, csic_rice_layout *layout);
+int  csic_rice_pack_host(const csic_params *p, const void *bits_frame, void *coded, size_t capacity, uint64_t *coded_bytes);
+int  csic_rice_unpack_host(const csic_params *p, const void *coded, size_t coded_bytes, void *bits_frame);
+int  csic_rice_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes);
+int  csic_rice_pack_device(csic_plan *plan, const void *d_bits, int32_t nframes, void *d_coded, uint64_t *d_sizes,
+                           void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int  csic_rice_unpack_device(csic_plan *plan, const void *d_coded, int32_t nframes, void *d_bits, void *hip_stream);
+const char *csic_rice_kernel_name(const csic_plan *plan);
+
 /* ---- .csic files: the compressed frames on disk (host only, usable without a GPU) --------------------------------------------
  * A container holds `nframes` CSIC_FMT_PLANAR_BITS frames of one parameter set: the only thing this library writes to a file that
  * is smaller than its input (a 6/5/5 4:2:0 frame: 1.06 bytes per pixel at factor 1; group-coded, version 3 below, less).  Version 1,
@@ -750,7 +828,7 @@ const char *csic_pack_kernel_name(const csic_plan *plan);
  *                            when the parameters are invalid or p->in_format is not ARGB; nframes outside 1 .. 65535: CSIC_EINVAL_SIZE.
  *   csic_container_info_of : header, parameters and length of a file (everything csic_container_read checks except the CRC).
  *   csic_container_read    : frames_bytes must equal nframes * frame_bytes (CSIC_EINVAL_SIZE otherwise; ask csic_container_info_of).
- * CSIC_EFORMAT: bad magic, a version other than 1 or 3, nframes out of range, parameters that fail csic_validate (or are not
+ * CSIC_EFORMAT: bad magic, a version other than 1, 3 or 4, nframes out of range, parameters that fail csic_validate (or are not
  * PLANAR_BITS), a length other than 80 + nframes * payload_bytes, a CRC mismatch.  CSIC_EIO: the file cannot be opened, read or
  * written.  NULL arguments: CSIC_EINVAL_NULL.
  *
@@ -772,7 +850,15 @@ const char *csic_pack_kernel_name(const csic_plan *plan);
  *   csic_container_coded_sizes : the stored bytes of each frame into sizes[0, n), n = the file's nframes (CSIC_EINVAL_SIZE otherwise):
  *                                the table of a version-3 file, payload_bytes for every frame of a version-1 file.
  * CSIC_EFORMAT for a version-3 file, beyond the above: coding != 1, reserved != 0, a coded_bytes below fixed_bytes, above fixed_bytes +
- * 4 sum_p G_p q_p or not a multiple of 4, a length other than 88 + 8 nframes + the sum of the table, any frame csic_unpack_host refuses. */
+ * 4 sum_p G_p q_p or not a multiple of 4, a length other than 88 + 8 nframes + the sum of the table, any frame csic_unpack_host refuses.
+ *
+ * Version 4 is version 3's layout byte for byte with version = 4 and coding = 3 (CSIC_CODING_RICE): the frames are Rice-coded
+ * (csic_rice_*).  A version / coding pair other than 3 / 1 or 4 / 3 is CSIC_EFORMAT; a version-4 file is refused in the cases of a
+ * version-3 file, with the Rice coding's sizes (fixed_bytes .. fixed_bytes + 4 sum_p B_p (248 q_p + 1)) and csic_rice_unpack_host.
+ *   csic_container_write_ex       : CSIC_CODING_RICE packs every frame on the host (csic_rice_pack_host) and writes version 4.
+ *   csic_container_write_coded_ex : csic_container_write_coded for either coding (CSIC_CODING_GROUPS or CSIC_CODING_RICE; another:
+ *                                   CSIC_EINVAL_FORMAT); csic_container_write_coded keeps meaning CSIC_CODING_GROUPS.
+ *   csic_container_read, csic_container_info_of, csic_container_coded_sizes read versions 1, 3 and 4. */
 typedef struct csic_container_info {
     csic_params params;            /* out_format = CSIC_FMT_PLANAR_BITS, in_format = CSIC_FMT_ARGB8888 */
     int32_t version, nframes;
@@ -785,6 +871,8 @@ int  csic_container_read(const char *path, void *frames, size_t frames_bytes);
 int  csic_container_write_ex(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding);
 int  csic_container_write_coded(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
                                 int32_t nframes);
+int  csic_container_write_coded_ex(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
+                                   int32_t nframes, int32_t coding);
 int  csic_container_coded_sizes(const char *path, uint64_t *sizes, int32_t n);
 
 /* ---- host-frame pipeline (the step either side of the hot path) -----------------------------------

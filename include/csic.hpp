@@ -125,18 +125,19 @@ inline csic_container_info containerInfo(const std::string &file)
     return info;
 }
 // frames: nframes PLANAR_BITS frame buffers of `p`, frame_bytes apart (p.out_format does not matter); coding = CSIC_CODING_RAW writes
-// version 1, CSIC_CODING_GROUPS packs every frame on the host and writes version 3.  readContainer reads both.
+// version 1, CSIC_CODING_GROUPS packs every frame on the host and writes version 3, CSIC_CODING_RICE version 4.  readContainer reads all.
 inline void writeContainer(const std::string &file, const csic_params &p, const void *frames, int nframes, int coding = CSIC_CODING_RAW)
 {
     check(csic_container_write_ex(file.c_str(), &p, frames, nframes, coding));
 }
-// version 3 from frames that are packed already (csic_pack_device's output on the host): frame k at coded + k * stride_bytes
+// version 3 (CSIC_CODING_GROUPS) or 4 (CSIC_CODING_RICE) from frames that are packed already (csic_pack_device's / csic_rice_pack_device's
+// output on the host): frame k at coded + k * stride_bytes
 inline void writeContainerCoded(const std::string &file, const csic_params &p, const void *coded, size_t stride_bytes,
-                                const std::vector<uint64_t> &sizes)
+                                const std::vector<uint64_t> &sizes, int coding = CSIC_CODING_GROUPS)
 {
-    check(csic_container_write_coded(file.c_str(), &p, coded, stride_bytes, sizes.data(), (int32_t)sizes.size()));
+    check(csic_container_write_coded_ex(file.c_str(), &p, coded, stride_bytes, sizes.data(), (int32_t)sizes.size(), coding));
 }
-// the stored bytes of each frame: a version-3 file's table, payload_bytes per frame for version 1
+// the stored bytes of each frame: a version-3 or version-4 file's table, payload_bytes per frame for version 1
 inline std::vector<uint64_t> containerCodedSizes(const std::string &file)
 {
     std::vector<uint64_t> sizes((size_t)containerInfo(file).nframes);
@@ -180,6 +181,31 @@ inline std::vector<uint8_t> unpack(const csic_params &p, const void *coded, size
     check(csic_planar_bits_layout_of(&q, &layout));
     std::vector<uint8_t> frame((size_t)layout.frame_bytes, 0);
     check(csic_unpack_host(&p, coded, codedBytes, frame.data()));
+    return frame;
+}
+// The same for the Rice coding (csic.h: csic_rice_*).
+inline csic_rice_layout riceLayout(const csic_params &p)
+{
+    csic_rice_layout layout;
+    check(csic_rice_layout_of(&p, &layout));
+    return layout;
+}
+inline std::vector<uint8_t> ricePack(const csic_params &p, const void *bitsFrame)
+{
+    std::vector<uint8_t> coded((size_t)riceLayout(p).bound_bytes);
+    uint64_t size = 0;
+    check(csic_rice_pack_host(&p, bitsFrame, coded.data(), coded.size(), &size));
+    coded.resize((size_t)size);
+    return coded;
+}
+inline std::vector<uint8_t> riceUnpack(const csic_params &p, const void *coded, size_t codedBytes)
+{
+    csic_params q = p;
+    q.out_format = CSIC_FMT_PLANAR_BITS;
+    csic_planar_bits_layout layout;
+    check(csic_planar_bits_layout_of(&q, &layout));
+    std::vector<uint8_t> frame((size_t)layout.frame_bytes, 0);
+    check(csic_rice_unpack_host(&p, coded, codedBytes, frame.data()));
     return frame;
 }
 
@@ -324,6 +350,25 @@ public:
         check(csic_unpack_device(plan_, d_coded, nframes, d_bits, d_workspace, workspace_bytes, hip_stream));
     }
     const char *packKernelName() { return csic_pack_kernel_name(plan_); }
+    // the Rice coding of this plan's PLANAR_BITS frames, host and device; riceUnpackDevice is one pass and takes no workspace
+    csic_rice_layout riceLayout() const { return csic::riceLayout(params_); }
+    std::vector<uint8_t> ricePack(const void *bitsFrame) const { return csic::ricePack(params_, bitsFrame); }
+    std::vector<uint8_t> riceUnpack(const void *coded, size_t codedBytes) const { return csic::riceUnpack(params_, coded, codedBytes); }
+    size_t riceWorkspaceBytes(int nframes = 1)
+    {
+        size_t bytes = 0;
+        check(csic_rice_workspace_bytes(plan_, nframes, &bytes));
+        return bytes;
+    }
+    void ricePackDevice(const void *d_bits, int nframes, void *d_coded, uint64_t *d_sizes, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+    {
+        check(csic_rice_pack_device(plan_, d_bits, nframes, d_coded, d_sizes, d_workspace, workspace_bytes, hip_stream));
+    }
+    void riceUnpackDevice(const void *d_coded, int nframes, void *d_bits, void *hip_stream)
+    {
+        check(csic_rice_unpack_device(plan_, d_coded, nframes, d_bits, hip_stream));
+    }
+    const char *riceKernelName() { return csic_rice_kernel_name(plan_); }
 
 private:
     csic_params params_;
