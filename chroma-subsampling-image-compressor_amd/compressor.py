@@ -431,40 +431,50 @@ class Plan:
         if t.device.index != self.device:
             raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: tensor is on a different device than the plan")
 
-    def pack_device(self, d_bits, nframes: int = 1, d_coded=None):
-        """d_bits: nframes PLANAR_BITS frame buffers on the device (frame_bytes each).  Returns (coded, sizes): a uint8 tensor
-        (nframes, bound_bytes) whose row k holds frame k's coded bytes in [0, sizes[k]) -- the rest of a row is not written -- and an
-        int64 tensor (nframes,) of the coded sizes.  Asynchronous on torch's current stream."""
+    def _pack_device(self, d_bits, nframes, d_coded, bound, workspace_bytes, pack):
+        """pack_device / rice_pack_device: `bound`, `workspace_bytes` and `pack` are the coding's bound_bytes, *_workspace_bytes method
+        and entry point."""
         import torch
-        fb, bound = self.planar_bits_layout.frame_bytes, self.pack_layout.bound_bytes
-        self._pack_check(d_bits, nframes * fb, "d_bits")
+        self._pack_check(d_bits, nframes * self.planar_bits_layout.frame_bytes, "d_bits")
         if d_coded is None:
             d_coded = torch.empty((nframes, bound), dtype=torch.uint8, device=d_bits.device)
         else:
             self._pack_check(d_coded, nframes * bound, "d_coded")
         sizes = torch.empty((nframes,), dtype=torch.int64, device=d_bits.device)
-        wsb = self.pack_workspace_bytes(nframes)
+        wsb = workspace_bytes(nframes)
         ws = torch.empty((wsb,), dtype=torch.uint8, device=d_bits.device)
-        N.check(N.lib().csic_pack_device(self._h, C.c_void_p(d_bits.data_ptr()), int(nframes), C.c_void_p(d_coded.data_ptr()),
-                                         C.c_void_p(sizes.data_ptr()), C.c_void_p(ws.data_ptr()), wsb, self._stream()))
+        N.check(pack(self._h, C.c_void_p(d_bits.data_ptr()), int(nframes), C.c_void_p(d_coded.data_ptr()), C.c_void_p(sizes.data_ptr()),
+                     C.c_void_p(ws.data_ptr()), wsb, self._stream()))
         return d_coded, sizes
 
-    def unpack_device(self, d_coded, nframes: int = 1, d_bits=None):
-        """The inverse of pack_device: d_coded holds nframes coded frames bound_bytes apart.  Returns the PLANAR_BITS frame buffers,
-        a uint8 tensor (nframes, frame_bytes) (one frame: (frame_bytes,)); only their payload ranges are written.  The device does
-        not validate: check untrusted bytes with unpack() first."""
+    def _unpack_device(self, d_coded, nframes, d_bits, bound, workspace_bytes, unpack):
+        """unpack_device / rice_unpack_device, as _pack_device; workspace_bytes is None for an entry point that takes no workspace."""
         import torch
-        fb, bound = self.planar_bits_layout.frame_bytes, self.pack_layout.bound_bytes
+        fb = self.planar_bits_layout.frame_bytes
         self._pack_check(d_coded, nframes * bound, "d_coded")
         if d_bits is None:
             d_bits = torch.empty((nframes, fb) if nframes > 1 else (fb,), dtype=torch.uint8, device=d_coded.device)
         else:
             self._pack_check(d_bits, nframes * fb, "d_bits")
-        wsb = self.pack_workspace_bytes(nframes)
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=d_coded.device)
-        N.check(N.lib().csic_unpack_device(self._h, C.c_void_p(d_coded.data_ptr()), int(nframes), C.c_void_p(d_bits.data_ptr()),
-                                           C.c_void_p(ws.data_ptr()), wsb, self._stream()))
+        ws_args = ()
+        if workspace_bytes is not None:
+            wsb = workspace_bytes(nframes)
+            ws = torch.empty((wsb,), dtype=torch.uint8, device=d_coded.device)
+            ws_args = (C.c_void_p(ws.data_ptr()), wsb)
+        N.check(unpack(self._h, C.c_void_p(d_coded.data_ptr()), int(nframes), C.c_void_p(d_bits.data_ptr()), *ws_args, self._stream()))
         return d_bits
+
+    def pack_device(self, d_bits, nframes: int = 1, d_coded=None):
+        """d_bits: nframes PLANAR_BITS frame buffers on the device (frame_bytes each).  Returns (coded, sizes): a uint8 tensor
+        (nframes, bound_bytes) whose row k holds frame k's coded bytes in [0, sizes[k]) -- the rest of a row is not written -- and an
+        int64 tensor (nframes,) of the coded sizes.  Asynchronous on torch's current stream."""
+        return self._pack_device(d_bits, nframes, d_coded, self.pack_layout.bound_bytes, self.pack_workspace_bytes, N.lib().csic_pack_device)
+
+    def unpack_device(self, d_coded, nframes: int = 1, d_bits=None):
+        """The inverse of pack_device: d_coded holds nframes coded frames bound_bytes apart.  Returns the PLANAR_BITS frame buffers,
+        a uint8 tensor (nframes, frame_bytes) (one frame: (frame_bytes,)); only their payload ranges are written.  The device does
+        not validate: check untrusted bytes with unpack() first."""
+        return self._unpack_device(d_coded, nframes, d_bits, self.pack_layout.bound_bytes, self.pack_workspace_bytes, N.lib().csic_unpack_device)
 
     def pack(self, bits_frame) -> np.ndarray:
         """csic_pack_host: one PLANAR_BITS frame buffer in host memory -> its coded bytes (uint8 array).  Needs no GPU."""
@@ -494,33 +504,12 @@ class Plan:
     def rice_pack_device(self, d_bits, nframes: int = 1, d_coded=None):
         """As pack_device, in the Rice coding: returns (coded, sizes), a uint8 tensor (nframes, rice_layout.bound_bytes) whose row k
         holds frame k's coded bytes in [0, sizes[k]), and an int64 tensor of the sizes.  Asynchronous on torch's current stream."""
-        import torch
-        fb, bound = self.planar_bits_layout.frame_bytes, self.rice_layout.bound_bytes
-        self._pack_check(d_bits, nframes * fb, "d_bits")
-        if d_coded is None:
-            d_coded = torch.empty((nframes, bound), dtype=torch.uint8, device=d_bits.device)
-        else:
-            self._pack_check(d_coded, nframes * bound, "d_coded")
-        sizes = torch.empty((nframes,), dtype=torch.int64, device=d_bits.device)
-        wsb = self.rice_workspace_bytes(nframes)
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=d_bits.device)
-        N.check(N.lib().csic_rice_pack_device(self._h, C.c_void_p(d_bits.data_ptr()), int(nframes), C.c_void_p(d_coded.data_ptr()),
-                                              C.c_void_p(sizes.data_ptr()), C.c_void_p(ws.data_ptr()), wsb, self._stream()))
-        return d_coded, sizes
+        return self._pack_device(d_bits, nframes, d_coded, self.rice_layout.bound_bytes, self.rice_workspace_bytes, N.lib().csic_rice_pack_device)
 
     def rice_unpack_device(self, d_coded, nframes: int = 1, d_bits=None):
         """The inverse of rice_pack_device, one pass without a workspace.  The device does not validate: check untrusted bytes with
         rice_unpack() first."""
-        import torch
-        fb, bound = self.planar_bits_layout.frame_bytes, self.rice_layout.bound_bytes
-        self._pack_check(d_coded, nframes * bound, "d_coded")
-        if d_bits is None:
-            d_bits = torch.empty((nframes, fb) if nframes > 1 else (fb,), dtype=torch.uint8, device=d_coded.device)
-        else:
-            self._pack_check(d_bits, nframes * fb, "d_bits")
-        N.check(N.lib().csic_rice_unpack_device(self._h, C.c_void_p(d_coded.data_ptr()), int(nframes), C.c_void_p(d_bits.data_ptr()),
-                                                self._stream()))
-        return d_bits
+        return self._unpack_device(d_coded, nframes, d_bits, self.rice_layout.bound_bytes, None, N.lib().csic_rice_unpack_device)
 
     def rice_pack(self, bits_frame) -> np.ndarray:
         """csic_rice_pack_host: one PLANAR_BITS frame buffer in host memory -> its Rice-coded bytes.  Needs no GPU."""

@@ -45,29 +45,41 @@ def pack_layout(c_params: N.CsicParams) -> N.CsicPackLayout:
     return lay
 
 
-def pack_frame_host(c_params: N.CsicParams, bits_frame) -> np.ndarray:
-    """csic_pack_host: one PLANAR_BITS frame buffer (frame_bytes) -> its coded bytes, a uint8 array of coded_bytes."""
+def _pack_host(c_params: N.CsicParams, bits_frame, layout_of, pack) -> np.ndarray:
+    """One PLANAR_BITS frame buffer -> its coded bytes through a coding's `layout_of` (pack_layout, rice_layout) and `*_pack_host`."""
     q, lay = _bits_params(c_params)
     a = np.ascontiguousarray(bits_frame).reshape(-1).view(np.uint8)
     if a.size != lay.frame_bytes:
         raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: a frame buffer of these parameters has {lay.frame_bytes} bytes, got {a.size}")
-    coded = np.empty(pack_layout(q).bound_bytes, dtype=np.uint8)
+    coded = np.empty(layout_of(q).bound_bytes, dtype=np.uint8)
     n = C.c_uint64()
-    N.check(N.lib().csic_pack_host(C.byref(q), a.ctypes.data_as(C.c_void_p), coded.ctypes.data_as(C.c_void_p), coded.size, C.byref(n)))
+    N.check(pack(C.byref(q), a.ctypes.data_as(C.c_void_p), coded.ctypes.data_as(C.c_void_p), coded.size, C.byref(n)))
     return coded[:n.value].copy()
 
 
-def unpack_frame_host(c_params: N.CsicParams, coded, out=None) -> np.ndarray:
-    """csic_unpack_host: coded bytes -> a PLANAR_BITS frame buffer.  `out` (uint8, frame_bytes) keeps its bytes outside the three
-    payload ranges; without it the buffer is zero there.  Damaged input raises CsicIOError (CSIC_EFORMAT)."""
+def _unpack_host(c_params: N.CsicParams, coded, out, unpack) -> np.ndarray:
+    """Coded bytes -> a PLANAR_BITS frame buffer through a coding's `*_unpack_host`.  Empty input goes in as a one-byte buffer of
+    length 0, so that the library refuses its size (CsicIOError) rather than a NULL pointer."""
     q, lay = _bits_params(c_params)
     a = np.ascontiguousarray(coded).reshape(-1).view(np.uint8)
     if out is None:
         out = np.zeros(lay.frame_bytes, dtype=np.uint8)
     elif out.dtype != np.uint8 or out.size != lay.frame_bytes or not out.flags.c_contiguous:
         raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: out must be a contiguous uint8 buffer of {lay.frame_bytes} bytes")
-    N.check(N.lib().csic_unpack_host(C.byref(q), a.ctypes.data_as(C.c_void_p), a.size, out.ctypes.data_as(C.c_void_p)))
+    src = a if a.size else np.zeros(1, dtype=np.uint8)
+    N.check(unpack(C.byref(q), src.ctypes.data_as(C.c_void_p), a.size, out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def pack_frame_host(c_params: N.CsicParams, bits_frame) -> np.ndarray:
+    """csic_pack_host: one PLANAR_BITS frame buffer (frame_bytes) -> its coded bytes, a uint8 array of coded_bytes."""
+    return _pack_host(c_params, bits_frame, pack_layout, N.lib().csic_pack_host)
+
+
+def unpack_frame_host(c_params: N.CsicParams, coded, out=None) -> np.ndarray:
+    """csic_unpack_host: coded bytes -> a PLANAR_BITS frame buffer.  `out` (uint8, frame_bytes) keeps its bytes outside the three
+    payload ranges; without it the buffer is zero there.  Damaged input raises CsicIOError (CSIC_EFORMAT)."""
+    return _unpack_host(c_params, coded, out, N.lib().csic_unpack_host)
 
 
 def rice_layout(c_params: N.CsicParams) -> N.CsicRiceLayout:
@@ -79,27 +91,12 @@ def rice_layout(c_params: N.CsicParams) -> N.CsicRiceLayout:
 
 def rice_pack_host(c_params: N.CsicParams, bits_frame) -> np.ndarray:
     """csic_rice_pack_host: one PLANAR_BITS frame buffer (frame_bytes) -> its Rice-coded bytes, a uint8 array of coded_bytes."""
-    q, lay = _bits_params(c_params)
-    a = np.ascontiguousarray(bits_frame).reshape(-1).view(np.uint8)
-    if a.size != lay.frame_bytes:
-        raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: a frame buffer of these parameters has {lay.frame_bytes} bytes, got {a.size}")
-    coded = np.empty(rice_layout(q).bound_bytes, dtype=np.uint8)
-    n = C.c_uint64()
-    N.check(N.lib().csic_rice_pack_host(C.byref(q), a.ctypes.data_as(C.c_void_p), coded.ctypes.data_as(C.c_void_p), coded.size, C.byref(n)))
-    return coded[:n.value].copy()
+    return _pack_host(c_params, bits_frame, rice_layout, N.lib().csic_rice_pack_host)
 
 
 def rice_unpack_host(c_params: N.CsicParams, coded, out=None) -> np.ndarray:
     """csic_rice_unpack_host: Rice-coded bytes -> a PLANAR_BITS frame buffer, as unpack_frame_host.  Damaged input raises CsicIOError."""
-    q, lay = _bits_params(c_params)
-    a = np.ascontiguousarray(coded).reshape(-1).view(np.uint8)
-    if out is None:
-        out = np.zeros(lay.frame_bytes, dtype=np.uint8)
-    elif out.dtype != np.uint8 or out.size != lay.frame_bytes or not out.flags.c_contiguous:
-        raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: out must be a contiguous uint8 buffer of {lay.frame_bytes} bytes")
-    src = a if a.size else np.zeros(1, dtype=np.uint8)
-    N.check(N.lib().csic_rice_unpack_host(C.byref(q), src.ctypes.data_as(C.c_void_p), a.size, out.ctypes.data_as(C.c_void_p)))
-    return out
+    return _unpack_host(c_params, coded, out, N.lib().csic_rice_unpack_host)
 
 
 def write_container(path: str, c_params: N.CsicParams, frames, coding="raw") -> None:

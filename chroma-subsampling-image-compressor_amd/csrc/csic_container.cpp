@@ -2,7 +2,8 @@
 // A file is an 80-byte header -- magic, version, frame count, CRC-32 of everything behind the CRC field, the parameters -- and per
 // frame the three planes' payload bytes back to back: the padding of a frame buffer never reaches the file, and reading zeroes it.
 // Version 3 holds the frames group-coded instead (csic_pack_host.cpp): a coding word, a table of the frames' coded sizes, the coded frames;
-// version 4 is the same layout with the frames Rice-coded (csic_rice_host.cpp).
+// version 4 is the same layout with the frames Rice-coded (csic_rice_host.cpp).  What differs between the two is one row of codec_of;
+// the little-endian dwords are csic_group_host.h's.
 #include <zlib.h>
 
 #include <cstdio>
@@ -10,7 +11,7 @@
 #include <new>
 #include <vector>
 
-#include "csic_internal.h"
+#include "csic_group_host.h"
 
 namespace csic {
 
@@ -19,8 +20,6 @@ constexpr uint32_t CONTAINER_VERSION = 1, CONTAINER_VERSION_CODED = 3, CONTAINER
 constexpr size_t CODED_BODY = 8;                  // versions 3 and 4: coding, reserved; then the table of sizes
 static const unsigned char CONTAINER_MAGIC[4] = {0x43, 0x53, 0x49, 0x43};   // "CSIC"
 
-static void put_u32(unsigned char *p, uint32_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24); }
-static uint32_t get_u32(const unsigned char *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 static void put_u64(unsigned char *p, uint64_t v) { put_u32(p, (uint32_t)v); put_u32(p + 4, (uint32_t)(v >> 32)); }
 static uint64_t get_u64(const unsigned char *p) { return (uint64_t)get_u32(p) | ((uint64_t)get_u32(p + 4) << 32); }
 
@@ -51,24 +50,30 @@ static csic_params params_of_fields(const int32_t f[16])
     return p;
 }
 
-// the geometry of both codings of one parameter set (R.pk is the group coding's), and what depends on the coding
-struct Codings {
-    RiceGeometry R;
-    const PackGeometry &pk() const { return R.pk; }
-    uint64_t lo(int coding) const { return (uint64_t)(coding == CSIC_CODING_RICE ? R.layout.fixed_bytes : R.pk.layout.fixed_bytes); }
-    uint64_t hi(int coding) const { return lo(coding) + 4 * (uint64_t)(coding == CSIC_CODING_RICE ? R.max_payload_dwords : R.pk.max_payload_dwords); }
-    size_t bound(int coding) const { return (size_t)(coding == CSIC_CODING_RICE ? R.layout.bound_bytes : R.pk.layout.bound_bytes); }
-    int check(int coding, const unsigned char *c, size_t n) const { return coding == CSIC_CODING_RICE ? rice_check_coded(R, c, n) : pack_check_coded(R.pk, c, n); }
-    int pack(int coding, const unsigned char *frame, unsigned char *c, size_t cap, uint64_t *n) const
-    {
-        return coding == CSIC_CODING_RICE ? rice_pack_frame(R, frame, c, cap, n) : pack_frame(R.pk, frame, c, cap, n);
-    }
-    int unpack(int coding, const unsigned char *c, size_t n, unsigned char *frame) const
-    {
-        return coding == CSIC_CODING_RICE ? rice_unpack_frame(R, c, n, frame) : unpack_frame(R.pk, c, n, frame);
-    }
+// What depends on the coding of a coded file, for one parameter set (R.pk is the group coding's geometry): a coded frame's least and
+// most bytes and its bound_bytes, and the host codec.  One row per coding; a file picks its row once.
+struct Codec {
+    int coding;
+    uint32_t version;
+    uint64_t lo, hi;
+    size_t bound;
+    int (*check)(const RiceGeometry &R, const unsigned char *c, size_t n);
+    int (*pack)(const RiceGeometry &R, const unsigned char *frame, unsigned char *c, size_t cap, uint64_t *n);
+    int (*unpack)(const RiceGeometry &R, const unsigned char *c, size_t n, unsigned char *frame);
 };
-static uint32_t version_of(int coding) { return coding == CSIC_CODING_RICE ? CONTAINER_VERSION_RICE : CONTAINER_VERSION_CODED; }
+static Codec codec_of(const RiceGeometry &R, int coding)
+{
+    const csic_pack_layout &P = R.pk.layout;
+    const csic_rice_layout &L = R.layout;
+    const Codec rows[2] = {
+        {CSIC_CODING_GROUPS, CONTAINER_VERSION_CODED, (uint64_t)P.fixed_bytes, (uint64_t)(P.fixed_bytes + 4 * R.pk.max_payload_dwords), (size_t)P.bound_bytes,
+         [](const RiceGeometry &G, const unsigned char *c, size_t n) { return pack_check_coded(G.pk, c, n); },
+         [](const RiceGeometry &G, const unsigned char *f, unsigned char *c, size_t cap, uint64_t *n) { return pack_frame(G.pk, f, c, cap, n); },
+         [](const RiceGeometry &G, const unsigned char *c, size_t n, unsigned char *f) { return unpack_frame(G.pk, c, n, f); }},
+        {CSIC_CODING_RICE, CONTAINER_VERSION_RICE, (uint64_t)L.fixed_bytes, (uint64_t)(L.fixed_bytes + 4 * R.max_payload_dwords), (size_t)L.bound_bytes,
+         rice_check_coded, rice_pack_frame, rice_unpack_frame}};
+    return rows[coding == CSIC_CODING_RICE];
+}
 
 struct FileCloser {
     FILE *f;
@@ -78,7 +83,7 @@ struct FileCloser {
 // Reads and checks everything but the CRC (and, version 3, the coded frames themselves): header fields, parameters, the table of
 // sizes, the file's length.  `sizes` (may be NULL) receives the stored bytes of each frame; the file pointer is left behind the
 // header (version 1) or the table (version 3).  *stored_crc may be NULL.
-static int read_header(FILE *f, const char *path, csic_container_info *info, Codings *G, uint32_t *stored_crc, std::vector<uint64_t> *sizes)
+static int read_header(FILE *f, const char *path, csic_container_info *info, RiceGeometry *G, uint32_t *stored_crc, std::vector<uint64_t> *sizes)
 {
     unsigned char h[CONTAINER_HEADER];
     if (fseek(f, 0, SEEK_END) != 0) return set_error(CSIC_EIO, "cannot seek in %s", path);
@@ -94,9 +99,9 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Cod
     int32_t fields[16];
     for (int i = 0; i < 16; ++i) fields[i] = (int32_t)get_u32(h + 16 + 4 * i);
     const csic_params p = params_of_fields(fields);
-    if (p.out_format != CSIC_FMT_PLANAR_BITS || rice_geometry(&p, &G->R) != CSIC_OK)
+    if (p.out_format != CSIC_FMT_PLANAR_BITS || rice_geometry(&p, G) != CSIC_OK)
         return set_error(CSIC_EFORMAT, "%s: the stored parameters are not a valid PLANAR_BITS parameter set", path);
-    const csic_planar_bits_layout &L = G->pk().bits;
+    const csic_planar_bits_layout &L = G->pk.bits;
     if (version == CONTAINER_VERSION) {
         const long long want = (long long)CONTAINER_HEADER + (long long)nframes * L.payload_bytes;
         if (size != want) return set_error(CSIC_EFORMAT, "%s: %lld bytes, but %u frames of these parameters make %lld", path, size, nframes, want);
@@ -110,7 +115,8 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Cod
         if (get_u32(t.data()) != (uint32_t)coding || get_u32(t.data() + 4) != 0)
             return set_error(CSIC_EFORMAT, "%s: coding %u (reserved word %u) is not what version %u holds (%d, 0)", path, get_u32(t.data()), get_u32(t.data() + 4),
                              version, coding);
-        const uint64_t lo = G->lo(coding), hi = G->hi(coding);
+        const Codec codec = codec_of(*G, coding);
+        const uint64_t lo = codec.lo, hi = codec.hi;
         long long want = front;
         if (sizes) sizes->resize(nframes);
         for (uint32_t k = 0; k < nframes; ++k) {
@@ -144,23 +150,23 @@ static void fill_header(unsigned char h[CONTAINER_HEADER], uint32_t version, con
 }
 
 // the parameters a file stores, and their geometry; nframes checked
-static int writer_params(const csic_params *p, int32_t nframes, csic_params *q, Codings *G)
+static int writer_params(const csic_params *p, int32_t nframes, csic_params *q, RiceGeometry *G)
 {
     *q = *p;
     q->out_format = CSIC_FMT_PLANAR_BITS;
-    const int st = rice_geometry(q, &G->R);           // csic_validate first: refuses in_format != ARGB for PLANAR_BITS
+    const int st = rice_geometry(q, G);           // csic_validate first: refuses in_format != ARGB for PLANAR_BITS
     if (st != CSIC_OK) return st;
     if (nframes < 1 || nframes > 65535) return set_error(CSIC_EINVAL_SIZE, "nframes must be in 1..65535. Got %d", nframes);
     return CSIC_OK;
 }
 
 // A version-3 or version-4 file from coded frames in memory: frame k is frames[k][0, sizes[k]).
-static int write_coded_file(const char *path, const csic_params &q, const unsigned char *const *frames, const uint64_t *sizes, int32_t nframes, int coding)
+static int write_coded_file(const char *path, const csic_params &q, const unsigned char *const *frames, const uint64_t *sizes, int32_t nframes, const Codec &codec)
 {
     unsigned char h[CONTAINER_HEADER];
-    fill_header(h, version_of(coding), q, nframes);
+    fill_header(h, codec.version, q, nframes);
     std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
-    put_u32(t.data(), (uint32_t)coding);
+    put_u32(t.data(), (uint32_t)codec.coding);
     put_u32(t.data() + 4, 0);
     for (int32_t k = 0; k < nframes; ++k) put_u64(t.data() + CODED_BODY + 8 * (size_t)k, sizes[k]);
     uLong crc = crc32(0L, h + CONTAINER_CRC_FROM, (uInt)(CONTAINER_HEADER - CONTAINER_CRC_FROM));
@@ -191,7 +197,7 @@ int csic_container_info_of(const char *path, csic_container_info *info)
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
     try {
-        Codings G;
+        RiceGeometry G;
         csic_container_info ci;
         const int st = read_header(fc.f, path, &ci, &G, nullptr, nullptr);
         if (st != CSIC_OK) return st;
@@ -209,7 +215,7 @@ int csic_container_coded_sizes(const char *path, uint64_t *sizes, int32_t n)
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
     try {
-        Codings G;
+        RiceGeometry G;
         csic_container_info ci;
         std::vector<uint64_t> table;
         const int st = read_header(fc.f, path, &ci, &G, nullptr, &table);
@@ -227,10 +233,10 @@ int csic_container_write(const char *path, const csic_params *p, const void *fra
 {
     if (!path || !p || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
     csic_params q;
-    Codings C;
+    RiceGeometry C;
     const int st = writer_params(p, nframes, &q, &C);
     if (st != CSIC_OK) return st;
-    const PackGeometry &G = C.pk();
+    const PackGeometry &G = C.pk;
     const csic_planar_bits_layout &L = G.bits;
 
     unsigned char h[CONTAINER_HEADER];
@@ -262,24 +268,25 @@ int csic_container_write_ex(const char *path, const csic_params *p, const void *
     if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE)
         return set_error(CSIC_EINVAL_FORMAT, "coding must be CSIC_CODING_RAW(0), CSIC_CODING_GROUPS(1) or CSIC_CODING_RICE(3). Got %d", coding);
     csic_params q;
-    Codings G;
+    RiceGeometry G;
     int st = writer_params(p, nframes, &q, &G);
     if (st != CSIC_OK) return st;
+    const Codec codec = codec_of(G, coding);
     try {
         // the table of sizes stands in front of the frames: every frame is coded before the first byte is written
         std::vector<unsigned char> all;
         std::vector<uint64_t> sizes((size_t)nframes);
         for (int32_t k = 0; k < nframes; ++k) {
             const size_t at = all.size();
-            all.resize(at + G.bound(coding));
-            st = G.pack(coding, static_cast<const unsigned char *>(frames) + (int64_t)k * G.pk().bits.frame_bytes, all.data() + at, G.bound(coding), &sizes[k]);
+            all.resize(at + codec.bound);
+            st = codec.pack(G, static_cast<const unsigned char *>(frames) + (int64_t)k * G.pk.bits.frame_bytes, all.data() + at, codec.bound, &sizes[k]);
             if (st != CSIC_OK) return st;
             all.resize(at + (size_t)sizes[k]);
         }
         std::vector<const unsigned char *> ptrs((size_t)nframes);
         size_t at = 0;
         for (int32_t k = 0; k < nframes; ++k) { ptrs[k] = all.data() + at; at += (size_t)sizes[k]; }
-        st = write_coded_file(path, q, ptrs.data(), sizes.data(), nframes, coding);
+        st = write_coded_file(path, q, ptrs.data(), sizes.data(), nframes, codec);
     } catch (const std::bad_alloc &) {
         return set_error(CSIC_ENOMEM, "out of host memory coding %d frames for %s", nframes, path);
     }
@@ -295,19 +302,20 @@ int csic_container_write_coded_ex(const char *path, const csic_params *p, const 
     if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE)
         return set_error(CSIC_EINVAL_FORMAT, "coded frames are CSIC_CODING_GROUPS(1) or CSIC_CODING_RICE(3). Got %d", coding);
     csic_params q;
-    Codings G;
+    RiceGeometry G;
     int st = writer_params(p, nframes, &q, &G);
     if (st != CSIC_OK) return st;
+    const Codec codec = codec_of(G, coding);
     try {
         std::vector<const unsigned char *> ptrs((size_t)nframes);
         for (int32_t k = 0; k < nframes; ++k) {
             if (sizes[k] > stride_bytes)
                 return set_error(CSIC_EINVAL_SIZE, "frame %d: %llu coded bytes do not fit the stride of %zu", k, (unsigned long long)sizes[k], stride_bytes);
             ptrs[k] = static_cast<const unsigned char *>(coded) + (size_t)k * stride_bytes;
-            st = G.check(coding, ptrs[k], (size_t)sizes[k]);
+            st = codec.check(G, ptrs[k], (size_t)sizes[k]);
             if (st != CSIC_OK) return st;
         }
-        st = write_coded_file(path, q, ptrs.data(), sizes, nframes, coding);
+        st = write_coded_file(path, q, ptrs.data(), sizes, nframes, codec);
     } catch (const std::bad_alloc &) {
         return set_error(CSIC_ENOMEM, "out of host memory writing %s", path);
     }
@@ -326,13 +334,13 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
 {
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
-    Codings C;
+    RiceGeometry C;
     csic_container_info ci;
     uint32_t stored = 0;
     std::vector<uint64_t> sizes;
     int st = read_header(fc.f, path, &ci, &C, &stored, &sizes);
     if (st != CSIC_OK) return st;
-    const PackGeometry &G = C.pk();
+    const PackGeometry &G = C.pk;
     const csic_planar_bits_layout &L = G.bits;
     const size_t need = (size_t)ci.nframes * (size_t)L.frame_bytes;
     if (frames_bytes != need)
@@ -347,6 +355,7 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
     unsigned char *base = static_cast<unsigned char *>(frames);
     std::memset(base, 0, need);
     std::vector<unsigned char> coded;
+    const Codec codec = codec_of(C, ci.version == (int32_t)CONTAINER_VERSION_RICE ? CSIC_CODING_RICE : CSIC_CODING_GROUPS);   // (unused by version 1)
     for (int32_t k = 0; k < ci.nframes && st == CSIC_OK; ++k) {
         unsigned char *fr = base + (int64_t)k * L.frame_bytes;
         if (ci.version == (int32_t)CONTAINER_VERSION) {
@@ -359,7 +368,7 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
             coded.resize((size_t)sizes[k]);            // within the coding's sizes: read_header checked the table
             if (fread(coded.data(), 1, coded.size(), fc.f) != coded.size()) return set_error(CSIC_EIO, "cannot read %s", path);
             crc = crc_long(crc, coded.data(), (int64_t)coded.size());
-            st = C.unpack(ci.version == (int32_t)CONTAINER_VERSION_RICE ? CSIC_CODING_RICE : CSIC_CODING_GROUPS, coded.data(), coded.size(), fr);
+            st = codec.unpack(C, coded.data(), coded.size(), fr);
         }
     }
     if (st == CSIC_OK && (uint32_t)crc != stored)

@@ -25,8 +25,9 @@ int  derive_geometry(const csic_params *p, Geometry *g);   // validates first
 void planar_layout(const Geometry &g, const csic_params *p, csic_planar_layout *layout);   // csic.h: CSIC_FMT_PLANAR
 void planar_bits_layout(const Geometry &g, const csic_params *p, csic_planar_bits_layout *layout);   // csic.h: CSIC_FMT_PLANAR_BITS
 
-// csic_pack_host.cpp: the group coding (csic.h: csic_pack_*).  Everything both codecs and the container derive from the parameters, the
-// host codec on one frame, and the checks csic_unpack_host makes on their own (csic_container_write_coded).
+// csic_pack_host.cpp: the group coding (csic.h: csic_pack_*).  Everything both codecs, the Rice coding and the container derive from the
+// parameters, the host codec on one frame, and the checks csic_unpack_host makes on their own (csic_container_write_coded).
+constexpr int64_t RICE_BLOCK = 256;           // groups per block: a block of the Rice format and of both device codecs' kernels
 struct PackGeometry {
     csic_planar_bits_layout bits;             // the PLANAR_BITS frame the coding reads and restores
     csic_pack_layout layout;
@@ -34,6 +35,7 @@ struct PackGeometry {
     int32_t q[3];                             // bits per code
     int64_t src_offset[3], src_bytes[3];      // the planes' payload ranges inside a frame buffer
     int64_t max_payload_dwords;               // sum of G_p q_p: no frame's payload is longer
+    int64_t blocks[3], block0[3], nblocks;    // blocks of RICE_BLOCK groups: per plane, a plane's first block number, per frame (NB)
 };
 int pack_geometry(const csic_params *p, PackGeometry *G);     // validates first (out_format ignored)
 int pack_frame(const PackGeometry &G, const unsigned char *frame, unsigned char *coded, size_t capacity, uint64_t *coded_bytes);
@@ -41,13 +43,12 @@ int unpack_frame(const PackGeometry &G, const unsigned char *coded, size_t coded
 int pack_check_coded(const PackGeometry &G, const unsigned char *coded, size_t coded_bytes);
 
 // csic_rice_host.cpp: the Rice coding (csic.h: csic_rice_*), the same three for it.  `pk` is the group coding's geometry of the same
-// parameters: the PLANAR_BITS frame, n, q and the payload ranges are shared, pk.layout is not used.
-constexpr int64_t RICE_BLOCK = 256;                       // groups per block
+// parameters: the PLANAR_BITS frame, n, q, the payload ranges, the groups, the blocks and -- in pk.layout -- the nibble and anchors
+// sections are the group coding's; `layout` repeats them in the Rice coding's public struct.
 inline int64_t rice_chunk_cap(int q) { return 248 * (int64_t)q + 1; }     // dwords: no chunk of a plane of q bits per code is longer
 struct RiceGeometry {
     PackGeometry pk;
     csic_rice_layout layout;
-    int64_t block0[3], nblocks;               // a plane's first block number; NB
     int64_t max_payload_dwords;               // sum of B_p (248 q_p + 1)
 };
 int rice_geometry(const csic_params *p, RiceGeometry *G);

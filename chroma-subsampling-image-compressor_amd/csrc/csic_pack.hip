@@ -21,10 +21,12 @@
 // The plane's last group may be ragged: it is loaded and stored byte by byte up to the last byte that holds a sample, its slots
 // behind the last sample repeat the last code (pack) and are stored as zero bits (unpack).  Nothing is validated on the device: with
 // w <= q no payload offset leaves fixed_bytes + 4 sum G_p q_p <= bound_bytes, whatever the nibbles say.
-// Every global access goes through the accessors of csic_pack_common.h (shared with csic_rice.hip), which the CSIC_DEBUG build checks against frame_bytes, bound_bytes and the
-// workspace's entries.  CSIC_TUNE_NONTEMPORAL selects the accesses of the PLANAR_BITS frames; the block size is fixed.
+// Every global access goes through the accessors of csic_pack_common.h, which the CSIC_DEBUG build checks against frame_bytes,
+// bound_bytes and the workspace's entries.  CSIC_TUNE_NONTEMPORAL selects the accesses of the PLANAR_BITS frames; the block size is fixed.
+// csic_pack_common.h holds what csic_rice.hip does as well -- the group load, the store of a block's sections, the nibble and anchor reads,
+// the repacking and store of a decoded group, and the launch side's filler, refusals and per-width launches; this unit holds their
+// non-template bodies (pk_fill_args, pk_check_buffers, pack_scan_launch with k_pack_scan, pk_kernel_name).
 #include <cstdio>
-#include <cstring>
 
 #include "csic_pack_common.h"
 
@@ -51,26 +53,7 @@ __global__ void __launch_bounds__(PK_T) k_pack_widths(PkArgs e)
     uint32_t total;
     (void)pk_block_scan(w, s_tot, total);                                   // (its barriers also publish s_w and s_a)
     if (t == 0) *pk_ws(e, blockIdx.z, e.block0[plane] + blockIdx.x) = total;
-    if (t < 32u) {
-        // wave 0: dword t of the block's nibbles = groups g0 + 8 t .. + 7
-        if (g0 + 8u * t < G) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v |= s_w[8u * t + (uint32_t)k] << (4 * k);
-            pk_coded_st4(e, cb, (int64_t)e.woff[plane] + 4 * (int64_t)(g0 / 8u + t), v);
-        }
-    } else if (t >= 64u && t < 64u + 8u * Q) {
-        // wave 1: dword a of the block's anchors = bits [32 a, 32 a + 32) of 256 codes at Q bits
-        const uint32_t a = t - 64u, dw = blockIdx.x * (8u * Q) + a;
-        if (dw < e.adw[plane]) {
-            uint32_t v = 0;
-            for (uint32_t i = 32u * a / Q; i * Q < 32u * a + 32u; ++i) {    // (i < 256: the block's string is 256 Q bits)
-                const int sh = (int)(i * Q) - (int)(32u * a);
-                v |= sh >= 0 ? s_a[i] << sh : s_a[i] >> -sh;
-            }
-            pk_coded_st4(e, cb, (int64_t)e.aoff[plane] + 4 * (int64_t)dw, v);
-        }
-    }
+    pk_store_sections<Q>(e, cb, plane, G, g0, s_w, s_a);
 }
 
 // One block per frame (blockIdx.x): the frame's block totals -> their exclusive prefix sums, in place.
@@ -127,8 +110,7 @@ __global__ void __launch_bounds__(PK_T) k_pack_emit(PkArgs e)
 // the width of group g as the device takes it: never above q
 __device__ __forceinline__ uint32_t pk_width(const PkArgs &e, gpdst_t cb, int plane, uint32_t g)
 {
-    const uint32_t d = pk_coded_ld4(e, cb, (int64_t)e.woff[plane] + 4 * (int64_t)(g >> 3));
-    return min((d >> (4u * (g & 7u))) & 15u, (uint32_t)e.q[plane]);
+    return min(pk_nibble(e, cb, plane, g), (uint32_t)e.q[plane]);
 }
 
 __global__ void __launch_bounds__(PK_T) k_unpack_sums(PkArgs e)
@@ -156,19 +138,13 @@ __global__ void __launch_bounds__(PK_T) k_unpack_emit(PkArgs e)
     uint32_t total;
     const uint32_t before = pk_block_scan(w, s_tot, total);
     if (g >= G) return;
-    // the anchor: Q bits at [g Q, g Q + Q) of the anchors section (g Q < 2^29)
-    const uint32_t abit = g * Q, as = abit & 31u;
-    const int64_t aat = (int64_t)e.aoff[plane] + 4 * (int64_t)(abit >> 5);
-    uint32_t c = pk_coded_ld4(e, cb, aat) >> as;
-    if (as + Q > 32u) c |= pk_coded_ld4(e, cb, aat + 4) << (32u - as);     // (a straddling code has both dwords inside the section)
-    c &= MASK;
+    uint32_t c = pk_anchor<Q>(e, cb, plane, g);
     // 32 steps of the prefix, the payload dwords loaded as they are used up: 32 w bits = exactly w loads
     const uint32_t n = e.n[plane], wmask = (1u << w) - 1u;
     int64_t at = e.payload_offset + 4 * ((int64_t)*pk_ws(e, blockIdx.z, e.block0[plane] + blockIdx.x) + before);
     uint64_t acc = 0;
-    uint32_t have = 0, d[Q];
-#pragma unroll
-    for (int i = 0; i < Q; ++i) d[i] = 0;
+    uint32_t have = 0;
+    PkGroupOut<Q> out;
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
         if (have < w) {
@@ -179,91 +155,51 @@ __global__ void __launch_bounds__(PK_T) k_unpack_emit(PkArgs e)
         const uint32_t uu = (uint32_t)acc & wmask;
         acc >>= w;
         have -= w;
-        if (j > 0) c = (c + (((uu & 1u) ? ~(uu >> 1) : (uu >> 1)))) & MASK;
-        const uint32_t v = 32u * g + (uint32_t)j < n ? c : 0u;              // slots behind the last sample: zero bits
-        const int wi = (j * Q) >> 5, s = (j * Q) & 31;
-        d[wi] |= v << s;
-        if (s + Q > 32) d[(wi + 1) % Q] |= v >> ((32 - s) & 31);
+        if (j > 0) c = (c + rice_unfold(uu, MASK)) & MASK;
+        out.put(j, 32u * g + (uint32_t)j < n ? c : 0u);                     // slots behind the last sample: zero bits
     }
-    const gpdst_t fb = pk_bits_frame(e);
-    const int64_t base = e.off[plane] + 4 * (int64_t)g * Q;
-    if (32u * g + 32u <= n) {
-#pragma unroll
-        for (int i = 0; i < Q; ++i) pk_bits_st4<NT>(e, fb, base + 4 * i, d[i]);
-    } else {
-        const int64_t end = e.off[plane] + e.bytes[plane];
-#pragma unroll
-        for (int i = 0; i < Q; ++i)
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (base + 4 * i + k < end) pk_bits_st1(e, fb, base + 4 * i + k, (d[i] >> (8 * k)) & 0xFFu);
-    }
+    out.template store<NT>(e, pk_bits_frame(e), plane, g);
 }
 
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-using PkFn = void (*)(PkArgs);
-
-static int fill_pk_args(const csic_plan *pl, PkArgs *e)
+int pk_fill_args(const csic_plan *pl, const PackGeometry &G, const int64_t (&nibbles_offset)[3], const int64_t (&anchors_offset)[3],
+                 int64_t payload_offset, int64_t bound_bytes, const char *entry, PkArgs *e)
 {
-    std::memset(e, 0, sizeof *e);
-    PackGeometry G;
-    const int st = pack_geometry(&pl->p, &G);
-    if (st != CSIC_OK) return st;
-    if ((int64_t)pl->g.W * pl->g.H >= ((int64_t)1 << 31)) return set_error(CSIC_EINVAL_SIZE, "frame too large for csic_pack_device");
+    *e = PkArgs{};
+    if ((int64_t)pl->g.W * pl->g.H >= ((int64_t)1 << 31)) return set_error(CSIC_EINVAL_SIZE, "frame too large for %s", entry);
     e->frame_bytes = G.bits.frame_bytes;
-    e->bound_bytes = G.layout.bound_bytes;
-    e->payload_offset = G.layout.payload_offset;
-    uint32_t blocks = 0;
+    e->bound_bytes = bound_bytes;
+    e->payload_offset = payload_offset;
     for (int p = 0; p < 3; ++p) {
         e->off[p] = G.src_offset[p];
         e->bytes[p] = G.src_bytes[p];
         e->n[p] = (uint32_t)G.n[p];
         e->groups[p] = (uint32_t)G.layout.groups[p];
         e->q[p] = G.q[p];
-        e->woff[p] = (uint32_t)G.layout.widths_offset[p];
-        e->aoff[p] = (uint32_t)G.layout.anchors_offset[p];
+        e->woff[p] = (uint32_t)nibbles_offset[p];
+        e->aoff[p] = (uint32_t)anchors_offset[p];
         e->adw[p] = (uint32_t)((G.layout.groups[p] * G.q[p] + 31) / 32);
-        e->block0[p] = blocks;
-        blocks += (e->groups[p] + PK_T - 1) / PK_T;
+        e->block0[p] = (uint32_t)G.block0[p];
     }
-    e->nblocks = blocks;
+    e->nblocks = (uint32_t)G.nblocks;
     return CSIC_OK;
 }
 
-static PkFn pk_kernel(int which, int q, bool nt)       // 0 = k_pack_widths, 1 = k_pack_emit, 2 = k_unpack_emit
+static int fill_pk_args(const csic_plan *pl, PkArgs *e)
 {
-    return with_const<true, false>(nt, [&](auto n) -> PkFn {
-        constexpr bool NT = CSIC_CONST(n);
-        return with_const<1, 2, 3, 4, 5, 6, 7, 8>(q, [&](auto qq) -> PkFn {
-            constexpr int Q = CSIC_CONST(qq);
-            return which == 0 ? k_pack_widths<Q, NT> : which == 1 ? k_pack_emit<Q, NT> : k_unpack_emit<Q, NT>;
-        });
-    });
+    PackGeometry G;
+    const int st = pack_geometry(&pl->p, &G);
+    if (st != CSIC_OK) return st;
+    return pk_fill_args(pl, G, G.layout.widths_offset, G.layout.anchors_offset, G.layout.payload_offset, G.layout.bound_bytes, "csic_pack_device", e);
 }
 
-// one launch per run of planes of equal width
-static int pk_launch_planes(const csic_plan *plan, PkArgs &e, int which, int nframes, hipStream_t stream)
-{
-    for (int p0 = 0; p0 < 3;) {
-        int p1 = p0 + 1;
-        while (p1 < 3 && e.q[p1] == e.q[p0]) ++p1;
-        uint32_t gmax = 0;
-        for (int p = p0; p < p1; ++p) gmax = e.groups[p] > gmax ? e.groups[p] : gmax;
-        if (gmax > 0) {
-            e.plane0 = p0;
-            const PkFn fn = pk_kernel(which, e.q[p0], !plan->tune.no_nt);
-            void *params[1] = {&e};
-            HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3((gmax + PK_T - 1) / PK_T, (unsigned)(p1 - p0), (unsigned)nframes),
-                                    dim3(PK_T, 1, 1), params, 0, stream));
-        }
-        p0 = p1;
-    }
-    return CSIC_OK;
-}
+static const auto pack_widths = [](auto q, auto nt) { return k_pack_widths<CSIC_CONST(q), CSIC_CONST(nt)>; };
+static const auto pack_emit = [](auto q, auto nt) { return k_pack_emit<CSIC_CONST(q), CSIC_CONST(nt)>; };
+static const auto unpack_emit = [](auto q, auto nt) { return k_unpack_emit<CSIC_CONST(q), CSIC_CONST(nt)>; };
 
-static int pk_launch(PkFn fn, PkArgs &e, dim3 grid, hipStream_t stream)
+static int pk_launch(void (*fn)(PkArgs), PkArgs &e, dim3 grid, hipStream_t stream)
 {
     void *params[1] = {&e};
     HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), grid, dim3(PK_T, 1, 1), params, 0, stream));
@@ -272,23 +208,22 @@ static int pk_launch(PkFn fn, PkArgs &e, dim3 grid, hipStream_t stream)
 
 int pack_scan_launch(PkArgs &e, int nframes, hipStream_t stream) { return pk_launch(k_pack_scan, e, dim3((unsigned)nframes, 1, 1), stream); }
 
-// everything both directions refuse, before any device is touched
-static int pk_prepare(const csic_plan *plan, const void *d_bits, const void *d_coded, int32_t nframes, const void *d_workspace,
-                      size_t workspace_bytes, PkArgs *e)
+int pk_check_buffers(const csic_plan *plan, const void *d_bits, const void *d_coded, int32_t nframes, bool has_ws, const void *d_workspace)
 {
     if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
-    if (!d_bits || !d_coded || !d_workspace) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
+    if (!d_bits || !d_coded || (has_ws && !d_workspace)) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
     if (nframes < 1 || nframes > 65535) return set_error(CSIC_EINVAL_SIZE, "nframes must be 1..65535. Got %d", nframes);
     if (((uintptr_t)d_bits | (uintptr_t)d_coded) & 255u) return set_error(CSIC_EINVAL_SIZE, "PLANAR_BITS and coded frame buffers must be 256-byte aligned");
-    if ((uintptr_t)d_workspace & 7u) return set_error(CSIC_EINVAL_SIZE, "d_workspace must be 8-byte aligned");
-    const int st = fill_pk_args(plan, e);
-    if (st != CSIC_OK) return st;
-    const size_t need = ((size_t)nframes * e->nblocks * sizeof(uint32_t) + 7) / 8 * 8;
-    if (workspace_bytes < need) return set_error(CSIC_EINVAL_SIZE, "workspace of %zu bytes, %d frames need %zu", workspace_bytes, nframes, need);
-    e->bits = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_bits));
-    e->coded = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_coded));
-    e->ws = const_cast<uint32_t *>(static_cast<const uint32_t *>(d_workspace));
+    if (has_ws && ((uintptr_t)d_workspace & 7u)) return set_error(CSIC_EINVAL_SIZE, "d_workspace must be 8-byte aligned");
     return CSIC_OK;
+}
+
+const char *pk_kernel_name(const char *family, const csic_plan *plan)
+{
+    static thread_local char buf[64];
+    if (!plan) return "";
+    std::snprintf(buf, sizeof buf, "%s<q%d,%d,%d,%s>", family, plan->p.y_bits, plan->p.cb_bits, plan->p.cr_bits, plan->tune.no_nt ? "cached" : "nt");
+    return buf;
 }
 
 } // namespace csic
@@ -297,40 +232,24 @@ using namespace csic;
 
 extern "C" {
 
-const char *csic_pack_kernel_name(const csic_plan *plan)
-{
-    static thread_local char buf[64];
-    if (!plan) return "";
-    std::snprintf(buf, sizeof buf, "k_pack<q%d,%d,%d,%s>", plan->p.y_bits, plan->p.cb_bits, plan->p.cr_bits, plan->tune.no_nt ? "cached" : "nt");
-    return buf;
-}
+const char *csic_pack_kernel_name(const csic_plan *plan) { return pk_kernel_name("k_pack", plan); }
 
-int csic_pack_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes)
-{
-    if (!plan || !bytes) return set_error(CSIC_EINVAL_NULL, "plan or bytes is NULL");
-    if (nframes < 1 || nframes > 65535) return set_error(CSIC_EINVAL_SIZE, "nframes must be 1..65535. Got %d", nframes);
-    PkArgs e;
-    const int st = fill_pk_args(plan, &e);
-    if (st != CSIC_OK) return st;
-    *bytes = ((size_t)nframes * e.nblocks * sizeof(uint32_t) + 7) / 8 * 8;
-    clear_error();
-    return CSIC_OK;
-}
+int csic_pack_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes) { return pk_workspace_bytes(plan, nframes, bytes, fill_pk_args); }
 
 int csic_pack_device(csic_plan *plan, const void *d_bits, int32_t nframes, void *d_coded, uint64_t *d_sizes, void *d_workspace,
                      size_t workspace_bytes, void *hip_stream)
 {
     if (plan && !d_sizes) return set_error(CSIC_EINVAL_NULL, "d_sizes is NULL");
     PkArgs e;
-    int st = pk_prepare(plan, d_bits, d_coded, nframes, d_workspace, workspace_bytes, &e);
+    int st = pk_prepare(plan, d_bits, d_coded, nframes, true, d_workspace, workspace_bytes, fill_pk_args, &e);
     if (st != CSIC_OK) return st;
     if ((uintptr_t)d_sizes & 7u) return set_error(CSIC_EINVAL_SIZE, "d_sizes must be 8-byte aligned");
     e.sizes = reinterpret_cast<unsigned long long *>(d_sizes);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     CSIC_DEVICE_SCOPE(plan->device);
-    if ((st = pk_launch_planes(plan, e, 0, nframes, stream)) != CSIC_OK) return st;
+    if ((st = pk_launch_planes(plan, e, nframes, stream, pack_widths)) != CSIC_OK) return st;
     if ((st = pack_scan_launch(e, nframes, stream)) != CSIC_OK) return st;
-    if ((st = pk_launch_planes(plan, e, 1, nframes, stream)) != CSIC_OK) return st;
+    if ((st = pk_launch_planes(plan, e, nframes, stream, pack_emit)) != CSIC_OK) return st;
     clear_error();
     return CSIC_OK;
 }
@@ -339,7 +258,7 @@ int csic_unpack_device(csic_plan *plan, const void *d_coded, int32_t nframes, vo
                        void *hip_stream)
 {
     PkArgs e;
-    int st = pk_prepare(plan, d_bits, d_coded, nframes, d_workspace, workspace_bytes, &e);
+    int st = pk_prepare(plan, d_bits, d_coded, nframes, true, d_workspace, workspace_bytes, fill_pk_args, &e);
     if (st != CSIC_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     CSIC_DEVICE_SCOPE(plan->device);
@@ -347,7 +266,7 @@ int csic_unpack_device(csic_plan *plan, const void *d_coded, int32_t nframes, vo
     for (int p = 0; p < 3; ++p) gmax = e.groups[p] > gmax ? e.groups[p] : gmax;
     if ((st = pk_launch(k_unpack_sums, e, dim3((gmax + PK_T - 1) / PK_T, 3, (unsigned)nframes), stream)) != CSIC_OK) return st;
     if ((st = pack_scan_launch(e, nframes, stream)) != CSIC_OK) return st;
-    if ((st = pk_launch_planes(plan, e, 2, nframes, stream)) != CSIC_OK) return st;
+    if ((st = pk_launch_planes(plan, e, nframes, stream, unpack_emit)) != CSIC_OK) return st;
     clear_error();
     return CSIC_OK;
 }

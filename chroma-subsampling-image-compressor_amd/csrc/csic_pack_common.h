@@ -1,8 +1,13 @@
-// csic_pack_common.h -- what the device codecs of the group coding (csic_pack.hip) and of the Rice coding (csic_rice.hip) share: the kernels'
-// argument, the checked accessors of the PLANAR_BITS and the coded frames, the block scan, the load of a group with its folded residuals,
-// and the launch of the scan over a frame's block totals (k_pack_scan itself lives in csic_pack.hip).
+// csic_pack_common.h -- what the device codecs of the group coding (csic_pack.hip) and of the Rice coding (csic_rice.hip) share.
+// Device: the kernels' argument, the checked accessors of the PLANAR_BITS and the coded frames, the block scan, the load of a group with
+// its folded residuals, the store of a block's nibble and anchors sections, the reads of a group's nibble and anchor, and the
+// accumulator that a decoded group is repacked in and stored from (the unfold u -> e is rice_unfold of csic_rice_decode.h, shared with
+// the host codecs).  Host: the filler of the argument from pack_geometry and a coding's own offsets, the refusals and the workspace
+// size of the entry points, the launch of one kernel per run of planes of equal width, the launch of the scan over a frame's block
+// totals and the kernel-name formatter (their bodies, like k_pack_scan itself, live in csic_pack.hip).
 #pragma once
 #include "csic_kernel_ops.h"
+#include "csic_rice_decode.h"
 
 namespace csic {
 
@@ -10,6 +15,7 @@ typedef const uint8_t CSIC_GLOBAL *gpsrc_t;
 typedef uint8_t CSIC_GLOBAL *gpdst_t;
 
 constexpr int PK_T = 256, PK_WAVES = PK_T / 64;
+static_assert(PK_T == RICE_BLOCK, "a block of the kernels is a block of the format: pack_geometry numbers both");
 
 // the kernels' argument
 struct PkArgs {
@@ -149,8 +155,154 @@ __device__ __forceinline__ uint32_t pk_fold_group(const PkArgs &e, gpdst_t fb, i
     return any ? 32u - (uint32_t)__builtin_clz(any) : 0u;
 }
 
+// The block's nibbles and anchors (one per thread in LDS, 0 behind the plane's last group: the sections' padding, and published by a
+// barrier) -> the dwords of the plane's nibble and anchors sections.  A block's first group g0 is a multiple of 256: both strings start
+// on a dword.  Every thread of the block calls it.
+template <int Q>
+__device__ __forceinline__ void pk_store_sections(const PkArgs &e, gpdst_t cb, int plane, uint32_t G, uint32_t g0, const uint32_t *s_nib, const uint32_t *s_a)
+{
+    const uint32_t t = threadIdx.x;
+    if (t < 32u) {
+        // wave 0: dword t of the block's nibbles = groups g0 + 8 t .. + 7
+        if (g0 + 8u * t < G) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v |= s_nib[8u * t + (uint32_t)k] << (4 * k);
+            pk_coded_st4(e, cb, (int64_t)e.woff[plane] + 4 * (int64_t)(g0 / 8u + t), v);
+        }
+    } else if (t >= 64u && t < 64u + 8u * Q) {
+        // wave 1: dword a of the block's anchors = bits [32 a, 32 a + 32) of 256 codes at Q bits
+        const uint32_t a = t - 64u, dw = blockIdx.x * (8u * Q) + a;
+        if (dw < e.adw[plane]) {
+            uint32_t v = 0;
+            for (uint32_t i = 32u * a / Q; i * Q < 32u * a + 32u; ++i) {    // (i < 256: the block's string is 256 Q bits)
+                const int sh = (int)(i * Q) - (int)(32u * a);
+                v |= sh >= 0 ? s_a[i] << sh : s_a[i] >> -sh;
+            }
+            pk_coded_st4(e, cb, (int64_t)e.aoff[plane] + 4 * (int64_t)dw, v);
+        }
+    }
+}
+
+// the nibble of group g as the coded frame holds it
+__device__ __forceinline__ uint32_t pk_nibble(const PkArgs &e, gpdst_t cb, int plane, uint32_t g)
+{
+    return (pk_coded_ld4(e, cb, (int64_t)e.woff[plane] + 4 * (int64_t)(g >> 3)) >> (4u * (g & 7u))) & 15u;
+}
+
+// the anchor of group g: Q bits at [g Q, g Q + Q) of the anchors section (g Q < 2^29)
+template <int Q> __device__ __forceinline__ uint32_t pk_anchor(const PkArgs &e, gpdst_t cb, int plane, uint32_t g)
+{
+    const uint32_t abit = g * Q, as = abit & 31u;
+    const int64_t aat = (int64_t)e.aoff[plane] + 4 * (int64_t)(abit >> 5);
+    uint32_t c = pk_coded_ld4(e, cb, aat) >> as;
+    if (as + Q > 32u) c |= pk_coded_ld4(e, cb, aat + 4) << (32u - as);     // (a straddling code has both dwords inside the section)
+    return c & ((1u << Q) - 1u);
+}
+
+// The Q dwords of a decoded group in a lane's registers: slot j takes its code (j a constant of an unrolled loop: compile-time shifts),
+// store() writes group g of the plane -- whole dwords, or byte by byte up to the plane's last byte when the plane ends in this group.
+template <int Q> struct PkGroupOut {
+    uint32_t d[Q];
+    __device__ __forceinline__ PkGroupOut()
+    {
+#pragma unroll
+        for (int i = 0; i < Q; ++i) d[i] = 0;
+    }
+    __device__ __forceinline__ void put(int j, uint32_t v)
+    {
+        const int wi = (j * Q) >> 5, s = (j * Q) & 31;
+        d[wi] |= v << s;
+        if (s + Q > 32) d[(wi + 1) % Q] |= v >> ((32 - s) & 31);
+    }
+    template <bool NT> __device__ __forceinline__ void store(const PkArgs &e, gpdst_t fb, int plane, uint32_t g) const
+    {
+        const int64_t base = e.off[plane] + 4 * (int64_t)g * Q;
+        if (32u * g + 32u <= e.n[plane]) {
+#pragma unroll
+            for (int i = 0; i < Q; ++i) pk_bits_st4<NT>(e, fb, base + 4 * i, d[i]);
+        } else {
+            const int64_t end = e.off[plane] + e.bytes[plane];
+#pragma unroll
+            for (int i = 0; i < Q; ++i)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (base + 4 * i + k < end) pk_bits_st1(e, fb, base + 4 * i + k, (d[i] >> (8 * k)) & 0xFFu);
+        }
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+// The PkArgs of a coding from the group coding's geometry and the coding's own nibble and anchors offsets, payload_offset and
+// bound_bytes; everything else is zero.  `entry` names the pack entry point in the refusal of a frame of 2^31 pixels or more.
+int pk_fill_args(const csic_plan *pl, const PackGeometry &G, const int64_t (&nibbles_offset)[3], const int64_t (&anchors_offset)[3],
+                 int64_t payload_offset, int64_t bound_bytes, const char *entry, PkArgs *e);
+
+// the bytes of a workspace of one uint32 per block of `nframes` frames
+inline size_t pk_workspace_need(int32_t nframes, uint32_t nblocks) { return ((size_t)nframes * nblocks * sizeof(uint32_t) + 7) / 8 * 8; }
+
+// Below, Args is the argument struct of a coding's kernels: PkArgs, or a struct derived from it; fill(plan, &args) fills it from the
+// plan's parameters.
+// What the four device entry points refuse before any device is touched, then the arguments filled; `has_ws` is false for the one
+// entry point without a workspace.
+int pk_check_buffers(const csic_plan *plan, const void *d_bits, const void *d_coded, int32_t nframes, bool has_ws, const void *d_workspace);
+template <class Args>
+int pk_prepare(const csic_plan *plan, const void *d_bits, const void *d_coded, int32_t nframes, bool has_ws, const void *d_workspace,
+               size_t workspace_bytes, int (*fill)(const csic_plan *, Args *), Args *e)
+{
+    int st = pk_check_buffers(plan, d_bits, d_coded, nframes, has_ws, d_workspace);
+    if (st == CSIC_OK) st = fill(plan, e);
+    if (st != CSIC_OK) return st;
+    if (has_ws && workspace_bytes < pk_workspace_need(nframes, e->nblocks))
+        return set_error(CSIC_EINVAL_SIZE, "workspace of %zu bytes, %d frames need %zu", workspace_bytes, nframes, pk_workspace_need(nframes, e->nblocks));
+    e->bits = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_bits));
+    e->coded = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_coded));
+    e->ws = const_cast<uint32_t *>(static_cast<const uint32_t *>(d_workspace));
+    return CSIC_OK;
+}
+
+// *_workspace_bytes of both codings
+template <class Args> int pk_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes, int (*fill)(const csic_plan *, Args *))
+{
+    if (!plan || !bytes) return set_error(CSIC_EINVAL_NULL, "plan or bytes is NULL");
+    if (nframes < 1 || nframes > 65535) return set_error(CSIC_EINVAL_SIZE, "nframes must be 1..65535. Got %d", nframes);
+    Args e;
+    const int st = fill(plan, &e);
+    if (st != CSIC_OK) return st;
+    *bytes = pk_workspace_need(nframes, e.nblocks);
+    clear_error();
+    return CSIC_OK;
+}
+
+// One launch per run of planes of equal width; choose(Q, NT) maps the two constants to the kernel.
+template <class Args, class Choose> int pk_launch_planes(const csic_plan *plan, Args &e, int nframes, hipStream_t stream, Choose choose)
+{
+    for (int p0 = 0; p0 < 3;) {
+        int p1 = p0 + 1;
+        while (p1 < 3 && e.q[p1] == e.q[p0]) ++p1;
+        uint32_t gmax = 0;
+        for (int p = p0; p < p1; ++p) gmax = e.groups[p] > gmax ? e.groups[p] : gmax;
+        if (gmax > 0) {
+            e.plane0 = p0;
+            void (*const fn)(Args) = with_const<true, false>(!plan->tune.no_nt, [&](auto nt) {
+                return with_const<1, 2, 3, 4, 5, 6, 7, 8>(e.q[p0], [&](auto q) -> void (*)(Args) { return choose(q, nt); });
+            });
+            void *params[1] = {&e};
+            HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3((gmax + PK_T - 1) / PK_T, (unsigned)(p1 - p0), (unsigned)nframes),
+                                    dim3(PK_T, 1, 1), params, 0, stream));
+        }
+        p0 = p1;
+    }
+    return CSIC_OK;
+}
+
 // k_pack_scan on `nframes` frames: the workspace's block totals -> their exclusive prefix sums, e.sizes[frame] (when not NULL) =
 // e.payload_offset + 4 * the frame's total
 int pack_scan_launch(PkArgs &e, int nframes, hipStream_t stream);
+
+// "<family><q y,cb,cr,nt|cached>" in a thread-local buffer: csic_pack_kernel_name, csic_rice_kernel_name
+const char *pk_kernel_name(const char *family, const csic_plan *plan);
 
 } // namespace csic

@@ -1,16 +1,15 @@
 // csic_pack_host.cpp -- the host codec of the group coding (csic_pack_layout_of, csic_pack_host, csic_unpack_host; host only, no device).
 // The format -- groups of 32 samples, anchors, folded residuals, widths, the sections of a coded frame -- is stated in include/csic.h;
 // this file is that statement written out sample by sample, with every access to the coded bytes behind a length that was checked
-// first: csic_unpack_host and the container reader take bytes nobody vouches for.  The device codec (csic_pack.hip) shares the
-// geometry (pack_geometry) and nothing else.
+// first: csic_unpack_host and the container reader take bytes nobody vouches for.  pack_geometry is the one place that derives the
+// groups, the nibble and anchors sections and the numbering of the 256-group blocks: the Rice coding (rice_geometry) and both device
+// codecs read them from it.  The byte and bit accessors, the load of a group and the check of the sections are csic_group_host.h's,
+// shared with csic_rice_host.cpp.
 #include <cstring>
 
-#include "csic_internal.h"
+#include "csic_group_host.h"
 
 namespace csic {
-
-static uint32_t get_u32(const unsigned char *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-static void put_u32(unsigned char *p, uint32_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24); }
 
 int pack_geometry(const csic_params *p, PackGeometry *G)
 {
@@ -29,9 +28,12 @@ int pack_geometry(const csic_params *p, PackGeometry *G)
     G->src_bytes[0] = B.y_bytes; G->src_bytes[1] = B.cb_bytes; G->src_bytes[2] = B.cr_bytes;
     csic_pack_layout &L = G->layout;
     int64_t at = 0;
-    G->max_payload_dwords = 0;
+    G->max_payload_dwords = G->nblocks = 0;
     for (int pl = 0; pl < 3; ++pl) {
         L.groups[pl] = (G->n[pl] + 31) / 32;
+        G->blocks[pl] = (L.groups[pl] + RICE_BLOCK - 1) / RICE_BLOCK;
+        G->block0[pl] = G->nblocks;
+        G->nblocks += G->blocks[pl];
         L.widths_offset[pl] = at;
         at += 4 * ((L.groups[pl] + 7) / 8);
         G->max_payload_dwords += L.groups[pl] * G->q[pl];
@@ -45,41 +47,6 @@ int pack_geometry(const csic_params *p, PackGeometry *G)
     return CSIC_OK;
 }
 
-// the q bits at [i q, i q + q) of a plane of `bytes` bytes; a code that straddles two bytes has both inside the plane
-static inline uint32_t code_at(const unsigned char *plane, int64_t bytes, int64_t i, int q)
-{
-    const int64_t bit = i * q, b = bit >> 3;
-    uint32_t v = plane[b];
-    if (b + 1 < bytes) v |= (uint32_t)plane[b + 1] << 8;
-    return (v >> (bit & 7)) & ((1u << q) - 1u);
-}
-
-// ORs a value of at most 8 bits into a zeroed bit string at bit position `bit` (both bytes lie inside the string when touched)
-static inline void or_bits(unsigned char *dst, int64_t bit, uint32_t v)
-{
-    const uint32_t s = v << (bit & 7);
-    dst[bit >> 3] |= (unsigned char)s;
-    if (s >> 8) dst[(bit >> 3) + 1] |= (unsigned char)(s >> 8);
-}
-
-// the 32 folded residuals of a group of codes; returns w
-static inline int fold_group(const uint32_t c[32], int q, uint32_t u[32])
-{
-    const uint32_t mask = (1u << q) - 1u, half = 1u << (q - 1);
-    uint32_t any = 0;
-    u[0] = 0;
-    for (int j = 1; j < 32; ++j) {
-        const uint32_t e = (c[j] - c[j - 1]) & mask;
-        u[j] = e < half ? 2u * e : 2u * (mask + 1u - e) - 1u;
-        any |= u[j];
-    }
-    int w = 0;
-    while (any) { ++w; any >>= 1; }
-    return w;
-}
-
-static inline uint32_t unfold(uint32_t u, uint32_t mask) { return ((u & 1u) ? ~(u >> 1) : (u >> 1)) & mask; }   // u -> e
-
 // What csic_unpack_host checks before it decodes: the sizes, every nibble, every padding bit.  Reads coded[0, coded_bytes) only.
 int pack_check_coded(const PackGeometry &G, const unsigned char *coded, size_t coded_bytes)
 {
@@ -89,18 +56,9 @@ int pack_check_coded(const PackGeometry &G, const unsigned char *coded, size_t c
                          (long long)(L.fixed_bytes + 4 * G.max_payload_dwords), coded_bytes);
     int64_t dwords = 0;
     for (int pl = 0; pl < 3; ++pl) {
-        const unsigned char *wd = coded + L.widths_offset[pl];
-        const int64_t groups = L.groups[pl], slots = (groups + 7) / 8 * 8;
-        for (int64_t g = 0; g < slots; ++g) {
-            const int w = (wd[g >> 1] >> (4 * (g & 1))) & 15;
-            if (g >= groups ? w != 0 : w > G.q[pl])
-                return set_error(CSIC_EFORMAT, "coded frame: width %d of group %lld of plane %d (%d bits per code)", w, (long long)g, pl, G.q[pl]);
-            dwords += w;
-        }
-        const unsigned char *an = coded + L.anchors_offset[pl];
-        const int64_t used = groups * G.q[pl], room = (used + 31) / 32 * 32;
-        for (int64_t bit = used; bit < room; ++bit)
-            if ((an[bit >> 3] >> (bit & 7)) & 1) return set_error(CSIC_EFORMAT, "coded frame: the anchors of plane %d are not zero-padded", pl);
+        const int st = check_plane_sections(G, coded, pl, "coded frame", "width", [](int w, int q) { return w <= q; });
+        if (st != CSIC_OK) return st;
+        for (int64_t g = 0; g < L.groups[pl]; ++g) dwords += nibble_at(coded + L.widths_offset[pl], g);
     }
     if ((int64_t)coded_bytes != L.fixed_bytes + 4 * dwords)
         return set_error(CSIC_EFORMAT, "coded frame: the widths imply %lld bytes, not %zu", (long long)(L.fixed_bytes + 4 * dwords), coded_bytes);
@@ -115,18 +73,11 @@ int pack_frame(const PackGeometry &G, const unsigned char *frame, unsigned char 
     std::memset(coded, 0, (size_t)L.fixed_bytes);
     size_t pos = (size_t)L.payload_offset;            // where the next group's dwords go; keeps counting past `capacity`
     for (int pl = 0; pl < 3; ++pl) {
-        const unsigned char *src = frame + G.src_offset[pl];
-        const int q = G.q[pl];
-        const int64_t n = G.n[pl];
         for (int64_t g = 0; g < L.groups[pl]; ++g) {
             uint32_t c[32], u[32];
-            for (int j = 0; j < 32; ++j) {
-                const int64_t i = 32 * g + j;
-                c[j] = i < n ? code_at(src, G.src_bytes[pl], i, q) : c[j - 1];       // (i >= n only behind a real sample of this group)
-            }
-            const int w = fold_group(c, q, u);
+            const int w = load_group(G, frame, pl, g, c, u);
             coded[L.widths_offset[pl] + (g >> 1)] |= (unsigned char)(w << (4 * (g & 1)));
-            or_bits(coded + L.anchors_offset[pl], g * q, c[0]);
+            or_bits(coded + L.anchors_offset[pl], g * G.q[pl], c[0]);
             if (pos + 4 * (size_t)w <= capacity) {
                 uint64_t acc = 0;
                 int fill = 0, out = 0;
@@ -157,7 +108,7 @@ int unpack_frame(const PackGeometry &G, const unsigned char *coded, size_t coded
         const int64_t n = G.n[pl];
         std::memset(dst, 0, (size_t)G.src_bytes[pl]);
         for (int64_t g = 0; g < L.groups[pl]; ++g) {
-            const int w = (coded[L.widths_offset[pl] + (g >> 1)] >> (4 * (g & 1))) & 15;
+            const int w = nibble_at(coded + L.widths_offset[pl], g);
             uint32_t c = code_at(coded + L.anchors_offset[pl], (L.groups[pl] * q + 7) / 8, g, q);
             const unsigned char *pay = coded + pos;
             for (int j = 0; j < 32 && 32 * g + j < n; ++j) {
@@ -165,7 +116,7 @@ int unpack_frame(const PackGeometry &G, const unsigned char *coded, size_t coded
                     const int bit = j * w, sh = bit & 31;
                     uint32_t u = get_u32(pay + 4 * (bit >> 5)) >> sh;
                     if (sh + w > 32) u |= get_u32(pay + 4 * (bit >> 5) + 4) << (32 - sh);      // (the next dword is one of the group's w)
-                    c = (c + unfold(u & ((1u << w) - 1u), mask)) & mask;
+                    c = (c + rice_unfold(u & ((1u << w) - 1u), mask)) & mask;
                 }
                 or_bits(dst, (32 * g + j) * q, c);
             }
@@ -183,37 +134,21 @@ extern "C" {
 
 int csic_pack_layout_of(const csic_params *p, csic_pack_layout *layout)
 {
-    if (!p || !layout) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    PackGeometry G;
-    const int st = pack_geometry(p, &G);
-    if (st != CSIC_OK) return st;
-    *layout = G.layout;
-    clear_error();
-    return CSIC_OK;
+    return host_codec_call(!p || !layout, p, pack_geometry, "", [&](const PackGeometry &G) { *layout = G.layout; return (int)CSIC_OK; });
 }
 
 int csic_pack_host(const csic_params *p, const void *bits_frame, void *coded, size_t capacity, uint64_t *coded_bytes)
 {
-    if (!p || !bits_frame || !coded || !coded_bytes) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    PackGeometry G;
-    int st = pack_geometry(p, &G);
-    if (st != CSIC_OK) return st;
-    st = pack_frame(G, static_cast<const unsigned char *>(bits_frame), static_cast<unsigned char *>(coded), capacity, coded_bytes);
-    if (st != CSIC_OK) return st;
-    clear_error();
-    return CSIC_OK;
+    return host_codec_call(!p || !bits_frame || !coded || !coded_bytes, p, pack_geometry, "out of host memory coding a frame", [&](const PackGeometry &G) {
+        return pack_frame(G, static_cast<const unsigned char *>(bits_frame), static_cast<unsigned char *>(coded), capacity, coded_bytes);
+    });
 }
 
 int csic_unpack_host(const csic_params *p, const void *coded, size_t coded_bytes, void *bits_frame)
 {
-    if (!p || !coded || !bits_frame) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    PackGeometry G;
-    int st = pack_geometry(p, &G);
-    if (st != CSIC_OK) return st;
-    st = unpack_frame(G, static_cast<const unsigned char *>(coded), coded_bytes, static_cast<unsigned char *>(bits_frame));
-    if (st != CSIC_OK) return st;
-    clear_error();
-    return CSIC_OK;
+    return host_codec_call(!p || !coded || !bits_frame, p, pack_geometry, "out of host memory decoding a frame", [&](const PackGeometry &G) {
+        return unpack_frame(G, static_cast<const unsigned char *>(coded), coded_bytes, static_cast<unsigned char *>(bits_frame));
+    });
 }
 
 } // extern "C"

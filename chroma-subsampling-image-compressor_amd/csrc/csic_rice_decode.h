@@ -3,7 +3,8 @@
 // dwords, __host__ __device__: k_rice_unpack (csic_rice.hip) runs it on a chunk in LDS, csic_rice_unpack_host on the bytes of a coded
 // frame, tests/cpp/rice_fuzz.cpp on exactly-sized heap blocks of random bytes under the sanitizers.  Nothing here trusts the bits: every
 // word index is compared with nwords first (a word behind the segment reads as 0), a unary run ends at `uend` at the latest, and every
-// loop is bounded by the segment's length.
+// loop is bounded by the segment's length.  rice_unfold, the inverse of the fold of a residual, is the one definition for both codings:
+// the group coding's codecs (csic_pack.hip, csic_pack_host.cpp) call it as well.
 #pragma once
 #include <cstdint>
 
@@ -92,6 +93,7 @@ CSIC_RICE_HD uint32_t rice_next_u(const uint32_t *seg, uint32_t nwords, uint32_t
     return u & ((1u << q) - 1u);
 }
 
+// a folded residual u -> e, the difference to the code before, modulo mask + 1
 CSIC_RICE_HD uint32_t rice_unfold(uint32_t u, uint32_t mask) { return ((u & 1u) ? ~(u >> 1) : (u >> 1)) & mask; }
 
 } // namespace csic

@@ -1,68 +1,37 @@
 // csic_rice_host.cpp -- the host codec of the Rice coding (csic_rice_layout_of, csic_rice_pack_host, csic_rice_unpack_host; host only, no
 // device).  The format -- modes, blocks, the directory, a chunk's R and U -- is stated in include/csic.h next to the group coding, whose
-// groups, anchors and folded residuals it shares (pack_geometry of csic_pack_host.cpp).  csic_rice_unpack_host and the container reader
-// take bytes nobody vouches for: rice_check_coded proves every length before anything is decoded, and the bit reads themselves are
-// those of csic_rice_decode.h, which the device codec (csic_rice.hip) runs as well.
+// groups, anchors, folded residuals, nibble and anchors sections and block numbering it takes from pack_geometry (csic_pack_host.cpp),
+// and whose byte accessors, group load and section check it shares through csic_group_host.h.  csic_rice_unpack_host and the
+// container reader take bytes nobody vouches for: rice_check_coded proves every length before anything is decoded, and the bit reads
+// themselves are those of csic_rice_decode.h, which the device codec (csic_rice.hip) runs as well.
 #include <cstring>
-#include <new>
 #include <vector>
 
-#include "csic_internal.h"
-#include "csic_rice_decode.h"
+#include "csic_group_host.h"
 
 namespace csic {
-
-static uint32_t get_u32(const unsigned char *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-static void put_u32(unsigned char *p, uint32_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24); }
 
 int rice_geometry(const csic_params *p, RiceGeometry *G)
 {
     if (!p || !G) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
     const int st = pack_geometry(p, &G->pk);
     if (st != CSIC_OK) return st;
+    const PackGeometry &P = G->pk;
     csic_rice_layout &L = G->layout;
-    int64_t at = 0;
-    G->nblocks = 0;
     G->max_payload_dwords = 0;
     for (int pl = 0; pl < 3; ++pl) {
-        L.groups[pl] = (G->pk.n[pl] + 31) / 32;
-        L.blocks[pl] = (L.groups[pl] + RICE_BLOCK - 1) / RICE_BLOCK;
-        G->block0[pl] = G->nblocks;
-        G->nblocks += L.blocks[pl];
-        G->max_payload_dwords += L.blocks[pl] * rice_chunk_cap(G->pk.q[pl]);
-        L.modes_offset[pl] = at;
-        at += 4 * ((L.groups[pl] + 7) / 8);
+        L.groups[pl] = P.layout.groups[pl];
+        L.blocks[pl] = P.blocks[pl];
+        L.modes_offset[pl] = P.layout.widths_offset[pl];
+        L.anchors_offset[pl] = P.layout.anchors_offset[pl];
+        G->max_payload_dwords += P.blocks[pl] * rice_chunk_cap(P.q[pl]);
     }
-    for (int pl = 0; pl < 3; ++pl) {
-        L.anchors_offset[pl] = at;
-        at += 4 * ((L.groups[pl] * G->pk.q[pl] + 31) / 32);
-    }
-    L.directory_offset = at;
-    at += 4 * (G->nblocks + 1);
-    L.payload_offset = L.fixed_bytes = at;
-    L.bound_bytes = (at + 4 * G->max_payload_dwords + 255) / 256 * 256;
+    L.directory_offset = P.layout.fixed_bytes;       // behind the anchors
+    L.payload_offset = L.fixed_bytes = L.directory_offset + 4 * (P.nblocks + 1);
+    L.bound_bytes = (L.fixed_bytes + 4 * G->max_payload_dwords + 255) / 256 * 256;
     if (G->max_payload_dwords >= ((int64_t)1 << 32)) return set_error(CSIC_EINVAL_SIZE, "frame too large for the Rice coding's directory");
     return CSIC_OK;
 }
-
-// the q bits at [i q, i q + q) of a plane of `bytes` bytes; a code that straddles two bytes has both inside the plane
-static inline uint32_t code_at(const unsigned char *plane, int64_t bytes, int64_t i, int q)
-{
-    const int64_t bit = i * q, b = bit >> 3;
-    uint32_t v = plane[b];
-    if (b + 1 < bytes) v |= (uint32_t)plane[b + 1] << 8;
-    return (v >> (bit & 7)) & ((1u << q) - 1u);
-}
-
-// ORs a value of at most 8 bits into a zeroed bit string at bit position `bit` (both bytes lie inside the string when touched)
-static inline void or_bits(unsigned char *dst, int64_t bit, uint32_t v)
-{
-    const uint32_t s = v << (bit & 7);
-    dst[bit >> 3] |= (unsigned char)s;
-    if (s >> 8) dst[(bit >> 3) + 1] |= (unsigned char)(s >> 8);
-}
-
-static inline int mode_at(const unsigned char *modes, int64_t g) { return (modes[g >> 1] >> (4 * (g & 1))) & 15; }
 
 // a growing string of bits, LSB first in dwords
 struct BitString {
@@ -84,12 +53,10 @@ struct BitString {
     }
 };
 
-// the mode of a group with these folded residuals: 15, or the cheapest k = 0 .. q (q: raw), the smallest on a tie
-static int choose_mode(const uint32_t u[32], int q)
+// the mode of a group with these folded residuals of w significant bits: 15, or the cheapest k = 0 .. q (q: raw), the smallest on a tie
+static int choose_mode(const uint32_t u[32], int w, int q)
 {
-    uint32_t any = 0;
-    for (int j = 1; j < 32; ++j) any |= u[j];
-    if (!any) return 15;
+    if (w == 0) return 15;
     int best = q;
     uint32_t cost = 31u * (uint32_t)q;
     for (int k = q - 1; k >= 0; --k) {
@@ -110,25 +77,14 @@ int rice_pack_frame(const RiceGeometry &G, const unsigned char *frame, unsigned 
     size_t pos = (size_t)L.payload_offset;            // where the next chunk goes; keeps counting past `capacity`
     BitString R, U;
     for (int pl = 0; pl < 3; ++pl) {
-        const unsigned char *src = frame + G.pk.src_offset[pl];
         const int q = G.pk.q[pl];
-        const int64_t n = G.pk.n[pl];
-        const uint32_t half = 1u << (q - 1), mask = (1u << q) - 1u;
         for (int64_t b = 0; b < L.blocks[pl]; ++b) {
             R.clear(); U.clear();
             const int64_t g1 = (b + 1) * RICE_BLOCK < L.groups[pl] ? (b + 1) * RICE_BLOCK : L.groups[pl];
             for (int64_t g = b * RICE_BLOCK; g < g1; ++g) {
                 uint32_t c[32], u[32];
-                for (int j = 0; j < 32; ++j) {
-                    const int64_t i = 32 * g + j;
-                    c[j] = i < n ? code_at(src, G.pk.src_bytes[pl], i, q) : c[j - 1];       // (i >= n only behind a real sample of this group)
-                }
-                u[0] = 0;
-                for (int j = 1; j < 32; ++j) {
-                    const uint32_t e = (c[j] - c[j - 1]) & mask;
-                    u[j] = e < half ? 2u * e : 2u * (mask + 1u - e) - 1u;
-                }
-                const int m = choose_mode(u, q);
+                const int w = load_group(G.pk, frame, pl, g, c, u);
+                const int m = choose_mode(u, w, q);
                 coded[L.modes_offset[pl] + (g >> 1)] |= (unsigned char)(m << (4 * (g & 1)));
                 or_bits(coded + L.anchors_offset[pl], g * q, c[0]);
                 if (m == 15) continue;
@@ -137,7 +93,7 @@ int rice_pack_frame(const RiceGeometry &G, const unsigned char *frame, unsigned 
                     if (m < q) U.unary(u[j] >> m);
                 }
             }
-            put_u32(dir + 4 * (G.block0[pl] + b), (uint32_t)((pos - (size_t)L.payload_offset) / 4));
+            put_u32(dir + 4 * (G.pk.block0[pl] + b), (uint32_t)((pos - (size_t)L.payload_offset) / 4));
             const size_t bytes = 4 * (R.w.size() + U.w.size());
             if (pos + bytes <= capacity) {
                 unsigned char *d = coded + pos;
@@ -147,7 +103,7 @@ int rice_pack_frame(const RiceGeometry &G, const unsigned char *frame, unsigned 
             pos += bytes;
         }
     }
-    put_u32(dir + 4 * G.nblocks, (uint32_t)((pos - (size_t)L.payload_offset) / 4));
+    put_u32(dir + 4 * G.pk.nblocks, (uint32_t)((pos - (size_t)L.payload_offset) / 4));
     *coded_bytes = pos;
     if (pos > capacity) return set_error(CSIC_EINVAL_SIZE, "this frame codes to %zu bytes, got room for %zu", pos, capacity);
     return CSIC_OK;
@@ -163,30 +119,23 @@ int rice_check_coded(const RiceGeometry &G, const unsigned char *coded, size_t c
                          (long long)(L.fixed_bytes + 4 * G.max_payload_dwords), coded_bytes);
     const unsigned char *dir = coded + L.directory_offset;
     const uint64_t total = (coded_bytes - (size_t)L.fixed_bytes) / 4;
-    if (get_u32(dir) != 0 || get_u32(dir + 4 * G.nblocks) != total)
+    if (get_u32(dir) != 0 || get_u32(dir + 4 * G.pk.nblocks) != total)
         return set_error(CSIC_EFORMAT, "Rice-coded frame: the directory runs from %u to %u dwords, the frame's size says 0 to %llu", get_u32(dir),
-                         get_u32(dir + 4 * G.nblocks), (unsigned long long)total);
+                         get_u32(dir + 4 * G.pk.nblocks), (unsigned long long)total);
     std::vector<uint32_t> w;
     for (int pl = 0; pl < 3; ++pl) {
         const unsigned char *md = coded + L.modes_offset[pl];
         const int q = G.pk.q[pl];
-        const int64_t groups = L.groups[pl], slots = (groups + 7) / 8 * 8;
-        for (int64_t g = 0; g < slots; ++g) {
-            const int m = mode_at(md, g);
-            if (g >= groups ? m != 0 : (m > q && m != 15))
-                return set_error(CSIC_EFORMAT, "Rice-coded frame: mode %d of group %lld of plane %d (%d bits per code)", m, (long long)g, pl, q);
-        }
-        const unsigned char *an = coded + L.anchors_offset[pl];
-        const int64_t used = groups * q, room = (used + 31) / 32 * 32;
-        for (int64_t bit = used; bit < room; ++bit)
-            if ((an[bit >> 3] >> (bit & 7)) & 1) return set_error(CSIC_EFORMAT, "Rice-coded frame: the anchors of plane %d are not zero-padded", pl);
+        const int64_t groups = L.groups[pl];
+        const int st = check_plane_sections(G.pk, coded, pl, "Rice-coded frame", "mode", [](int m, int qq) { return m <= qq || m == 15; });
+        if (st != CSIC_OK) return st;
         for (int64_t b = 0; b < L.blocks[pl]; ++b) {
-            const int64_t blk = G.block0[pl] + b;
+            const int64_t blk = G.pk.block0[pl] + b;
             const uint64_t d0 = get_u32(dir + 4 * blk), d1 = get_u32(dir + 4 * (blk + 1));
             const int64_t g0 = b * RICE_BLOCK, g1 = g0 + RICE_BLOCK < groups ? g0 + RICE_BLOCK : groups;
             int64_t rbits = 0, z = 0;
             for (int64_t g = g0; g < g1; ++g) {
-                const int m = mode_at(md, g);
+                const int m = nibble_at(md, g);
                 if (m != 15) { rbits += 31 * m; z += m < q; }
             }
             const uint64_t rdw = (uint64_t)((rbits + 31) / 32);
@@ -206,7 +155,7 @@ int rice_check_coded(const RiceGeometry &G, const unsigned char *coded, size_t c
                                  (long long)b, pl, (long long)ones, udw, (long long)z, (long long)(31 * z));
             uint32_t ubit = 32u * (uint32_t)rdw;
             for (int64_t g = g0; g < g1; ++g) {
-                const int m = mode_at(md, g);
+                const int m = nibble_at(md, g);
                 if (m >= q) continue;                  // zero and raw groups have no unary part
                 for (int j = 1; j < 32; ++j) {
                     bool terminated;
@@ -236,16 +185,16 @@ int rice_unpack_frame(const RiceGeometry &G, const unsigned char *coded, size_t 
         const int64_t n = G.pk.n[pl], groups = L.groups[pl];
         std::memset(dst, 0, (size_t)G.pk.src_bytes[pl]);
         for (int64_t b = 0; b < L.blocks[pl]; ++b) {
-            const uint64_t d0 = get_u32(dir + 4 * (G.block0[pl] + b)), d1 = get_u32(dir + 4 * (G.block0[pl] + b + 1));
+            const uint64_t d0 = get_u32(dir + 4 * (G.pk.block0[pl] + b)), d1 = get_u32(dir + 4 * (G.pk.block0[pl] + b + 1));
             const int64_t g0 = b * RICE_BLOCK, g1 = g0 + RICE_BLOCK < groups ? g0 + RICE_BLOCK : groups;
             const uint32_t nw = (uint32_t)(d1 - d0);
             w.resize(nw);
             for (uint32_t i = 0; i < nw; ++i) w[i] = get_u32(coded + L.payload_offset + 4 * (d0 + i));
             int64_t rtot = 0;
-            for (int64_t g = g0; g < g1; ++g) rtot += mode_at(md, g) == 15 ? 0 : 31 * mode_at(md, g);
+            for (int64_t g = g0; g < g1; ++g) rtot += nibble_at(md, g) == 15 ? 0 : 31 * nibble_at(md, g);
             uint32_t rbit = 0, ubit = 32u * (uint32_t)((rtot + 31) / 32);        // both step through the chunk group by group
             for (int64_t g = g0; g < g1; ++g) {
-                const int m = mode_at(md, g);
+                const int m = nibble_at(md, g);
                 uint32_t c = code_at(coded + L.anchors_offset[pl], (groups * q + 7) / 8, g, q);
                 for (int j = 0; j < 32 && 32 * g + j < n; ++j) {
                     if (j > 0 && m != 15) c = (c + rice_unfold(rice_next_u(w.data(), nw, &rbit, &ubit, 32u * nw, (uint32_t)m, (uint32_t)q), mask)) & mask;
@@ -266,45 +215,21 @@ extern "C" {
 
 int csic_rice_layout_of(const csic_params *p, csic_rice_layout *layout)
 {
-    if (!p || !layout) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    RiceGeometry G;
-    const int st = rice_geometry(p, &G);
-    if (st != CSIC_OK) return st;
-    *layout = G.layout;
-    clear_error();
-    return CSIC_OK;
+    return host_codec_call(!p || !layout, p, rice_geometry, "", [&](const RiceGeometry &G) { *layout = G.layout; return (int)CSIC_OK; });
 }
 
 int csic_rice_pack_host(const csic_params *p, const void *bits_frame, void *coded, size_t capacity, uint64_t *coded_bytes)
 {
-    if (!p || !bits_frame || !coded || !coded_bytes) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    RiceGeometry G;
-    int st = rice_geometry(p, &G);
-    if (st != CSIC_OK) return st;
-    try {
-        st = rice_pack_frame(G, static_cast<const unsigned char *>(bits_frame), static_cast<unsigned char *>(coded), capacity, coded_bytes);
-    } catch (const std::bad_alloc &) {
-        return set_error(CSIC_ENOMEM, "out of host memory coding a frame");
-    }
-    if (st != CSIC_OK) return st;
-    clear_error();
-    return CSIC_OK;
+    return host_codec_call(!p || !bits_frame || !coded || !coded_bytes, p, rice_geometry, "out of host memory coding a frame", [&](const RiceGeometry &G) {
+        return rice_pack_frame(G, static_cast<const unsigned char *>(bits_frame), static_cast<unsigned char *>(coded), capacity, coded_bytes);
+    });
 }
 
 int csic_rice_unpack_host(const csic_params *p, const void *coded, size_t coded_bytes, void *bits_frame)
 {
-    if (!p || !coded || !bits_frame) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    RiceGeometry G;
-    int st = rice_geometry(p, &G);
-    if (st != CSIC_OK) return st;
-    try {
-        st = rice_unpack_frame(G, static_cast<const unsigned char *>(coded), coded_bytes, static_cast<unsigned char *>(bits_frame));
-    } catch (const std::bad_alloc &) {
-        return set_error(CSIC_ENOMEM, "out of host memory decoding a frame");
-    }
-    if (st != CSIC_OK) return st;
-    clear_error();
-    return CSIC_OK;
+    return host_codec_call(!p || !coded || !bits_frame, p, rice_geometry, "out of host memory decoding a frame", [&](const RiceGeometry &G) {
+        return rice_unpack_frame(G, static_cast<const unsigned char *>(coded), coded_bytes, static_cast<unsigned char *>(bits_frame));
+    });
 }
 
 } // extern "C"

@@ -179,6 +179,27 @@ def test_device_and_host_codecs_read_each_other(csic, oracle):
         assert np.array_equal(back.cpu().numpy()[0], src)
 
 
+@pytest.mark.parametrize("bits", [(6, 5, 5), (1, 7, 4)])
+@pytest.mark.parametrize("W", [33, 8224])
+def test_both_device_codecs_store_the_same_anchors(csic, W, bits):
+    """One random frame through both device codecs, which store a block's nibble and anchors sections with the same code: the nibble
+    sections have the same extents, the anchors sections are the same bytes, and each coded frame is its host codec's."""
+    import torch
+    frame = np.random.default_rng(12650 + W + bits[0]).integers(0, 1 << 32, W, dtype=np.uint32)
+    with _plan(csic, W, 1, 4, 4, bits) as pl:
+        buf = _source(pl, frame)
+        g, gs = pl.pack_device(buf, 1, _filled((1, pl.pack_layout.bound_bytes)))
+        r, rs = pl.rice_pack_device(buf, 1, _filled((1, pl.rice_layout.bound_bytes)))
+        torch.cuda.synchronize()
+        src = buf.cpu().numpy()[0]
+        g, r = g.cpu().numpy()[0, :int(gs[0])], r.cpu().numpy()[0, :int(rs[0])]
+        pk, rl = pl.pack_layout, pl.rice_layout
+        assert list(pk.widths_offset) + [pk.anchors_offset[0]] == list(rl.modes_offset) + [rl.anchors_offset[0]]
+        assert list(pk.anchors_offset) + [pk.fixed_bytes] == list(rl.anchors_offset) + [rl.directory_offset]
+        assert g[pk.anchors_offset[0]:pk.fixed_bytes].tobytes() == r[rl.anchors_offset[0]:rl.directory_offset].tobytes()
+        assert np.array_equal(g, pl.pack(src)) and np.array_equal(r, pl.rice_pack(src))
+
+
 def test_container_from_device_output_is_the_host_writers_file(csic, oracle, tmp_path):
     import torch
     W, H, bits = 96, 50, (6, 5, 5)

@@ -9,7 +9,7 @@ import pytest
 
 from conftest import GOLDEN, load_png_rgb
 from test_container import CANARY, CSQ, _c_params, _frame_buffer, _layout, _random_sets, pack_codes
-from test_pack_host import codes_of, lib_pack, plane_bytes, ref_groups
+from test_pack_host import codes_of, lib_layout, lib_pack, plane_bytes, ref_groups
 
 import csic_amd as csic
 
@@ -196,6 +196,43 @@ def check_frame(cp, planes, bits, decode=True):
     if decode:
         assert [c.tolist() for c in ref_decode_rice(want, [c.size for c in planes], bits)] == [c.tolist() for c in planes]
     return size
+
+
+# ---- what the two codings share --------------------------------------------------------------------------
+def _nibbles(coded, offset, groups):
+    b = coded[offset:offset + (groups + 1) // 2]
+    return np.stack([b & 15, b >> 4], axis=1).reshape(-1)[:groups]
+
+
+@pytest.mark.parametrize("bits", [(8, 8, 8), (6, 5, 5), (1, 7, 4)])
+@pytest.mark.parametrize("W,H,a,b", [(1, 1, 4, 4), (33, 1, 4, 4), (8224, 1, 4, 4), (13, 9, 2, 0), (30, 34, 2, 0)])
+def test_the_two_codings_share_groups_sections_and_anchors(W, H, a, b, bits):
+    """The Rice coding takes its groups, nibble and anchors sections and blocks from the group coding's geometry: the two layouts agree
+    on them, the anchors sections of the two coded frames of one frame are the same bytes, and a group has width 0 exactly when it
+    has mode 15."""
+    cp = _c_params(W, H, a, b, bits, 1, CSQ)
+    pk, rl = lib_layout(cp), rice_layout(cp)
+    assert list(rl.groups) == list(pk.groups) and list(rl.modes_offset) == list(pk.widths_offset)
+    assert list(rl.anchors_offset) == list(pk.anchors_offset) and rl.directory_offset == pk.fixed_bytes
+    assert rl.fixed_bytes == pk.fixed_bytes + 4 * (sum(rl.blocks) + 1)
+    frame = np.random.default_rng(W * 1000 + H * 10 + bits[0]).integers(0, 256, _layout(cp).frame_bytes, dtype=np.uint8)
+    st, g, gsize = lib_pack(cp, frame)
+    st2, r, rsize = rice_pack(cp, frame)
+    assert st == N.OK and st2 == N.OK
+    a0 = pk.anchors_offset[0]
+    assert g[a0:pk.fixed_bytes].tobytes() == r[a0:rl.directory_offset].tobytes()
+    for p in range(3):
+        w, m = _nibbles(g, pk.widths_offset[p], pk.groups[p]), _nibbles(r, rl.modes_offset[p], rl.groups[p])
+        assert np.array_equal(w == 0, m == 15), (p, w.tolist(), m.tolist())
+
+
+def test_both_codings_refuse_empty_input():
+    cp = _c_params(33, 1, 4, 4, (6, 5, 5), 1, CSQ)
+    for unpack in (csic.unpack_frame_host, csic.rice_unpack_host):
+        with pytest.raises(csic.CsicIOError):
+            unpack(cp, b"")
+        with pytest.raises(csic.CsicIOError):
+            unpack(cp, np.zeros(0, dtype=np.uint8))
 
 
 # ---- the worked vector ---------------------------------------------------------------------------------
