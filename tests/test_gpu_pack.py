@@ -2,7 +2,10 @@
 the format (tests/test_pack_host.py) on the oracle's planes, nothing written behind a frame's coded_bytes or outside the payload
 ranges of a PLANAR_BITS frame; the smallest shapes that can go wrong, the block edge, a frame with more blocks than the scan has
 threads, batches, graph capture, the host codec in both directions, the container and the CLI.  Source frames come from the library's
-own PLANAR_BITS output into a buffer pre-filled with 0xEE, as are all destinations.  Run with `-m gpu` on an MI355X."""
+own PLANAR_BITS output into a buffer pre-filled with 0xEE, as are all destinations.  Planes built to order instead -- every width
+w = 0 .. q of every q as the Y and as a chroma plane, whole blocks of one width and shuffled ones, all-zero blocks between full ones
+(k_pack_emit, k_unpack_emit, pk_store_sections), groups stored wider than necessary into k_unpack_emit, and the cached instantiations
+k_pack<.., cached> -- are uploaded by tests/test_gpu_codec_planes.py, which shares _compare below.  Run with `-m gpu` on an MI355X."""
 import ctypes as C
 import os
 
@@ -53,6 +56,19 @@ def _roundtrip(pl, buf, nframes=1):
     return coded.cpu().numpy(), sizes.cpu().numpy(), back.cpu().numpy().reshape(nframes, -1)
 
 
+def _compare(tag, lay, bits, planes, src, coded, sizes, back, bound, wants):
+    """The comparison of both device codecs' tests (this module's, test_gpu_rice.py's and test_gpu_codec_planes.py's): frame k's source
+    buffer src[k] holds planes[k] and 0xEE elsewhere, its coded row, size and the unpacked frame are the reference's, wants[k]."""
+    for k, want in enumerate(wants):
+        # the source itself: the planes in the payload ranges, 0xEE elsewhere
+        assert np.array_equal(src[k], _frame_buffer(lay, [plane_bytes(c, q) for c, q in zip(planes[k], bits)], EE)), tag
+        assert int(sizes[k]) == len(want), (tag, k, int(sizes[k]), len(want))
+        assert coded[k, :len(want)].tobytes() == want, (tag, k)
+        assert np.all(coded[k, len(want):] == EE), (tag, k)                # nothing behind coded_bytes, up to the next frame
+        assert len(want) <= bound
+    assert len(wants) == len(src) and np.array_equal(back, src), tag        # payload ranges restored, 0xEE everywhere else
+
+
 def _check(csic, oracle, frames, W, H, a, b, bits, f=1, op=CSQ, rounding=0, avg=False):
     """`frames` (nframes, W * H) through the device codec against numpy.  Returns (the planes' codes per frame, the coded sizes)."""
     frames = np.ascontiguousarray(frames, dtype=np.uint32).reshape(-1, W * H)
@@ -64,15 +80,7 @@ def _check(csic, oracle, frames, W, H, a, b, bits, f=1, op=CSQ, rounding=0, avg=
         coded, sizes, back = _roundtrip(pl, buf, nframes)
         src = buf.cpu().numpy()
         planes = [codes_of(oracle, W, H, a, b, bits, f, op, rounding, avg, fr) for fr in frames]
-        for k in range(nframes):
-            # the source itself: the oracle's planes in the payload ranges, 0xEE elsewhere
-            assert np.array_equal(src[k], _frame_buffer(lay, [plane_bytes(c, q) for c, q in zip(planes[k], bits)], EE)), tag
-            want = ref_encode(planes[k], bits)
-            assert int(sizes[k]) == len(want), (tag, k, int(sizes[k]), len(want))
-            assert coded[k, :len(want)].tobytes() == want, (tag, k)
-            assert np.all(coded[k, len(want):] == EE), (tag, k)            # nothing behind coded_bytes, up to the next frame
-            assert len(want) <= bound
-        assert np.array_equal(back, src), tag                               # payload ranges restored, 0xEE everywhere else
+        _compare(tag, lay, bits, planes, src, coded, sizes, back, bound, [ref_encode(p, bits) for p in planes])
     return planes, sizes
 
 

@@ -2,8 +2,15 @@
 statement of the format (tests/test_rice_host.py) on the oracle's planes, nothing written behind a frame's coded_bytes or outside the
 payload ranges of a PLANAR_BITS frame, unpack restores the source; the shapes of tests/test_gpu_pack.py, a block in which zero, raw and
 Rice groups interleave, a frame with more blocks than the scan has threads, batches, graph capture, the host codec in both directions,
-the container and the CLI.  Sources and destinations are pre-filled with 0xEE.  No invalid stream is fed to the device (the clamping is
-shown on the host: tests/test_cpp_rice.py).  Run with `-m gpu` on an MI355X."""
+the container and the CLI; random parameter sets (AVG sampling, rounding, f = 8, the six stage orders) on three kinds of content.
+Sources and destinations are pre-filled with 0xEE.  No invalid stream is fed to the device (the clamping is shown on the host:
+tests/test_cpp_rice.py).  Every source here is process_device's output, so which modes and runs the kernels meet follows from the colour
+transform and the quantiser; tests/test_gpu_codec_planes.py uploads planes built to order instead, and is where to look for: every
+(q, mode) pair in whole blocks and shuffled, with three different widths per frame (test_runs_and_shuffled_frames: the bit offsets
+of RcWriter and its shared dwords); unary runs of 62 zeros and a dword of U without a terminator (test_long_unary_runs: the loop of
+RcWriter::unary, the plateau of s_cum); chunks of exactly 248 q + 1 dwords around an empty one (test_full_and_empty_chunks: the last
+element of s_chunk and s_cum); valid streams of another encoder -- mode q - 1, runs of up to 255 zeros -- into k_rice_unpack
+(test_foreign_streams_unpack); the cached instantiations (test_cached_variants).  Run with `-m gpu` on an MI355X."""
 import ctypes as C
 import os
 
@@ -11,9 +18,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from test_container import CSQ, _frame_buffer
-from test_gpu_pack import EE, _filled, _mixed, _plan, _source
-from test_pack_host import codes_of, plane_bytes, ref_groups
+from test_container import CSQ, ORDERS, _random_sets
+from test_gpu_pack import EE, _compare, _filled, _mixed, _plan, _source
+from test_pack_host import codes_of, ref_groups
 from test_rice_host import ref_encode_rice, ref_modes
 
 pytestmark = pytest.mark.gpu
@@ -47,15 +54,46 @@ def _check(csic, oracle, frames, W, H, a, b, bits, f=1, op=CSQ, rounding=0, avg=
         coded, sizes, back = _roundtrip(pl, buf, nframes)
         src = buf.cpu().numpy()
         planes = [codes_of(oracle, W, H, a, b, bits, f, op, rounding, avg, fr) for fr in frames]
-        for k in range(nframes):
-            assert np.array_equal(src[k], _frame_buffer(lay, [plane_bytes(c, q) for c, q in zip(planes[k], bits)], EE)), tag
-            want = ref_encode_rice(planes[k], bits)
-            assert int(sizes[k]) == len(want), (tag, k, int(sizes[k]), len(want))
-            assert coded[k, :len(want)].tobytes() == want, (tag, k)
-            assert np.all(coded[k, len(want):] == EE), (tag, k)            # nothing behind coded_bytes, up to the next frame
-            assert len(want) <= bound
-        assert np.array_equal(back, src), tag                               # payload ranges restored, 0xEE everywhere else
+        _compare(tag, lay, bits, planes, src, coded, sizes, back, bound, [ref_encode_rice(p, bits) for p in planes])
     return planes, sizes
+
+
+# ---- random parameters -----------------------------------------------------------------------------
+RANDOM_SEED = 12050
+
+
+def _random_frames(seed=RANDOM_SEED, count=40):
+    """The parameter sets of test_random_sets_vs_numpy with their frames: the three kinds of content of
+    test_rice_host.test_random_sets_match_the_reference_byte_for_byte, in turn over the sets and over a batch's frames."""
+    for i, (W, H, a, b, bits, f, op, rounding, avg, nframes, rng) in enumerate(_random_sets(count, seed)):
+        frames = []
+        for k in range(nframes):
+            argb = rng.integers(0, 1 << 32, W * H, dtype=np.uint32)
+            if (i + k) % 3 == 1:                              # smooth content: zero groups and small k
+                argb = (np.arange(W * H, dtype=np.uint32) // 3 * np.uint32(0x010101)) | np.uint32(0xFF000000)
+            elif (i + k) % 3 == 2:                            # a ramp with a few outliers: every k in between
+                argb = (np.arange(W * H, dtype=np.uint32) // 2 * np.uint32(0x010101)) | np.uint32(0xFF000000)
+                hit = rng.random(W * H) < 0.08
+                argb[hit] = rng.integers(0, 1 << 32, int(hit.sum()), dtype=np.uint32)
+            frames.append(argb)
+        yield (W, H, a, b, bits, f, op, rounding, avg), np.stack(frames)
+
+
+def test_random_sets_vs_numpy(csic, oracle):
+    """40 random parameter sets -- the six modes of subsampling, f = 1, 2, 4, 8, the six stage orders, both roundings, AVG sampling,
+    batches of 1 and 3 -- on noise, a smooth ramp and a ramp with 8 % outliers: every width and every mode that an encoder can emit."""
+    seen_bits, seen_modes, seen = set(), set(), set()
+    for (W, H, a, b, bits, f, op, rounding, avg), frames in _random_frames():
+        planes, _ = _check(csic, oracle, frames, W, H, a, b, bits, f, op, rounding, avg)
+        seen_bits |= set(bits)
+        seen |= {("f", f), ("avg", avg), ("rounding", rounding), ("op", op), ("n", len(frames))}
+        for fr in planes:
+            for c, q in zip(fr, bits):
+                seen_modes |= {(q, int(m)) for m in ref_modes(ref_groups(c, q)[2], q)}
+    assert seen_bits == set(range(1, 9))
+    assert {m for _, m in seen_modes} == set(range(0, 9)) | {15}
+    assert seen_modes == {(q, m) for q in range(1, 9) for m in [15] + [k for k in range(q + 1) if k != q - 1]}      # with seed 12050: all
+    assert seen >= {("f", 8), ("avg", True), ("rounding", 1), ("n", 1), ("n", 3)} | {("op", o) for o in ORDERS}
 
 
 # ---- the smallest shapes that can go wrong --------------------------------------------------------------

@@ -280,17 +280,14 @@ def test_every_mode_of_every_width():
     """Groups built to order: for each q, a frame whose Y groups take mode 15 and then every k that can be the cheapest, in turn: every
     k = 0 .. q but q - 1.  (k = q - 1 costs 31 q + sum (u >> (q - 1)) bits, never less than raw; on a tie every u is below 2^(q - 1), and
     then k = q - 2 costs no more and is the smaller one.  A decoder still has to take it: test_unpack_takes_every_mode_the_format_allows.)"""
+    from codec_planes import groups_of_mode                    # (imported here: codec_planes takes its reference from this module)
     for q in range(1, 9):
         rng = np.random.default_rng(11200 + q)
         groups, want = [np.full(32, 1, dtype=np.int64)], [15]
         for k in range(q + 1):
-            for _ in range(200):                               # steps of about k bits, until k is the cheapest parameter
-                mag = 1 << k
-                c = np.cumsum(rng.integers(-mag, mag + 1, 32)) % (1 << q)
-                if ref_modes(ref_groups(c, q)[2], q)[0] == k:
-                    groups.append(c)
-                    want.append(k)
-                    break
+            for c in groups_of_mode(q, k, rng, 1):             # steps of about k bits, until k is the cheapest parameter: 200 draws
+                groups.append(c)
+                want.append(k)
         assert want == [15] + [k for k in range(q + 1) if k != q - 1], (q, want)
         codes = np.concatenate(groups).astype(np.int64)
         assert ref_modes(ref_groups(codes, q)[2], q).tolist() == want
