@@ -22,8 +22,9 @@
 // Counting: one private pair of histograms (codes, residuals; 2 x 256 32-bit bins) per wave in LDS, 8 KiB per block, bumped with LDS
 // atomics (a block's 65 536 samples cannot overflow a bin); after one barrier thread t adds the four waves' bins t and, where the sum
 // is not zero, issues one 64-bit global atomic add into d_hist, which the entry point cleared with a memset on the same stream.
-// Integer adds commute: the result is exact whatever the schedule.  Every global load goes through the accessors below, which the
-// CSIC_DEBUG build checks against the frame's bytes; the flush is checked against the result's 3072 bins.
+// Integer adds commute: the result is exact whatever the schedule.  Every global load goes through the accessors of
+// csic_kernel_ops.h, which the CSIC_DEBUG build checks -- the forwards below name the limit, the frame's bytes; the flush is checked
+// against the result's 3072 bins.
 #include <cstdio>
 #include <cstring>
 
@@ -31,7 +32,6 @@
 
 namespace csic {
 
-typedef const uint8_t CSIC_GLOBAL *gcsrc_t;
 typedef unsigned long long CSIC_GLOBAL *gchist_t;
 
 constexpr int CS_T = CSTAT_T, CS_WAVES = CS_T / 64;
@@ -54,30 +54,12 @@ struct CsArgs {
     int32_t bits_form;             // k_cstat_gen: 1 = PLANAR_BITS, 0 = PLANAR
 };
 
-#if defined(CSIC_DEBUG) && CSIC_DEBUG
-#define CSIC_SCHECK(lim, off, cnt) CSIC_CHECK((int64_t)(off) >= 0 && (int64_t)(off) + (cnt) <= (lim))
-#else
-#define CSIC_SCHECK(lim, off, cnt) do { } while (0)
-#endif
+// source: 16 bytes (16-byte aligned), a dword (4-byte aligned) or a byte at a byte offset into the frame_bytes of the frame
+template <bool NT> __device__ __forceinline__ u32x4 cs_ld16(const CsArgs &e, gcbyte_t fb, int64_t off) { return by_ld16<NT>(e.frame_bytes, fb, off); }
+template <bool NT> __device__ __forceinline__ uint32_t cs_ld4(const CsArgs &e, gcbyte_t fb, int64_t off) { return by_ld4<NT>(e.frame_bytes, fb, off); }
+__device__ __forceinline__ uint32_t cs_ld1(const CsArgs &e, gcbyte_t fb, int64_t off) { return by_ld1(e.frame_bytes, fb, off); }
 
-// source: 16 bytes (16-byte aligned), a dword (4-byte aligned) or a byte at a byte offset into the frame
-template <bool NT> __device__ __forceinline__ u32x4 cs_ld16(const CsArgs &e, gcsrc_t fb, int64_t off)
-{
-    CSIC_SCHECK(e.frame_bytes, off, 16); (void)e;
-    return ld4<NT>((gin_t)(fb + off));
-}
-template <bool NT> __device__ __forceinline__ uint32_t cs_ld4(const CsArgs &e, gcsrc_t fb, int64_t off)
-{
-    CSIC_SCHECK(e.frame_bytes, off, 4); (void)e;
-    return ld1<NT>((gin_t)(fb + off));
-}
-__device__ __forceinline__ uint32_t cs_ld1(const CsArgs &e, gcsrc_t fb, int64_t off)
-{
-    CSIC_SCHECK(e.frame_bytes, off, 1); (void)e;
-    return fb[off];
-}
-
-__device__ __forceinline__ gcsrc_t cs_frame(const CsArgs &e) { return (gcsrc_t)(uintptr_t)e.src + (int64_t)blockIdx.z * e.frame_bytes; }
+__device__ __forceinline__ gcbyte_t cs_frame(const CsArgs &e) { return frame_at_z(e.src, e.frame_bytes); }
 
 // ------------------------------------------------------------------------------------------------
 // the LDS histograms
@@ -134,7 +116,7 @@ __device__ __forceinline__ uint32_t cs_pred(uint32_t last, uint32_t &carry)
 // ------------------------------------------------------------------------------------------------
 // chunk `ch` of a plane of n samples as four dwords: CHECK = the plane may end in or before it
 template <bool NT, bool CHECK>
-__device__ __forceinline__ u32x4 bytes_chunk(const CsArgs &e, gcsrc_t fb, int64_t plane_off, uint32_t ch, uint32_t n)
+__device__ __forceinline__ u32x4 bytes_chunk(const CsArgs &e, gcbyte_t fb, int64_t plane_off, uint32_t ch, uint32_t n)
 {
     if (!CHECK || 16u * ch + 16u <= n) return cs_ld16<NT>(e, fb, plane_off + 16 * (int64_t)ch);
     uint32_t w[4] = {0, 0, 0, 0};
@@ -143,7 +125,7 @@ __device__ __forceinline__ u32x4 bytes_chunk(const CsArgs &e, gcsrc_t fb, int64_
 }
 
 template <bool NT, bool CHECK>
-__device__ __forceinline__ void bytes_body(const CsArgs &e, gcsrc_t fb, uint32_t *wh, int plane, uint32_t i0)
+__device__ __forceinline__ void bytes_body(const CsArgs &e, gcbyte_t fb, uint32_t *wh, int plane, uint32_t i0)
 {
     const uint32_t n = e.n[plane], sh = 8u - (uint32_t)e.q[plane], mask = (1u << e.q[plane]) - 1u, lane = threadIdx.x & 63u;
     const int64_t off = e.off[plane];
@@ -188,7 +170,7 @@ __global__ void __launch_bounds__(CS_T) k_cstat_bytes(CsArgs e)
 // k_cstat_bits
 // ------------------------------------------------------------------------------------------------
 template <int Q, bool NT, bool CHECK>
-__device__ __forceinline__ void bits_body(const CsArgs &e, gcsrc_t fb, uint32_t *wh, int plane, uint32_t i0)
+__device__ __forceinline__ void bits_body(const CsArgs &e, gcbyte_t fb, uint32_t *wh, int plane, uint32_t i0)
 {
     constexpr uint32_t MASK = (1u << Q) - 1u;
     const uint32_t n = e.n[plane], ndw = e.ndw[plane], lane = threadIdx.x & 63u;
@@ -240,7 +222,7 @@ __global__ void __launch_bounds__(CS_T) k_cstat_bits(CsArgs e)
 // ------------------------------------------------------------------------------------------------
 // k_cstat_gen: the definition, one sample per lane and step
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t gen_code(const CsArgs &e, gcsrc_t fb, int plane, uint32_t i)
+__device__ __forceinline__ uint32_t gen_code(const CsArgs &e, gcbyte_t fb, int plane, uint32_t i)
 {
     const uint32_t q = (uint32_t)e.q[plane];
     if (!e.bits_form) return cs_ld1(e, fb, e.off[plane] + i) >> (8u - q);
@@ -258,7 +240,7 @@ __global__ void __launch_bounds__(CS_T) k_cstat_gen(CsArgs e)
     const uint32_t b0 = blockIdx.x * CS_BLOCK, n = e.n[plane];
     if (b0 >= n) return;
     uint32_t *wh = cs_begin(lds);
-    const gcsrc_t fb = cs_frame(e);
+    const gcbyte_t fb = cs_frame(e);
     const uint32_t end = n - b0 < CS_BLOCK ? n : b0 + CS_BLOCK, mask = (1u << e.q[plane]) - 1u;
     for (uint32_t i = b0 + threadIdx.x; i < end; i += CS_T)
         cs_count(wh, gen_code(e, fb, plane, i), i ? gen_code(e, fb, plane, i - 1u) : 0u, mask);
@@ -360,9 +342,8 @@ int csic_code_stats_device(csic_plan *plan, const void *d_src, int32_t src_forma
             e.plane0 = p0;
             const CsFn fn = cs_kernel(kind, e.q[p0], !plan->tune.no_nt);
             const unsigned blocks = (unsigned)(((uint64_t)nmax + CS_BLOCK - 1) / CS_BLOCK);
-            void *params[1] = {&e};
-            HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3(blocks, (unsigned)(p1 - p0), (unsigned)nframes), dim3(CS_T, 1, 1),
-                                    params, 0, stream));
+            st = launch(fn, dim3(blocks, (unsigned)(p1 - p0), (unsigned)nframes), dim3(CS_T, 1, 1), stream, e);
+            if (st != CSIC_OK) return st;
         }
         p0 = p1;
     }

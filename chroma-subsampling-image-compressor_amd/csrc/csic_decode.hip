@@ -22,16 +22,17 @@
 //   At factor 1 a planar source IS a reconstruct: csic_reconstruct_bits_device / csic_reconstruct_device (k_rbits / k_recon) are
 //   called, and csic_decode_kernel_name says so.  (Not for a batch of frames whose W * H is not a multiple of 4: those kernels store
 //   16 bytes at a time from each frame's base, which only the first frame's alignment check covers.)
-// Every global access goes through the accessors below, which the CSIC_DEBUG build range-checks: loads against the source frame's
-// bytes, stores against the W * H pixels of the output frame.
+// The planes are read through csic_plane_read.h (the chroma sample of a position, the window of a bit plane, the per-position read of
+// k_decode_gen), which k_recon and k_rbits use too.  Every global access goes through the accessors of csic_kernel_ops.h, which the
+// CSIC_DEBUG build range-checks; the forwards below name the limits: loads against the source frame's bytes, stores against the
+// W * H pixels of the output frame.
 #include <cstdio>
 #include <cstring>
 
 #include "csic_kernel_ops.h"
+#include "csic_plane_read.h"
 
 namespace csic {
-
-typedef const uint8_t CSIC_GLOBAL *gdsrc_t;
 
 enum { S_ARGB = CSIC_FMT_ARGB8888, S_YCC = CSIC_FMT_YCBCR888X, S_PLANAR = CSIC_FMT_PLANAR, S_BITS = CSIC_FMT_PLANAR_BITS };
 
@@ -50,82 +51,32 @@ struct DecArgs {
     int64_t npieces, nwhole;       // fast kernel: P * out_height pieces; those of source rows that expand to F whole output rows
 };
 
-#if defined(CSIC_DEBUG) && CSIC_DEBUG
-#define CSIC_DCHECK(lim, off, cnt) CSIC_CHECK((int64_t)(off) >= 0 && (int64_t)(off) + (cnt) <= (lim))
-#else
-#define CSIC_DCHECK(lim, off, cnt) do { } while (0)
-#endif
+// source: a dword at a byte offset (4-byte aligned), 4 or 2 pixels at a pixel offset, all against the source frame's bytes; output: 1 or
+// 4 pixels at a pixel offset against the W * H pixels of the output frame
+__device__ __forceinline__ uint32_t dsrc4(const DecArgs &e, gcbyte_t fb, int64_t off) { return by_ld4<false>(e.src_frame_bytes, fb, off); }
+template <bool NT> __device__ __forceinline__ u32x4 dsrc16(const DecArgs &e, gcbyte_t fb, uint32_t px) { return px_ld4n<NT>(e.src_frame_bytes >> 2, (gin_t)fb, px); }
+template <bool NT> __device__ __forceinline__ u32x2 dsrc8(const DecArgs &e, gcbyte_t fb, uint32_t px) { return px_ld2n<NT>(e.src_frame_bytes >> 2, (gin_t)fb, px); }
+__device__ __forceinline__ void dout1(const DecArgs &e, gout_t out, int64_t px, uint32_t v) { px_st1<false>(e.out_px, out, px, v); }
+template <bool NT> __device__ __forceinline__ void dout4(const DecArgs &e, gout_t out, uint32_t px, u32x4 v) { px_st4n<NT>(e.out_px, out, px, v); }
 
-// source: a dword at a byte offset (4-byte aligned), 4 or 2 pixels at a pixel offset; output: 1 or 4 pixels at a pixel offset
-__device__ __forceinline__ uint32_t dsrc4(const DecArgs &e, gdsrc_t fb, int64_t off)
-{
-    CSIC_DCHECK(e.src_frame_bytes, off, 4); (void)e;
-    return *(gin_t)(fb + off);
-}
-template <bool NT> __device__ __forceinline__ u32x4 dsrc16(const DecArgs &e, gdsrc_t fb, uint32_t px)
-{
-    CSIC_DCHECK(e.src_frame_bytes, 4 * (int64_t)px, 16); (void)e;
-    return ld4<NT>((gin_t)(fb + (uint64_t)(px << 2)));
-}
-template <bool NT> __device__ __forceinline__ u32x2 dsrc8(const DecArgs &e, gdsrc_t fb, uint32_t px)
-{
-    CSIC_DCHECK(e.src_frame_bytes, 4 * (int64_t)px, 8); (void)e;
-    typedef const u32x2 CSIC_GLOBAL *vp;
-    const vp p = (vp)(fb + (uint64_t)(px << 2));
-    return NT ? __builtin_nontemporal_load(p) : *p;
-}
-__device__ __forceinline__ void dout1(const DecArgs &e, gout_t out, int64_t px, uint32_t v)
-{
-    CSIC_DCHECK(e.out_px, px, 1); (void)e;
-    out[px] = v;
-}
-template <bool NT> __device__ __forceinline__ void dout4(const DecArgs &e, gout_t out, uint32_t px, u32x4 v)
-{
-    CSIC_DCHECK(e.out_px, px, 4); (void)e;
-    st4<NT>((gout_t)((char CSIC_GLOBAL *)out + (uint64_t)(px << 2)), v);
-}
-
-__device__ __forceinline__ gdsrc_t dec_src(const DecArgs &e) { return (gdsrc_t)(uintptr_t)e.src + (int64_t)blockIdx.z * e.src_frame_bytes; }
+__device__ __forceinline__ gcbyte_t dec_src(const DecArgs &e) { return frame_at_z(e.src, e.src_frame_bytes); }
 __device__ __forceinline__ gout_t dec_dst(const DecArgs &e) { return (gout_t)(uintptr_t)e.dst + (int64_t)blockIdx.z * e.out_px; }
 
-// ------------------------------------------------------------------------------------------------
-// planar sources: bit planes (csic_planar_bits_layout; PLANAR = the same at 8 bits per sample)
-// ------------------------------------------------------------------------------------------------
-// bits [bit, bit + 32) of plane p: the dword that holds `bit` and the next one, clamped to the plane's last dword (planes are padded
-// to 256 bytes, so that dword is inside the frame; what it cannot supply lies past the plane's end)
-__device__ __forceinline__ uint32_t dec_window(const DecArgs &e, gdsrc_t fb, int p, uint64_t bit)
-{
-    const int64_t dw = (int64_t)(bit >> 5), last = (e.nbytes[p] + 3) / 4 - 1;
-    const uint32_t lo = dsrc4(e, fb, e.off[p] + 4 * dw);
-    const uint32_t hi = dsrc4(e, fb, e.off[p] + 4 * min(dw + 1, last));
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (bit & 31u));
-}
-__device__ __forceinline__ uint32_t dec_code(uint32_t win, uint32_t i, uint32_t q) { return ((win >> (i * q)) & ((1u << q) - 1u)) << (8u - q); }
-
-// chroma sample of stream position (r, c): csic_reconstruct_device's rule
-__device__ __forceinline__ uint64_t dec_sample(const DecArgs &e, uint32_t r, uint32_t c)
-{
-    if ((r & ((1u << e.lve) - 1u)) == 0 || !e.replay_last) return (uint64_t)(r >> e.lve) * e.Wc + (c >> e.lhe);
-    return (uint64_t)((r - 1u) >> e.lve) * e.Wc + (e.Wc - 1);          // ChromaSubsampler.scala:52-65: the last sample of the row above
-}
+// planar sources: the bit planes of csic_plane_read.h (csic_planar_bits_layout; PLANAR = the same at 8 bits per sample)
+template <int SRC> using DecPlanes = BitPlanes<DecArgs, &DecArgs::src_frame_bytes, SRC == S_PLANAR>;
 
 template <int SRC> __device__ __forceinline__ uint32_t dec_q(const DecArgs &e, int p) { return SRC == S_PLANAR ? 8u : (uint32_t)e.q[p]; }
 
 // source position j by the definition: the packed pixel o[j] in FMT
 template <int SRC, int FMT>
-__device__ __forceinline__ uint32_t dec_pixel(const DecArgs &e, gdsrc_t fb, uint32_t j)
+__device__ __forceinline__ uint32_t dec_pixel(const DecArgs &e, gcbyte_t fb, uint32_t j)
 {
     if (SRC == S_ARGB || SRC == S_YCC) {
         const uint32_t v = dsrc4(e, fb, 4 * (int64_t)j);
         if (SRC == S_YCC && FMT == F_ARGB) return finish_y<F_ARGB>(v & 0xFFu, chroma_term_q<F_ARGB>((v >> 8) & 0xFFu, (v >> 16) & 0xFFu));
         return v;
     }
-    const uint32_t qy = dec_q<SRC>(e, 0), qb = dec_q<SRC>(e, 1), qr = dec_q<SRC>(e, 2);
-    const uint32_t r = (uint32_t)(((uint64_t)j * e.mWm) >> e.kWm), c = j - r * (uint32_t)e.Wm;
-    const uint64_t k = dec_sample(e, r, c);
-    const uint32_t y = dec_code(dec_window(e, fb, 0, (uint64_t)j * qy), 0, qy);
-    const uint32_t cb = dec_code(dec_window(e, fb, 1, k * qb), 0, qb), cr = dec_code(dec_window(e, fb, 2, k * qr), 0, qr);
-    return finish_y<FMT>(y, chroma_term_q<FMT>(cb, cr));
+    return plane_pixel<FMT>(e, DecPlanes<SRC>{e, fb}, j);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -143,7 +94,7 @@ struct DecGroup {
 };                              // code i >> sh
 
 template <int SRC, int NP, bool NT>
-__device__ __forceinline__ DecGroup dec_load(const DecArgs &e, gdsrc_t fb, uint32_t j0)
+__device__ __forceinline__ DecGroup dec_load(const DecArgs &e, gcbyte_t fb, uint32_t j0)
 {
     DecGroup g;
     g.px[0] = g.px[1] = g.px[2] = g.px[3] = 0;
@@ -159,11 +110,12 @@ __device__ __forceinline__ DecGroup dec_load(const DecArgs &e, gdsrc_t fb, uint3
     // the row above
     const uint32_t r = (uint32_t)(((uint64_t)j0 * e.mWm) >> e.kWm), c0 = j0 - r * (uint32_t)e.Wm;
     const bool replay = (r & ((1u << e.lve) - 1u)) != 0 && e.replay_last;
-    const uint64_t k0 = dec_sample(e, r, c0);
+    const uint64_t k0 = chroma_index<uint64_t>(e, r, c0);
     g.sh = replay ? 2u : (uint32_t)e.lhe;
-    g.yw = dec_window(e, fb, 0, (uint64_t)j0 * dec_q<SRC>(e, 0));
-    g.bw = dec_window(e, fb, 1, k0 * dec_q<SRC>(e, 1));
-    g.rw = dec_window(e, fb, 2, k0 * dec_q<SRC>(e, 2));
+    const DecPlanes<SRC> s{e, fb};
+    g.yw = s.template y_word<false>(j0);
+    g.bw = s.c_word(1, k0);
+    g.rw = s.c_word(2, k0);
     return g;
 }
 
@@ -179,24 +131,24 @@ __device__ __forceinline__ void dec_group_pixels(const DecArgs &e, const DecGrou
         return;
     }
     const uint32_t qy = dec_q<SRC>(e, 0), qb = dec_q<SRC>(e, 1), qr = dec_q<SRC>(e, 2);
-    const ChromaTerm t0 = chroma_term_q<FMT>(dec_code(g.bw, 0, qb), dec_code(g.rw, 0, qr));
-    o[0] = finish_y<FMT>(dec_code(g.yw, 0, qy), t0);
+    const ChromaTerm t0 = chroma_term_q<FMT>(code_at(g.bw, 0, qb), code_at(g.rw, 0, qr));
+    o[0] = finish_y<FMT>(code_at(g.yw, 0, qy), t0);
     if (NP == 1) return;
     if (g.sh != 0u) {                                                     // positions 0 and 1 share a sample
-        o[1] = finish_y<FMT>(dec_code(g.yw, 1, qy), t0);
+        o[1] = finish_y<FMT>(code_at(g.yw, 1, qy), t0);
         if (NP == 2) return;
-        const ChromaTerm t1 = g.sh == 2u ? t0 : chroma_term_q<FMT>(dec_code(g.bw, 1, qb), dec_code(g.rw, 1, qr));
-        o[2] = finish_y<FMT>(dec_code(g.yw, 2, qy), t1);
-        o[3] = finish_y<FMT>(dec_code(g.yw, 3, qy), t1);
+        const ChromaTerm t1 = g.sh == 2u ? t0 : chroma_term_q<FMT>(code_at(g.bw, 1, qb), code_at(g.rw, 1, qr));
+        o[2] = finish_y<FMT>(code_at(g.yw, 2, qy), t1);
+        o[3] = finish_y<FMT>(code_at(g.yw, 3, qy), t1);
         return;
     }
 #pragma unroll
     for (int i = 1; i < NP; ++i)
-        o[i] = finish_y<FMT>(dec_code(g.yw, i, qy), chroma_term_q<FMT>(dec_code(g.bw, i, qb), dec_code(g.rw, i, qr)));
+        o[i] = finish_y<FMT>(code_at(g.yw, i, qy), chroma_term_q<FMT>(code_at(g.bw, i, qb), code_at(g.rw, i, qr)));
 }
 
 template <int SRC, int FMT, int F, bool NT, bool CHECK>
-__device__ __forceinline__ void decode_body(const DecArgs &e, gdsrc_t fb, gout_t out, uint32_t t0, uint32_t T, uint32_t npieces)
+__device__ __forceinline__ void decode_body(const DecArgs &e, gcbyte_t fb, gout_t out, uint32_t t0, uint32_t T, uint32_t npieces)
 {
     constexpr int K = dec_pieces_per_lane<F>(), NP = dec_np<F>();
     constexpr int LF = F == 1 ? 0 : F == 2 ? 1 : F == 4 ? 2 : 3;
@@ -233,7 +185,7 @@ __global__ void __launch_bounds__(256) k_decode(DecArgs e)
     const uint32_t npieces = (uint32_t)e.npieces;                      // (W / 4) * out_height
     const uint32_t per_block = T * (uint32_t)dec_pieces_per_lane<F>();
     const uint32_t b0 = blockIdx.x * per_block;
-    const gdsrc_t fb = dec_src(e);
+    const gcbyte_t fb = dec_src(e);
     const gout_t out = dec_dst(e);
     // straight-line body: a whole block of pieces, none of them in a ragged last source row
     if (b0 + per_block <= (uint32_t)e.nwhole) decode_body<SRC, FMT, F, NT, false>(e, fb, out, b0 + threadIdx.x, T, npieces);
@@ -257,8 +209,6 @@ __global__ void __launch_bounds__(256) k_decode_gen(DecArgs e)
 // host side
 // ------------------------------------------------------------------------------------------------
 using DecFn = void (*)(DecArgs);
-
-static int dlog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 
 static bool dec_is_planar(int src_format) { return src_format == CSIC_FMT_PLANAR || src_format == CSIC_FMT_PLANAR_BITS; }
 
@@ -289,10 +239,10 @@ static void fill_dec_args(const csic_plan *pl, int src_format, DecArgs *e)
     e->src_frame_bytes = dec_src_frame_bytes(pl, src_format);
     e->n = (int64_t)g.Wo * g.Ho;
     e->out_px = (int64_t)g.W * g.H;
-    e->Wm = G.module_width; e->Wc = G.chroma_width; e->lhe = dlog2(G.hold_h); e->lve = dlog2(G.hold_v); e->replay_last = G.replay_last;
+    e->Wm = G.module_width; e->Wc = G.chroma_width; e->lhe = ilog2(G.hold_h); e->lve = ilog2(G.hold_v); e->replay_last = G.replay_last;
     magic_div((uint32_t)G.module_width, &e->mWm, &e->kWm);
     magic_div((uint32_t)g.W, &e->mW, &e->kW);
-    e->W = g.W; e->H = g.H; e->Wo = g.Wo; e->lf = dlog2(g.f);
+    e->W = g.W; e->H = g.H; e->Wo = g.Wo; e->lf = ilog2(g.f);
     e->P = g.W / 4 > 0 ? g.W / 4 : 1;
     magic_div((uint32_t)e->P, &e->mP, &e->kP);
     e->npieces = (int64_t)e->P * g.Ho;
@@ -400,10 +350,8 @@ int csic_decode_device(csic_plan *plan, const void *d_src, int32_t src_format, v
                                                   : csic_reconstruct_device(plan, d_src, d_out, nframes, out_format, hip_stream);
     const DecFn fn = decode_kernel(kind, src_format, out_format, g.f, !plan->tune.no_nt);
     CSIC_DEVICE_SCOPE(plan->device);
-    const int bt = plan->tune.block_threads;
-    const int T = (bt == 64 || bt == 128 || bt == 256) ? bt : 256;
-    for (int f0 = 0; f0 < nframes; f0 += 65535) {                       // grid z limit
-        const int nz = nframes - f0 < 65535 ? nframes - f0 : 65535;
+    const int T = tune_block_threads(plan->tune, 256);
+    st = for_frame_batches(nframes, [&](int f0, int nz) {
         DecArgs e;
         fill_dec_args(plan, src_format, &e);
         e.src = static_cast<const uint8_t *>(d_src) + (int64_t)f0 * e.src_frame_bytes;
@@ -416,10 +364,9 @@ int csic_decode_device(csic_plan *plan, const void *d_src, int32_t src_format, v
         } else {
             blocks = (e.out_px + T - 1) / T;
         }
-        void *params[1] = {&e};
-        HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3((unsigned)blocks, 1, (unsigned)nz), dim3((unsigned)T, 1, 1), params, 0,
-                                stream));
-    }
+        return launch(fn, dim3((unsigned)blocks, 1, (unsigned)nz), dim3((unsigned)T, 1, 1), stream, e);
+    });
+    if (st != CSIC_OK) return st;
     clear_error();
     return CSIC_OK;
 }

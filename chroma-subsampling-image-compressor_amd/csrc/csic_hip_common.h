@@ -1,7 +1,8 @@
 // csic_hip_common.h -- shared by the HIP translation units (csic_kernels.hip, csic_planar.hip, csic_planar_bits.hip,
 // csic_decode.hip, csic_distortion.hip, csic_ssim.hip, csic_pipeline.hip, csic_files.hip, csic_multi.hip, csic_graph.hip): error
 // macro, the HIP instantiation of the device guard, the plan, the launch descriptor that csic_kernels.hip prepares for the other
-// units, the device staging of the synchronous *_host wrappers and the run-time-value -> template-argument helper.
+// units, the device staging of the synchronous *_host wrappers, the run-time-value -> template-argument helper and the launch
+// shell of the units' entry points (ilog2, tune_block_threads, for_frame_batches, launch, reconstruct_device).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -136,5 +137,75 @@ auto with_const(T v, Fn &&fn)
     else return v == (T)V0 ? fn(std::integral_constant<decltype(V0), V0>{}) : with_const<Vs...>(v, fn);
 }
 #define CSIC_CONST(x) decltype(x)::value     // the value of a with_const argument, usable as a template argument inside nested lambdas
+
+// ------------------------------------------------------------------------------------------------
+// the launch shell of the units' entry points
+// ------------------------------------------------------------------------------------------------
+inline int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
+
+// threads per block of the kernels that take CSIC_TUNE_BLOCK_THREADS: 64 / 128 / 256 as tuned, the kernel's own default otherwise
+inline int tune_block_threads(const Tune &t, int dflt)
+{
+    const int bt = t.block_threads;
+    return (bt == 64 || bt == 128 || bt == 256) ? bt : dflt;
+}
+
+// fn(f0, nz) for every batch of at most 65535 frames (the grid z limit): frames f0 .. f0 + nz - 1.  Stops at the first status
+// that is not CSIC_OK and returns it.
+template <class Fn> int for_frame_batches(int nframes, Fn &&fn)
+{
+    for (int f0 = 0; f0 < nframes; f0 += 65535) {
+        const int st = fn(f0, nframes - f0 < 65535 ? nframes - f0 : 65535);
+        if (st != CSIC_OK) return st;
+    }
+    return CSIC_OK;
+}
+
+// One kernel launch: the arguments are converted to the kernel's parameter types and copied, as <<< >>> would.
+template <class... P>
+int launch(void (*fn)(P...), dim3 grid, dim3 block, hipStream_t stream, std::common_type_t<P>... args)
+{
+    void *params[] = {static_cast<void *>(&args)...};
+    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), grid, block, params, 0, stream));
+    return CSIC_OK;
+}
+
+// csic_reconstruct_device / csic_reconstruct_bits_device: the refusals, the kernel for (out_format, fast, nontemporal) and one launch
+// per batch of frames -- K groups of 4 positions per lane.  Extra is the kernels' second argument (PExtra, BExtra: frame_bytes, n, Wm,
+// T, packed and the source pointer *src); fill(plan, &e) fills it from the plan's layout, pick(fmt, fast, nt) names the kernel.
+template <class Extra, class Fill, class Pick>
+int reconstruct_device(csic_plan *plan, const void *d_src, uint8_t *Extra::*src, void *d_out, int32_t nframes, int32_t out_format,
+                       void *hip_stream, const char *entry, const char *align_msg, int K, Fill fill, Pick pick)
+{
+    if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
+    if (!d_src || !d_out) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
+    if (nframes <= 0) return set_error(CSIC_EINVAL_SIZE, "nframes must be positive. Got %d", nframes);
+    if (out_format != CSIC_FMT_ARGB8888 && out_format != CSIC_FMT_YCBCR888X)
+        return set_error(CSIC_EINVAL_FORMAT, "%s writes ARGB8888(0) or YCBCR888X(1). Got %d", entry, out_format);
+    if (((uintptr_t)d_src & 255u) || ((uintptr_t)d_out & 15u)) return set_error(CSIC_EINVAL_SIZE, "%s", align_msg);
+    using Fn = void (*)(KArgs, Extra);
+    KArgs a;
+    fill_base_args(plan->g, plan->g.W, plan->g.Wo, &a);
+    Extra e;
+    fill(plan, &e);
+    CSIC_DEVICE_SCOPE(plan->device);
+    const bool fast = e.Wm % 4 == 0 && plan->tune.variant != 9;
+    const Fn fn = with_const<(int)CSIC_FMT_ARGB8888, (int)CSIC_FMT_YCBCR888X>(out_format, [&](auto fmt) {
+        return with_const<true, false>(fast, [&](auto fa) {
+            return with_const<true, false>(!plan->tune.no_nt, [&](auto nt) -> Fn { return pick(fmt, fa, nt); });
+        });
+    });
+    const int T = e.T = tune_block_threads(plan->tune, 64);
+    const int64_t ngroups = (e.n + 3) / 4, per_block = (int64_t)T * K;
+    const int st = for_frame_batches(nframes, [&](int f0, int nz) {
+        e.*src = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_src)) + (int64_t)f0 * e.frame_bytes;
+        e.packed = static_cast<uint32_t *>(d_out) + (int64_t)f0 * e.n;
+        return launch(fn, dim3((unsigned)((ngroups + per_block - 1) / per_block), 1, (unsigned)nz), dim3((unsigned)T, 1, 1),
+                      static_cast<hipStream_t>(hip_stream), a, e);
+    });
+    if (st != CSIC_OK) return st;
+    clear_error();
+    return CSIC_OK;
+}
 
 } // namespace csic

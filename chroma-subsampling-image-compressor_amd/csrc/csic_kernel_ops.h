@@ -1,8 +1,10 @@
 // csic_kernel_ops.h -- device-side building blocks shared by the kernel translation units (csic_kernels.hip, csic_planar.hip,
-// csic_planar_bits.hip, csic_decode.hip and, through csic_measure.h, csic_distortion.hip and csic_ssim.hip):
-// the wave prologue, address-space-qualified pixel pointers, streaming (non-temporal) accesses, the per-pixel arithmetic of
-// the forward / inverse transforms and the quantiser, one output pixel by the definition for both samplings (avg_pixel_generic,
-// hold_pixel_generic), and -- in the CSIC_DEBUG build -- the range checks of every global access.
+// csic_planar_bits.hip, csic_decode.hip, csic_code_stats.hip and, through csic_measure.h and csic_pack_common.h,
+// csic_distortion.hip, csic_ssim.hip, csic_pack.hip and csic_rice.hip):
+// the wave prologue, address-space-qualified pixel pointers, streaming (non-temporal) accesses, the ONE layer of range-checked
+// accessors every unit's global accesses go through (CSIC_RANGE_CHECK: live in the CSIC_DEBUG build, nothing otherwise), the
+// per-pixel arithmetic of the forward / inverse transforms and the quantiser, and one output pixel by the definition for both
+// samplings (avg_pixel_generic, hold_pixel_generic).  The reader of the planar formats is csic_plane_read.h.
 // Citations are relative to /root/reference/.
 #pragma once
 #include "csic_hip_common.h"
@@ -58,6 +60,8 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 template <bool NT> __device__ __forceinline__ uint32_t ld1(gin_t p)
 { return NT ? __builtin_nontemporal_load(p) : *p; }
+template <bool NT> __device__ __forceinline__ u32x2 ld2(gin_t p)
+{ typedef const u32x2 CSIC_GLOBAL *vp; return NT ? __builtin_nontemporal_load((vp)p) : *(vp)p; }
 template <bool NT> __device__ __forceinline__ u32x4 ld4(gin_t p)
 { typedef const u32x4 CSIC_GLOBAL *vp; return NT ? __builtin_nontemporal_load((vp)p) : *(vp)p; }
 template <bool NT> __device__ __forceinline__ void st1(gout_t p, uint32_t v)
@@ -74,56 +78,87 @@ template <bool NT> __device__ __forceinline__ void st2(uint32_t *p, u32x2 v) { s
 template <bool NT> __device__ __forceinline__ void st4(uint32_t *p, u32x4 v) { st4<NT>((gout_t)(uintptr_t)p, v); }
 
 // ------------------------------------------------------------------------------------------------
-// frame accessors -- and, in the CSIC_DEBUG build (`make debug` -> libcsic_hip_debug.so), the bounds of every access
+// range-checked accessors -- and, in the CSIC_DEBUG build (`make debug` -> libcsic_hip_debug.so), the bounds of every access
 // ------------------------------------------------------------------------------------------------
-// Every pixel kernel addresses its frame as  base + offset-in-pixels.  The accessors below are what the kernels call; in
-// the product build they are the bare non-temporal access.  With -DCSIC_DEBUG each one first checks that
-// [off, off + n) lies inside the frame's extent -- (H - 1) * pitch + W pixels of input, (Ho - 1) * pitch + Wo of output,
-// the last row being only as long as the image -- and executes s_trap otherwise: the queue reports a hardware exception and
-// the launch fails instead of reading or writing a neighbour's memory silently.  This is the GPU-side stand-in for a
-// sanitizer (GPU AddressSanitizer / xnack+ are not available on the pool); tests: `CSIC_LIB=.../libcsic_hip_debug.so pytest -m gpu`.
+// Every kernel addresses a frame as  base + offset.  The accessors below are what the kernels call, in every unit; in the product
+// build they are the bare access.  With -DCSIC_DEBUG each one first checks that [off, off + cnt) lies inside [0, lim) -- in the
+// unit of the access: pixels for the packed frames, bytes for the planes and the coded frames -- and executes s_trap otherwise:
+// the queue reports a hardware exception and the launch fails instead of reading or writing a neighbour's memory silently.  This
+// is the GPU-side stand-in for a sanitizer (GPU AddressSanitizer / xnack+ are not available on the pool); tests:
+// `CSIC_LIB=.../libcsic_hip_debug.so pytest -m gpu`.  The units keep one-line forwards that only name their limit (the frame's
+// bytes, the output's pixels); CSIC_RANGE_CHECK is the one statement of the check.
 #if defined(CSIC_DEBUG) && CSIC_DEBUG
 #define CSIC_CHECK(cond) do { if (!(cond)) __builtin_trap(); } while (0)
 #else
 #define CSIC_CHECK(cond) do { } while (0)
 #endif
+#define CSIC_RANGE_CHECK(lim, off, cnt) CSIC_CHECK((int64_t)(off) >= 0 && (int64_t)(off) + (cnt) <= (int64_t)(lim))
+
+// packed frames: limit and offset in PIXELS; 1, 2 or 4 pixels (4, 8, 16 bytes)
+template <bool NT> __device__ __forceinline__ uint32_t px_ld1(int64_t lim, gin_t base, int64_t off)
+{ CSIC_RANGE_CHECK(lim, off, 1); (void)lim; return ld1<NT>(base + off); }
+template <bool NT> __device__ __forceinline__ u32x4 px_ld4(int64_t lim, gin_t base, int64_t off)
+{ CSIC_RANGE_CHECK(lim, off, 4); (void)lim; return ld4<NT>(base + off); }
+template <bool NT> __device__ __forceinline__ void px_st1(int64_t lim, gout_t base, int64_t off, uint32_t v)
+{ CSIC_RANGE_CHECK(lim, off, 1); (void)lim; st1<NT>(base + off, v); }
+template <bool NT> __device__ __forceinline__ void px_st2(int64_t lim, gout_t base, int64_t off, u32x2 v)
+{ CSIC_RANGE_CHECK(lim, off, 2); (void)lim; st2<NT>(base + off, v); }
+template <bool NT> __device__ __forceinline__ void px_st4(int64_t lim, gout_t base, int64_t off, u32x4 v)
+{ CSIC_RANGE_CHECK(lim, off, 4); (void)lim; st4<NT>(base + off, v); }
+// The same with a 32-bit pixel offset, for kernels that are only launched on frames whose extents fit 2^30 pixels (the flat
+// kernels, k_decode): the byte offset is a uint32, and "uniform base + zero-extended 32-bit lane offset" is the saddr form of
+// global_load / global_store -- the frame base stays in SGPRs and no lane computes a 64-bit address.
+template <bool NT> __device__ __forceinline__ uint32_t px_ld1n(int64_t lim, gin_t base, uint32_t off)
+{ CSIC_RANGE_CHECK(lim, off, 1); (void)lim; return ld1<NT>((gin_t)((const char CSIC_GLOBAL *)base + (uint64_t)(off << 2))); }
+template <bool NT> __device__ __forceinline__ u32x2 px_ld2n(int64_t lim, gin_t base, uint32_t off)
+{ CSIC_RANGE_CHECK(lim, off, 2); (void)lim; return ld2<NT>((gin_t)((const char CSIC_GLOBAL *)base + (uint64_t)(off << 2))); }
+template <bool NT> __device__ __forceinline__ u32x4 px_ld4n(int64_t lim, gin_t base, uint32_t off)
+{ CSIC_RANGE_CHECK(lim, off, 4); (void)lim; return ld4<NT>((gin_t)((const char CSIC_GLOBAL *)base + (uint64_t)(off << 2))); }
+template <bool NT> __device__ __forceinline__ void px_st1n(int64_t lim, gout_t base, uint32_t off, uint32_t v)
+{ CSIC_RANGE_CHECK(lim, off, 1); (void)lim; st1<NT>((gout_t)((char CSIC_GLOBAL *)base + (uint64_t)(off << 2)), v); }
+template <bool NT> __device__ __forceinline__ void px_st4n(int64_t lim, gout_t base, uint32_t off, u32x4 v)
+{ CSIC_RANGE_CHECK(lim, off, 4); (void)lim; st4<NT>((gout_t)((char CSIC_GLOBAL *)base + (uint64_t)(off << 2)), v); }
+
+// planes and coded frames: limit and offset in BYTES; 1, 2, 4 or 16 bytes, the wider ones at their natural alignment
+typedef uint8_t CSIC_GLOBAL *gbyte_t;
+typedef const uint8_t CSIC_GLOBAL *gcbyte_t;
+__device__ __forceinline__ uint32_t by_ld1(int64_t lim, gcbyte_t base, int64_t off)
+{ CSIC_RANGE_CHECK(lim, off, 1); (void)lim; return base[off]; }
+__device__ __forceinline__ uint32_t by_ld2(int64_t lim, gcbyte_t base, int64_t off)
+{ CSIC_RANGE_CHECK(lim, off, 2); (void)lim; return *(const unsigned short CSIC_GLOBAL *)(base + off); }
+template <bool NT> __device__ __forceinline__ uint32_t by_ld4(int64_t lim, gcbyte_t base, int64_t off)
+{ CSIC_RANGE_CHECK(lim, off, 4); (void)lim; return ld1<NT>((gin_t)(base + off)); }
+template <bool NT> __device__ __forceinline__ u32x4 by_ld16(int64_t lim, gcbyte_t base, int64_t off)
+{ CSIC_RANGE_CHECK(lim, off, 16); (void)lim; return ld4<NT>((gin_t)(base + off)); }
+template <bool NT> __device__ __forceinline__ void by_st1(int64_t lim, gbyte_t base, int64_t off, uint32_t v)
+{ CSIC_RANGE_CHECK(lim, off, 1); (void)lim; if (NT) __builtin_nontemporal_store((uint8_t)v, base + off); else base[off] = (uint8_t)v; }
+template <bool NT> __device__ __forceinline__ void by_st2(int64_t lim, gbyte_t base, int64_t off, uint32_t v)
+{
+    typedef unsigned short CSIC_GLOBAL *sp;
+    CSIC_RANGE_CHECK(lim, off, 2); (void)lim;
+    if (NT) __builtin_nontemporal_store((unsigned short)v, (sp)(base + off)); else *(sp)(base + off) = (unsigned short)v;
+}
+template <bool NT> __device__ __forceinline__ void by_st4(int64_t lim, gbyte_t base, int64_t off, uint32_t v)
+{ CSIC_RANGE_CHECK(lim, off, 4); (void)lim; st1<NT>((gout_t)(base + off), v); }
+
+// base of the frame this block works on in a batch of consecutive buffers `stride` bytes apart (grid z = frame)
+__device__ __forceinline__ gbyte_t frame_at_z(const uint8_t *first, int64_t stride)
+{ return (gbyte_t)(uintptr_t)first + (int64_t)blockIdx.z * stride; }
+
+// The fused kernels' frames: (H - 1) * pitch + W pixels of input, (Ho - 1) * pitch + Wo of output, the last row being only as
+// long as the image.
 __device__ __forceinline__ int64_t in_extent(const KArgs &a) { return (int64_t)(a.H - 1) * a.ip + a.W; }
 __device__ __forceinline__ int64_t out_extent(const KArgs &a) { return (int64_t)(a.Ho - 1) * a.op + a.Wo; }
 
-template <bool NT> __device__ __forceinline__ uint32_t in1(const KArgs &a, gin_t in, int64_t off)
-{ CSIC_CHECK(off >= 0 && off + 1 <= in_extent(a)); (void)a; return ld1<NT>(in + off); }
-template <bool NT> __device__ __forceinline__ u32x4 in4(const KArgs &a, gin_t in, int64_t off)
-{ CSIC_CHECK(off >= 0 && off + 4 <= in_extent(a)); (void)a; return ld4<NT>(in + off); }
-template <bool NT> __device__ __forceinline__ void out1(const KArgs &a, gout_t out, int64_t off, uint32_t v)
-{ CSIC_CHECK(off >= 0 && off + 1 <= out_extent(a)); (void)a; st1<NT>(out + off, v); }
-template <bool NT> __device__ __forceinline__ void out2(const KArgs &a, gout_t out, int64_t off, u32x2 v)
-{ CSIC_CHECK(off >= 0 && off + 2 <= out_extent(a)); (void)a; st2<NT>(out + off, v); }
-template <bool NT> __device__ __forceinline__ void out4(const KArgs &a, gout_t out, int64_t off, u32x4 v)
-{ CSIC_CHECK(off >= 0 && off + 4 <= out_extent(a)); (void)a; st4<NT>(out + off, v); }
-
-// The same with a 32-bit pixel offset, for kernels that are only launched on frames whose extents fit 2^30 pixels (the flat
-// kernels): the byte offset is a uint32, and "uniform base + zero-extended 32-bit lane offset" is the saddr form of
-// global_load / global_store -- the frame base stays in SGPRs and no lane computes a 64-bit address.
-template <bool NT> __device__ __forceinline__ uint32_t in1n(const KArgs &a, gin_t in, uint32_t off)
-{
-    CSIC_CHECK((int64_t)off + 1 <= in_extent(a)); (void)a;
-    return ld1<NT>((gin_t)((const char CSIC_GLOBAL *)in + (uint64_t)(off << 2)));
-}
-template <bool NT> __device__ __forceinline__ u32x4 in4n(const KArgs &a, gin_t in, uint32_t off)
-{
-    CSIC_CHECK((int64_t)off + 4 <= in_extent(a)); (void)a;
-    return ld4<NT>((gin_t)((const char CSIC_GLOBAL *)in + (uint64_t)(off << 2)));
-}
-template <bool NT> __device__ __forceinline__ void out4n(const KArgs &a, gout_t out, uint32_t off, u32x4 v)
-{
-    CSIC_CHECK((int64_t)off + 4 <= out_extent(a)); (void)a;
-    st4<NT>((gout_t)((char CSIC_GLOBAL *)out + (uint64_t)(off << 2)), v);
-}
-template <bool NT> __device__ __forceinline__ void out1n(const KArgs &a, gout_t out, uint32_t off, uint32_t v)
-{
-    CSIC_CHECK((int64_t)off + 1 <= out_extent(a)); (void)a;
-    st1<NT>((gout_t)((char CSIC_GLOBAL *)out + (uint64_t)(off << 2)), v);
-}
+template <bool NT> __device__ __forceinline__ uint32_t in1(const KArgs &a, gin_t in, int64_t off) { return px_ld1<NT>(in_extent(a), in, off); }
+template <bool NT> __device__ __forceinline__ u32x4 in4(const KArgs &a, gin_t in, int64_t off) { return px_ld4<NT>(in_extent(a), in, off); }
+template <bool NT> __device__ __forceinline__ void out1(const KArgs &a, gout_t out, int64_t off, uint32_t v) { px_st1<NT>(out_extent(a), out, off, v); }
+template <bool NT> __device__ __forceinline__ void out2(const KArgs &a, gout_t out, int64_t off, u32x2 v) { px_st2<NT>(out_extent(a), out, off, v); }
+template <bool NT> __device__ __forceinline__ void out4(const KArgs &a, gout_t out, int64_t off, u32x4 v) { px_st4<NT>(out_extent(a), out, off, v); }
+template <bool NT> __device__ __forceinline__ uint32_t in1n(const KArgs &a, gin_t in, uint32_t off) { return px_ld1n<NT>(in_extent(a), in, off); }
+template <bool NT> __device__ __forceinline__ u32x4 in4n(const KArgs &a, gin_t in, uint32_t off) { return px_ld4n<NT>(in_extent(a), in, off); }
+template <bool NT> __device__ __forceinline__ void out4n(const KArgs &a, gout_t out, uint32_t off, u32x4 v) { px_st4n<NT>(out_extent(a), out, off, v); }
+template <bool NT> __device__ __forceinline__ void out1n(const KArgs &a, gout_t out, uint32_t off, uint32_t v) { px_st1n<NT>(out_extent(a), out, off, v); }
 
 // A kernel that picks, block-uniformly, between a straight-line body and a bounds-checked copy of it ends both with the same
 // store; LLVM's SimplifyCFG then sinks that store into a common tail -- and the hardware waits there with s_waitcnt vmcnt(0) for

@@ -733,16 +733,15 @@ static int launch(csic_plan *pl, const void *d_in, void *d_out, int nframes, hip
         if (st == CSIC_OK) clear_error();
         return st;
     }
-    for (int f0 = 0; f0 < nframes; f0 += 65535) {     // grid z limit
-        const int nz = (nframes - f0 < 65535) ? nframes - f0 : 65535;
+    const int st = for_frame_batches(nframes, [&](int f0, int nz) {
         LaunchDesc d;
-        int st = prepare_launch(pl, d_in, d_out, nz, in_pitch, out_pitch, &d);
-        if (st != CSIC_OK) return st;
+        const int pst = prepare_launch(pl, d_in, d_out, nz, in_pitch, out_pitch, &d);
+        if (pst != CSIC_OK) return pst;
         d.args.in += (int64_t)f0 * d.args.in_frame_px;
         d.args.out += (int64_t)f0 * d.args.out_frame_px;
-        st = enqueue(d, stream);
-        if (st != CSIC_OK) return st;
-    }
+        return enqueue(d, stream);
+    });
+    if (st != CSIC_OK) return st;
     clear_error();
     return CSIC_OK;
 }

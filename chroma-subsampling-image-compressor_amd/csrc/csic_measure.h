@@ -184,14 +184,11 @@ int measure_device(csic_plan *plan, const void *d_in, int32_t nframes, void *d_r
     e.nblk = U::blocks(plan, kind);
     U::fill_extra(plan, kind, &e);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    void *params[2] = {&a, &e};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3(e.nblk, 1, (unsigned)nframes), dim3(MEAS_T, 1, 1), params, 0, stream));
-    const uint64_t *part = static_cast<const uint64_t *>(d_workspace);
-    uint64_t *sums = static_cast<uint64_t *>(d_result);
-    uint32_t nblk = e.nblk;
-    void *rparams[3] = {&part, &nblk, &sums};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(k_sum_partials), dim3((unsigned)nframes, 1, 1), dim3(MEAS_T, 1, 1), rparams, 0,
-                            stream));
+    int lst = launch(fn, dim3(e.nblk, 1, (unsigned)nframes), dim3(MEAS_T, 1, 1), stream, a, e);
+    if (lst == CSIC_OK)
+        lst = launch(k_sum_partials, dim3((unsigned)nframes, 1, 1), dim3(MEAS_T, 1, 1), stream, static_cast<const uint64_t *>(d_workspace), e.nblk,
+                     static_cast<uint64_t *>(d_result));
+    if (lst != CSIC_OK) return lst;
     clear_error();
     return CSIC_OK;
 }

@@ -199,14 +199,7 @@ static const auto pack_widths = [](auto q, auto nt) { return k_pack_widths<CSIC_
 static const auto pack_emit = [](auto q, auto nt) { return k_pack_emit<CSIC_CONST(q), CSIC_CONST(nt)>; };
 static const auto unpack_emit = [](auto q, auto nt) { return k_unpack_emit<CSIC_CONST(q), CSIC_CONST(nt)>; };
 
-static int pk_launch(void (*fn)(PkArgs), PkArgs &e, dim3 grid, hipStream_t stream)
-{
-    void *params[1] = {&e};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), grid, dim3(PK_T, 1, 1), params, 0, stream));
-    return CSIC_OK;
-}
-
-int pack_scan_launch(PkArgs &e, int nframes, hipStream_t stream) { return pk_launch(k_pack_scan, e, dim3((unsigned)nframes, 1, 1), stream); }
+int pack_scan_launch(PkArgs &e, int nframes, hipStream_t stream) { return launch(k_pack_scan, dim3((unsigned)nframes, 1, 1), dim3(PK_T, 1, 1), stream, e); }
 
 int pk_check_buffers(const csic_plan *plan, const void *d_bits, const void *d_coded, int32_t nframes, bool has_ws, const void *d_workspace)
 {
@@ -264,7 +257,7 @@ int csic_unpack_device(csic_plan *plan, const void *d_coded, int32_t nframes, vo
     CSIC_DEVICE_SCOPE(plan->device);
     uint32_t gmax = 0;
     for (int p = 0; p < 3; ++p) gmax = e.groups[p] > gmax ? e.groups[p] : gmax;
-    if ((st = pk_launch(k_unpack_sums, e, dim3((gmax + PK_T - 1) / PK_T, 3, (unsigned)nframes), stream)) != CSIC_OK) return st;
+    if ((st = launch(k_unpack_sums, dim3((gmax + PK_T - 1) / PK_T, 3, (unsigned)nframes), dim3(PK_T, 1, 1), stream, e)) != CSIC_OK) return st;
     if ((st = pack_scan_launch(e, nframes, stream)) != CSIC_OK) return st;
     if ((st = pk_launch_planes(plan, e, nframes, stream, unpack_emit)) != CSIC_OK) return st;
     clear_error();

@@ -34,44 +34,14 @@ struct PkArgs {
     int32_t plane0;                // plane of blockIdx.y = 0
 };
 
-#if defined(CSIC_DEBUG) && CSIC_DEBUG
-#define CSIC_PCHECK(lim, off, cnt) CSIC_CHECK((int64_t)(off) >= 0 && (int64_t)(off) + (cnt) <= (int64_t)(lim))
-#else
-#define CSIC_PCHECK(lim, off, cnt) do { } while (0)
-#endif
-
-// the PLANAR_BITS frame: a dword (4-byte aligned) or a byte at a byte offset
-template <bool NT> __device__ __forceinline__ uint32_t pk_bits_ld4(const PkArgs &e, gpdst_t fb, int64_t off)
-{
-    CSIC_PCHECK(e.frame_bytes, off, 4); (void)e;
-    return ld1<NT>((gin_t)(fb + off));
-}
-__device__ __forceinline__ uint32_t pk_bits_ld1(const PkArgs &e, gpdst_t fb, int64_t off)
-{
-    CSIC_PCHECK(e.frame_bytes, off, 1); (void)e;
-    return fb[off];
-}
-template <bool NT> __device__ __forceinline__ void pk_bits_st4(const PkArgs &e, gpdst_t fb, int64_t off, uint32_t v)
-{
-    CSIC_PCHECK(e.frame_bytes, off, 4); (void)e;
-    st1<NT>((gout_t)(fb + off), v);
-}
-__device__ __forceinline__ void pk_bits_st1(const PkArgs &e, gpdst_t fb, int64_t off, uint32_t v)
-{
-    CSIC_PCHECK(e.frame_bytes, off, 1); (void)e;
-    fb[off] = (uint8_t)v;
-}
-// the coded frame: dwords
-__device__ __forceinline__ uint32_t pk_coded_ld4(const PkArgs &e, gpdst_t cb, int64_t off)
-{
-    CSIC_PCHECK(e.bound_bytes, off, 4); (void)e;
-    return *(gin_t)(cb + off);
-}
-__device__ __forceinline__ void pk_coded_st4(const PkArgs &e, gpdst_t cb, int64_t off, uint32_t v)
-{
-    CSIC_PCHECK(e.bound_bytes, off, 4); (void)e;
-    *(gout_t)(cb + off) = v;
-}
+// the PLANAR_BITS frame: a dword (4-byte aligned) or a byte at a byte offset into its frame_bytes
+template <bool NT> __device__ __forceinline__ uint32_t pk_bits_ld4(const PkArgs &e, gpdst_t fb, int64_t off) { return by_ld4<NT>(e.frame_bytes, fb, off); }
+__device__ __forceinline__ uint32_t pk_bits_ld1(const PkArgs &e, gpdst_t fb, int64_t off) { return by_ld1(e.frame_bytes, fb, off); }
+template <bool NT> __device__ __forceinline__ void pk_bits_st4(const PkArgs &e, gpdst_t fb, int64_t off, uint32_t v) { by_st4<NT>(e.frame_bytes, fb, off, v); }
+__device__ __forceinline__ void pk_bits_st1(const PkArgs &e, gpdst_t fb, int64_t off, uint32_t v) { by_st1<false>(e.frame_bytes, fb, off, v); }
+// the coded frame: dwords at a byte offset into its bound_bytes
+__device__ __forceinline__ uint32_t pk_coded_ld4(const PkArgs &e, gpdst_t cb, int64_t off) { return by_ld4<false>(e.bound_bytes, cb, off); }
+__device__ __forceinline__ void pk_coded_st4(const PkArgs &e, gpdst_t cb, int64_t off, uint32_t v) { by_st4<false>(e.bound_bytes, cb, off, v); }
 // the workspace entry of block `b` of this block's frame (`frame` < 65535: the grid's z or, for the scan, x)
 __device__ __forceinline__ gout_t pk_ws(const PkArgs &e, uint32_t frame, uint32_t b)
 {
@@ -79,8 +49,8 @@ __device__ __forceinline__ gout_t pk_ws(const PkArgs &e, uint32_t frame, uint32_
     return (gout_t)(uintptr_t)e.ws + ((uint64_t)frame * e.nblocks + b);
 }
 
-__device__ __forceinline__ gpdst_t pk_bits_frame(const PkArgs &e) { return (gpdst_t)(uintptr_t)e.bits + (int64_t)blockIdx.z * e.frame_bytes; }
-__device__ __forceinline__ gpdst_t pk_coded_frame(const PkArgs &e) { return (gpdst_t)(uintptr_t)e.coded + (int64_t)blockIdx.z * e.bound_bytes; }
+__device__ __forceinline__ gpdst_t pk_bits_frame(const PkArgs &e) { return frame_at_z(e.bits, e.frame_bytes); }
+__device__ __forceinline__ gpdst_t pk_coded_frame(const PkArgs &e) { return frame_at_z(e.coded, e.bound_bytes); }
 
 // Exclusive scan of one value per thread over the block, and the block's total.  Every thread of the block calls it.
 __device__ __forceinline__ uint32_t pk_block_scan(uint32_t v, uint32_t *s_tot, uint32_t &total)
@@ -289,9 +259,8 @@ template <class Args, class Choose> int pk_launch_planes(const csic_plan *plan, 
             void (*const fn)(Args) = with_const<true, false>(!plan->tune.no_nt, [&](auto nt) {
                 return with_const<1, 2, 3, 4, 5, 6, 7, 8>(e.q[p0], [&](auto q) -> void (*)(Args) { return choose(q, nt); });
             });
-            void *params[1] = {&e};
-            HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3((gmax + PK_T - 1) / PK_T, (unsigned)(p1 - p0), (unsigned)nframes),
-                                    dim3(PK_T, 1, 1), params, 0, stream));
+            const int st = launch(fn, dim3((gmax + PK_T - 1) / PK_T, (unsigned)(p1 - p0), (unsigned)nframes), dim3(PK_T, 1, 1), stream, e);
+            if (st != CSIC_OK) return st;
         }
         p0 = p1;
     }

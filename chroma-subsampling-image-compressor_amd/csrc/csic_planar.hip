@@ -27,54 +27,31 @@
 //   k_planar_avg_gen<ROUND>  AVG, anything else: one output position per lane by the definition (avg_pixel_generic).
 //   k_recon<FMT, FAST, NT>  planar -> packed: K = 4 groups of 4 positions per lane; per group one 4-byte Y load and the aligned
 //                      dword that holds the group's chroma samples (branch-free: shifted into place), one 16-byte store;
-//                      FAST needs module_width % 4 == 0, otherwise position by position.
+//                      FAST needs module_width % 4 == 0, otherwise position by position.  The body is recon_body of
+//                      csic_plane_read.h (shared with k_rbits) over BytePlanes, this format's plane source.
 // Measured on 8192x8192 (profiles/r04_bench_all_configs.jsonl, r04_planar_bt.log): 4:2:0 at factor 1 -- 5.5 algorithmic bytes per pixel
 // instead of 8 -- k_planar_flat 77 % of the 8 TB/s roofline (59.8 us per frame against 87.3 us for the packed k_f1x4),
 // k_planar_avg_f1 77 %; factor 2 (3 bytes per output pixel) k_planar_strided 72-74 % (the 4-consecutive form: 45 %);
 // k_recon 67-72 %.
 // Algorithmic bytes: input as for the packed path (4 * W * ceil(H / f), AVG: 4 * W * H) + csic_planar_layout.payload_bytes;
 // reconstruct: payload_bytes + 4 * n.
+// Every global access goes through the accessors of csic_kernel_ops.h, which the CSIC_DEBUG build range-checks: the input against
+// the extent of KArgs, the planes against the frame's frame_bytes (pst1 / pst2 / pst4 name that limit), k_recon's output stores
+// -- the 16-byte ones of both paths and the tail's single pixels -- against the frame's n pixels.  The host side (block size,
+// batches of 65535 frames, the launch, csic_reconstruct_device's body) is the shell of csic_hip_common.h.
 #include <cstdio>
 #include <cstring>
 
 #include "csic_kernel_ops.h"
+#include "csic_plane_read.h"
 #include "csic_avg_tile.h"
 
 namespace csic {
 
-typedef uint8_t CSIC_GLOBAL *gbyte_t;
-typedef const uint8_t CSIC_GLOBAL *gcbyte_t;
-typedef unsigned short CSIC_GLOBAL *gshort_t;
-typedef const unsigned short CSIC_GLOBAL *gcshort_t;
-
-#if defined(CSIC_DEBUG) && CSIC_DEBUG
-#define CSIC_PCHECK(e, off, nbytes) CSIC_CHECK((off) >= 0 && (int64_t)(off) + (nbytes) <= (e).frame_bytes)
-#else
-#define CSIC_PCHECK(e, off, nbytes) do { } while (0)
-#endif
-
-template <bool NT> __device__ __forceinline__ void pst1(const PExtra &e, gbyte_t base, int64_t off, uint32_t v)
-{
-    CSIC_PCHECK(e, off, 1); (void)e;
-    if (NT) __builtin_nontemporal_store((uint8_t)v, base + off); else base[off] = (uint8_t)v;
-}
-template <bool NT> __device__ __forceinline__ void pst2(const PExtra &e, gbyte_t base, int64_t off, uint32_t v)
-{
-    CSIC_PCHECK(e, off, 2); (void)e;
-    if (NT) __builtin_nontemporal_store((unsigned short)v, (gshort_t)(base + off)); else *(gshort_t)(base + off) = (unsigned short)v;
-}
-template <bool NT> __device__ __forceinline__ void pst4(const PExtra &e, gbyte_t base, int64_t off, uint32_t v)
-{
-    CSIC_PCHECK(e, off, 4); (void)e;
-    if (NT) __builtin_nontemporal_store(v, (gout_t)(base + off)); else *(gout_t)(base + off) = v;
-}
-__device__ __forceinline__ uint32_t pld1(const PExtra &e, gcbyte_t base, int64_t off) { CSIC_PCHECK(e, off, 1); (void)e; return base[off]; }
-__device__ __forceinline__ uint32_t pld2(const PExtra &e, gcbyte_t base, int64_t off) { CSIC_PCHECK(e, off, 2); (void)e; return *(gcshort_t)(base + off); }
-template <bool NT> __device__ __forceinline__ uint32_t pld4(const PExtra &e, gcbyte_t base, int64_t off)
-{
-    CSIC_PCHECK(e, off, 4); (void)e;
-    return NT ? __builtin_nontemporal_load((gin_t)(base + off)) : *(gin_t)(base + off);
-}
+// the planar frame's accessors: byte offsets into the frame_bytes of the frame
+template <bool NT> __device__ __forceinline__ void pst1(const PExtra &e, gbyte_t fb, int64_t off, uint32_t v) { by_st1<NT>(e.frame_bytes, fb, off, v); }
+template <bool NT> __device__ __forceinline__ void pst2(const PExtra &e, gbyte_t fb, int64_t off, uint32_t v) { by_st2<NT>(e.frame_bytes, fb, off, v); }
+template <bool NT> __device__ __forceinline__ void pst4(const PExtra &e, gbyte_t fb, int64_t off, uint32_t v) { by_st4<NT>(e.frame_bytes, fb, off, v); }
 
 // base of the planar frame this block works on (grid z = frame): consecutive buffers, or -- frame-table mode -- whatever the
 // device-resident table names (read through the constant address space: one wave-uniform s_load, as frame_in / frame_out)
@@ -87,14 +64,6 @@ __device__ __forceinline__ gbyte_t planar_frame(const PExtra &e)
 // ------------------------------------------------------------------------------------------------
 // forward, HOLD_DECIMATE
 // ------------------------------------------------------------------------------------------------
-// input offset of output stream position j: decimated (ro, co) = (j / Wo, j % Wo) -> image (ro * f, co * f)
-__device__ __forceinline__ int64_t stream_in_off(const KArgs &a, uint32_t j)
-{
-    const uint32_t ro = (uint32_t)(((uint64_t)j * a.mWo) >> a.kWo);
-    const uint32_t co = j - ro * (uint32_t)a.Wo;
-    return (int64_t)(ro * (uint32_t)a.f) * a.ip + co * (uint32_t)a.f;
-}
-
 // one position on its own (the stream's ragged tail, and every position of MODE 0)
 template <int ROUND, bool NT>
 __device__ __forceinline__ void planar_one(const KArgs &a, const PExtra &e, gin_t in, gbyte_t fb, uint32_t j, uint32_t px, bool store_y)
@@ -430,92 +399,26 @@ __global__ void __launch_bounds__(256) k_planar_avg_gen(KArgs a, PExtra e)
 // ------------------------------------------------------------------------------------------------
 // reconstruct: planar -> packed
 // ------------------------------------------------------------------------------------------------
-// chroma sample index of stream position (r, c) -- csic.h, csic_planar_layout
-__device__ __forceinline__ int64_t recon_index(const PExtra &e, uint32_t r, uint32_t c)
-{
-    if ((r & ((1u << e.lve) - 1u)) == 0 || !e.replay_last) return (int64_t)(r >> e.lve) * e.Wc + (c >> e.lhe);
-    return (int64_t)((r - 1u) >> e.lve) * e.Wc + (e.Wc - 1);          // ChromaSubsampler.scala:52-65: the last sample of the row above
-}
-
-// one group of (up to) 4 positions, position by position: the stream's ragged tail, and groups that may straddle chroma rows
-template <int FMT, bool NT>
-__device__ __forceinline__ void recon_slow(const PExtra &e, gcbyte_t fb, gout_t out, uint32_t j0, uint32_t n)
-{
-    uint32_t o[4];
-    const uint32_t cnt = min(4u, n - j0);
-    for (uint32_t q = 0; q < cnt; ++q) {
-        const uint32_t j = j0 + q;
-        const uint32_t r = (uint32_t)(((uint64_t)j * e.mWm) >> e.kWm), c = j - r * (uint32_t)e.Wm;
-        const int64_t k = recon_index(e, r, c);
-        o[q] = finish_y<FMT>(pld1(e, fb, (int64_t)j), chroma_term_q<FMT>(pld1(e, fb, e.cb_off + k), pld1(e, fb, e.cr_off + k)));
-    }
-    if (cnt == 4u) { const u32x4 ov = {o[0], o[1], o[2], o[3]}; st4<NT>(out + j0, ov); }
-    else for (uint32_t q = 0; q < cnt; ++q) out[j0 + q] = o[q];
-}
+// PLANAR as a plane source of csic_plane_read.h: a sample is a byte, a word the aligned dword that holds the first sample, shifted
+// into place (planes are padded to 256 bytes)
+struct BytePlanes {
+    typedef int64_t idx;
+    const PExtra &e;
+    gcbyte_t fb;
+    __device__ __forceinline__ int64_t plane(int p) const { return p == 1 ? e.cb_off : e.cr_off; }
+    template <bool NT> __device__ __forceinline__ uint32_t y_word(uint32_t j0) const { return by_ld4<NT>(e.frame_bytes, fb, (int64_t)j0); }
+    __device__ __forceinline__ uint32_t c_word(int p, idx k0) const
+    { return by_ld4<false>(e.frame_bytes, fb, (plane(p) + k0) & ~(int64_t)3) >> (8u * (uint32_t)(k0 & 3)); }
+    __device__ __forceinline__ uint32_t y_at(uint32_t w, uint32_t i) const { return (w >> (8u * i)) & 0xFFu; }
+    __device__ __forceinline__ uint32_t c_at(int, uint32_t w, uint32_t i) const { return (w >> (8u * i)) & 0xFFu; }
+    __device__ __forceinline__ uint32_t y_one(uint32_t j) const { return by_ld1(e.frame_bytes, fb, (int64_t)j); }
+    __device__ __forceinline__ uint32_t c_one(int p, idx k) const { return by_ld1(e.frame_bytes, fb, plane(p) + k); }
+};
 
 #ifndef CSIC_RECON_K
 #define CSIC_RECON_K 4
 #endif
 constexpr int RECON_K = CSIC_RECON_K;
-
-// K groups per lane spaced by the block size: all their loads (one Y dword and the group's chroma samples each) are in flight
-// before the first inverse transform starts.  The first version took one group per lane -- 8 bytes in flight per lane -- and
-// ran at 58 % of the roofline on a kernel that is three quarters stores.
-template <int FMT, bool FAST, bool NT, bool CHECK>
-__device__ __forceinline__ void recon_body(const PExtra &e, gcbyte_t fb, gout_t out, uint32_t g0, uint32_t T, uint32_t ngroups)
-{
-    const uint32_t n = (uint32_t)e.n;
-    uint32_t y4[RECON_K], cbw[RECON_K], crw[RECON_K], sh[RECON_K];
-    bool live[RECON_K], fast[RECON_K];
-#pragma unroll
-    for (int k = 0; k < RECON_K; ++k) {
-        const uint32_t g = g0 + (uint32_t)k * T;
-        live[k] = !CHECK || g < ngroups;
-        const uint32_t j0 = 4u * (CHECK ? min(g, ngroups - 1u) : g);
-        fast[k] = FAST && (!CHECK || j0 + 3u < n);
-        y4[k] = cbw[k] = crw[k] = sh[k] = 0;
-        if (fast[k]) {
-            // module_width % 4 == 0: the group lies in one chroma row at a column that is a multiple of 4, so its samples are
-            // 4, 2 or 1 consecutive bytes (h = 1, 2, 4) -- or ONE byte on a row that replays the last sample of the row above.
-            // Branch-free: the aligned dword that holds them is loaded and shifted (planes are padded to 256 bytes), position q
-            // then takes byte q >> sh.  With a branch per case the K groups' loads did not stay in flight together.
-            y4[k] = pld4<NT>(e, fb, (int64_t)j0);
-            const uint32_t r = (uint32_t)(((uint64_t)j0 * e.mWm) >> e.kWm), c0 = j0 - r * (uint32_t)e.Wm;
-            const bool replay = (r & ((1u << e.lve) - 1u)) != 0 && e.replay_last;
-            const int64_t k0 = replay ? (int64_t)((r - 1u) >> e.lve) * e.Wc + (e.Wc - 1) : (int64_t)(r >> e.lve) * e.Wc + (c0 >> e.lhe);
-            sh[k] = replay ? 2u : (uint32_t)e.lhe;
-            const uint32_t bit = 8u * (uint32_t)(k0 & 3);
-            cbw[k] = pld4<false>(e, fb, (e.cb_off + k0) & ~(int64_t)3) >> bit;
-            crw[k] = pld4<false>(e, fb, (e.cr_off + k0) & ~(int64_t)3) >> bit;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < RECON_K; ++k) {
-        if (!live[k]) continue;
-        const uint32_t j0 = 4u * (g0 + (uint32_t)k * T);
-        if (!fast[k]) { recon_slow<FMT, NT>(e, fb, out, j0, n); continue; }
-        // the chroma half of the inverse transform once per DISTINCT sample of the group (4, 2 or 1), not once per pixel: the kernel
-        // is as much VALU as memory (27 VALU per pixel on 5.5 bytes with a term per pixel; 69 % of the roofline)
-        uint32_t o[4];
-        const uint32_t y0 = y4[k] & 0xFFu, y1 = (y4[k] >> 8) & 0xFFu, y2 = (y4[k] >> 16) & 0xFFu, y3 = y4[k] >> 24;
-        if (sh[k] == 2u) {
-            const ChromaTerm t = chroma_term_q<FMT>(cbw[k] & 0xFFu, crw[k] & 0xFFu);
-            o[0] = finish_y<FMT>(y0, t); o[1] = finish_y<FMT>(y1, t); o[2] = finish_y<FMT>(y2, t); o[3] = finish_y<FMT>(y3, t);
-        } else if (sh[k] == 1u) {
-            const ChromaTerm t0 = chroma_term_q<FMT>(cbw[k] & 0xFFu, crw[k] & 0xFFu);
-            const ChromaTerm t1 = chroma_term_q<FMT>((cbw[k] >> 8) & 0xFFu, (crw[k] >> 8) & 0xFFu);
-            o[0] = finish_y<FMT>(y0, t0); o[1] = finish_y<FMT>(y1, t0); o[2] = finish_y<FMT>(y2, t1); o[3] = finish_y<FMT>(y3, t1);
-        } else {
-            o[0] = finish_y<FMT>(y0, chroma_term_q<FMT>(cbw[k] & 0xFFu, crw[k] & 0xFFu));
-            o[1] = finish_y<FMT>(y1, chroma_term_q<FMT>((cbw[k] >> 8) & 0xFFu, (crw[k] >> 8) & 0xFFu));
-            o[2] = finish_y<FMT>(y2, chroma_term_q<FMT>((cbw[k] >> 16) & 0xFFu, (crw[k] >> 16) & 0xFFu));
-            o[3] = finish_y<FMT>(y3, chroma_term_q<FMT>(cbw[k] >> 24, crw[k] >> 24));
-        }
-        const u32x4 ov = {o[0], o[1], o[2], o[3]};
-        st4<NT>(out + j0, ov);
-    }
-    if (!CHECK) keep_tail_apart();
-}
 
 template <int FMT, bool FAST, bool NT>
 __global__ void __launch_bounds__(256) k_recon(KArgs a, PExtra e)
@@ -528,17 +431,15 @@ __global__ void __launch_bounds__(256) k_recon(KArgs a, PExtra e)
     const gcbyte_t fb = (gcbyte_t)planar_frame(e);
     const gout_t out = (gout_t)(uintptr_t)e.packed + (int64_t)blockIdx.z * e.n;
     if (b0 + T * RECON_K <= ngroups && (uint64_t)4 * (b0 + T * RECON_K) <= (uint64_t)e.n)
-        recon_body<FMT, FAST, NT, false>(e, fb, out, b0 + threadIdx.x, T, ngroups);
+        recon_body<FMT, FAST, NT, false, RECON_K, BytePlanes>(e, fb, out, b0 + threadIdx.x, T, ngroups);
     else
-        recon_body<FMT, FAST, NT, true>(e, fb, out, b0 + threadIdx.x, T, ngroups);
+        recon_body<FMT, FAST, NT, true, RECON_K, BytePlanes>(e, fb, out, b0 + threadIdx.x, T, ngroups);
 }
 
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 using PlanarFn = void (*)(KArgs, PExtra);
-
-static int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 
 static void fill_extra(const csic_planar_layout &L, PExtra *e)
 {
@@ -620,13 +521,6 @@ void planar_kernel_name(const csic_plan *pl, char *buf, size_t len)
     }
 }
 
-static int launch_pk(PlanarFn fn, dim3 grid, dim3 block, KArgs a, PExtra e, hipStream_t stream)
-{
-    void *params[2] = {&a, &e};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), grid, block, params, 0, stream));
-    return CSIC_OK;
-}
-
 // kernel, grid, block and both argument blocks of one forward launch over nz <= 65535 frames; the frame pointers stay unset
 static int planar_resolve(const csic_plan *pl, int nz, PlanarLaunchDesc *d)
 {
@@ -652,18 +546,16 @@ static int planar_resolve(const csic_plan *pl, int nz, PlanarLaunchDesc *d)
         e.T = 256;
     } else if (kind == 1) {
         // k_planar_strided: 4 positions per lane, T * 4 positions per block
-        const int bt = pl->tune.block_threads;
-        const int T = (bt == 64 || bt == 128 || bt == 256) ? bt : 256;
+        const int T = tune_block_threads(pl->tune, 256);
         e.T = T;
         block = dim3((unsigned)T, 1, 1);
         grid = dim3((unsigned)((e.n + (int64_t)T * 4 - 1) / ((int64_t)T * 4)), 1, (unsigned)nz);
         a.bdx = T; a.bdy = 1; a.row_step = 1;
     } else if (kind <= 2 || kind == 5) {
         const int64_t ngroups = (e.n + 3) / 4;
-        const int bt = pl->tune.block_threads;
         // one-wave blocks for the 16-byte-load kernel: a wave's four loads then cover 4 KiB of consecutive pixels
         // (8192x8192 4:2:0: 71.7 % of the roofline with 256-thread blocks, 77.6 % with 64; profiles/r04_planar_bt.log)
-        const int T = (bt == 64 || bt == 128 || bt == 256) ? bt : (kind == 2 ? 64 : 256);
+        const int T = tune_block_threads(pl->tune, kind == 2 ? 64 : 256);
         e.T = T;
         block = dim3((unsigned)T, 1, 1);
         grid = dim3((unsigned)((ngroups + (int64_t)T * PLANAR_K - 1) / ((int64_t)T * PLANAR_K)), 1, (unsigned)nz);
@@ -686,24 +578,21 @@ static int planar_resolve(const csic_plan *pl, int nz, PlanarLaunchDesc *d)
     return CSIC_OK;
 }
 
-int planar_enqueue(const PlanarLaunchDesc &d, hipStream_t stream) { return launch_pk(d.fn, d.grid, d.block, d.args, d.extra, stream); }
+int planar_enqueue(const PlanarLaunchDesc &d, hipStream_t stream) { return launch(d.fn, d.grid, d.block, stream, d.args, d.extra); }
 
 int planar_forward(const csic_plan *pl, const void *d_in, void *d_planar, int nframes, hipStream_t stream)
 {
     if (!d_in || !d_planar) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
     if (((uintptr_t)d_planar & 255u) || ((uintptr_t)d_in & 3u))
         return set_error(CSIC_EINVAL_SIZE, "a planar frame buffer must be 256-byte aligned (and the input 4-byte aligned)");
-    for (int f0 = 0; f0 < nframes; f0 += 65535) {            // grid z limit
-        const int nz = nframes - f0 < 65535 ? nframes - f0 : 65535;
+    return for_frame_batches(nframes, [&](int f0, int nz) {
         PlanarLaunchDesc d;
-        int st = planar_resolve(pl, nz, &d);
+        const int st = planar_resolve(pl, nz, &d);
         if (st != CSIC_OK) return st;
         d.args.in = static_cast<const uint32_t *>(d_in) + (int64_t)f0 * d.args.in_frame_px;
         d.extra.planar = static_cast<uint8_t *>(d_planar) + (int64_t)f0 * d.extra.frame_bytes;
-        st = planar_enqueue(d, stream);
-        if (st != CSIC_OK) return st;
-    }
-    return CSIC_OK;
+        return planar_enqueue(d, stream);
+    });
 }
 
 int planar_prepare_table(const csic_plan *pl, const void *const *d_in_tab, void *const *d_planar_tab, uintptr_t align_bits, int nframes,
@@ -727,40 +616,8 @@ using namespace csic;
 extern "C" int csic_reconstruct_device(csic_plan *plan, const void *d_planar, void *d_out, int32_t nframes, int32_t out_format,
                                        void *hip_stream)
 {
-    if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
-    if (!d_planar || !d_out) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
-    if (nframes <= 0) return set_error(CSIC_EINVAL_SIZE, "nframes must be positive. Got %d", nframes);
-    if (out_format != CSIC_FMT_ARGB8888 && out_format != CSIC_FMT_YCBCR888X)
-        return set_error(CSIC_EINVAL_FORMAT, "csic_reconstruct_device writes ARGB8888(0) or YCBCR888X(1). Got %d", out_format);
-    if (((uintptr_t)d_planar & 255u) || ((uintptr_t)d_out & 15u))
-        return set_error(CSIC_EINVAL_SIZE, "a planar frame buffer must be 256-byte aligned and the packed output 16-byte aligned");
-    const csic_params &p = plan->p;
-    const Geometry &g = plan->g;
-    csic_planar_layout L;
-    planar_layout(g, &p, &L);
-    CSIC_DEVICE_SCOPE(plan->device);
-    const bool fast = L.module_width % 4 == 0 && plan->tune.variant != 9;
-    const PlanarFn fn = with_const<F_ARGB, F_YCC>(out_format, [&](auto fmt) {
-        return with_const<true, false>(fast, [&](auto fa) {
-            return with_const<true, false>(!plan->tune.no_nt, [](auto nt) -> PlanarFn { return k_recon<CSIC_CONST(fmt), CSIC_CONST(fa), CSIC_CONST(nt)>; });
-        });
-    });
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    for (int f0 = 0; f0 < nframes; f0 += 65535) {
-        const int nz = nframes - f0 < 65535 ? nframes - f0 : 65535;
-        KArgs a;
-        fill_base_args(g, g.W, g.Wo, &a);
-        PExtra e;
-        fill_extra(L, &e);
-        e.planar = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_planar)) + (int64_t)f0 * L.frame_bytes;
-        e.packed = static_cast<uint32_t *>(d_out) + (int64_t)f0 * e.n;
-        const int bt = plan->tune.block_threads;
-        const int T = (bt == 64 || bt == 128 || bt == 256) ? bt : 64;
-        e.T = T;
-        const int64_t ngroups = (e.n + 3) / 4, per_block = (int64_t)T * RECON_K;
-        const int st = launch_pk(fn, dim3((unsigned)((ngroups + per_block - 1) / per_block), 1, (unsigned)nz), dim3((unsigned)T, 1, 1), a, e, stream);
-        if (st != CSIC_OK) return st;
-    }
-    clear_error();
-    return CSIC_OK;
+    return reconstruct_device(plan, d_planar, &PExtra::planar, d_out, nframes, out_format, hip_stream, "csic_reconstruct_device",
+                              "a planar frame buffer must be 256-byte aligned and the packed output 16-byte aligned", RECON_K,
+                              [](const csic_plan *pl, PExtra *e) { csic_planar_layout L; planar_layout(pl->g, &pl->p, &L); fill_extra(L, e); },
+                              [](auto fmt, auto fast, auto nt) -> PlanarFn { return k_recon<CSIC_CONST(fmt), CSIC_CONST(fast), CSIC_CONST(nt)>; });
 }

@@ -16,19 +16,19 @@
 //                      definition (the input pixel of its stream position; AVG: the box / pool averages of avg_pixel_generic); the
 //                      lane writes the q bytes of its group.  CSIC_TUNE_VARIANT 9 forces it.
 //   k_rbits<FMT, FAST, NT>      bits -> packed ARGB / YCbCr, k_recon's replay rule; K = 4 groups of 4 positions per lane, per group the
-//                      two dwords that hold its codes in each plane, one 16-byte store.  FAST needs module_width % 4 == 0.
+//                      two dwords that hold its codes in each plane, one 16-byte store.  FAST needs module_width % 4 == 0.  The body
+//                      is k_recon's -- recon_body of csic_plane_read.h -- over BitPlanes, the bit planes' source.
 // Every output byte is written by exactly one lane (no read-modify-write, no atomics); the fast kernels store dwords only (their
-// planes are whole dwords: n and every chroma row are multiples of 32 samples).  Every global access goes through the CSIC_DEBUG
-// range checks: the input extent of KArgs, the frame's frame_bytes for the bit planes.
+// planes are whole dwords: n and every chroma row are multiples of 32 samples).  Every global access goes through the accessors of
+// csic_kernel_ops.h, which the CSIC_DEBUG build range-checks: the input against the extent of KArgs, the bit planes against the
+// frame's frame_bytes (bst1 / bst4 name that limit), k_rbits' output stores against the frame's n pixels.
 #include <cstdio>
 #include <cstring>
 
 #include "csic_kernel_ops.h"
+#include "csic_plane_read.h"
 
 namespace csic {
-
-typedef uint8_t CSIC_GLOBAL *gbbyte_t;
-typedef const uint8_t CSIC_GLOBAL *gcbbyte_t;
 
 // the second kernel argument of the kernels below
 struct BExtra {
@@ -44,40 +44,10 @@ struct BExtra {
     int64_t ngy, ngc;           // general kernel: groups of 8 samples of Y / of the chroma planes
 };
 
-#if defined(CSIC_DEBUG) && CSIC_DEBUG
-#define CSIC_BCHECK(e, off, nbytes) CSIC_CHECK((off) >= 0 && (int64_t)(off) + (nbytes) <= (e).frame_bytes)
-#else
-#define CSIC_BCHECK(e, off, nbytes) do { } while (0)
-#endif
-
-template <bool NT> __device__ __forceinline__ void bst1(const BExtra &e, gbbyte_t base, int64_t off, uint32_t v)
-{
-    CSIC_BCHECK(e, off, 1); (void)e;
-    if (NT) __builtin_nontemporal_store((uint8_t)v, base + off); else base[off] = (uint8_t)v;
-}
-template <bool NT> __device__ __forceinline__ void bst4(const BExtra &e, gbbyte_t base, int64_t off, uint32_t v)
-{
-    CSIC_BCHECK(e, off, 4); (void)e;
-    if (NT) __builtin_nontemporal_store(v, (gout_t)(base + off)); else *(gout_t)(base + off) = v;
-}
-__device__ __forceinline__ uint32_t bld4(const BExtra &e, gcbbyte_t base, int64_t off)
-{
-    CSIC_BCHECK(e, off, 4); (void)e;
-    return *(gin_t)(base + off);
-}
-
-__device__ __forceinline__ gbbyte_t bits_frame(const BExtra &e)
-{
-    return (gbbyte_t)(uintptr_t)e.bits + (int64_t)blockIdx.z * e.frame_bytes;
-}
-
-// input offset of output stream position j: decimated (ro, co) = (j / Wo, j % Wo) -> image (ro * f, co * f)
-__device__ __forceinline__ int64_t bits_in_off(const KArgs &a, uint32_t j)
-{
-    const uint32_t ro = (uint32_t)(((uint64_t)j * a.mWo) >> a.kWo);
-    const uint32_t co = j - ro * (uint32_t)a.Wo;
-    return (int64_t)(ro * (uint32_t)a.f) * a.ip + co * (uint32_t)a.f;
-}
+// the bit-packed frame's accessors: byte offsets into the frame_bytes of the frame
+template <bool NT> __device__ __forceinline__ void bst1(const BExtra &e, gbyte_t fb, int64_t off, uint32_t v) { by_st1<NT>(e.frame_bytes, fb, off, v); }
+template <bool NT> __device__ __forceinline__ void bst4(const BExtra &e, gbyte_t fb, int64_t off, uint32_t v) { by_st4<NT>(e.frame_bytes, fb, off, v); }
+__device__ __forceinline__ gbyte_t bits_frame(const BExtra &e) { return frame_at_z(e.bits, e.frame_bytes); }
 
 // ------------------------------------------------------------------------------------------------
 // fast forward, HOLD_DECIMATE: chunks and their assembly into output dwords
@@ -141,7 +111,7 @@ __device__ __forceinline__ PlaneAsm make_plane_asm(const BExtra &e, uint32_t u, 
 // one group of 4 consecutive positions j0 .. j0 + 3 (one chroma row; y4 / cb4 / cr4: their unquantised values, byte i = position
 // j0 + i): assemble and store.  live: the group lies in the stream (a whole packing group is live or dead together).
 template <bool NT>
-__device__ __forceinline__ void pbits_emit(const BExtra &e, const PlaneAsm &pa, gbbyte_t fb, uint32_t j0, bool live,
+__device__ __forceinline__ void pbits_emit(const BExtra &e, const PlaneAsm &pa, gbyte_t fb, uint32_t j0, bool live,
                                            uint32_t y4, uint32_t cb4, uint32_t cr4)
 {
     const uint32_t qy = (uint32_t)e.q[0], qb = (uint32_t)e.q[1], qr = (uint32_t)e.q[2];
@@ -162,7 +132,7 @@ __device__ __forceinline__ void pbits_emit(const BExtra &e, const PlaneAsm &pa, 
 constexpr int PBITS_K = 4;
 
 template <int ROUND, bool NT, bool CHECK>
-__device__ __forceinline__ void pbits_f1_body(const KArgs &a, const BExtra &e, gin_t in, gbbyte_t fb, const PlaneAsm &pa, uint32_t g0,
+__device__ __forceinline__ void pbits_f1_body(const KArgs &a, const BExtra &e, gin_t in, gbyte_t fb, const PlaneAsm &pa, uint32_t g0,
                                               uint32_t T, uint32_t ngroups)
 {
     u32x4 v[PBITS_K];
@@ -170,7 +140,7 @@ __device__ __forceinline__ void pbits_f1_body(const KArgs &a, const BExtra &e, g
     for (int k = 0; k < PBITS_K; ++k) {
         const uint32_t g = g0 + (uint32_t)k * T;
         const uint32_t gc = CHECK ? min(g, ngroups - 1u) : g;            // clamp: every lane stays in the exchange
-        v[k] = in4<NT>(a, in, bits_in_off(a, 4u * gc));
+        v[k] = in4<NT>(a, in, stream_in_off(a, 4u * gc));
     }
 #pragma unroll
     for (int k = 0; k < PBITS_K; ++k) {
@@ -198,7 +168,7 @@ __global__ void __launch_bounds__(256) k_pbits_f1(KArgs a, BExtra e)
     const uint32_t ngroups = (uint32_t)(e.n >> 2);
     const uint32_t b0 = blockIdx.x * (T * PBITS_K);
     const gin_t in = frame_in(a);
-    const gbbyte_t fb = bits_frame(e);
+    const gbyte_t fb = bits_frame(e);
     // a wave's lanes hold 64 consecutive groups (256 positions, 256-aligned) in every round
     const PlaneAsm pa = make_plane_asm(e, threadIdx.x & 63u, 0u, 1u);
     if (b0 + T * PBITS_K <= ngroups) pbits_f1_body<ROUND, NT, false>(a, e, in, fb, pa, b0 + threadIdx.x, T, ngroups);
@@ -216,7 +186,7 @@ __device__ __forceinline__ uint32_t pbits_quad_transpose(uint32_t w, uint32_t se
 }
 
 template <int ROUND, bool NT, bool CHECK>
-__device__ __forceinline__ void pbits_strided_body(const KArgs &a, const BExtra &e, gin_t in, gbbyte_t fb, const PlaneAsm &pa,
+__device__ __forceinline__ void pbits_strided_body(const KArgs &a, const BExtra &e, gin_t in, gbyte_t fb, const PlaneAsm &pa,
                                                    uint32_t b0, uint32_t T)
 {
     const uint32_t n = (uint32_t)e.n;
@@ -225,7 +195,7 @@ __device__ __forceinline__ void pbits_strided_body(const KArgs &a, const BExtra 
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const uint32_t j = b0 + (uint32_t)k * T + tid;
-        px[k] = in1<NT>(a, in, bits_in_off(a, CHECK ? min(j, n - 1u) : j));
+        px[k] = in1<NT>(a, in, stream_in_off(a, CHECK ? min(j, n - 1u) : j));
     }
     uint32_t wy = 0, wb = 0, wr = 0;                                      // byte k = position b0 + k * T + tid
 #pragma unroll
@@ -254,7 +224,7 @@ __global__ void __launch_bounds__(256) k_pbits_strided(KArgs a, BExtra e)
     const uint32_t T = (uint32_t)e.T;                 // a multiple of 64
     const uint32_t b0 = blockIdx.x * (T * 4u);
     const gin_t in = frame_in(a);
-    const gbbyte_t fb = bits_frame(e);
+    const gbyte_t fb = bits_frame(e);
     const PlaneAsm pa = make_plane_asm(e, (threadIdx.x & 63u) >> 2, threadIdx.x & 3u, 4u);
     if ((uint64_t)b0 + (uint64_t)T * 4u <= (uint64_t)e.n) pbits_strided_body<ROUND, NT, false>(a, e, in, fb, pa, b0, T);
     else                                                   pbits_strided_body<ROUND, NT, true>(a, e, in, fb, pa, b0, T);
@@ -278,7 +248,7 @@ __device__ __forceinline__ uint32_t avg_y_generic(const KArgs &a, gin_t in, int 
 }
 
 // the q bytes of one group of 8 codes (fewer at the plane's tail: the plane ends at byte nbytes)
-__device__ __forceinline__ void store_group(const BExtra &e, gbbyte_t fb, int64_t off, int64_t g, uint32_t q, int64_t nbytes, uint64_t acc)
+__device__ __forceinline__ void store_group(const BExtra &e, gbyte_t fb, int64_t off, int64_t g, uint32_t q, int64_t nbytes, uint64_t acc)
 {
     const int64_t b0 = g * q;
     const int nb = (int)min((int64_t)q, nbytes - b0);
@@ -292,7 +262,7 @@ __global__ void __launch_bounds__(256) k_pbits_gen(KArgs a, BExtra e)
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= e.ngy + e.ngc) return;
     const gin_t in = frame_in(a);
-    const gbbyte_t fb = bits_frame(e);
+    const gbyte_t fb = bits_frame(e);
     if (t < e.ngy) {                                                      // Y: positions 8 t .. 8 t + 7
         const uint32_t q = (uint32_t)e.q[0];
         uint64_t acc = 0;
@@ -301,7 +271,7 @@ __global__ void __launch_bounds__(256) k_pbits_gen(KArgs a, BExtra e)
             if (j >= e.n) break;
             uint32_t y;
             if (AVG) y = avg_y_generic<ROUND>(a, in, (int)(j / a.Wo), (int)(j % a.Wo));
-            else     y = fwd_y(in1<false>(a, in, bits_in_off(a, (uint32_t)j)));
+            else     y = fwd_y(in1<false>(a, in, stream_in_off(a, (uint32_t)j)));
             acc |= (uint64_t)(y >> (8 - q)) << (i * q);
         }
         store_group(e, fb, e.off[0], t, q, e.nbytes[0], acc);
@@ -321,7 +291,7 @@ __global__ void __launch_bounds__(256) k_pbits_gen(KArgs a, BExtra e)
             const uint32_t ycc = avg_pixel_generic<ROUND, F_YCC, F_ARGB>(a, in, (int)r, (int)c);
             cb = (ycc >> 8) & 0xFFu; cr = (ycc >> 16) & 0xFFu;
         } else {
-            fwd_c<ROUND>(in1<false>(a, in, bits_in_off(a, (uint32_t)(r * e.Wm + c))), cb, cr);
+            fwd_c<ROUND>(in1<false>(a, in, stream_in_off(a, (uint32_t)(r * e.Wm + c))), cb, cr);
         }
         ab |= (uint64_t)(cb >> (8 - qb)) << (i * qb);
         ar |= (uint64_t)(cr >> (8 - qr)) << (i * qr);
@@ -333,94 +303,8 @@ __global__ void __launch_bounds__(256) k_pbits_gen(KArgs a, BExtra e)
 // ------------------------------------------------------------------------------------------------
 // reconstruct: bits -> packed
 // ------------------------------------------------------------------------------------------------
-// bits [bit, bit + 32) of plane p (bit < 8 * nbytes[p]): the dword that holds `bit` and the next one, clamped to the plane's last
-// dword (planes are padded to 256 bytes, so that dword is inside the frame; the bits it cannot supply are past the plane's end)
-__device__ __forceinline__ uint32_t plane_window(const BExtra &e, gcbbyte_t fb, int p, uint64_t bit)
-{
-    const int64_t dw = (int64_t)(bit >> 5), last = (e.nbytes[p] + 3) / 4 - 1;
-    const uint32_t lo = bld4(e, fb, e.off[p] + 4 * dw);
-    const uint32_t hi = bld4(e, fb, e.off[p] + 4 * min(dw + 1, last));
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (bit & 31u));
-}
-__device__ __forceinline__ uint32_t code_at(uint32_t win, uint32_t i, uint32_t q) { return ((win >> (i * q)) & ((1u << q) - 1u)) << (8u - q); }
-
-__device__ __forceinline__ int64_t rbits_index(const BExtra &e, uint32_t r, uint32_t c)
-{
-    if ((r & ((1u << e.lve) - 1u)) == 0 || !e.replay_last) return (int64_t)(r >> e.lve) * e.Wc + (c >> e.lhe);
-    return (int64_t)((r - 1u) >> e.lve) * e.Wc + (e.Wc - 1);           // ChromaSubsampler.scala:52-65: the last sample of the row above
-}
-
-template <int FMT, bool NT>
-__device__ __forceinline__ void rbits_slow(const BExtra &e, gcbbyte_t fb, gout_t out, uint32_t j0, uint32_t n)
-{
-    uint32_t o[4];
-    const uint32_t cnt = min(4u, n - j0);
-    const uint32_t qy = (uint32_t)e.q[0], qb = (uint32_t)e.q[1], qr = (uint32_t)e.q[2];
-    for (uint32_t i = 0; i < cnt; ++i) {
-        const uint32_t j = j0 + i;
-        const uint32_t r = (uint32_t)(((uint64_t)j * e.mWm) >> e.kWm), c = j - r * (uint32_t)e.Wm;
-        const uint64_t k = (uint64_t)rbits_index(e, r, c);
-        const uint32_t y = code_at(plane_window(e, fb, 0, (uint64_t)j * qy), 0, qy);
-        const uint32_t cb = code_at(plane_window(e, fb, 1, k * qb), 0, qb), cr = code_at(plane_window(e, fb, 2, k * qr), 0, qr);
-        o[i] = finish_y<FMT>(y, chroma_term_q<FMT>(cb, cr));
-    }
-    if (cnt == 4u) { const u32x4 ov = {o[0], o[1], o[2], o[3]}; st4<NT>(out + j0, ov); }
-    else for (uint32_t i = 0; i < cnt; ++i) out[j0 + i] = o[i];
-}
-
 constexpr int RBITS_K = 4;
-
-template <int FMT, bool FAST, bool NT, bool CHECK>
-__device__ __forceinline__ void rbits_body(const BExtra &e, gcbbyte_t fb, gout_t out, uint32_t g0, uint32_t T, uint32_t ngroups)
-{
-    const uint32_t n = (uint32_t)e.n;
-    const uint32_t qy = (uint32_t)e.q[0], qb = (uint32_t)e.q[1], qr = (uint32_t)e.q[2];
-    uint32_t yw[RBITS_K], bw[RBITS_K], rw[RBITS_K], sh[RBITS_K];
-    bool live[RBITS_K], fast[RBITS_K];
-#pragma unroll
-    for (int k = 0; k < RBITS_K; ++k) {
-        const uint32_t g = g0 + (uint32_t)k * T;
-        live[k] = !CHECK || g < ngroups;
-        const uint32_t j0 = 4u * (CHECK ? min(g, ngroups - 1u) : g);
-        fast[k] = FAST && (!CHECK || j0 + 3u < n);
-        yw[k] = bw[k] = rw[k] = sh[k] = 0;
-        if (fast[k]) {
-            // module_width % 4 == 0: the group lies in one chroma row at a column that is a multiple of 4 -- its samples are 4, 2 or 1
-            // consecutive codes (h = 1, 2, 4), or ONE on a row that replays the last sample of the row above (k_recon's rule)
-            yw[k] = plane_window(e, fb, 0, (uint64_t)j0 * qy);
-            const uint32_t r = (uint32_t)(((uint64_t)j0 * e.mWm) >> e.kWm), c0 = j0 - r * (uint32_t)e.Wm;
-            const bool replay = (r & ((1u << e.lve) - 1u)) != 0 && e.replay_last;
-            const uint64_t k0 = replay ? (uint64_t)((r - 1u) >> e.lve) * e.Wc + (e.Wc - 1) : (uint64_t)(r >> e.lve) * e.Wc + (c0 >> e.lhe);
-            sh[k] = replay ? 2u : (uint32_t)e.lhe;
-            bw[k] = plane_window(e, fb, 1, k0 * qb);
-            rw[k] = plane_window(e, fb, 2, k0 * qr);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < RBITS_K; ++k) {
-        if (!live[k]) continue;
-        const uint32_t j0 = 4u * (g0 + (uint32_t)k * T);
-        if (!fast[k]) { rbits_slow<FMT, NT>(e, fb, out, j0, n); continue; }
-        uint32_t o[4];
-        const uint32_t y0 = code_at(yw[k], 0, qy), y1 = code_at(yw[k], 1, qy), y2 = code_at(yw[k], 2, qy), y3 = code_at(yw[k], 3, qy);
-        if (sh[k] == 2u) {
-            const ChromaTerm t = chroma_term_q<FMT>(code_at(bw[k], 0, qb), code_at(rw[k], 0, qr));
-            o[0] = finish_y<FMT>(y0, t); o[1] = finish_y<FMT>(y1, t); o[2] = finish_y<FMT>(y2, t); o[3] = finish_y<FMT>(y3, t);
-        } else if (sh[k] == 1u) {
-            const ChromaTerm t0 = chroma_term_q<FMT>(code_at(bw[k], 0, qb), code_at(rw[k], 0, qr));
-            const ChromaTerm t1 = chroma_term_q<FMT>(code_at(bw[k], 1, qb), code_at(rw[k], 1, qr));
-            o[0] = finish_y<FMT>(y0, t0); o[1] = finish_y<FMT>(y1, t0); o[2] = finish_y<FMT>(y2, t1); o[3] = finish_y<FMT>(y3, t1);
-        } else {
-            o[0] = finish_y<FMT>(y0, chroma_term_q<FMT>(code_at(bw[k], 0, qb), code_at(rw[k], 0, qr)));
-            o[1] = finish_y<FMT>(y1, chroma_term_q<FMT>(code_at(bw[k], 1, qb), code_at(rw[k], 1, qr)));
-            o[2] = finish_y<FMT>(y2, chroma_term_q<FMT>(code_at(bw[k], 2, qb), code_at(rw[k], 2, qr)));
-            o[3] = finish_y<FMT>(y3, chroma_term_q<FMT>(code_at(bw[k], 3, qb), code_at(rw[k], 3, qr)));
-        }
-        const u32x4 ov = {o[0], o[1], o[2], o[3]};
-        st4<NT>(out + j0, ov);
-    }
-    if (!CHECK) keep_tail_apart();
-}
+using RbitsPlanes = BitPlanes<BExtra, &BExtra::frame_bytes>;
 
 template <int FMT, bool FAST, bool NT>
 __global__ void __launch_bounds__(256) k_rbits(KArgs a, BExtra e)
@@ -430,20 +314,18 @@ __global__ void __launch_bounds__(256) k_rbits(KArgs a, BExtra e)
     const uint32_t T = (uint32_t)e.T;
     const uint32_t ngroups = (uint32_t)((e.n + 3) >> 2);
     const uint32_t b0 = blockIdx.x * (T * RBITS_K);
-    const gcbbyte_t fb = (gcbbyte_t)bits_frame(e);
+    const gcbyte_t fb = (gcbyte_t)bits_frame(e);
     const gout_t out = (gout_t)(uintptr_t)e.packed + (int64_t)blockIdx.z * e.n;
     if (b0 + T * RBITS_K <= ngroups && (uint64_t)4 * (b0 + T * RBITS_K) <= (uint64_t)e.n)
-        rbits_body<FMT, FAST, NT, false>(e, fb, out, b0 + threadIdx.x, T, ngroups);
+        recon_body<FMT, FAST, NT, false, RBITS_K, RbitsPlanes>(e, fb, out, b0 + threadIdx.x, T, ngroups);
     else
-        rbits_body<FMT, FAST, NT, true>(e, fb, out, b0 + threadIdx.x, T, ngroups);
+        recon_body<FMT, FAST, NT, true, RBITS_K, RbitsPlanes>(e, fb, out, b0 + threadIdx.x, T, ngroups);
 }
 
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 using BitsFn = void (*)(KArgs, BExtra);
-
-static int blog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 
 static void fill_bits_extra(const csic_planar_bits_layout &L, BExtra *e)
 {
@@ -455,7 +337,7 @@ static void fill_bits_extra(const csic_planar_bits_layout &L, BExtra *e)
     e->n = (int64_t)G.y_width * G.y_height;
     e->ns = G.chroma_samples;
     e->q[0] = L.y_bits; e->q[1] = L.cb_bits; e->q[2] = L.cr_bits;
-    e->Wm = G.module_width; e->Wc = G.chroma_width; e->lhe = blog2(G.hold_h); e->lve = blog2(G.hold_v); e->hold_v = G.hold_v;
+    e->Wm = G.module_width; e->Wc = G.chroma_width; e->lhe = ilog2(G.hold_h); e->lve = ilog2(G.hold_v); e->hold_v = G.hold_v;
     e->replay_last = G.replay_last;
     magic_div((uint32_t)G.module_width, &e->mWm, &e->kWm);
     e->ngy = (e->n + 7) / 8;
@@ -490,13 +372,6 @@ void planar_bits_kernel_name(const csic_plan *pl, char *buf, size_t len)
     }
 }
 
-static int launch_bits(BitsFn fn, dim3 grid, dim3 block, KArgs a, BExtra e, hipStream_t stream)
-{
-    void *params[2] = {&a, &e};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), grid, block, params, 0, stream));
-    return CSIC_OK;
-}
-
 int planar_bits_forward(const csic_plan *pl, const void *d_in, void *d_bits, int nframes, hipStream_t stream)
 {
     if (!d_in || !d_bits) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
@@ -517,9 +392,7 @@ int planar_bits_forward(const csic_plan *pl, const void *d_in, void *d_bits, int
             return k_pbits_gen<CSIC_CONST(round), CSIC_CONST(b)>;
         });
     });
-    const int bt = pl->tune.block_threads;
-    for (int f0 = 0; f0 < nframes; f0 += 65535) {                       // grid z limit
-        const int nz = nframes - f0 < 65535 ? nframes - f0 : 65535;
+    return for_frame_batches(nframes, [&](int f0, int nz) {
         KArgs a;
         fill_base_args(g, g.W, g.Wo, &a);
         BExtra e;
@@ -527,7 +400,7 @@ int planar_bits_forward(const csic_plan *pl, const void *d_in, void *d_bits, int
         a.in = static_cast<const uint32_t *>(d_in) + (int64_t)f0 * a.in_frame_px;
         e.bits = static_cast<uint8_t *>(d_bits) + (int64_t)f0 * L.frame_bytes;
         // one-wave blocks for the 16-byte-load kernel (as k_planar_flat MODE 2), 256 threads for the others
-        const int T = (bt == 64 || bt == 128 || bt == 256) ? bt : (kind == 1 ? 64 : 256);
+        const int T = tune_block_threads(pl->tune, kind == 1 ? 64 : 256);
         e.T = T;
         a.bdx = T; a.bdy = 1; a.row_step = 1;
         int64_t blocks;
@@ -535,10 +408,8 @@ int planar_bits_forward(const csic_plan *pl, const void *d_in, void *d_bits, int
         else if (kind == 2) blocks = (e.n + (int64_t)T * 4 - 1) / ((int64_t)T * 4);
         else blocks = (e.ngy + e.ngc + T - 1) / T;
         if (blocks > 0x7FFFFFFF) return set_error(CSIC_EINVAL_SIZE, "frame too large for one launch");
-        const int st = launch_bits(fn, dim3((unsigned)blocks, 1, (unsigned)nz), dim3((unsigned)T, 1, 1), a, e, stream);
-        if (st != CSIC_OK) return st;
-    }
-    return CSIC_OK;
+        return launch(fn, dim3((unsigned)blocks, 1, (unsigned)nz), dim3((unsigned)T, 1, 1), stream, a, e);
+    });
 }
 
 } // namespace csic
@@ -548,40 +419,8 @@ using namespace csic;
 extern "C" int csic_reconstruct_bits_device(csic_plan *plan, const void *d_bits, void *d_out, int32_t nframes, int32_t out_format,
                                             void *hip_stream)
 {
-    if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
-    if (!d_bits || !d_out) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
-    if (nframes <= 0) return set_error(CSIC_EINVAL_SIZE, "nframes must be positive. Got %d", nframes);
-    if (out_format != CSIC_FMT_ARGB8888 && out_format != CSIC_FMT_YCBCR888X)
-        return set_error(CSIC_EINVAL_FORMAT, "csic_reconstruct_bits_device writes ARGB8888(0) or YCBCR888X(1). Got %d", out_format);
-    if (((uintptr_t)d_bits & 255u) || ((uintptr_t)d_out & 15u))
-        return set_error(CSIC_EINVAL_SIZE, "a bit-packed planar frame buffer must be 256-byte aligned and the packed output 16-byte aligned");
-    const csic_params &p = plan->p;
-    const Geometry &g = plan->g;
-    csic_planar_bits_layout L;
-    planar_bits_layout(g, &p, &L);
-    CSIC_DEVICE_SCOPE(plan->device);
-    const bool fast = L.geometry.module_width % 4 == 0 && plan->tune.variant != 9;
-    const BitsFn fn = with_const<F_ARGB, F_YCC>(out_format, [&](auto fmt) {
-        return with_const<true, false>(fast, [&](auto fa) {
-            return with_const<true, false>(!plan->tune.no_nt, [](auto nt) -> BitsFn { return k_rbits<CSIC_CONST(fmt), CSIC_CONST(fa), CSIC_CONST(nt)>; });
-        });
-    });
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    for (int f0 = 0; f0 < nframes; f0 += 65535) {
-        const int nz = nframes - f0 < 65535 ? nframes - f0 : 65535;
-        KArgs a;
-        fill_base_args(g, g.W, g.Wo, &a);
-        BExtra e;
-        fill_bits_extra(L, &e);
-        e.bits = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_bits)) + (int64_t)f0 * L.frame_bytes;
-        e.packed = static_cast<uint32_t *>(d_out) + (int64_t)f0 * e.n;
-        const int bt = plan->tune.block_threads;
-        const int T = (bt == 64 || bt == 128 || bt == 256) ? bt : 64;
-        e.T = T;
-        const int64_t ngroups = (e.n + 3) / 4, per_block = (int64_t)T * RBITS_K;
-        const int st = launch_bits(fn, dim3((unsigned)((ngroups + per_block - 1) / per_block), 1, (unsigned)nz), dim3((unsigned)T, 1, 1), a, e, stream);
-        if (st != CSIC_OK) return st;
-    }
-    clear_error();
-    return CSIC_OK;
+    return reconstruct_device(plan, d_bits, &BExtra::bits, d_out, nframes, out_format, hip_stream, "csic_reconstruct_bits_device",
+                              "a bit-packed planar frame buffer must be 256-byte aligned and the packed output 16-byte aligned", RBITS_K,
+                              [](const csic_plan *pl, BExtra *e) { csic_planar_bits_layout L; planar_bits_layout(pl->g, &pl->p, &L); fill_bits_extra(L, e); },
+                              [](auto fmt, auto fast, auto nt) -> BitsFn { return k_rbits<CSIC_CONST(fmt), CSIC_CONST(fast), CSIC_CONST(nt)>; });
 }

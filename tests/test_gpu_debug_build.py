@@ -3,7 +3,9 @@ GPU AddressSanitizer is not available on the pool, so this is the device-side sa
 access of the pixel kernels is checked against the frame extent and traps.  Two things are shown here, in CHILD processes
 (CSIC_LIB selects the library at import time, and a trap ends its process):
   * the checks are live: one checked read outside the frame kills the child (and the same read inside the frame does not);
-  * a broad parity sample through every kernel family runs clean under them.
+  * a broad parity sample through every kernel family runs clean under them;
+  * so do the readers of the planar formats -- reconstruct (whose output stores are checked too), decode, code statistics -- at the
+    smallest shapes at which they take each of their paths.
 The whole `-m gpu` suite under the debug library is run by tools/run_debug_suite.sh (log: profiles/r04_gpu_tests_debug.log)."""
 import os
 import subprocess
@@ -99,3 +101,95 @@ def test_every_kernel_family_runs_clean_under_the_range_checks():
     assert r.returncode == 0 and "clean" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     for fam in ("k_avg", "k_dec", "k_decflat", "k_f1flat", "k_f1x4", "k_flatgen", "k_generic", "k_planar_flat", "k_planar_strided", "k_planar_avg_f1", "k_planar_avg_gen"):
         assert f"'{fam}'" in r.stdout, (fam, r.stdout)
+
+
+# The plane readers -- the reconstruct kernels (whose output stores are range-checked against the frame's n pixels), the decode
+# kernels and the code statistics -- on VALID inputs only, at the smallest shapes at which they take each of their paths:
+#   reconstruct  64 x 40 at factors 1 and 2 (factor 1: 2560 positions = two whole blocks of 64 threads x 4 groups x 4 positions on the
+#                straight-line body, the rest on the checked one; module width % 4 == 0: the fast path), 37 x 21 (module width % 4 != 0:
+#                every group position by position, a ragged tail of 1), 200 x 26 x 3 frames (the per-frame extent on frames 1 and 2);
+#                each with the default kernels, CSIC_TUNE_VARIANT 9 and non-temporal accesses off;
+#   decode       64 x 40 and 36 x 22 at factors 1, 2, 4, 8 (the fast kernel, from planes at factor 1 the reconstruct kernels; 22 is ragged
+#                against 4 and 8), 37 x 21 at factor 2 (the general kernel);
+#   code stats   13 x 9, the smallest shape of test_gpu_code_stats.py, all three kernels.
+# Every operation order, 4:4:4 / 4:2:2 / 4:2:0 / 4:1:1, bits (8, 8, 8) and (7, 6, 5); every result is held against the oracle.
+PLANE_READERS = """
+import itertools, numpy as np, torch, csic_amd as csic
+from oracle import oracle as orc
+N = csic._native
+assert N.lib().csic_debug_build() == 1
+ARGB, YCC, PLANAR, BITS = N.FMT_ARGB8888, N.FMT_YCBCR888X, N.FMT_PLANAR, N.FMT_PLANAR_BITS
+rng = np.random.default_rng(505)
+stems, checked = set(), 0
+
+def plan(W, H, a, b, bits, f, op, fmt):
+    return csic.Plan(csic.make_c_params(W, H, a, b, *bits, f, op, out_format=fmt), 0)
+def oparams(W, H, a, b, bits, f, op, fmt=ARGB):
+    return orc.OracleParams(width=W, height=H, chroma_a=a, chroma_b=b, y_bits=bits[0], cb_bits=bits[1], cr_bits=bits[2], factor=f, op=op, out_format=fmt)
+def dev(x):
+    return torch.from_numpy(np.ascontiguousarray(x).reshape(-1).view(np.int32)).cuda()
+def host(t):
+    return t.cpu().numpy().view(np.uint32)
+def hists(planes, bits):
+    out = np.zeros((2, 3, 256), dtype=np.uint64)
+    for p, (v, q) in enumerate(zip(planes, bits)):
+        c = np.asarray(v, dtype=np.uint8).reshape(-1).astype(np.int64) >> (8 - q)
+        out[0, p] = np.bincount(c, minlength=256)
+        out[1, p] = np.bincount(np.concatenate([c[:1], np.diff(c) % (1 << q)]), minlength=256)
+    return out
+
+TUNES = ((N.TUNE_VARIANT, 0), (N.TUNE_VARIANT, 9), (N.TUNE_NONTEMPORAL, 0))
+for op, (a, b), bits in itertools.product(itertools.permutations((1, 2, 3)), ((4, 4), (2, 2), (2, 0), (1, 1)), ((8, 8, 8), (7, 6, 5))):
+    for W, H, f, nf in ((64, 40, 1, 1), (64, 40, 2, 1), (37, 21, 1, 1), (200, 26, 1, 3)):
+        frames = rng.integers(0, 1 << 32, (nf, W * H), dtype=np.uint32)
+        want = {o: np.stack([orc.process(oparams(W, H, a, b, bits, f, op, o), fr).reshape(-1) for fr in frames]) for o in (ARGB, YCC)}
+        for fmt in (PLANAR, BITS):
+            with plan(W, H, a, b, bits, f, op, fmt) as pl:
+                buf = pl.process_device(dev(frames), nframes=nf)
+                recon = pl.reconstruct_device if fmt == PLANAR else pl.reconstruct_bits_device
+                for knob, value in TUNES:
+                    pl.tune(N.TUNE_VARIANT, 0); pl.tune(N.TUNE_NONTEMPORAL, 1); pl.tune(knob, value)
+                    for o in (ARGB, YCC):
+                        got = host(recon(buf, nframes=nf, out_format=o)).reshape(nf, -1)
+                        assert np.array_equal(got, want[o]), ("reconstruct", W, H, f, nf, op, a, b, bits, fmt, knob, value, o)
+                        checked += 1
+    for W, H, f in [(W, H, f) for W, H in ((64, 40), (36, 22)) for f in (1, 2, 4, 8)] + [(37, 21, 2)]:
+        frame = rng.integers(0, 1 << 32, W * H, dtype=np.uint32)
+        srcs = {}
+        for s in (YCC, PLANAR, BITS):
+            with plan(W, H, a, b, bits, f, op, s) as ps:
+                srcs[s] = ps.process_device(dev(frame))
+        with plan(W, H, a, b, bits, f, op, ARGB) as pl:
+            for o in (ARGB, YCC):
+                small = orc.process(oparams(W, H, a, b, bits, f, op, o), frame).reshape(-(-H // f), -(-W // f))
+                want = small[np.arange(H)[:, None] // f, np.arange(W)[None, :] // f]
+                for s, src in srcs.items():
+                    name = pl.decode_kernel_name(s, o)
+                    stems.add(name.split("<")[0])
+                    assert np.array_equal(host(pl.decode_device(src, s, out_format=o)), want), (name, W, H, f, op, a, b, bits)
+                    checked += 1
+    W, H = 13, 9
+    frame = rng.integers(0, 1 << 32, W * H, dtype=np.uint32)
+    want = hists(orc.planar(oparams(W, H, a, b, bits, 1, op), frame)[1:], bits)
+    for fmt in (PLANAR, BITS):
+        with plan(W, H, a, b, bits, 1, op, fmt) as pl:
+            buf = pl.process_device(dev(frame))
+            for force in (0, 1):
+                pl.tune(N.TUNE_FORCE_GENERIC, force)
+                name = pl.code_stats_kernel_name()
+                stems.add(name.split("<")[0])
+                got = pl.code_stats_device(buf).cpu().numpy().view(np.uint64)[0]
+                assert np.array_equal(got, want), (name, op, a, b, bits)
+                checked += 1
+torch.cuda.synchronize()
+print("clean", checked, sorted(stems))
+"""
+
+
+def test_the_plane_readers_run_clean_under_the_range_checks():
+    r = _child(PLANE_READERS, timeout=300)
+    # 6 orders x 4 modes x 2 bit triples, each: 4 shapes x 2 formats x 3 tunings x 2 outputs reconstructed, 9 shapes x 3 sources x 2
+    # outputs decoded, 2 formats x 2 kernels counted
+    assert r.returncode == 0 and f"clean {48 * (48 + 54 + 4)} " in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    for stem in ("k_recon", "k_rbits", "k_decode", "k_decode_gen", "k_cstat_bytes", "k_cstat_bits", "k_cstat_gen"):
+        assert f"'{stem}'" in r.stdout, (stem, r.stdout)
