@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from test_code_stats_host import oracle_code_stats, plane_hists
-from test_container import pack_codes
+from plane_frames import _frame_from_codes, pack_codes
 
 pytestmark = pytest.mark.gpu
 
@@ -133,21 +133,6 @@ def test_every_bit_width_on_a_ragged_plane(csic, oracle, q):
 
 
 # ---- block boundaries: the predecessor across lanes, waves and blocks --------------------------------
-def _frame_from_codes(csic, pl, fmt, planes, bits, fill=0xA5):
-    """A frame buffer of `fmt` that holds the given codes (one array per plane), everything else `fill`."""
-    if fmt == BITS:
-        lay = pl.planar_bits_layout
-        offs, data = (lay.y_offset, lay.cb_offset, lay.cr_offset), [pack_codes(c.astype(np.uint8) << (8 - q), q) for c, q in zip(planes, bits)]
-    else:
-        lay = pl.planar_layout
-        # the low bits of a PLANAR byte are ignored: set them
-        offs, data = (lay.y_offset, lay.cb_offset, lay.cr_offset), [(c.astype(np.uint8) << (8 - q)) | ((1 << (8 - q)) - 1) for c, q in zip(planes, bits)]
-    buf = np.full(lay.frame_bytes, fill, dtype=np.uint8)
-    for off, d in zip(offs, data):
-        buf[off:off + d.size] = d
-    return buf
-
-
 @pytest.mark.parametrize("fmt", [PLANAR, BITS])
 @pytest.mark.parametrize("bits", [(8, 8, 8), (6, 5, 5), (3, 7, 1)])
 def test_block_boundaries(csic, oracle, fmt, bits):

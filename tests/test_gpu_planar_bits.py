@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_png_rgb
+from plane_frames import pack_codes
 
 pytestmark = pytest.mark.gpu
 
@@ -20,16 +21,6 @@ CANARY = 0xEE
 
 with open(os.path.join(GOLDEN, "manifest.json")) as _fh:
     _GOLDENS = json.load(_fh)["goldens"]
-
-
-def pack_codes(values, q):
-    """8-bit sample values -> the plane's ceil(s q / 8) bytes: code v >> (8 - q) at bits [i q, i q + q), LSB first."""
-    codes = np.asarray(values, dtype=np.uint8).reshape(-1).astype(np.uint64) >> np.uint64(8 - q)
-    s = codes.size
-    groups = np.zeros(((s + 7) // 8) * 8, dtype=np.uint64)
-    groups[:s] = codes
-    acc = (groups.reshape(-1, 8) << (np.arange(8, dtype=np.uint64) * np.uint64(q))).sum(axis=1, dtype=np.uint64)
-    return acc.astype("<u8").view(np.uint8).reshape(-1, 8)[:, :q].reshape(-1)[:(s * q + 7) // 8]
 
 
 def test_packer_matches_the_worked_vectors():
