@@ -11,14 +11,16 @@ HIP launch.
 Two leading verbs go past what the reference's app does (it only ever writes the reconstructed pixels as a PNG):
 
     python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ... [--coding raw|groups|rice]
-    python -m csic_amd.app decompress --input x.csic --output x.png
+    python -m csic_amd.app compress   --inputs a.png,b.png,... --gop K --coding groups|rice --output x.csic ...
+    python -m csic_amd.app decompress --input x.csic --output x.png [--frame K | --output-pattern frame_%03d.png]
 
     python -m csic_amd.app inspect    --input x.csic
 
 `compress` writes the bit-packed planes as a .csic container (include/csic.h) -- as they are (`--coding raw`, the default: version 1)
 or coded on the GPU (`--coding groups`: csic_pack_device, version 3; `--coding rice`: csic_rice_pack_device, version 4; both lossless, the
-second smaller) --, `decompress` decodes any of them back
-to a PNG of the original size, `inspect` prints a container's header, its coding and stored bytes per frame and, per frame, what its samples carry: the entropies of the codes and of
+second smaller) --, or, with `--inputs` and `--gop`, frames of equal size as a sequence (csic_delta_device in front of the device
+coder: version 5) --, `decompress` decodes any of them back
+to a PNG of the original size (frame 0, `--frame K`, or every frame through `--output-pattern`), `inspect` prints a container's header, its coding and stored bytes per frame and, per frame, what its samples carry: the entropies of the codes and of
 their left-predicted residuals and the sizes an entropy coder could reach (csic_code_stats_*).  The verb must be the first
 argument; with any other first argument main() behaves as described above.
 """
@@ -32,7 +34,8 @@ import numpy as np
 
 from .compressor import ImageCompressorTop, Plan
 from . import _native as N
-from .container import container_coded_sizes, container_info, read_container, write_container, write_container_coded
+from .container import (container_coded_sizes, container_info, container_inter_groups, delta_layout, read_container, write_container,
+                        write_container_coded)
 from .model import Image, ImageProcessorModel
 from .params import PixelFormat, ProcessingStep, Sampling
 
@@ -114,13 +117,62 @@ class ImageCompressionApp:
         return os.path.getsize(outputPath)
 
     @staticmethod
-    def decompressImage(inputPath: str, outputImagePath: str, *, device: int = 0) -> None:
-        """.csic container -> plan from the stored parameters -> csic_decode_* -> PNG of width x height (the first frame of a
-        container that holds several)."""
-        c_params, _, frames = read_container(inputPath)
+    def compressSequence(inputImagePaths, outputPath: str,
+                         chromaParamA: int, chromaParamB: int,
+                         yTargetBits: int, cbTargetBits: int, crTargetBits: int,
+                         spatialFactorToUse: int,
+                         op1: ProcessingStep, op2: ProcessingStep, op3: ProcessingStep,
+                         sampling: Sampling = Sampling.HOLD_DECIMATE, *, device: int = 0, coding: str = "rice", gop: int = 16) -> int:
+        """PNGs of equal size -> one CSIC_FMT_PLANAR_BITS plan -> csic_delta_device -> the device coder -> a version-5 .csic container
+        (csic_container_write_coded_seq).  Returns the bytes written."""
+        if coding not in ("groups", "rice"):
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: a sequence takes --coding groups or rice, got {coding!r}")
+        paths = list(inputImagePaths)
+        if not paths:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: no input image")
+        images = [ImageProcessorModel.readImage(p) for p in paths]
+        W, H = images[0].width, images[0].height
+        for p, im in zip(paths, images):
+            if (im.width, im.height) != (W, H):
+                raise N.IllegalArgumentException(N.EINVAL_DIMS, f"requirement failed: {p} is {im.width}x{im.height}, the sequence is {W}x{H}")
+        top = ImageCompressorTop(W, H, chromaParamA, chromaParamB, yTargetBits, cbTargetBits, crTargetBits, spatialFactorToUse, op1, op2, op3,
+                                 device=device, sampling=sampling)
+        try:
+            import torch
+            plan = top.plan(PixelFormat.PLANAR_BITS)
+            os.makedirs(os.path.dirname(os.path.abspath(outputPath)), exist_ok=True)
+            n = len(images)
+            argb = np.stack([np.ascontiguousarray(im.argb, dtype=np.uint32).reshape(-1) for im in images])
+            d_in = torch.from_numpy(argb.reshape(-1).view(np.int32)).to(f"cuda:{device}")
+            bits = plan.process_device(d_in, None, n).reshape(n, plan.frame_bytes)
+            diff, maps = plan.delta_device(bits, n, gop)
+            pack = plan.pack_device if coding == "groups" else plan.rice_pack_device
+            coded, sizes = pack(diff, n)
+            write_container_coded(outputPath, plan.c_params, coded.cpu().numpy(), sizes.cpu().numpy(), coding=coding, maps=maps.cpu().numpy(), gop=gop)
+        finally:
+            top.close()
+        return os.path.getsize(outputPath)
+
+    @staticmethod
+    def decompressImage(inputPath: str, outputImagePath: str, *, device: int = 0, frame: int = 0) -> None:
+        """.csic container -> plan from the stored parameters -> csic_decode_* -> PNG of width x height: frame `frame` of a container
+        that holds several (the first by default)."""
+        c_params, nframes, frames = read_container(inputPath)
+        if not 0 <= frame < nframes:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: --frame must be in 0..{nframes - 1}, got {frame}")
         with Plan(c_params, device) as plan:
-            argb = plan.decode_host(frames[0])
+            argb = plan.decode_host(frames[frame])
         ImageProcessorModel.writeImage(Image(argb), outputImagePath)
+
+    @staticmethod
+    def decompressImages(inputPath: str, outputPattern: str, *, device: int = 0) -> List[str]:
+        """Every frame of a container to outputPattern % k (a printf pattern such as "frame_%03d.png").  Returns the paths written."""
+        c_params, nframes, frames = read_container(inputPath)
+        paths = [outputPattern % k for k in range(nframes)]
+        with Plan(c_params, device) as plan:
+            for k, path in enumerate(paths):
+                ImageProcessorModel.writeImage(Image(plan.decode_host(frames[k])), path)
+        return paths
 
     @staticmethod
     def processImages(inputImagePaths, outputImagePaths, chromaParamA: int, chromaParamB: int,
@@ -209,6 +261,15 @@ def _main_container(verb: str, args: List[str]) -> int:
     """`compress` / `decompress`: the keys of the verb-less CLI with its defaults, plus --output and (compress) --sampling avg and
     --coding raw|groups|rice."""
     argsMap = _args_map(args)
+    if verb == "compress" and "--inputs" in argsMap:
+        return _main_sequence(argsMap)
+    if verb == "decompress" and "--output-pattern" in argsMap and "--input" in argsMap:
+        if not os.path.exists(argsMap["--input"]):
+            print(f"[ERROR] Input not found: {argsMap['--input']}")
+            return 1
+        paths = ImageCompressionApp.decompressImages(argsMap["--input"], argsMap["--output-pattern"])
+        print(f"Decompression complete. {len(paths)} frames saved to: {argsMap['--output-pattern']}")
+        return 0
     if "--input" not in argsMap or "--output" not in argsMap:
         print(f"[ERROR] {verb} needs --input and --output")
         return 2
@@ -217,7 +278,7 @@ def _main_container(verb: str, args: List[str]) -> int:
         print(f"[ERROR] Input not found: {inputPath}")
         return 1
     if verb == "decompress":
-        ImageCompressionApp.decompressImage(inputPath, outputPath)
+        ImageCompressionApp.decompressImage(inputPath, outputPath, frame=int(argsMap.get("--frame", "0")))
         print(f"Decompression complete. Output saved to: {outputPath}")
         return 0
     sampling = Sampling.AVG if argsMap.get("--sampling", "hold").lower() == "avg" else Sampling.HOLD_DECIMATE
@@ -231,6 +292,30 @@ def _main_container(verb: str, args: List[str]) -> int:
         ProcessingStep.parse(argsMap.get("--op1", "spatial")), ProcessingStep.parse(argsMap.get("--op2", "color")),
         ProcessingStep.parse(argsMap.get("--op3", "chroma")), sampling, coding=coding)
     print(f"Compression complete. {os.path.getsize(inputPath)} -> {size} bytes. Output saved to: {outputPath}")
+    return 0
+
+
+def _main_sequence(argsMap: Dict[str, str]) -> int:
+    """`compress --inputs a.png,b.png,... --gop K --coding groups|rice --output x.csic`: frames of equal size as one version-5 container."""
+    if "--output" not in argsMap:
+        print("[ERROR] compress needs --inputs and --output")
+        return 2
+    paths = [p for p in argsMap["--inputs"].split(",") if p]
+    for p in paths:
+        if not os.path.exists(p):
+            print(f"[ERROR] Input not found: {p}")
+            return 1
+    coding = argsMap.get("--coding", "rice").lower()
+    if coding not in ("groups", "rice") or not paths:
+        print(f"[ERROR] a sequence needs at least one input and --coding groups or rice, got {coding}")
+        return 2
+    sampling = Sampling.AVG if argsMap.get("--sampling", "hold").lower() == "avg" else Sampling.HOLD_DECIMATE
+    size = ImageCompressionApp.compressSequence(
+        paths, argsMap["--output"], int(argsMap.get("--a", "4")), int(argsMap.get("--b", "4")), int(argsMap.get("--yq", "8")),
+        int(argsMap.get("--cbq", "8")), int(argsMap.get("--crq", "8")), int(argsMap.get("--sf", "8")),
+        ProcessingStep.parse(argsMap.get("--op1", "spatial")), ProcessingStep.parse(argsMap.get("--op2", "color")),
+        ProcessingStep.parse(argsMap.get("--op3", "chroma")), sampling, coding=coding, gop=int(argsMap.get("--gop", "16")))
+    print(f"Compression complete. {len(paths)} frames, {sum(os.path.getsize(p) for p in paths)} -> {size} bytes. Output saved to: {argsMap['--output']}")
     return 0
 
 
@@ -251,9 +336,18 @@ def _main_inspect(args: List[str]) -> int:
     print(f"Image: {p.width}x{p.height}, chroma 4:{p.chroma_a}:{p.chroma_b}, bits Y/Cb/Cr {p.y_bits}/{p.cb_bits}/{p.cr_bits}, "
           f"factor {p.factor}, order {ops}, rounding {p.rounding}, sampling {p.sampling}")
     print(f"Frames: {info.nframes}, payload bytes per frame: {info.payload_bytes}")
-    print(f"Frame coding: {({3: 'groups', 4: 'rice'}).get(info.version, 'raw')}")
-    for k, stored in enumerate(container_coded_sizes(inputPath)):
-        print(f"  frame {k}: stored in {int(stored)} bytes, {int(stored) / info.payload_bytes:.4f} of raw")
+    if info.version == 5:
+        print(f"Frame coding: {({1: 'groups', 3: 'rice'}).get(info.coding, 'raw')}, temporal delta with gop {info.gop}")
+        groups = [max(int(g), 1) for g in delta_layout(p).groups]
+        inter = container_inter_groups(inputPath)
+        for k, stored in enumerate(container_coded_sizes(inputPath)):
+            share = ", ".join(f"{name} {int(inter[k][i]) / groups[i]:.3f}" for i, name in enumerate(("Y", "Cb", "Cr")))
+            print(f"  frame {k} ({'key' if k % info.gop == 0 else 'delta'}): stored in {int(stored)} bytes, {int(stored) / info.payload_bytes:.4f} of raw, "
+                  f"inter groups {share}")
+    else:
+        print(f"Frame coding: {({3: 'groups', 4: 'rice'}).get(info.version, 'raw')}")
+        for k, stored in enumerate(container_coded_sizes(inputPath)):
+            print(f"  frame {k}: stored in {int(stored)} bytes, {int(stored) / info.payload_bytes:.4f} of raw")
     try:
         c_params, nframes, frames = read_container(inputPath)
         with Plan(c_params, 0) as plan:

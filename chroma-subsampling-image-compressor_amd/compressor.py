@@ -19,7 +19,7 @@ from typing import Tuple
 import numpy as np
 
 from . import _native as N
-from .container import pack_frame_host, rice_pack_host, rice_unpack_host, unpack_frame_host
+from .container import delta_host, delta_layout, pack_frame_host, rice_pack_host, rice_unpack_host, undelta_host, unpack_frame_host
 from .params import (ImageProcessorParams, PixelFormat, ProcessingStep, Rounding, Sampling, make_c_params)
 
 
@@ -518,6 +518,59 @@ class Plan:
     def rice_unpack(self, coded, out=None) -> np.ndarray:
         """csic_rice_unpack_host: Rice-coded bytes -> a PLANAR_BITS frame buffer."""
         return rice_unpack_host(self.c_params, coded, out)
+
+    # -- temporal delta coding of sequences of PLANAR_BITS frames (csic_delta_*) -------------------------
+    @property
+    def delta_layout(self) -> N.CsicDeltaLayout:
+        """csic_delta_layout of these parameters: groups, the map's section offsets, map_bytes, map_stride."""
+        return delta_layout(self.c_params)
+
+    @property
+    def delta_kernel_name(self) -> str:
+        return N.lib().csic_delta_kernel_name(self._h).decode()
+
+    def _delta_buffers(self, d_a, nframes, d_b, d_maps, what):
+        """The frames of one side checked, the other side's and the maps allocated unless given (`d_b` may be `d_a`: in place)."""
+        import torch
+        fb, ms = self.planar_bits_layout.frame_bytes, self.delta_layout.map_stride
+        self._pack_check(d_a, nframes * fb, what)
+        if d_b is None:
+            d_b = torch.empty((nframes, fb), dtype=torch.uint8, device=d_a.device)
+        else:
+            self._pack_check(d_b, nframes * fb, "the output frames")
+        if d_maps is None:
+            d_maps = torch.zeros((nframes, ms), dtype=torch.uint8, device=d_a.device)
+        else:
+            self._pack_check(d_maps, nframes * ms, "d_maps")
+        return d_b, d_maps
+
+    def delta_device(self, d_frames, nframes: int = 1, gop: int = 1, d_diff=None, d_maps=None):
+        """d_frames: nframes PLANAR_BITS frame buffers on the device (frame_bytes each).  Returns (diff, maps): the difference frames, a
+        uint8 tensor (nframes, frame_bytes) of which only the payload ranges are written -- `d_diff` may be `d_frames` itself, in place --
+        and the maps, uint8 (nframes, map_stride) with map_bytes of each row written.  Either coder then packs `diff` as it packs
+        frames.  Asynchronous on torch's current stream."""
+        d_diff, d_maps = self._delta_buffers(d_frames, nframes, d_diff, d_maps, "d_frames")
+        N.check(N.lib().csic_delta_device(self._h, C.c_void_p(d_frames.data_ptr()), int(nframes), int(gop), C.c_void_p(d_diff.data_ptr()),
+                                          C.c_void_p(d_maps.data_ptr()), self._stream()))
+        return d_diff, d_maps
+
+    def undelta_device(self, d_diff, d_maps, nframes: int = 1, gop: int = 1, d_frames=None):
+        """The inverse of delta_device (`d_frames` may be `d_diff`, in place).  The device does not validate the maps: check untrusted
+        ones with undelta() first."""
+        if d_maps is None:
+            raise N.IllegalArgumentException(N.EINVAL_NULL, "requirement failed: d_maps is None")
+        d_frames, _ = self._delta_buffers(d_diff, nframes, d_frames, d_maps, "d_diff")
+        N.check(N.lib().csic_undelta_device(self._h, C.c_void_p(d_diff.data_ptr()), C.c_void_p(d_maps.data_ptr()), int(nframes), int(gop),
+                                            C.c_void_p(d_frames.data_ptr()), self._stream()))
+        return d_frames
+
+    def delta(self, frames, gop: int, out=None):
+        """csic_delta_host: frame buffers in host memory (nframes, frame_bytes) -> (diff, maps).  Needs no GPU."""
+        return delta_host(self.c_params, frames, gop, out)
+
+    def undelta(self, diff, maps, gop: int, out=None) -> np.ndarray:
+        """csic_undelta_host: the inverse; damaged maps raise CsicIOError."""
+        return undelta_host(self.c_params, diff, maps, gop, out)
 
     # -- compute ----------------------------------------------------------------------------------
     def _stream(self):

@@ -1,6 +1,7 @@
 """.csic files: CSIC_FMT_PLANAR_BITS frames on disk (csic_container_*; byte layout in include/csic.h), raw (version 1), group-coded
-(version 3) or Rice-coded (version 4), and the host codecs of both codings (csic_pack_host / csic_unpack_host, csic_rice_pack_host /
-csic_rice_unpack_host).  Host only: nothing here needs a GPU."""
+(version 3), Rice-coded (version 4) or as a sequence through the temporal layer (version 5), the host codecs of both codings
+(csic_pack_host / csic_unpack_host, csic_rice_pack_host / csic_rice_unpack_host) and the host codec of the temporal layer
+(csic_delta_host / csic_undelta_host).  Host only: nothing here needs a GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,9 +14,18 @@ from . import _native as N
 
 
 def container_info(path: str) -> N.CsicContainerInfo:
-    """Header, parameters and length of a .csic file (csic_container_info_of; everything read_container checks but the CRC)."""
+    """Header, parameters and length of a .csic file (csic_container_info_of; everything read_container checks but the CRC), and as
+    plain attributes its `gop` (csic_container_gop) and the `coding` of its frames."""
     info = N.CsicContainerInfo()
     N.check(N.lib().csic_container_info_of(os.fsencode(path), C.byref(info)))
+    gop = C.c_int32()
+    N.check(N.lib().csic_container_gop(os.fsencode(path), C.byref(gop)))
+    info.gop = gop.value                              # csic_container_gop: 1 below version 5 (every frame stands alone)
+    info.coding = {1: N.CODING_RAW, 3: N.CODING_GROUPS, 4: N.CODING_RICE}.get(info.version)
+    if info.coding is None:                           # version 5 names its coding in the word behind the parameters (checked: 1 or 3)
+        with open(path, "rb") as fh:
+            fh.seek(80)
+            info.coding = int.from_bytes(fh.read(4), "little")
     return info
 
 
@@ -99,13 +109,63 @@ def rice_unpack_host(c_params: N.CsicParams, coded, out=None) -> np.ndarray:
     return _unpack_host(c_params, coded, out, N.lib().csic_rice_unpack_host)
 
 
-def write_container(path: str, c_params: N.CsicParams, frames, coding="raw") -> None:
+def delta_layout(c_params: N.CsicParams) -> N.CsicDeltaLayout:
+    """csic_delta_layout_of: groups, the sections' offsets, map_bytes and map_stride of a frame's map."""
+    lay = N.CsicDeltaLayout()
+    N.check(N.lib().csic_delta_layout_of(C.byref(c_params), C.byref(lay)))
+    return lay
+
+
+def _frames_2d(frames, frame_bytes: int) -> np.ndarray:
+    if isinstance(frames, (list, tuple)):
+        frames = np.stack([np.ascontiguousarray(f).reshape(-1).view(np.uint8) for f in frames])
+    a = np.ascontiguousarray(frames).reshape(-1).view(np.uint8)
+    if a.size == 0 or a.size % frame_bytes != 0:
+        raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: frames must hold whole frame buffers of {frame_bytes} bytes, got {a.size}")
+    return a.reshape(-1, frame_bytes)
+
+
+def delta_host(c_params: N.CsicParams, frames, gop: int, out=None):
+    """csic_delta_host: PLANAR_BITS frame buffers (nframes, frame_bytes) -> (diff, maps): the difference frames, an array of the same
+    shape (zero outside the payload ranges, or `out` -- which may be `frames` itself, in place), and the maps, uint8 (nframes,
+    map_stride) with map_bytes of each row written."""
+    q, lay = _bits_params(c_params)
+    ml = delta_layout(q)
+    a = _frames_2d(frames, lay.frame_bytes)
+    diff = np.zeros_like(a) if out is None else out
+    maps = np.zeros((a.shape[0], ml.map_stride), dtype=np.uint8)
+    N.check(N.lib().csic_delta_host(C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], int(gop), diff.ctypes.data_as(C.c_void_p),
+                                    maps.ctypes.data_as(C.c_void_p)))
+    return diff, maps
+
+
+def undelta_host(c_params: N.CsicParams, diff, maps, gop: int, out=None) -> np.ndarray:
+    """csic_undelta_host: the inverse of delta_host.  The maps are untrusted: a set padding bit or a non-zero map of a key frame raises
+    CsicIOError (CSIC_EFORMAT) and nothing is written."""
+    q, lay = _bits_params(c_params)
+    ml = delta_layout(q)
+    d = _frames_2d(diff, lay.frame_bytes)
+    m = np.ascontiguousarray(maps).view(np.uint8).reshape(d.shape[0], -1)
+    if m.shape[1] != ml.map_stride:
+        raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: maps must be (nframes, {ml.map_stride}), got {m.shape}")
+    frames = np.zeros_like(d) if out is None else out
+    N.check(N.lib().csic_undelta_host(C.byref(q), d.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), d.shape[0], int(gop),
+                                      frames.ctypes.data_as(C.c_void_p)))
+    return frames
+
+
+def write_container(path: str, c_params: N.CsicParams, frames, coding="raw", gop=None) -> None:
     """frames: the PLANAR_BITS frame buffers of `c_params` (its out_format does not matter), frame_bytes each -- one buffer, an
     array (nframes, frame_bytes), or a list of buffers.  Only the planes' payload bytes reach the file.  coding = "raw" (version 1,
     the bytes as they are), "groups" (version 3, every frame group-coded on the host: csic_container_write_ex) or "rice" (version 4,
-    every frame Rice-coded on the host)."""
+    every frame Rice-coded on the host).  With a `gop` the frames are a sequence: version 5, delta and packing on the host
+    (csic_container_write_seq; coding "groups" or "rice")."""
     q, lay = _bits_params(c_params)
     coding = _coding(coding)
+    if gop is not None:
+        a = _frames_2d(frames, lay.frame_bytes)
+        N.check(N.lib().csic_container_write_seq(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], coding, int(gop)))
+        return
     if isinstance(frames, (list, tuple)):
         frames = np.stack([np.ascontiguousarray(f).reshape(-1).view(np.uint8) for f in frames])
     a = np.ascontiguousarray(frames).reshape(-1).view(np.uint8)
@@ -117,10 +177,14 @@ def write_container(path: str, c_params: N.CsicParams, frames, coding="raw") -> 
         N.check(N.lib().csic_container_write_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.size // lay.frame_bytes, coding))
 
 
-def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, coding="groups") -> None:
+def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, coding="groups", maps=None, gop=None) -> None:
     """Version 3 (coding "groups") or 4 ("rice") from frames that are packed already (csic_container_write_coded_ex): `coded` is an
     array (nframes, stride) -- what Plan.pack_device / Plan.rice_pack_device returns, copied to the host -- or a list of coded frames;
-    sizes[k] is frame k's coded_bytes.  Every frame is validated before anything is written."""
+    sizes[k] is frame k's coded_bytes.  Every frame is validated before anything is written.  With `maps` and `gop` -- what
+    Plan.delta_device returned, copied to the host: uint8 (nframes, map_stride) -- the coded frames are difference frames and the file is
+    version 5 (csic_container_write_coded_seq)."""
+    if (maps is None) != (gop is None):
+        raise N.IllegalArgumentException(N.EINVAL_NULL, "requirement failed: maps and gop go together")
     q, _ = _bits_params(c_params)
     coding = _coding(coding)
     sz = np.ascontiguousarray(np.asarray(sizes).reshape(-1), dtype=np.uint64)
@@ -135,6 +199,14 @@ def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, codin
         a = a.reshape(sz.size, -1) if sz.size and a.size % sz.size == 0 else a.reshape(1, -1)
     if sz.size == 0 or a.shape[0] != sz.size:
         raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: {a.shape[0]} coded frames but {sz.size} sizes")
+    if maps is not None:
+        m = np.ascontiguousarray(maps).view(np.uint8)
+        if m.size == 0 or m.size % sz.size != 0:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: {m.size} bytes of maps for {sz.size} frames")
+        N.check(N.lib().csic_container_write_coded_seq(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1],
+                                                       sz.ctypes.data_as(C.POINTER(C.c_uint64)), m.ctypes.data_as(C.c_void_p), m.size // sz.size,
+                                                       int(sz.size), coding, int(gop)))
+        return
     N.check(N.lib().csic_container_write_coded_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1],
                                                   sz.ctypes.data_as(C.POINTER(C.c_uint64)), int(sz.size), coding))
 
@@ -146,6 +218,15 @@ def container_coded_sizes(path: str) -> np.ndarray:
     sizes = np.zeros(info.nframes, dtype=np.uint64)
     N.check(N.lib().csic_container_coded_sizes(os.fsencode(path), sizes.ctypes.data_as(C.POINTER(C.c_uint64)), info.nframes))
     return sizes
+
+
+def container_inter_groups(path: str) -> np.ndarray:
+    """csic_container_inter_groups: uint64 (nframes, 3), the inter groups of each frame and plane (the popcounts of a version-5 file's
+    maps; zeros for key frames and for versions 1, 3 and 4)."""
+    info = container_info(path)
+    counts = np.zeros((info.nframes, 3), dtype=np.uint64)
+    N.check(N.lib().csic_container_inter_groups(os.fsencode(path), counts.ctypes.data_as(C.POINTER(C.c_uint64)), 3 * info.nframes))
+    return counts
 
 
 def read_container(path: str) -> Tuple[N.CsicParams, int, np.ndarray]:

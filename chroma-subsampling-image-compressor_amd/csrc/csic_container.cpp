@@ -3,7 +3,8 @@
 // frame the three planes' payload bytes back to back: the padding of a frame buffer never reaches the file, and reading zeroes it.
 // Version 3 holds the frames group-coded instead (csic_pack_host.cpp): a coding word, a table of the frames' coded sizes, the coded frames;
 // version 4 is the same layout with the frames Rice-coded (csic_rice_host.cpp).  What differs between the two is one row of codec_of;
-// the little-endian dwords are csic_group_host.h's.
+// the little-endian dwords are csic_group_host.h's.  Version 5 holds a sequence through the temporal layer (csic_delta_host.cpp): the word
+// behind the coding is the gop, a key frame's record is its coded frame, a delta frame's its map and then its coded difference frame.
 #include <zlib.h>
 
 #include <cstdio>
@@ -16,8 +17,8 @@
 namespace csic {
 
 constexpr size_t CONTAINER_HEADER = 80, CONTAINER_CRC_FROM = 16;
-constexpr uint32_t CONTAINER_VERSION = 1, CONTAINER_VERSION_CODED = 3, CONTAINER_VERSION_RICE = 4;
-constexpr size_t CODED_BODY = 8;                  // versions 3 and 4: coding, reserved; then the table of sizes
+constexpr uint32_t CONTAINER_VERSION = 1, CONTAINER_VERSION_CODED = 3, CONTAINER_VERSION_RICE = 4, CONTAINER_VERSION_SEQ = 5;
+constexpr size_t CODED_BODY = 8;                  // versions 3, 4 and 5: coding, reserved (5: gop); then the table of sizes
 static const unsigned char CONTAINER_MAGIC[4] = {0x43, 0x53, 0x49, 0x43};   // "CSIC"
 
 static void put_u64(unsigned char *p, uint64_t v) { put_u32(p, (uint32_t)v); put_u32(p + 4, (uint32_t)(v >> 32)); }
@@ -83,8 +84,23 @@ struct FileCloser {
 // Reads and checks everything but the CRC (and, version 3, the coded frames themselves): header fields, parameters, the table of
 // sizes, the file's length.  `sizes` (may be NULL) receives the stored bytes of each frame; the file pointer is left behind the
 // header (version 1) or the table (version 3).  *stored_crc may be NULL.
-static int read_header(FILE *f, const char *path, csic_container_info *info, RiceGeometry *G, uint32_t *stored_crc, std::vector<uint64_t> *sizes)
+// What a coded file's body says in front of its table: the coding, the gop (1 below version 5) and the bytes of a delta frame's map.
+struct CodedBody {
+    int coding = CSIC_CODING_RAW;
+    int32_t gop = 1;
+    int64_t map_bytes = 0;
+};
+static int64_t map_bytes_of(const PackGeometry &G)
 {
+    int64_t b = 0;
+    for (int pl = 0; pl < 3; ++pl) b += 4 * ((G.layout.groups[pl] + 31) / 32);
+    return b;
+}
+
+static int read_header(FILE *f, const char *path, csic_container_info *info, RiceGeometry *G, uint32_t *stored_crc, std::vector<uint64_t> *sizes,
+                       CodedBody *body = nullptr)
+{
+    CodedBody cb;
     unsigned char h[CONTAINER_HEADER];
     if (fseek(f, 0, SEEK_END) != 0) return set_error(CSIC_EIO, "cannot seek in %s", path);
     const long long size = ftello(f);
@@ -93,8 +109,8 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Ric
     if (fread(h, 1, sizeof h, f) != sizeof h) return set_error(CSIC_EIO, "cannot read %s", path);
     if (std::memcmp(h, CONTAINER_MAGIC, 4) != 0) return set_error(CSIC_EFORMAT, "%s is not a .csic file (bad magic)", path);
     const uint32_t version = get_u32(h + 4), nframes = get_u32(h + 8);
-    if (version != CONTAINER_VERSION && version != CONTAINER_VERSION_CODED && version != CONTAINER_VERSION_RICE)
-        return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1, 3 and 4 are)", path, version);
+    if (version != CONTAINER_VERSION && version != CONTAINER_VERSION_CODED && version != CONTAINER_VERSION_RICE && version != CONTAINER_VERSION_SEQ)
+        return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1, 3, 4 and 5 are)", path, version);
     if (nframes < 1 || nframes > 65535) return set_error(CSIC_EFORMAT, "%s: nframes must be in 1..65535. Got %u", path, nframes);
     int32_t fields[16];
     for (int i = 0; i < 16; ++i) fields[i] = (int32_t)get_u32(h + 16 + 4 * i);
@@ -111,16 +127,24 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Ric
         if (size < front) return set_error(CSIC_EFORMAT, "%s: %lld bytes is shorter than the size table of %u frames", path, size, nframes);
         std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
         if (fread(t.data(), 1, t.size(), f) != t.size()) return set_error(CSIC_EIO, "cannot read %s", path);
-        const int coding = version == CONTAINER_VERSION_RICE ? CSIC_CODING_RICE : CSIC_CODING_GROUPS;
-        if (get_u32(t.data()) != (uint32_t)coding || get_u32(t.data() + 4) != 0)
+        int coding = version == CONTAINER_VERSION_RICE ? CSIC_CODING_RICE : CSIC_CODING_GROUPS;
+        if (version == CONTAINER_VERSION_SEQ) {
+            const uint32_t c = get_u32(t.data()), gop = get_u32(t.data() + 4);
+            if (c != CSIC_CODING_GROUPS && c != CSIC_CODING_RICE) return set_error(CSIC_EFORMAT, "%s: coding %u is not one version 5 holds (1 or 3)", path, c);
+            if (gop < 1 || gop > 65535) return set_error(CSIC_EFORMAT, "%s: gop must be in 1..65535. Got %u", path, gop);
+            coding = (int)c;
+            cb.gop = (int32_t)gop;
+            cb.map_bytes = map_bytes_of(G->pk);
+        } else if (get_u32(t.data()) != (uint32_t)coding || get_u32(t.data() + 4) != 0)
             return set_error(CSIC_EFORMAT, "%s: coding %u (reserved word %u) is not what version %u holds (%d, 0)", path, get_u32(t.data()), get_u32(t.data() + 4),
                              version, coding);
+        cb.coding = coding;
         const Codec codec = codec_of(*G, coding);
-        const uint64_t lo = codec.lo, hi = codec.hi;
         long long want = front;
         if (sizes) sizes->resize(nframes);
         for (uint32_t k = 0; k < nframes; ++k) {
             const uint64_t sz = get_u64(t.data() + CODED_BODY + 8 * (size_t)k);
+            const uint64_t map = k % (uint32_t)cb.gop ? (uint64_t)cb.map_bytes : 0, lo = codec.lo + map, hi = codec.hi + map;     // a delta record: map, then coded frame
             if (sz < lo || sz > hi || sz % 4 != 0)
                 return set_error(CSIC_EFORMAT, "%s: frame %u is stored in %llu bytes; these parameters code to %llu .. %llu, in dwords", path, k,
                                  (unsigned long long)sz, (unsigned long long)lo, (unsigned long long)hi);
@@ -135,6 +159,7 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Ric
     info->payload_bytes = L.payload_bytes;
     info->file_bytes = size;
     if (stored_crc) *stored_crc = get_u32(h + 12);
+    if (body) *body = cb;
     return CSIC_OK;
 }
 
@@ -160,24 +185,31 @@ static int writer_params(const csic_params *p, int32_t nframes, csic_params *q, 
     return CSIC_OK;
 }
 
-// A version-3 or version-4 file from coded frames in memory: frame k is frames[k][0, sizes[k]).
-static int write_coded_file(const char *path, const csic_params &q, const unsigned char *const *frames, const uint64_t *sizes, int32_t nframes, const Codec &codec)
+// A version-3 or version-4 file from coded frames in memory: frame k is frames[k][0, sizes[k]).  With a gop (> 0) a version-5 file:
+// maps[k][0, map_bytes) stands in front of every delta frame.
+static int write_coded_file(const char *path, const csic_params &q, const unsigned char *const *frames, const uint64_t *sizes, int32_t nframes, const Codec &codec,
+                            int32_t gop = 0, const unsigned char *const *maps = nullptr, size_t map_bytes = 0)
 {
+    const auto map_of = [&](int32_t k) { return gop > 0 && k % gop ? map_bytes : (size_t)0; };
     unsigned char h[CONTAINER_HEADER];
-    fill_header(h, codec.version, q, nframes);
+    fill_header(h, gop > 0 ? CONTAINER_VERSION_SEQ : codec.version, q, nframes);
     std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
     put_u32(t.data(), (uint32_t)codec.coding);
-    put_u32(t.data() + 4, 0);
-    for (int32_t k = 0; k < nframes; ++k) put_u64(t.data() + CODED_BODY + 8 * (size_t)k, sizes[k]);
+    put_u32(t.data() + 4, (uint32_t)gop);
+    for (int32_t k = 0; k < nframes; ++k) put_u64(t.data() + CODED_BODY + 8 * (size_t)k, sizes[k] + map_of(k));
     uLong crc = crc32(0L, h + CONTAINER_CRC_FROM, (uInt)(CONTAINER_HEADER - CONTAINER_CRC_FROM));
     crc = crc_long(crc, t.data(), (int64_t)t.size());
-    for (int32_t k = 0; k < nframes; ++k) crc = crc_long(crc, frames[k], (int64_t)sizes[k]);
+    for (int32_t k = 0; k < nframes; ++k) {
+        if (map_of(k)) crc = crc_long(crc, maps[k], (int64_t)map_bytes);
+        crc = crc_long(crc, frames[k], (int64_t)sizes[k]);
+    }
     put_u32(h + 12, (uint32_t)crc);
 
     FileCloser fc{fopen(path, "wb")};
     if (!fc.f) return set_error(CSIC_EIO, "cannot open %s for writing", path);
     bool ok = fwrite(h, 1, sizeof h, fc.f) == sizeof h && fwrite(t.data(), 1, t.size(), fc.f) == t.size();
-    for (int32_t k = 0; ok && k < nframes; ++k) ok = fwrite(frames[k], 1, (size_t)sizes[k], fc.f) == (size_t)sizes[k];
+    for (int32_t k = 0; ok && k < nframes; ++k)
+        ok = (!map_of(k) || fwrite(maps[k], 1, map_bytes, fc.f) == map_bytes) && fwrite(frames[k], 1, (size_t)sizes[k], fc.f) == (size_t)sizes[k];
     FILE *f = fc.f;
     fc.f = nullptr;
     if (fclose(f) != 0) ok = false;
@@ -330,6 +362,135 @@ int csic_container_write_coded(const char *path, const csic_params *p, const voi
     return csic_container_write_coded_ex(path, p, coded, stride_bytes, sizes, nframes, CSIC_CODING_GROUPS);
 }
 
+// csic_container_write_seq and csic_container_write_coded_seq: what they refuse of coding and gop
+static int seq_check(int32_t coding, int32_t gop)
+{
+    if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE)
+        return set_error(CSIC_EINVAL_FORMAT, "a sequence is coded with CSIC_CODING_GROUPS(1) or CSIC_CODING_RICE(3). Got %d", coding);
+    if (gop < 1 || gop > 65535) return set_error(CSIC_EINVAL_SIZE, "gop must be in 1..65535. Got %d", gop);
+    return CSIC_OK;
+}
+
+int csic_container_write_seq(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding, int32_t gop)
+{
+    if (!path || !p || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    int st = seq_check(coding, gop);
+    if (st != CSIC_OK) return st;
+    csic_params q;
+    RiceGeometry G;
+    DeltaGeometry D;
+    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = delta_geometry(&q, &D)) != CSIC_OK) return st;
+    const Codec codec = codec_of(G, coding);
+    try {
+        const size_t fb = (size_t)G.pk.bits.frame_bytes, mb = (size_t)D.layout.map_bytes;
+        const unsigned char *x = static_cast<const unsigned char *>(frames);
+        std::vector<unsigned char> diff(fb), maps((size_t)nframes * mb), all;
+        std::vector<uint64_t> sizes((size_t)nframes);
+        for (int32_t k = 0; k < nframes; ++k) {
+            delta_frame(D, x + (size_t)k * fb, k % gop ? x + (size_t)(k - 1) * fb : nullptr, diff.data(), maps.data() + (size_t)k * mb);
+            const size_t at = all.size();
+            all.resize(at + codec.bound);
+            st = codec.pack(G, diff.data(), all.data() + at, codec.bound, &sizes[k]);
+            if (st != CSIC_OK) return st;
+            all.resize(at + (size_t)sizes[k]);
+        }
+        std::vector<const unsigned char *> ptrs((size_t)nframes), mptrs((size_t)nframes);
+        size_t at = 0;
+        for (int32_t k = 0; k < nframes; ++k) { ptrs[k] = all.data() + at; at += (size_t)sizes[k]; mptrs[k] = maps.data() + (size_t)k * mb; }
+        st = write_coded_file(path, q, ptrs.data(), sizes.data(), nframes, codec, gop, mptrs.data(), mb);
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory coding %d frames for %s", nframes, path);
+    }
+    if (st != CSIC_OK) return st;
+    clear_error();
+    return CSIC_OK;
+}
+
+int csic_container_write_coded_seq(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
+                                   const void *maps, size_t map_stride, int32_t nframes, int32_t coding, int32_t gop)
+{
+    if (!path || !p || !coded || !sizes || !maps) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    int st = seq_check(coding, gop);
+    if (st != CSIC_OK) return st;
+    csic_params q;
+    RiceGeometry G;
+    DeltaGeometry D;
+    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = delta_geometry(&q, &D)) != CSIC_OK) return st;
+    if (map_stride < (size_t)D.layout.map_bytes)
+        return set_error(CSIC_EINVAL_SIZE, "a map of these parameters has %lld bytes: a map_stride of %zu cannot hold it", (long long)D.layout.map_bytes, map_stride);
+    const Codec codec = codec_of(G, coding);
+    try {
+        std::vector<const unsigned char *> ptrs((size_t)nframes), mptrs((size_t)nframes);
+        for (int32_t k = 0; k < nframes; ++k) {
+            if (sizes[k] > stride_bytes)
+                return set_error(CSIC_EINVAL_SIZE, "frame %d: %llu coded bytes do not fit the stride of %zu", k, (unsigned long long)sizes[k], stride_bytes);
+            ptrs[k] = static_cast<const unsigned char *>(coded) + (size_t)k * stride_bytes;
+            mptrs[k] = static_cast<const unsigned char *>(maps) + (size_t)k * map_stride;
+            if ((st = codec.check(G, ptrs[k], (size_t)sizes[k])) != CSIC_OK || (st = delta_check_map(D, mptrs[k], k % gop == 0, k)) != CSIC_OK) return st;
+        }
+        st = write_coded_file(path, q, ptrs.data(), sizes, nframes, codec, gop, mptrs.data(), (size_t)D.layout.map_bytes);
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory writing %s", path);
+    }
+    if (st != CSIC_OK) return st;
+    clear_error();
+    return CSIC_OK;
+}
+
+int csic_container_gop(const char *path, int32_t *gop)
+{
+    if (!path || !gop) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    FileCloser fc{fopen(path, "rb")};
+    if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
+    try {
+        RiceGeometry G;
+        csic_container_info ci;
+        CodedBody body;
+        const int st = read_header(fc.f, path, &ci, &G, nullptr, nullptr, &body);
+        if (st != CSIC_OK) return st;
+        *gop = body.gop;
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
+    }
+    clear_error();
+    return CSIC_OK;
+}
+
+int csic_container_inter_groups(const char *path, uint64_t *counts, int32_t n)
+{
+    if (!path || !counts) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    FileCloser fc{fopen(path, "rb")};
+    if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
+    try {
+        RiceGeometry G;
+        DeltaGeometry D;
+        csic_container_info ci;
+        CodedBody body;
+        std::vector<uint64_t> table;
+        int st = read_header(fc.f, path, &ci, &G, nullptr, &table, &body);
+        if (st != CSIC_OK) return st;
+        if (n != 3 * ci.nframes) return set_error(CSIC_EINVAL_SIZE, "expected room for %d counts, got %d", 3 * ci.nframes, n);
+        std::vector<uint64_t> got((size_t)n, 0);
+        if (body.map_bytes > 0 && (st = delta_geometry(&ci.params, &D)) != CSIC_OK) return st;
+        std::vector<unsigned char> map((size_t)body.map_bytes);
+        long long at = ftello(fc.f);                   // where the records begin
+        for (int32_t k = 0; k < ci.nframes; ++k) {
+            if (body.map_bytes > 0 && k % body.gop) {
+                if (fseeko(fc.f, at, SEEK_SET) != 0 || fread(map.data(), 1, map.size(), fc.f) != map.size()) return set_error(CSIC_EIO, "cannot read %s", path);
+                if ((st = delta_check_map(D, map.data(), false, k)) != CSIC_OK) return st;
+                for (int pl = 0; pl < 3; ++pl)
+                    for (int64_t b = 0; b < 4 * ((D.layout.groups[pl] + 31) / 32); ++b) got[3 * (size_t)k + pl] += (uint64_t)__builtin_popcount(map[D.layout.map_offset[pl] + b]);
+            }
+            at += (long long)table[k];
+        }
+        std::memcpy(counts, got.data(), got.size() * sizeof(uint64_t));
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
+    }
+    clear_error();
+    return CSIC_OK;
+}
+
 static int container_read(const char *path, void *frames, size_t frames_bytes)
 {
     FileCloser fc{fopen(path, "rb")};
@@ -338,9 +499,12 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
     csic_container_info ci;
     uint32_t stored = 0;
     std::vector<uint64_t> sizes;
-    int st = read_header(fc.f, path, &ci, &C, &stored, &sizes);
+    CodedBody body;
+    int st = read_header(fc.f, path, &ci, &C, &stored, &sizes, &body);
     if (st != CSIC_OK) return st;
     const PackGeometry &G = C.pk;
+    DeltaGeometry D;
+    if (ci.version == (int32_t)CONTAINER_VERSION_SEQ && (st = delta_geometry(&ci.params, &D)) != CSIC_OK) return st;
     const csic_planar_bits_layout &L = G.bits;
     const size_t need = (size_t)ci.nframes * (size_t)L.frame_bytes;
     if (frames_bytes != need)
@@ -355,7 +519,7 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
     unsigned char *base = static_cast<unsigned char *>(frames);
     std::memset(base, 0, need);
     std::vector<unsigned char> coded;
-    const Codec codec = codec_of(C, ci.version == (int32_t)CONTAINER_VERSION_RICE ? CSIC_CODING_RICE : CSIC_CODING_GROUPS);   // (unused by version 1)
+    const Codec codec = codec_of(C, body.coding);     // (unused by version 1)
     for (int32_t k = 0; k < ci.nframes && st == CSIC_OK; ++k) {
         unsigned char *fr = base + (int64_t)k * L.frame_bytes;
         if (ci.version == (int32_t)CONTAINER_VERSION) {
@@ -368,7 +532,10 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
             coded.resize((size_t)sizes[k]);            // within the coding's sizes: read_header checked the table
             if (fread(coded.data(), 1, coded.size(), fc.f) != coded.size()) return set_error(CSIC_EIO, "cannot read %s", path);
             crc = crc_long(crc, coded.data(), (int64_t)coded.size());
-            st = codec.unpack(C, coded.data(), coded.size(), fr);
+            const size_t map = k % body.gop ? (size_t)body.map_bytes : 0;      // version 5: a delta frame's map first (read_header: the record holds it)
+            if (map) st = delta_check_map(D, coded.data(), false, k);
+            if (st == CSIC_OK) st = codec.unpack(C, coded.data() + map, coded.size() - map, fr);
+            if (st == CSIC_OK && map) undelta_frame(D, fr, coded.data(), fr - L.frame_bytes, fr);      // the difference frame -> the frame, in place
         }
     }
     if (st == CSIC_OK && (uint32_t)crc != stored)

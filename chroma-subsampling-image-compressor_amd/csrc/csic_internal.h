@@ -56,6 +56,21 @@ int rice_pack_frame(const RiceGeometry &G, const unsigned char *frame, unsigned 
 int rice_unpack_frame(const RiceGeometry &G, const unsigned char *coded, size_t coded_bytes, unsigned char *frame);
 int rice_check_coded(const RiceGeometry &G, const unsigned char *coded, size_t coded_bytes);
 
+// csic_delta_host.cpp: the temporal layer (csic.h: csic_delta_*).  `pk` is the group coding's geometry of the same parameters; `layout`
+// is the map's.  delta_frame writes the difference frame of `cur` against `prev` (NULL: a key frame) and its map; undelta_frame is the
+// inverse; both allow diff == cur.  delta_check_map is what csic_undelta_host and the container ask of a map nobody vouches for.
+struct DeltaGeometry {
+    PackGeometry pk;
+    csic_delta_layout layout;
+};
+int delta_geometry(const csic_params *p, DeltaGeometry *G);
+void delta_frame(const DeltaGeometry &G, const unsigned char *cur, const unsigned char *prev, unsigned char *diff, unsigned char *map);
+void undelta_frame(const DeltaGeometry &G, const unsigned char *diff, const unsigned char *map, const unsigned char *prev, unsigned char *cur);
+int delta_check_map(const DeltaGeometry &G, const unsigned char *map, bool key, int frame);
+// what the four csic_delta_* / csic_undelta_* entry points refuse (NULLs are the callers'): nframes, gop, and any overlap of the three
+// buffers other than diff == frames exactly
+int delta_check_call(const DeltaGeometry &G, const void *frames, const void *diff, const void *maps, int32_t nframes, int32_t gop);
+
 // Exact unsigned division by a run-time constant without a divide (k_generic's stream-index arithmetic): for
 // 1 <= d < 2^31 and every n < 2^31,  n / d == (uint64(n) * m) >> k  with  k = 31 + ceil(log2 d),  m = ceil(2^k / d) < 2^32.
 // (Error term e = m*d - 2^k < d <= 2^ceil(log2 d), and n * e < 2^31 * 2^ceil(log2 d) = 2^k.)  Host side, csic_host.cpp;

@@ -1,6 +1,8 @@
-// csic_pack_common.h -- what the device codecs of the group coding (csic_pack.hip) and of the Rice coding (csic_rice.hip) share.
-// Device: the kernels' argument, the checked accessors of the PLANAR_BITS and the coded frames, the block scan, the load of a group with
-// its folded residuals, the store of a block's nibble and anchors sections, the reads of a group's nibble and anchor, and the
+// csic_pack_common.h -- what the device codecs of the group coding (csic_pack.hip) and of the Rice coding (csic_rice.hip) share, and the
+// temporal layer in front of them (csic_delta.hip) with both.
+// Device: the kernels' argument, the checked accessors of the PLANAR_BITS and the coded frames, the block scan, the load of a group's
+// dwords with the ragged-tail rule, the cut of one code and the fold of one residual, and from them the load of a group with its folded
+// residuals, the store of a block's nibble and anchors sections, the reads of a group's nibble and anchor, and the
 // accumulator that a decoded group is repacked in and stored from (the unfold u -> e is rice_unfold of csic_rice_decode.h, shared with
 // the host codecs).  Host: the filler of the argument from pack_geometry and a coding's own offsets, the refusals and the workspace
 // size of the entry points, the launch of one kernel per run of planes of equal width, the launch of the scan over a frame's block
@@ -76,20 +78,16 @@ __device__ __forceinline__ uint32_t pk_block_scan(uint32_t v, uint32_t *s_tot, u
     return before + inc - v;
 }
 
-// Group g of a plane -> its 32 folded residuals, its width (returned) and its anchor.
+// The Q dwords of group g of a plane: whole dwords, or -- the plane ends in this group -- byte by byte up to the last byte that holds
+// a sample (the bytes behind it read as 0).
 template <int Q, bool NT>
-__device__ __forceinline__ uint32_t pk_fold_group(const PkArgs &e, gpdst_t fb, int plane, uint32_t g, uint32_t (&u)[32], uint32_t &anchor)
+__device__ __forceinline__ void pk_load_group(const PkArgs &e, gpdst_t fb, int plane, uint32_t g, uint32_t (&d)[Q])
 {
-    constexpr uint32_t MASK = (1u << Q) - 1u, HALF = 1u << (Q - 1);
-    const uint32_t n = e.n[plane];
     const int64_t base = e.off[plane] + 4 * (int64_t)g * Q;
-    const bool whole = 32u * g + 32u <= n;             // (g < 2^26)
-    uint32_t d[Q];
-    if (whole) {
+    if (32u * g + 32u <= e.n[plane]) {                 // (g < 2^26)
 #pragma unroll
         for (int i = 0; i < Q; ++i) d[i] = pk_bits_ld4<NT>(e, fb, base + 4 * i);
     } else {
-        // the plane ends in this group: byte by byte up to the last byte that holds a sample
         const int64_t end = e.off[plane] + e.bytes[plane];
 #pragma unroll
         for (int i = 0; i < Q; ++i) {
@@ -99,14 +97,36 @@ __device__ __forceinline__ uint32_t pk_fold_group(const PkArgs &e, gpdst_t fb, i
                 if (base + 4 * i + k < end) d[i] |= pk_bits_ld1(e, fb, base + 4 * i + k) << (8 * k);
         }
     }
+}
+
+// the code of slot j of a group's Q dwords (j a constant of an unrolled loop: compile-time shifts)
+template <int Q> __device__ __forceinline__ uint32_t pk_code(const uint32_t (&d)[Q], int j)
+{
+    const int w = (j * Q) >> 5, s = (j * Q) & 31;
+    uint32_t v = d[w] >> s;
+    if (s + Q > 32) v |= d[(w + 1) % Q] << ((32 - s) & 31);         // (w + 1 < Q whenever a code straddles)
+    return v & ((1u << Q) - 1u);
+}
+
+// the folded, centred residual u of a difference r = (c_j - c_(j - 1)) mod 2^Q
+template <int Q> __device__ __forceinline__ uint32_t pk_fold(uint32_t r)
+{
+    constexpr uint32_t MASK = (1u << Q) - 1u, HALF = 1u << (Q - 1);
+    return r < HALF ? 2u * r : 2u * (MASK + 1u - r) - 1u;
+}
+
+// Group g of a plane -> its 32 folded residuals, its width (returned) and its anchor.
+template <int Q, bool NT>
+__device__ __forceinline__ uint32_t pk_fold_group(const PkArgs &e, gpdst_t fb, int plane, uint32_t g, uint32_t (&u)[32], uint32_t &anchor)
+{
+    constexpr uint32_t MASK = (1u << Q) - 1u;
+    const uint32_t n = e.n[plane];
+    const bool whole = 32u * g + 32u <= n;
+    uint32_t d[Q];
+    pk_load_group<Q, NT>(e, fb, plane, g, d);
     uint32_t c[32];
 #pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int w = (j * Q) >> 5, s = (j * Q) & 31;
-        uint32_t v = d[w] >> s;
-        if (s + Q > 32) v |= d[(w + 1) % Q] << ((32 - s) & 31);     // (w + 1 < Q whenever a code straddles)
-        c[j] = v & MASK;
-    }
+    for (int j = 0; j < 32; ++j) c[j] = pk_code<Q>(d, j);
     if (!whole) {
         // behind the last sample: the last real code again (bits there are never read into a value)
 #pragma unroll
@@ -118,8 +138,7 @@ __device__ __forceinline__ uint32_t pk_fold_group(const PkArgs &e, gpdst_t fb, i
     u[0] = 0;
 #pragma unroll
     for (int j = 1; j < 32; ++j) {
-        const uint32_t r = (c[j] - c[j - 1]) & MASK;
-        u[j] = r < HALF ? 2u * r : 2u * (MASK + 1u - r) - 1u;
+        u[j] = pk_fold<Q>((c[j] - c[j - 1]) & MASK);
         any |= u[j];
     }
     return any ? 32u - (uint32_t)__builtin_clz(any) : 0u;

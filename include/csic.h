@@ -806,6 +806,70 @@ int  csic_rice_pack_device(csic_plan *plan, const void *d_bits, int32_t nframes,
 int  csic_rice_unpack_device(csic_plan *plan, const void *d_coded, int32_t nframes, void *d_bits, void *hip_stream);
 const char *csic_rice_kernel_name(const csic_plan *plan);
 
+/* ---- temporal delta coding of frame sequences (csic_delta_*) ------------------------------------------------------------------------
+ * Both codings above code every frame on its own.  This layer sits in front of them: it turns a sequence of CSIC_FMT_PLANAR_BITS
+ * frames into a sequence of DIFFERENCE frames of the same layout, which either coding then codes as it codes any frame, and one small
+ * map per frame.  It is lossless.  Prediction across the groups of a frame would need a scan over a plane; across frames the
+ * dependency is per sample -- sample i of frame k depends on sample i of frame k - 1 only -- so encode and decode stay one lane per
+ * group.  There is no motion compensation: content that stays in place gains, a pan gains nothing and loses the map at most.
+ *
+ * Input: frames x_0 .. x_(n - 1) of one parameter set and gop >= 1.  Frame k is a KEY frame iff k % gop == 0; every other frame is a
+ * DELTA frame against x_(k - 1), the source frame itself (the coding is lossless: the decoder has it exactly).  Planes, q_p, n_p and the
+ * groups of 32 (G_p = ceil(n_p / 32)) are those of csic_pack_*.
+ *
+ * For group g of a delta frame, with c the frame's codes and r the previous frame's, slot by slot:
+ *     d_i     = (c_i - r_i) mod 2^q
+ *     cost(v) = the sum over the group's real slots j >= 1 of u_j, the folded, centred left residuals of csic_pack_* computed over the
+ *               values v; slots behind the plane's last sample add nothing (a group of one sample costs 0 either way)
+ *     t_g     = 1 (inter) iff cost(d) < cost(c); a tie is intra
+ * The group of the difference frame D_k holds d where t_g = 1 and c where t_g = 0.  D_k is a PLANAR_BITS frame: the bits behind a
+ * plane's last sample are 0, bytes outside the three payload ranges are not written.  For a key frame D_k = x_k.
+ *
+ * The map of a frame has three sections, Y, Cb, Cr, of 4 * ceil(G_p / 32) bytes each: bit g of a section (LSB first) is t_g, padding
+ * bits are 0, the map of a key frame is all zeros.  map_bytes is the sum of the sections, map_stride the next multiple of 256: the
+ * distance between the maps of consecutive frames in a buffer of maps, on the host and on the device.  A buffer of `nframes` maps
+ * needs (nframes - 1) * map_stride + map_bytes bytes; bytes of a map behind its map_bytes are not touched.
+ *
+ * Inverse, frame after frame from each key frame: c_i = (d_i + r_i) mod 2^q where t_g = 1, c_i = d_i otherwise.
+ *
+ * Worked vectors, one plane alone, q = 3 (the bytes are the plane's payload in the bit layout):
+ *     identical frames   c = r = 1,2,3,4,5,6,7,0: d = 0 x 8, cost(d) = 0 < cost(c) = 14 -> map 01 00 00 00, D = 00 00 00
+ *     a tie              c = 0,1 and r = 1,1: d = 7,0, cost(d) = 2 = cost(c) -> intra, map 00 00 00 00, D = 08
+ *     the wrap           c = 0,4,0 and r = 7,3,7 (2^q - 1 under a 0): d = 1,1,1, cost(d) = 0 < cost(c) = 14 -> map 01 00 00 00,
+ *                        D = 49 00; back: (1 + 7) mod 8 = 0
+ *     a ragged group     q = 2, n = 34: group 1 has the two samples 32, 33.  c = 3,0 and r = 2,3 there: d = 1,1, cost(d) = 0 <
+ *                        cost(c) = 2 -> bit 1 of the map; the 30 slots behind sample 33 take no part and are stored as zero bits
+ *
+ * Host codec (no GPU; parameters and statuses as for csic_pack_*):
+ *   csic_delta_layout_of : groups, the sections' offsets, map_bytes and map_stride of these parameters.
+ *   csic_delta_host      : frames (frame_bytes apart) -> diff (frame_bytes apart) and maps (map_stride apart).
+ *   csic_undelta_host    : the inverse.  The maps are untrusted: a padding bit that is set or a non-zero map of a key frame gives
+ *                          CSIC_EFORMAT; a refused call writes nothing.  (The difference frames need no check: any codes are codes.)
+ * Device codec (gfx950): asynchronous on `hip_stream`, no allocation, no synchronisation, no workspace, hipGraph-capturable; one launch
+ * per run of planes of one width, grid z over the ceil(nframes / gop) runs of frames that begin with a key frame; a lane walks its
+ * group through a run with the previous frame's group in registers, so every frame is read once and written once.
+ *   csic_delta_device    : d_frames -> d_diff and d_maps; the source is only read.
+ *   csic_undelta_device  : the inverse.  It does NOT validate and has nothing to clamp: any map bit decodes to valid codes; a key
+ *                          frame's map is ignored.
+ *   csic_delta_kernel_name : "k_delta<q6,5,5,nt>", as csic_pack_kernel_name.
+ * For all four calls: diff == frames, exactly in place, is allowed; any other overlap of the frames, the difference frames and the
+ * maps is CSIC_EINVAL_SIZE, as are nframes outside 1..65535, gop < 1 (a gop above nframes means one key frame) and, on the device, a
+ * buffer that is not 256-byte aligned.  NULL arguments: CSIC_EINVAL_NULL; parameters the container does not take: csic_validate's
+ * status -- all before any device is touched.  CSIC_TUNE_NONTEMPORAL applies to the accesses of the frames; the other knobs are ignored. */
+typedef struct csic_delta_layout {
+    int64_t groups[3];             /* G_p                                                              */
+    int64_t map_offset[3];         /* byte offsets of the sections inside a map                        */
+    int64_t map_bytes;             /* sum_p 4 * ceil(G_p / 32)                                         */
+    int64_t map_stride;            /* multiple of 256: the distance of maps in a buffer of maps        */
+} csic_delta_layout;
+int  csic_delta_layout_of(const csic_params *p, csic_delta_layout *layout);
+int  csic_delta_host(const csic_params *p, const void *frames, int32_t nframes, int32_t gop, void *diff, void *maps);
+int  csic_undelta_host(const csic_params *p, const void *diff, const void *maps, int32_t nframes, int32_t gop, void *frames);
+int  csic_delta_device(csic_plan *plan, const void *d_frames, int32_t nframes, int32_t gop, void *d_diff, void *d_maps, void *hip_stream);
+int  csic_undelta_device(csic_plan *plan, const void *d_diff, const void *d_maps, int32_t nframes, int32_t gop, void *d_frames,
+                         void *hip_stream);
+const char *csic_delta_kernel_name(const csic_plan *plan);
+
 /* ---- .csic files: the compressed frames on disk (host only, usable without a GPU) --------------------------------------------
  * A container holds `nframes` CSIC_FMT_PLANAR_BITS frames of one parameter set: the only thing this library writes to a file that
  * is smaller than its input (a 6/5/5 4:2:0 frame: 1.06 bytes per pixel at factor 1; group-coded, version 3 below, less).  Version 1,
@@ -828,7 +892,7 @@ const char *csic_rice_kernel_name(const csic_plan *plan);
  *                            when the parameters are invalid or p->in_format is not ARGB; nframes outside 1 .. 65535: CSIC_EINVAL_SIZE.
  *   csic_container_info_of : header, parameters and length of a file (everything csic_container_read checks except the CRC).
  *   csic_container_read    : frames_bytes must equal nframes * frame_bytes (CSIC_EINVAL_SIZE otherwise; ask csic_container_info_of).
- * CSIC_EFORMAT: bad magic, a version other than 1, 3 or 4, nframes out of range, parameters that fail csic_validate (or are not
+ * CSIC_EFORMAT: bad magic, a version other than 1, 3, 4 or 5, nframes out of range, parameters that fail csic_validate (or are not
  * PLANAR_BITS), a length other than 80 + nframes * payload_bytes, a CRC mismatch.  CSIC_EIO: the file cannot be opened, read or
  * written.  NULL arguments: CSIC_EINVAL_NULL.
  *
@@ -858,7 +922,33 @@ const char *csic_rice_kernel_name(const csic_plan *plan);
  *   csic_container_write_ex       : CSIC_CODING_RICE packs every frame on the host (csic_rice_pack_host) and writes version 4.
  *   csic_container_write_coded_ex : csic_container_write_coded for either coding (CSIC_CODING_GROUPS or CSIC_CODING_RICE; another:
  *                                   CSIC_EINVAL_FORMAT); csic_container_write_coded keeps meaning CSIC_CODING_GROUPS.
- *   csic_container_read, csic_container_info_of, csic_container_coded_sizes read versions 1, 3 and 4. */
+ *   csic_container_read, csic_container_info_of, csic_container_coded_sizes read versions 1, 3 and 4.
+ *
+ * Version 5 holds a SEQUENCE: the frames go through the temporal layer (csic_delta_*) and their difference frames through one of the
+ * two codings.  Bytes 0 .. 79 are as in version 1 with version = 5, the CRC covers [16, end of file), and the body is
+ *
+ *         80     4                     uint32 coding = 1 (CSIC_CODING_GROUPS) or 3 (CSIC_CODING_RICE)
+ *         84     4                     uint32 gop, 1 .. 65535
+ *         88     8 * nframes           uint64 stored bytes of each frame's record
+ *         88 + 8 * nframes             the records back to back: a key frame (k % gop == 0) is its coded frame exactly as in version
+ *                                      3 / 4; a delta frame is its map (map_bytes of csic_delta_layout_of) followed by the coded frame
+ *                                      of its difference frame
+ *
+ *   csic_container_write_seq       : delta (csic_delta_host) and packing on the host, version 5.  coding other than GROUPS or RICE:
+ *                                    CSIC_EINVAL_FORMAT; gop outside 1 .. 65535: CSIC_EINVAL_SIZE.
+ *   csic_container_write_coded_seq : version 5 from what the device made: coded difference frames coded[k * stride_bytes, + sizes[k])
+ *                                    (sizes[k] is the coded frame's bytes, without the map) and the maps, map_stride apart (the maps of
+ *                                    key frames are read too: they must be zero).  Every coded frame and every map is validated
+ *                                    before anything is written (CSIC_EFORMAT); sizes[k] > stride_bytes or map_stride < map_bytes:
+ *                                    CSIC_EINVAL_SIZE.
+ *   csic_container_gop             : the gop of a version-5 file; 1 for versions 1, 3 and 4 (every frame stands alone).
+ *   csic_container_inter_groups    : counts[3 k + p] = the groups of plane p of frame k that are inter, the popcount of that section of
+ *                                    the map; n must be 3 * nframes (CSIC_EINVAL_SIZE otherwise).  All zeros for versions 1, 3 and 4.
+ *   csic_container_read resolves the chains on the host and returns the frames themselves; csic_container_info_of reports version 5;
+ *   csic_container_coded_sizes gives the table (maps included).
+ * CSIC_EFORMAT for a version-5 file, beyond the cases of versions 3 / 4 (with the sizes of the file's coding; a delta record holds
+ * map_bytes more): a coding other than 1 or 3, a gop out of range, a delta record shorter than map_bytes + fixed_bytes, a padding bit
+ * that is set in a map, any coded frame the coding's host decoder refuses.  Versions 1, 3 and 4 keep their behaviour. */
 typedef struct csic_container_info {
     csic_params params;            /* out_format = CSIC_FMT_PLANAR_BITS, in_format = CSIC_FMT_ARGB8888 */
     int32_t version, nframes;
@@ -874,6 +964,11 @@ int  csic_container_write_coded(const char *path, const csic_params *p, const vo
 int  csic_container_write_coded_ex(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
                                    int32_t nframes, int32_t coding);
 int  csic_container_coded_sizes(const char *path, uint64_t *sizes, int32_t n);
+int  csic_container_write_seq(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding, int32_t gop);
+int  csic_container_write_coded_seq(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
+                                    const void *maps, size_t map_stride, int32_t nframes, int32_t coding, int32_t gop);
+int  csic_container_gop(const char *path, int32_t *gop);
+int  csic_container_inter_groups(const char *path, uint64_t *counts, int32_t n);
 
 /* ---- host-frame pipeline (the step either side of the hot path) -----------------------------------
  * Replaces the reference's per-image  readImage -> per-pixel poke ... peek -> writeImage  flow

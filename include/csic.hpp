@@ -209,6 +209,53 @@ inline std::vector<uint8_t> riceUnpack(const csic_params &p, const void *coded, 
     return frame;
 }
 
+// The temporal layer in front of either coding (csic.h: csic_delta_*), host codec: needs no GPU.  delta: nframes frame buffers
+// (frame_bytes apart) -> their difference frames (zero outside the planes' payload) and the maps (map_stride apart, map_bytes of each
+// written); undelta: the inverse, damaged maps surface as csic::RuntimeError with status CSIC_EFORMAT.
+struct DeltaFrames {
+    std::vector<uint8_t> diff, maps;
+};
+inline csic_delta_layout deltaLayout(const csic_params &p)
+{
+    csic_delta_layout layout;
+    check(csic_delta_layout_of(&p, &layout));
+    return layout;
+}
+inline DeltaFrames delta(const csic_params &p, const void *frames, int nframes, int gop)
+{
+    csic_params q = p;
+    q.out_format = CSIC_FMT_PLANAR_BITS;
+    csic_planar_bits_layout layout;
+    check(csic_planar_bits_layout_of(&q, &layout));
+    DeltaFrames d;
+    d.diff.assign((size_t)(nframes > 0 ? nframes : 0) * (size_t)layout.frame_bytes, 0);
+    d.maps.assign((size_t)(nframes > 0 ? nframes : 0) * (size_t)deltaLayout(p).map_stride, 0);
+    check(csic_delta_host(&p, frames, nframes, gop, d.diff.data(), d.maps.data()));
+    return d;
+}
+inline std::vector<uint8_t> undelta(const csic_params &p, const void *diff, const void *maps, int nframes, int gop)
+{
+    csic_params q = p;
+    q.out_format = CSIC_FMT_PLANAR_BITS;
+    csic_planar_bits_layout layout;
+    check(csic_planar_bits_layout_of(&q, &layout));
+    std::vector<uint8_t> frames((size_t)(nframes > 0 ? nframes : 0) * (size_t)layout.frame_bytes, 0);
+    check(csic_undelta_host(&p, diff, maps, nframes, gop, frames.data()));
+    return frames;
+}
+// version 5: the frames as a sequence, delta and packing on the host (coding CSIC_CODING_GROUPS or CSIC_CODING_RICE); readContainer
+// returns the frames themselves
+inline void writeContainerSeq(const std::string &file, const csic_params &p, const void *frames, int nframes, int coding, int gop)
+{
+    check(csic_container_write_seq(file.c_str(), &p, frames, nframes, coding, gop));
+}
+inline int containerGop(const std::string &file)
+{
+    int32_t gop = 0;
+    check(csic_container_gop(file.c_str(), &gop));
+    return gop;
+}
+
 // The six sums of squared errors of one frame (csic.h: csic_distortion_*), in the order R, G, B, Y, Cb, Cr, over `pixels` input
 // pixels, with the PSNR helpers (+inf at zero error).
 struct Distortion {
@@ -369,6 +416,19 @@ public:
         check(csic_rice_unpack_device(plan_, d_coded, nframes, d_bits, hip_stream));
     }
     const char *riceKernelName() { return csic_rice_kernel_name(plan_); }
+    // the temporal layer over this plan's PLANAR_BITS frames, host and device (no workspace; d_diff may be d_frames, in place)
+    csic_delta_layout deltaLayout() const { return csic::deltaLayout(params_); }
+    DeltaFrames delta(const void *frames, int nframes, int gop) const { return csic::delta(params_, frames, nframes, gop); }
+    std::vector<uint8_t> undelta(const void *diff, const void *maps, int nframes, int gop) const { return csic::undelta(params_, diff, maps, nframes, gop); }
+    void deltaDevice(const void *d_frames, int nframes, int gop, void *d_diff, void *d_maps, void *hip_stream)
+    {
+        check(csic_delta_device(plan_, d_frames, nframes, gop, d_diff, d_maps, hip_stream));
+    }
+    void undeltaDevice(const void *d_diff, const void *d_maps, int nframes, int gop, void *d_frames, void *hip_stream)
+    {
+        check(csic_undelta_device(plan_, d_diff, d_maps, nframes, gop, d_frames, hip_stream));
+    }
+    const char *deltaKernelName() { return csic_delta_kernel_name(plan_); }
 
 private:
     csic_params params_;
