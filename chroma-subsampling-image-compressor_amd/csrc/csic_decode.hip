@@ -10,7 +10,7 @@
 //                      source positions at F = 1 / 2 / 4 / 8 (planar sources: the two dwords that hold their codes in each plane,
 //                      k_rbits' replay rule, PLANAR being the bit-packed frame at 8 / 8 / 8; packed sources: one 16 / 8 / 4-byte load),
 //                      so the inverse transform runs once per source pixel up to F = 4 and twice at F = 8.  K = 4 / 2 / 1 pieces per
-//                      lane, spaced by the block size, all loads issued before any arithmetic.  Conditions (decode_kind): width % 4 == 0
+//                      lane, spaced by the block size, all loads issued before any arithmetic.  Conditions (plan_decode, csic_select.cpp): width % 4 == 0
 //                      (pieces tile the rows; the NP positions of a piece then start at a multiple of NP in a chroma row whose length
 //                      is a multiple of NP, whatever the order class), width * height <= 2^30 (32-bit byte offsets), output and packed source
 //                      16-byte aligned.  The height is free: a ragged last source row stores fewer rows.
@@ -84,8 +84,7 @@ __device__ __forceinline__ uint32_t dec_pixel(const DecArgs &e, gcbyte_t fb, uin
 // ------------------------------------------------------------------------------------------------
 // A lane owns one PIECE: 4 consecutive output pixels of one output row, written to the F output rows of its source row.  Its NP
 // source positions (4 / F of them, at least 1) are consecutive and start at a multiple of NP.
-template <int F> constexpr int dec_np() { return F == 1 ? 4 : F == 2 ? 2 : 1; }
-template <int F> constexpr int dec_pieces_per_lane() { return F == 1 ? 4 : F == 2 ? 2 : 1; }
+template <int F> constexpr int dec_np() { return F == 1 ? 4 : F == 2 ? 2 : 1; }      // (pieces per lane: dec_pieces_per_lane, csic_select.h)
 
 // what a lane holds of its source positions once its loads are back
 struct DecGroup {
@@ -150,7 +149,7 @@ __device__ __forceinline__ void dec_group_pixels(const DecArgs &e, const DecGrou
 template <int SRC, int FMT, int F, bool NT, bool CHECK>
 __device__ __forceinline__ void decode_body(const DecArgs &e, gcbyte_t fb, gout_t out, uint32_t t0, uint32_t T, uint32_t npieces)
 {
-    constexpr int K = dec_pieces_per_lane<F>(), NP = dec_np<F>();
+    constexpr int K = dec_pieces_per_lane(F), NP = dec_np<F>();
     constexpr int LF = F == 1 ? 0 : F == 2 ? 1 : F == 4 ? 2 : 3;
     DecGroup grp[K];
     uint32_t ro[K], pc[K];
@@ -183,7 +182,7 @@ __global__ void __launch_bounds__(256) k_decode(DecArgs e)
 {
     const uint32_t T = (uint32_t)e.T;
     const uint32_t npieces = (uint32_t)e.npieces;                      // (W / 4) * out_height
-    const uint32_t per_block = T * (uint32_t)dec_pieces_per_lane<F>();
+    const uint32_t per_block = T * (uint32_t)dec_pieces_per_lane(F);
     const uint32_t b0 = blockIdx.x * per_block;
     const gcbyte_t fb = dec_src(e);
     const gout_t out = dec_dst(e);
@@ -249,22 +248,7 @@ static void fill_dec_args(const csic_plan *pl, int src_format, DecArgs *e)
     e->nwhole = (int64_t)e->P * (g.H / g.f);
 }
 
-enum { DEC_GEN = 0, DEC_FAST = 1, DEC_RECON = 2 };
-
-// which kernel a call takes; align_bits: the output pointer, OR-ed with the source pointer for a packed source
-static int decode_kind(const csic_plan *pl, int src_format, uintptr_t align_bits, int nframes)
-{
-    const Geometry &g = pl->g;
-    if (pl->tune.variant == 9 || pl->tune.force_generic || pl->tune.no_vec || (align_bits & 15u)) return DEC_GEN;
-    // the reconstruct kernels store 16 bytes at a time from each frame's base: frames after the first start 4 W H bytes further on
-    if (g.f == 1 && dec_is_planar(src_format) && (nframes == 1 || ((int64_t)g.W * g.H) % 4 == 0)) return DEC_RECON;
-    // width % 4 == 0 is all a planar source needs too: the module width is W or out_width, a multiple of NP (4 at factor 1, 2 at 2, 1
-    // above), and so is every piece's first stream position
-    if (g.W % 4 != 0 || (int64_t)g.W * g.H > ((int64_t)1 << 30)) return DEC_GEN;
-    return DEC_FAST;
-}
-
-static DecFn decode_kernel(int kind, int src_format, int out_format, int f, bool nt)
+static DecFn decode_kernel(DecodeKind kind, int src_format, int out_format, int f, bool nt)
 {
     // an ARGB source is only ever replicated (ARGB -> YCbCr is refused): it takes the YCbCr -> YCbCr instantiations, a plain copy
     if (src_format == S_ARGB) { src_format = S_YCC; out_format = F_YCC; }
@@ -281,15 +265,6 @@ static DecFn decode_kernel(int kind, int src_format, int out_format, int f, bool
             });
         });
     });
-}
-
-static const char *dec_src_name(int src_format)
-{
-    switch (src_format) {
-    case CSIC_FMT_PLANAR_BITS: return "bits";
-    case CSIC_FMT_PLANAR: return "planar";
-    default: return "ycc";
-    }
 }
 
 static int decode_check_formats(int32_t src_format, int32_t out_format)
@@ -313,20 +288,9 @@ const char *csic_decode_kernel_name(const csic_plan *plan, int32_t src_format, i
 {
     static thread_local char buf[96];
     if (!plan || decode_check_formats(src_format, out_format) != CSIC_OK) return "";
-    // an ARGB source runs the YCbCr -> YCbCr instantiation (a copy): the name is the kernel's, as a profiler shows it
-    const char *fmt = out_format == CSIC_FMT_ARGB8888 && src_format != CSIC_FMT_ARGB8888 ? "argb" : "ycc";
-    const char *nt = !plan->tune.no_nt ? "nt" : "cached";
-    switch (decode_kind(plan, src_format, 0, 1)) {
-    case DEC_RECON: {
-        csic_planar_layout L;
-        planar_layout(plan->g, &plan->p, &L);
-        snprintf(buf, sizeof buf, "%s<%s,%s,%s>", src_format == CSIC_FMT_PLANAR_BITS ? "k_rbits" : "k_recon", fmt,
-                 L.module_width % 4 == 0 ? "fast" : "slow", nt);
-        break;
-    }
-    case DEC_FAST: snprintf(buf, sizeof buf, "k_decode<%s,%s,f%d,%s>", dec_src_name(src_format), fmt, plan->g.f, nt); break;
-    default: snprintf(buf, sizeof buf, "k_decode_gen<%s,%s>", dec_src_name(src_format), fmt); break;
-    }
+    DecodePlan dp;                                                      // one frame in aligned buffers
+    plan_decode(plan->p, plan->g, plan->tune, src_format, 0, 1, &dp);
+    decode_kernel_name(dp, plan->g, plan->tune, src_format, out_format, buf, sizeof buf);
     return buf;
 }
 
@@ -343,28 +307,21 @@ int csic_decode_device(csic_plan *plan, const void *d_src, int32_t src_format, v
     if (((uintptr_t)d_src & 3u) || ((uintptr_t)d_out & 3u)) return set_error(CSIC_EINVAL_SIZE, "source and output must be 4-byte aligned");
     const Geometry &g = plan->g;
     if ((int64_t)g.W * g.H >= ((int64_t)1 << 31)) return set_error(CSIC_EINVAL_SIZE, "frame too large for csic_decode_device");
-    const int kind = decode_kind(plan, src_format, (uintptr_t)d_out | (planar ? 0 : (uintptr_t)d_src), nframes);
+    DecodePlan dp;                                                      // kind, threads and blocks: csic_select.cpp
+    plan_decode(plan->p, g, plan->tune, src_format, (uintptr_t)d_out | (planar ? 0 : (uintptr_t)d_src), nframes, &dp);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (kind == DEC_RECON)
+    if (dp.kind == DEC_RECON)
         return src_format == CSIC_FMT_PLANAR_BITS ? csic_reconstruct_bits_device(plan, d_src, d_out, nframes, out_format, hip_stream)
                                                   : csic_reconstruct_device(plan, d_src, d_out, nframes, out_format, hip_stream);
-    const DecFn fn = decode_kernel(kind, src_format, out_format, g.f, !plan->tune.no_nt);
+    const DecFn fn = decode_kernel(dp.kind, src_format, out_format, g.f, !plan->tune.no_nt);
     CSIC_DEVICE_SCOPE(plan->device);
-    const int T = tune_block_threads(plan->tune, 256);
     st = for_frame_batches(nframes, [&](int f0, int nz) {
         DecArgs e;
         fill_dec_args(plan, src_format, &e);
         e.src = static_cast<const uint8_t *>(d_src) + (int64_t)f0 * e.src_frame_bytes;
         e.dst = static_cast<uint32_t *>(d_out) + (int64_t)f0 * e.out_px;
-        e.T = T;
-        int64_t blocks;
-        if (kind == DEC_FAST) {
-            const int64_t per_block = (int64_t)T * (g.f == 1 ? 4 : g.f == 2 ? 2 : 1);
-            blocks = (e.npieces + per_block - 1) / per_block;
-        } else {
-            blocks = (e.out_px + T - 1) / T;
-        }
-        return launch(fn, dim3((unsigned)blocks, 1, (unsigned)nz), dim3((unsigned)T, 1, 1), stream, e);
+        e.T = dp.T;
+        return launch(fn, dim3(dp.grid.x, 1, (unsigned)nz), dim3(dp.block.x, 1, 1), stream, e);
     });
     if (st != CSIC_OK) return st;
     clear_error();

@@ -2,7 +2,8 @@
 // csic_decode.hip, csic_distortion.hip, csic_ssim.hip, csic_pipeline.hip, csic_files.hip, csic_multi.hip, csic_graph.hip): error
 // macro, the HIP instantiation of the device guard, the plan, the launch descriptor that csic_kernels.hip prepares for the other
 // units, the device staging of the synchronous *_host wrappers, the run-time-value -> template-argument helper and the launch
-// shell of the units' entry points (ilog2, tune_block_threads, for_frame_batches, launch, reconstruct_device).
+// shell of the units' entry points (ilog2, for_frame_batches, launch, reconstruct_device).  Which kernel a plane unit takes and with
+// what grid and block is csic_select.cpp's (plan_planar, plan_planar_bits, plan_reconstruct, plan_decode).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -119,10 +120,8 @@ int planar_forward(const csic_plan *pl, const void *d_in, void *d_planar, int nf
 int planar_prepare_table(const csic_plan *pl, const void *const *d_in_tab, void *const *d_planar_tab, uintptr_t align_bits, int nframes,
                          PlanarLaunchDesc *d);
 int planar_enqueue(const PlanarLaunchDesc &d, hipStream_t stream);
-void planar_kernel_name(const csic_plan *pl, char *buf, size_t len);
-// csic_planar_bits.hip: out_format = CSIC_FMT_PLANAR_BITS (forward: packed input -> bit-packed planar frame buffers; kernel name)
+// csic_planar_bits.hip: out_format = CSIC_FMT_PLANAR_BITS (forward: packed input -> bit-packed planar frame buffers)
 int planar_bits_forward(const csic_plan *pl, const void *d_in, void *d_bits, int nframes, hipStream_t stream);
-void planar_bits_kernel_name(const csic_plan *pl, char *buf, size_t len);
 void plan_sizes(const csic_plan *pl, size_t *in_px, size_t *out_px);
 int64_t plan_algorithmic_bytes(const csic_plan *pl);          // per frame (csic_algorithmic_bytes of the plan's parameters)
 
@@ -142,13 +141,6 @@ auto with_const(T v, Fn &&fn)
 // the launch shell of the units' entry points
 // ------------------------------------------------------------------------------------------------
 inline int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
-
-// threads per block of the kernels that take CSIC_TUNE_BLOCK_THREADS: 64 / 128 / 256 as tuned, the kernel's own default otherwise
-inline int tune_block_threads(const Tune &t, int dflt)
-{
-    const int bt = t.block_threads;
-    return (bt == 64 || bt == 128 || bt == 256) ? bt : dflt;
-}
 
 // fn(f0, nz) for every batch of at most 65535 frames (the grid z limit): frames f0 .. f0 + nz - 1.  Stops at the first status
 // that is not CSIC_OK and returns it.
@@ -171,7 +163,7 @@ int launch(void (*fn)(P...), dim3 grid, dim3 block, hipStream_t stream, std::com
 }
 
 // csic_reconstruct_device / csic_reconstruct_bits_device: the refusals, the kernel for (out_format, fast, nontemporal) and one launch
-// per batch of frames -- K groups of 4 positions per lane.  Extra is the kernels' second argument (PExtra, BExtra: frame_bytes, n, Wm,
+// per batch of frames as plan_reconstruct lays it out -- K groups of 4 positions per lane.  Extra is the kernels' second argument (PExtra, BExtra: frame_bytes, n, Wm,
 // T, packed and the source pointer *src); fill(plan, &e) fills it from the plan's layout, pick(fmt, fast, nt) names the kernel.
 template <class Extra, class Fill, class Pick>
 int reconstruct_device(csic_plan *plan, const void *d_src, uint8_t *Extra::*src, void *d_out, int32_t nframes, int32_t out_format,
@@ -189,19 +181,18 @@ int reconstruct_device(csic_plan *plan, const void *d_src, uint8_t *Extra::*src,
     Extra e;
     fill(plan, &e);
     CSIC_DEVICE_SCOPE(plan->device);
-    const bool fast = e.Wm % 4 == 0 && plan->tune.variant != 9;
+    ReconPlan rp;
+    plan_reconstruct(plan->g, plan->tune, e.Wm, K, nframes, &rp);
     const Fn fn = with_const<(int)CSIC_FMT_ARGB8888, (int)CSIC_FMT_YCBCR888X>(out_format, [&](auto fmt) {
-        return with_const<true, false>(fast, [&](auto fa) {
+        return with_const<true, false>(rp.fast, [&](auto fa) {
             return with_const<true, false>(!plan->tune.no_nt, [&](auto nt) -> Fn { return pick(fmt, fa, nt); });
         });
     });
-    const int T = e.T = tune_block_threads(plan->tune, 64);
-    const int64_t ngroups = (e.n + 3) / 4, per_block = (int64_t)T * K;
+    e.T = rp.T;
     const int st = for_frame_batches(nframes, [&](int f0, int nz) {
         e.*src = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_src)) + (int64_t)f0 * e.frame_bytes;
         e.packed = static_cast<uint32_t *>(d_out) + (int64_t)f0 * e.n;
-        return launch(fn, dim3((unsigned)((ngroups + per_block - 1) / per_block), 1, (unsigned)nz), dim3((unsigned)T, 1, 1),
-                      static_cast<hipStream_t>(hip_stream), a, e);
+        return launch(fn, dim3(rp.grid.x, 1, (unsigned)nz), dim3(rp.block.x, 1, 1), static_cast<hipStream_t>(hip_stream), a, e);
     });
     if (st != CSIC_OK) return st;
     clear_error();

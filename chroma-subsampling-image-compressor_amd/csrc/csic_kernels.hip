@@ -648,9 +648,17 @@ KernelFn resolve(const KernelId &id)
 static void select(csic_plan *pl)
 {
     pl->sel = select_kernel(pl->p, pl->g, pl->tune, Constraints{false, false});
-    if (pl->p.out_format == CSIC_FMT_PLANAR) planar_kernel_name(pl, pl->name, sizeof pl->name);
-    else if (pl->p.out_format == CSIC_FMT_PLANAR_BITS) planar_bits_kernel_name(pl, pl->name, sizeof pl->name);
-    else kernel_name(pl->sel.id, pl->g, pl->name, sizeof pl->name);
+    if (pl->p.out_format == CSIC_FMT_PLANAR) {               // the kind of one frame in aligned buffers (the kind is set whatever the status)
+        PlanarPlan pp;
+        (void)plan_planar(pl->p, pl->g, pl->tune, 0, 1, &pp);
+        planar_kernel_name(pp.kind, pl->p, pl->g, pl->tune, pl->name, sizeof pl->name);
+    } else if (pl->p.out_format == CSIC_FMT_PLANAR_BITS) {
+        BitsPlan bp;
+        (void)plan_planar_bits(pl->p, pl->g, pl->tune, 0, 1, &bp);
+        planar_bits_kernel_name(bp.kind, pl->p, pl->g, pl->tune, pl->name, sizeof pl->name);
+    } else {
+        kernel_name(pl->sel.id, pl->g, pl->name, sizeof pl->name);
+    }
 }
 
 // Resolves kernel, grid and arguments for `nframes` frames (<= 65535, the grid z limit) whose base pointers OR to

@@ -37,8 +37,9 @@
 // reconstruct: payload_bytes + 4 * n.
 // Every global access goes through the accessors of csic_kernel_ops.h, which the CSIC_DEBUG build range-checks: the input against
 // the extent of KArgs, the planes against the frame's frame_bytes (pst1 / pst2 / pst4 name that limit), k_recon's output stores
-// -- the 16-byte ones of both paths and the tail's single pixels -- against the frame's n pixels.  The host side (block size,
-// batches of 65535 frames, the launch, csic_reconstruct_device's body) is the shell of csic_hip_common.h.
+// -- the 16-byte ones of both paths and the tail's single pixels -- against the frame's n pixels.  Which kernel a plan takes, its
+// name, grid and block are plan_planar / plan_reconstruct of csic_select.cpp (host only); batches of 65535 frames, the launch and
+// csic_reconstruct_device's body are the shell of csic_hip_common.h.
 #include <cstdio>
 #include <cstring>
 
@@ -141,8 +142,6 @@ __device__ __forceinline__ void planar_flat_body(const KArgs &a, const PExtra &e
     }
     if (!CHECK) keep_tail_apart();
 }
-
-constexpr int PLANAR_K = 4;
 
 template <int ROUND, int MODE, bool NT>
 __global__ void __launch_bounds__(256) k_planar_flat(KArgs a, PExtra e)
@@ -415,11 +414,6 @@ struct BytePlanes {
     __device__ __forceinline__ uint32_t c_one(int p, idx k) const { return by_ld1(e.frame_bytes, fb, plane(p) + k); }
 };
 
-#ifndef CSIC_RECON_K
-#define CSIC_RECON_K 4
-#endif
-constexpr int RECON_K = CSIC_RECON_K;
-
 template <int FMT, bool FAST, bool NT>
 __global__ void __launch_bounds__(256) k_recon(KArgs a, PExtra e)
 {
@@ -450,37 +444,8 @@ static void fill_extra(const csic_planar_layout &L, PExtra *e)
     magic_div((uint32_t)L.module_width, &e->mWm, &e->kWm);
 }
 
-// The packed-output plan whose k_avg the planar AVG tile kernel follows (same body, csic_avg_tile.h; same selection and geometry).
-static csic_params packed_twin(csic_params p)
-{
-    p.out_format = CSIC_FMT_YCBCR888X;
-    return p;
-}
-
-// which forward kernel a plan takes: 0 = flat MODE 0, 1 = strided, 2 = flat MODE 2, 3 = avg_f1, 4 = avg_gen, 5 = flat MODE 1, 6 = avg_tile
-static int forward_kind(const csic_plan *pl, const csic_planar_layout &L)
-{
-    const csic_params &p = pl->p;
-    const Geometry &g = pl->g;
-    const bool general = pl->tune.variant == 9;                 // CSIC_TUNE_VARIANT 9: the general kernels (A/B, tests)
-    if (p.sampling == CSIC_SAMPLING_AVG) {
-        const bool f1_whole = g.f == 1 && g.W % 4 == 0 && g.H % g.v == 0;
-        // factor 1 on frames of whole tiles: the dedicated kernel (Y bytes straight from the loaded pixels, no per-pixel write-back of
-        // the block averages) is 3 points ahead of k_avg's body there -- 8192x8192 4:2:0: 77.5 against 74.1 % of the roofline,
-        // profiles/r04_planar_avg_tile_ab.log; CSIC_TUNE_VARIANT 12 takes the tile body all the same (A/B, tests)
-        if (!general && f1_whole && (pl->tune.variant != 12 || pl->tune.no_nt)) return 3;
-        if (!general && !pl->tune.no_nt) {                  // k_avg's body wherever k_avg itself would run
-            if (select_kernel(packed_twin(pl->p), g, pl->tune, Constraints{false, false}).id.fam == FAM_AVG) return 6;
-        }
-        return (!general && f1_whole) ? 3 : 4;
-    }
-    if (general || L.module_width % 4 != 0) return 0;
-    if (g.f == 1 && g.W % 4 == 0) return 2;
-    return pl->tune.variant == 10 ? 5 : 1;
-}
-
 // the kernel of a forward kind (he, ve: the layout's holds; g: the plan's geometry, for the tile kernel)
-static PlanarFn forward_kernel(int kind, int rounding, bool nontemporal, int he, int ve, const Geometry &g)
+static PlanarFn forward_kernel(PlanarKind kind, int rounding, bool nontemporal, int he, int ve, const Geometry &g)
 {
     return with_const<R_FLOOR, R_TRUNC>(rounding, [&](auto round) {
     return with_const<true, false>(nontemporal, [&](auto nt) -> PlanarFn {
@@ -490,91 +455,36 @@ static PlanarFn forward_kernel(int kind, int rounding, bool nontemporal, int he,
             return with_const<1, 2, 4>(h, [&](auto hc) { return with_const<1, 2>(v, [&](auto vc) { return pick(hc, vc); }); });
         };
         switch (kind) {
-        case 0: return k_planar_flat<ROUND, 0, NT>;
-        case 1: return k_planar_strided<ROUND, NT>;
-        case 5: return k_planar_flat<ROUND, 1, NT>;           // the first form of kind 1 (4 consecutive positions per lane): A/B, CSIC_TUNE_VARIANT 10
-        case 2: return k_planar_flat<ROUND, 2, NT>;
-        case 3: return hv(he, ve, [](auto h, auto v) -> PlanarFn { return k_planar_avg_f1<ROUND, CSIC_CONST(h), CSIC_CONST(v), NT>; });
-        case 6:
+        case PLANAR_FLAT_GEN: return k_planar_flat<ROUND, 0, NT>;
+        case PLANAR_STRIDED: return k_planar_strided<ROUND, NT>;
+        case PLANAR_FLAT_4PL: return k_planar_flat<ROUND, 1, NT>;
+        case PLANAR_FLAT_F1X4: return k_planar_flat<ROUND, 2, NT>;
+        case PLANAR_AVG_F1: return hv(he, ve, [](auto h, auto v) -> PlanarFn { return k_planar_avg_f1<ROUND, CSIC_CONST(h), CSIC_CONST(v), NT>; });
+        case PLANAR_AVG_TILE:
             return with_const<1, 2, 4, 8>(g.f, [&](auto f) {
                 return hv(g.h, g.v, [](auto h, auto v) -> PlanarFn { return k_planar_avg_tile<ROUND, CSIC_CONST(f), CSIC_CONST(h), CSIC_CONST(v)>; });
             });
-        default: return k_planar_avg_gen<ROUND>;
+        case PLANAR_AVG_GEN: break;
         }
+        return k_planar_avg_gen<ROUND>;
     }); });
 }
 
-void planar_kernel_name(const csic_plan *pl, char *buf, size_t len)
+// kernel, grid, block and both argument blocks of one forward launch over nz <= 65535 frames whose pointers OR to align_bits: what
+// plan_planar decides (csic_select.cpp), the kernel of that kind and PExtra from the layout; the frame pointers stay unset
+static int planar_resolve(const csic_plan *pl, uintptr_t align_bits, int nz, PlanarLaunchDesc *d)
 {
+    PlanarPlan pp;
+    const int st = plan_planar(pl->p, pl->g, pl->tune, align_bits, nz, &pp);
+    if (st != CSIC_OK) return st;
     csic_planar_layout L;
     planar_layout(pl->g, &pl->p, &L);
-    const char *rn = pl->p.rounding == CSIC_ROUND_FLOOR_HW ? "floor" : "trunc";
-    const char *nt = !pl->tune.no_nt ? "nt" : "cached";
-    switch (forward_kind(pl, L)) {
-    case 0: snprintf(buf, len, "k_planar_flat<%s,general,h%d,v%d,%s>", rn, L.hold_h, L.hold_v, nt); break;
-    case 1: snprintf(buf, len, "k_planar_strided<%s,f%d,h%d,v%d,%s>", rn, pl->g.f, L.hold_h, L.hold_v, nt); break;
-    case 5: snprintf(buf, len, "k_planar_flat<%s,f%d,h%d,v%d,%s>", rn, pl->g.f, L.hold_h, L.hold_v, nt); break;
-    case 2: snprintf(buf, len, "k_planar_flat<%s,f1x4,h%d,v%d,%s>", rn, L.hold_h, L.hold_v, nt); break;
-    case 3: snprintf(buf, len, "k_planar_avg_f1<%s,h%d,v%d,%s>", rn, L.hold_h, L.hold_v, nt); break;
-    case 6: snprintf(buf, len, "k_planar_avg_tile<%s,f%d,h%d,v%d,nt>", rn, pl->g.f, pl->g.h, pl->g.v); break;
-    default: snprintf(buf, len, "k_planar_avg_gen<%s,h%d,v%d>", rn, L.hold_h, L.hold_v); break;
-    }
-}
-
-// kernel, grid, block and both argument blocks of one forward launch over nz <= 65535 frames; the frame pointers stay unset
-static int planar_resolve(const csic_plan *pl, int nz, PlanarLaunchDesc *d)
-{
-    const csic_params &p = pl->p;
-    const Geometry &g = pl->g;
-    csic_planar_layout L;
-    planar_layout(g, &p, &L);
-    const int kind = forward_kind(pl, L);
-    const PlanarFn fn = forward_kernel(kind, p.rounding, !pl->tune.no_nt, L.hold_h, L.hold_v, g);
-    KArgs &a = d->args;
-    PExtra &e = d->extra;
-    fill_base_args(g, g.W, g.Wo, &a);
-    fill_extra(L, &e);
-    dim3 grid, block;
-    if (kind == 6) {
-        // k_avg's own geometry (block shape, edge blocks, XCD rotation): plan_launch on the plan's packed twin
-        LaunchPlan lp;
-        const int st = plan_launch(packed_twin(p), g, pl->tune, 0, nz, 0, 0, &lp);
-        if (st != CSIC_OK) return st;
-        if (lp.id.fam != FAM_AVG) return set_error(CSIC_EHIP, "internal: the planar AVG tile kernel was selected for a plan k_avg does not take");
-        a = lp.args;
-        grid = dim3(lp.grid.x, lp.grid.y, lp.grid.z); block = dim3(lp.block.x, lp.block.y, lp.block.z);
-        e.T = 256;
-    } else if (kind == 1) {
-        // k_planar_strided: 4 positions per lane, T * 4 positions per block
-        const int T = tune_block_threads(pl->tune, 256);
-        e.T = T;
-        block = dim3((unsigned)T, 1, 1);
-        grid = dim3((unsigned)((e.n + (int64_t)T * 4 - 1) / ((int64_t)T * 4)), 1, (unsigned)nz);
-        a.bdx = T; a.bdy = 1; a.row_step = 1;
-    } else if (kind <= 2 || kind == 5) {
-        const int64_t ngroups = (e.n + 3) / 4;
-        // one-wave blocks for the 16-byte-load kernel: a wave's four loads then cover 4 KiB of consecutive pixels
-        // (8192x8192 4:2:0: 71.7 % of the roofline with 256-thread blocks, 77.6 % with 64; profiles/r04_planar_bt.log)
-        const int T = tune_block_threads(pl->tune, kind == 2 ? 64 : 256);
-        e.T = T;
-        block = dim3((unsigned)T, 1, 1);
-        grid = dim3((unsigned)((ngroups + (int64_t)T * PLANAR_K - 1) / ((int64_t)T * PLANAR_K)), 1, (unsigned)nz);
-        a.bdx = T; a.bdy = 1; a.row_step = 1;
-    } else {
-        // row-tiled kernels: lanes along x (tiles of 4 pixels for avg_f1 with 2 tiles per lane, output pixels for avg_gen)
-        const int lanes_x = kind == 3 ? (g.W / 4 + 1) / 2 : g.Wo;
-        const int rows = kind == 3 ? g.H / g.v : g.Ho;
-        int bx = 1;
-        while (bx < lanes_x && bx < 256) bx <<= 1;
-        const int by = 256 / bx;
-        unsigned gy = (unsigned)((rows + by - 1) / by);
-        if (gy > 65535u) gy = 65535u;
-        block = dim3(bx, by, 1);
-        grid = dim3((unsigned)((lanes_x + bx - 1) / bx), gy, (unsigned)nz);
-        a.bdx = bx; a.bdy = by; a.row_step = (int32_t)gy * by;
-        e.T = 256;
-    }
-    d->fn = fn; d->grid = grid; d->block = block;
+    fill_extra(L, &d->extra);
+    d->extra.T = pp.T;
+    d->args = pp.args;
+    d->fn = forward_kernel(pp.kind, pl->p.rounding, !pl->tune.no_nt, L.hold_h, L.hold_v, pl->g);
+    d->grid = dim3(pp.grid.x, pp.grid.y, pp.grid.z);
+    d->block = dim3(pp.block.x, pp.block.y, pp.block.z);
     return CSIC_OK;
 }
 
@@ -587,7 +497,7 @@ int planar_forward(const csic_plan *pl, const void *d_in, void *d_planar, int nf
         return set_error(CSIC_EINVAL_SIZE, "a planar frame buffer must be 256-byte aligned (and the input 4-byte aligned)");
     return for_frame_batches(nframes, [&](int f0, int nz) {
         PlanarLaunchDesc d;
-        const int st = planar_resolve(pl, nz, &d);
+        const int st = planar_resolve(pl, (uintptr_t)d_in | (uintptr_t)d_planar, nz, &d);
         if (st != CSIC_OK) return st;
         d.args.in = static_cast<const uint32_t *>(d_in) + (int64_t)f0 * d.args.in_frame_px;
         d.extra.planar = static_cast<uint8_t *>(d_planar) + (int64_t)f0 * d.extra.frame_bytes;
@@ -602,7 +512,7 @@ int planar_prepare_table(const csic_plan *pl, const void *const *d_in_tab, void 
     if (!d_in_tab || !d_planar_tab) return set_error(CSIC_EINVAL_NULL, "frame table is NULL");
     if (nframes <= 0 || nframes > 65535) return set_error(CSIC_EINVAL_SIZE, "nframes per launch must be in 1..65535. Got %d", nframes);
     if (align_bits & 3u) return set_error(CSIC_EINVAL_SIZE, "frame buffers must be 4-byte aligned");
-    const int st = planar_resolve(pl, nframes, d);
+    const int st = planar_resolve(pl, align_bits, nframes, d);
     if (st != CSIC_OK) return st;
     d->args.in_tab = reinterpret_cast<const uint32_t *const *>(d_in_tab);
     d->extra.planar_tab = reinterpret_cast<const uint64_t *>(d_planar_tab);

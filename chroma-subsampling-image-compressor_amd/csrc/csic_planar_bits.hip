@@ -21,7 +21,8 @@
 // Every output byte is written by exactly one lane (no read-modify-write, no atomics); the fast kernels store dwords only (their
 // planes are whole dwords: n and every chroma row are multiples of 32 samples).  Every global access goes through the accessors of
 // csic_kernel_ops.h, which the CSIC_DEBUG build range-checks: the input against the extent of KArgs, the bit planes against the
-// frame's frame_bytes (bst1 / bst4 name that limit), k_rbits' output stores against the frame's n pixels.
+// frame's frame_bytes (bst1 / bst4 name that limit), k_rbits' output stores against the frame's n pixels.  Which forward kernel a
+// call takes, its name, threads and blocks are plan_planar_bits of csic_select.cpp (host only).
 #include <cstdio>
 #include <cstring>
 
@@ -128,8 +129,6 @@ __device__ __forceinline__ void pbits_emit(const BExtra &e, const PlaneAsm &pa, 
     if (pa.a[1].D < qb) bst4<NT>(e, fb, e.off[1] + kg * (4 * qb) + 4 * pa.a[1].D, db);
     if (pa.a[2].D < qr) bst4<NT>(e, fb, e.off[2] + kg * (4 * qr) + 4 * pa.a[2].D, dr);
 }
-
-constexpr int PBITS_K = 4;
 
 template <int ROUND, bool NT, bool CHECK>
 __device__ __forceinline__ void pbits_f1_body(const KArgs &a, const BExtra &e, gin_t in, gbyte_t fb, const PlaneAsm &pa, uint32_t g0,
@@ -303,7 +302,6 @@ __global__ void __launch_bounds__(256) k_pbits_gen(KArgs a, BExtra e)
 // ------------------------------------------------------------------------------------------------
 // reconstruct: bits -> packed
 // ------------------------------------------------------------------------------------------------
-constexpr int RBITS_K = 4;
 using RbitsPlanes = BitPlanes<BExtra, &BExtra::frame_bytes>;
 
 template <int FMT, bool FAST, bool NT>
@@ -344,34 +342,6 @@ static void fill_bits_extra(const csic_planar_bits_layout &L, BExtra *e)
     e->ngc = (e->ns + 7) / 8;
 }
 
-// 0 = general, 1 = factor 1 fast, 2 = chroma before spatial, factor >= 2, fast
-static int bits_kind(const csic_plan *pl, const csic_planar_bits_layout &L)
-{
-    const csic_params &p = pl->p;
-    const Geometry &g = pl->g;
-    if (pl->tune.variant == 9 || p.sampling != CSIC_SAMPLING_HOLD_DECIMATE) return 0;
-    // the fast kernels assemble dwords of 32 samples inside one row: every row a whole number of 128 positions (hold_h <= 4)
-    if (L.geometry.module_width % 128 != 0) return 0;
-    if (g.f == 1) return 1;
-    return g.s_first ? 0 : 2;
-}
-
-void planar_bits_kernel_name(const csic_plan *pl, char *buf, size_t len)
-{
-    csic_planar_bits_layout L;
-    planar_bits_layout(pl->g, &pl->p, &L);
-    const char *rn = pl->p.rounding == CSIC_ROUND_FLOOR_HW ? "floor" : "trunc";
-    const char *nt = !pl->tune.no_nt ? "nt" : "cached";
-    switch (bits_kind(pl, L)) {
-    case 1: snprintf(buf, len, "k_pbits_f1<%s,h%d,v%d,%s>", rn, L.geometry.hold_h, L.geometry.hold_v, nt); break;
-    case 2: snprintf(buf, len, "k_pbits_strided<%s,f%d,h%d,%s>", rn, pl->g.f, L.geometry.hold_h, nt); break;
-    default:
-        snprintf(buf, len, "k_pbits_gen<%s,%s,h%d,v%d>", rn, pl->p.sampling == CSIC_SAMPLING_AVG ? "avg" : "hold",
-                 L.geometry.hold_h, L.geometry.hold_v);
-        break;
-    }
-}
-
 int planar_bits_forward(const csic_plan *pl, const void *d_in, void *d_bits, int nframes, hipStream_t stream)
 {
     if (!d_in || !d_bits) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
@@ -379,16 +349,17 @@ int planar_bits_forward(const csic_plan *pl, const void *d_in, void *d_bits, int
     const Geometry &g = pl->g;
     csic_planar_bits_layout L;
     planar_bits_layout(g, &p, &L);
-    int kind = bits_kind(pl, L);
     if ((uintptr_t)d_bits & 255u) return set_error(CSIC_EINVAL_SIZE, "a bit-packed planar frame buffer must be 256-byte aligned");
     if ((uintptr_t)d_in & 3u) return set_error(CSIC_EINVAL_SIZE, "the input must be 4-byte aligned");
-    if (kind == 1 && ((uintptr_t)d_in & 15u)) kind = 0;                 // the 16-byte loads need a 16-byte aligned input
+    BitsPlan bp;                                                        // kind, threads and blocks: csic_select.cpp
+    const int st = plan_planar_bits(p, g, pl->tune, (uintptr_t)d_in, nframes, &bp);
+    if (st != CSIC_OK) return st;
     const bool nt = !pl->tune.no_nt;
     const bool avg = p.sampling == CSIC_SAMPLING_AVG;
     const BitsFn fn = with_const<R_FLOOR, R_TRUNC>(p.rounding, [&](auto round) {
-        return with_const<true, false>(kind == 0 ? avg : nt, [&](auto b) -> BitsFn {      // b: k_pbits_gen's AVG, the others' NT
-            if (kind == 1) return k_pbits_f1<CSIC_CONST(round), CSIC_CONST(b)>;
-            if (kind == 2) return k_pbits_strided<CSIC_CONST(round), CSIC_CONST(b)>;
+        return with_const<true, false>(bp.kind == PBITS_GEN ? avg : nt, [&](auto b) -> BitsFn {      // b: k_pbits_gen's AVG, the others' NT
+            if (bp.kind == PBITS_F1) return k_pbits_f1<CSIC_CONST(round), CSIC_CONST(b)>;
+            if (bp.kind == PBITS_STRIDED) return k_pbits_strided<CSIC_CONST(round), CSIC_CONST(b)>;
             return k_pbits_gen<CSIC_CONST(round), CSIC_CONST(b)>;
         });
     });
@@ -399,16 +370,9 @@ int planar_bits_forward(const csic_plan *pl, const void *d_in, void *d_bits, int
         fill_bits_extra(L, &e);
         a.in = static_cast<const uint32_t *>(d_in) + (int64_t)f0 * a.in_frame_px;
         e.bits = static_cast<uint8_t *>(d_bits) + (int64_t)f0 * L.frame_bytes;
-        // one-wave blocks for the 16-byte-load kernel (as k_planar_flat MODE 2), 256 threads for the others
-        const int T = tune_block_threads(pl->tune, kind == 1 ? 64 : 256);
-        e.T = T;
-        a.bdx = T; a.bdy = 1; a.row_step = 1;
-        int64_t blocks;
-        if (kind == 1) blocks = (e.n / 4 + (int64_t)T * PBITS_K - 1) / ((int64_t)T * PBITS_K);
-        else if (kind == 2) blocks = (e.n + (int64_t)T * 4 - 1) / ((int64_t)T * 4);
-        else blocks = (e.ngy + e.ngc + T - 1) / T;
-        if (blocks > 0x7FFFFFFF) return set_error(CSIC_EINVAL_SIZE, "frame too large for one launch");
-        return launch(fn, dim3((unsigned)blocks, 1, (unsigned)nz), dim3((unsigned)T, 1, 1), stream, a, e);
+        e.T = bp.T;
+        a.bdx = bp.bdx; a.bdy = bp.bdy; a.row_step = bp.row_step;
+        return launch(fn, dim3(bp.grid.x, 1, (unsigned)nz), dim3(bp.block.x, 1, 1), stream, a, e);
     });
 }
 

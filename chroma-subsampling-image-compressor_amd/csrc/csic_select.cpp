@@ -1,5 +1,5 @@
-// csic_select.cpp -- kernel selection, kernel names and launch geometry of the packed kernels, kernel selection and names of the
-// measurement units (see csic_select.h).  Host only.
+// csic_select.cpp -- kernel selection, kernel names and launch geometry of the packed kernels and of the plane units (planar and
+// bit-plane forward, reconstruct, decode), kernel selection and names of the measurement units (see csic_select.h).  Host only.
 // Every rule here is backed by a measurement under profiles/; tests/data/launch_table.txt records what the rules give.
 #include "csic_select.h"
 
@@ -169,7 +169,7 @@ void kernel_name(const KernelId &id, const Geometry &g, char *buf, size_t len)
         break;
     case FAM_FLATGEN: snprintf(buf, len, "k_flatgen<%s,%s,K%d,%s>", rn, fn, DEC_K, ntn); break;
     case FAM_GENERIC: snprintf(buf, len, "k_generic<%s,%s%s>", rn, fn, ycc_in); break;
-    case FAM_PLANAR: snprintf(buf, len, "%s", ""); break;   // csic_planar.hip / csic_planar_bits.hip name their kernels
+    case FAM_PLANAR: snprintf(buf, len, "%s", ""); break;   // planar_kernel_name / planar_bits_kernel_name below
     }
 }
 
@@ -194,18 +194,23 @@ void fill_base_args(const Geometry &g, int32_t ip, int32_t op, KArgs *pa)
 }
 
 // ---- launch geometry, one function per mapping -------------------------------------------------------------------------
-static int forced_threads(const Tune &t)
+int tune_block_threads(const Tune &t, int dflt)
 {
-    return (t.block_threads == 64 || t.block_threads == 128 || t.block_threads == 256) ? t.block_threads : 0;
+    return (t.block_threads == 64 || t.block_threads == 128 || t.block_threads == 256) ? t.block_threads : dflt;
+}
+
+static int64_t flat_blocks(int64_t n, int K, int T)
+{
+    const int64_t per_block = (int64_t)T * K;
+    return (n + per_block - 1) / per_block;
 }
 
 // Lanes over a flat stream of `n` units, K per lane spaced by the block: one-dimensional blocks of T threads.
 static void launch_flat(int64_t n, int K, int T, int nframes, LaunchPlan *lp)
 {
-    const int64_t per_block = (int64_t)T * K;
     lp->block = Dim3{(uint32_t)T, 1, 1};
     lp->args.bdx = T; lp->args.bdy = 1; lp->args.row_step = 1;
-    lp->grid = Dim3{(uint32_t)((n + per_block - 1) / per_block), 1, (uint32_t)nframes};
+    lp->grid = Dim3{(uint32_t)flat_blocks(n, K, T), 1, (uint32_t)nframes};
 }
 
 // Blocks of bx lanes by tpb / bx rows over `lanes_x` lanes and `rows` rows; the kernels stride over rows past the grid y limit.
@@ -244,8 +249,7 @@ static int pow2_block_x(int lanes_x, int tpb)
 
 static void launch_f1flat(const Geometry &g, const Tune &t, int nframes, LaunchPlan *lp)
 {
-    const int forced = forced_threads(t);
-    launch_flat((int64_t)(g.W / 4) * g.H, 4, forced ? forced : 64, nframes, lp);
+    launch_flat((int64_t)(g.W / 4) * g.H, 4, tune_block_threads(t, 64), nframes, lp);
 }
 
 static void launch_decflat(const Geometry &g, const Tune &t, int nframes, LaunchPlan *lp)
@@ -255,8 +259,7 @@ static void launch_decflat(const Geometry &g, const Tune &t, int nframes, Launch
     // and for long rows at f = 4 / 8 (3840x2160 f = 4: 74.7 -> 76.7 %, 8192x8192 f = 8: 75.9 -> 77.0); four-wave blocks for
     // short rows at f = 4 / 8 (1000x1000 f = 4: 72.3 % against 69.4 / 68.4 % with 128 / 64 threads; 1920x1080 f = 8: 75.7
     // against 75.2 / 71.1).                                                      profiles/r03_probe_flat.log
-    const int forced = forced_threads(t);
-    launch_flat((int64_t)g.Wo * g.Ho, DEC_K, forced ? forced : ((g.f == 2 || g.Wo >= 512) ? 128 : 256), nframes, lp);
+    launch_flat((int64_t)g.Wo * g.Ho, DEC_K, tune_block_threads(t, (g.f == 2 || g.Wo >= 512) ? 128 : 256), nframes, lp);
 }
 
 static void launch_dec(const Geometry &g, const Tune &t, int hold, int nframes, LaunchPlan *lp)
@@ -268,8 +271,9 @@ static void launch_dec(const Geometry &g, const Tune &t, int hold, int nframes, 
     // where 128 lanes do not divide the row into full waves (7680x4320: 17.29 -> 17.93).  CSIC_TUNE_BLOCK_THREADS overrides.
     const int lanes_x = (g.Wo + DEC_K - 1) / DEC_K;
     const bool whole = g.Wo % DEC_K == 0;
+    const int forced = tune_block_threads(t, 0);
     int tpb = 256;
-    if (forced_threads(t)) tpb = forced_threads(t);
+    if (forced) tpb = forced;
     else if (nframes == 1 && whole && lanes_x % 128 == 0 && 4ll * ((int64_t)g.W * g.Ho + (int64_t)g.Wo * g.Ho) >= (64ll << 20))
         tpb = 128;
     else if (whole && lanes_x >= 16 && lanes_x <= 128) {
@@ -291,7 +295,7 @@ static void launch_dec(const Geometry &g, const Tune &t, int hold, int nframes, 
 
 static void launch_f1x4(const Geometry &g, const Tune &t, int nframes, LaunchPlan *lp)
 {
-    const int lanes_x = g.W / 4, forced = forced_threads(t), tpb = forced ? forced : 256;
+    const int lanes_x = g.W / 4, forced = tune_block_threads(t, 0), tpb = tune_block_threads(t, 256);
     int bx = pow2_block_x(lanes_x, tpb);
     if (!forced) {
         // One 16-byte load and store per lane: this kernel lives on the wave launch rate, so waves that exit at once (the idle
@@ -309,7 +313,7 @@ static void launch_f1x4(const Geometry &g, const Tune &t, int nframes, LaunchPla
 static void launch_avg(const Geometry &g, const Tune &t, int tiles, int nframes, LaunchPlan *lp)
 {
     const int units = (g.W + 3) / 4, lanes_x = (units + tiles - 1) / tiles, avg_th = g.f > g.v ? g.f : g.v;
-    const int forced = forced_threads(t), tpb = forced ? forced : 256;
+    const int forced = tune_block_threads(t, 0), tpb = tune_block_threads(t, 256);
     int bx = pow2_block_x(lanes_x, tpb);
     if (!forced && lanes_x % 64 == 0 && lanes_x > 256 && lanes_x <= 512 && lanes_x % 256 != 0) {
         // the same as k_f1x4 on rows of at most two blocks: 1280-wide f = 4 / 8 (320 lanes) 64 / 61 % -> 80 % with blocks of whole
@@ -334,7 +338,7 @@ static void launch_avg(const Geometry &g, const Tune &t, int tiles, int nframes,
 // k_dec2v, k_generic, k_avg_generic: one unit per lane along x, rows of the output along y
 static void launch_per_lane(const Geometry &g, const Tune &t, int units, int nframes, LaunchPlan *lp)
 {
-    const int tpb = forced_threads(t) ? forced_threads(t) : 256;
+    const int tpb = tune_block_threads(t, 256);
     launch_rows(units, g.Ho, pow2_block_x(units, tpb), tpb, -1, nframes, lp);
 }
 
@@ -422,6 +426,197 @@ void code_stats_kernel_name(CodeStatsKind kind, int src_format, const csic_param
     case CSTAT_BYTES: snprintf(buf, len, "k_cstat_bytes<%s>", nt); break;
     case CSTAT_BITS: snprintf(buf, len, "k_cstat_bits<q%d,%d,%d,%s>", p.y_bits, p.cb_bits, p.cr_bits, nt); break;
     default: snprintf(buf, len, "k_cstat_gen<%s>", src_format == CSIC_FMT_PLANAR_BITS ? "bits" : "planar"); break;
+    }
+}
+
+// ---- the plane units ------------------------------------------------------------------------------------------------------
+// a flat launch (launch_flat) as a plane unit's plan
+static void plane_flat(int64_t n, int K, int T, int nframes, PlaneLaunch *pl)
+{
+    LaunchPlan lp;
+    launch_flat(n, K, T, nframes, &lp);
+    *pl = PlaneLaunch{lp.grid, lp.block, T, lp.args.bdx, lp.args.bdy, lp.args.row_step};
+}
+
+// The packed-output plan whose k_avg the planar AVG tile kernel follows (same body, csic_avg_tile.h; same selection and geometry).
+static csic_params packed_twin(csic_params p)
+{
+    p.out_format = CSIC_FMT_YCBCR888X;
+    return p;
+}
+
+static PlanarKind planar_kind(const csic_params &p, const Geometry &g, const Tune &t, const csic_planar_layout &L)
+{
+    const bool general = t.variant == 9;                        // CSIC_TUNE_VARIANT 9: the general kernels (A/B, tests)
+    if (p.sampling == CSIC_SAMPLING_AVG) {
+        const bool f1_whole = g.f == 1 && g.W % 4 == 0 && g.H % g.v == 0;
+        // factor 1 on frames of whole tiles: the dedicated kernel (Y bytes straight from the loaded pixels, no per-pixel write-back of
+        // the block averages) is 3 points ahead of k_avg's body there -- 8192x8192 4:2:0: 77.5 against 74.1 % of the roofline,
+        // profiles/r04_planar_avg_tile_ab.log; CSIC_TUNE_VARIANT 12 takes the tile body all the same (A/B, tests)
+        if (!general && f1_whole && (t.variant != 12 || t.no_nt)) return PLANAR_AVG_F1;
+        if (!general && !t.no_nt) {                             // k_avg's body wherever k_avg itself would run
+            if (select_kernel(packed_twin(p), g, t, Constraints{false, false}).id.fam == FAM_AVG) return PLANAR_AVG_TILE;
+        }
+        return (!general && f1_whole) ? PLANAR_AVG_F1 : PLANAR_AVG_GEN;
+    }
+    if (general || L.module_width % 4 != 0) return PLANAR_FLAT_GEN;
+    if (g.f == 1 && g.W % 4 == 0) return PLANAR_FLAT_F1X4;
+    return t.variant == 10 ? PLANAR_FLAT_4PL : PLANAR_STRIDED;
+}
+
+int plan_planar(const csic_params &p, const Geometry &g, const Tune &t, uintptr_t align_bits, int nframes, PlanarPlan *pp)
+{
+    (void)align_bits;
+    csic_planar_layout L;
+    planar_layout(g, &p, &L);
+    const int64_t n = (int64_t)g.Wo * g.Ho;
+    pp->kind = planar_kind(p, g, t, L);
+    fill_base_args(g, g.W, g.Wo, &pp->args);
+    switch (pp->kind) {
+    case PLANAR_AVG_TILE: {
+        // k_avg's own geometry (block shape, edge blocks, XCD rotation): plan_launch on the plan's packed twin
+        LaunchPlan lp;
+        const int st = plan_launch(packed_twin(p), g, t, 0, nframes, 0, 0, &lp);
+        if (st != CSIC_OK) return st;
+        if (lp.id.fam != FAM_AVG) return set_error(CSIC_EHIP, "internal: the planar AVG tile kernel was selected for a plan k_avg does not take");
+        pp->args = lp.args;
+        static_cast<PlaneLaunch &>(*pp) = PlaneLaunch{lp.grid, lp.block, 256, lp.args.bdx, lp.args.bdy, lp.args.row_step};
+        return CSIC_OK;
+    }
+    case PLANAR_STRIDED:                                        // 4 positions per lane, T * 4 positions per block
+        plane_flat(n, 4, tune_block_threads(t, 256), nframes, pp);
+        break;
+    case PLANAR_FLAT_GEN:
+    case PLANAR_FLAT_F1X4:
+    case PLANAR_FLAT_4PL:
+        // one-wave blocks for the 16-byte-load kernel: a wave's four loads then cover 4 KiB of consecutive pixels
+        // (8192x8192 4:2:0: 71.7 % of the roofline with 256-thread blocks, 77.6 % with 64; profiles/r04_planar_bt.log)
+        plane_flat((n + 3) / 4, PLANAR_K, tune_block_threads(t, pp->kind == PLANAR_FLAT_F1X4 ? 64 : 256), nframes, pp);
+        break;
+    case PLANAR_AVG_F1:
+    case PLANAR_AVG_GEN: {
+        // row-tiled kernels: lanes along x (tiles of 4 pixels for avg_f1 with 2 tiles per lane, output pixels for avg_gen), always
+        // 256 threads.  Not launch_rows: these kernels clamp grid y at 65535 (launch_rows keeps one row back for edge blocks) and
+        // leave KArgs.edge_y0 alone.
+        const bool f1 = pp->kind == PLANAR_AVG_F1;
+        const int lanes_x = f1 ? (g.W / 4 + 1) / 2 : g.Wo, rows = f1 ? g.H / g.v : g.Ho;
+        const int bx = pow2_block_x(lanes_x, 256), by = 256 / bx;
+        uint32_t gy = (uint32_t)((rows + by - 1) / by);
+        if (gy > 65535u) gy = 65535u;
+        static_cast<PlaneLaunch &>(*pp) = PlaneLaunch{Dim3{(uint32_t)((lanes_x + bx - 1) / bx), gy, (uint32_t)nframes},
+                                                      Dim3{(uint32_t)bx, (uint32_t)by, 1}, 256, bx, by, (int32_t)gy * by};
+        break;
+    }
+    }
+    pp->args.bdx = pp->bdx; pp->args.bdy = pp->bdy; pp->args.row_step = pp->row_step;
+    return CSIC_OK;
+}
+
+void planar_kernel_name(PlanarKind kind, const csic_params &p, const Geometry &g, const Tune &t, char *buf, size_t len)
+{
+    csic_planar_layout L;
+    planar_layout(g, &p, &L);
+    const char *rn = p.rounding == CSIC_ROUND_FLOOR_HW ? "floor" : "trunc";
+    const char *nt = !t.no_nt ? "nt" : "cached";
+    switch (kind) {
+    case PLANAR_FLAT_GEN: snprintf(buf, len, "k_planar_flat<%s,general,h%d,v%d,%s>", rn, L.hold_h, L.hold_v, nt); break;
+    case PLANAR_STRIDED: snprintf(buf, len, "k_planar_strided<%s,f%d,h%d,v%d,%s>", rn, g.f, L.hold_h, L.hold_v, nt); break;
+    case PLANAR_FLAT_4PL: snprintf(buf, len, "k_planar_flat<%s,f%d,h%d,v%d,%s>", rn, g.f, L.hold_h, L.hold_v, nt); break;
+    case PLANAR_FLAT_F1X4: snprintf(buf, len, "k_planar_flat<%s,f1x4,h%d,v%d,%s>", rn, L.hold_h, L.hold_v, nt); break;
+    case PLANAR_AVG_F1: snprintf(buf, len, "k_planar_avg_f1<%s,h%d,v%d,%s>", rn, L.hold_h, L.hold_v, nt); break;
+    case PLANAR_AVG_TILE: snprintf(buf, len, "k_planar_avg_tile<%s,f%d,h%d,v%d,nt>", rn, g.f, g.h, g.v); break;
+    case PLANAR_AVG_GEN: snprintf(buf, len, "k_planar_avg_gen<%s,h%d,v%d>", rn, L.hold_h, L.hold_v); break;
+    }
+}
+
+int plan_planar_bits(const csic_params &p, const Geometry &g, const Tune &t, uintptr_t in_align_bits, int nframes, BitsPlan *pp)
+{
+    csic_planar_layout L;
+    planar_layout(g, &p, &L);
+    const int64_t n = (int64_t)g.Wo * g.Ho;
+    // the fast kernels assemble dwords of 32 samples inside one row: every row a whole number of 128 positions (hold_h <= 4)
+    if (t.variant == 9 || p.sampling != CSIC_SAMPLING_HOLD_DECIMATE || L.module_width % 128 != 0) pp->kind = PBITS_GEN;
+    else if (g.f == 1) pp->kind = (in_align_bits & 15u) ? PBITS_GEN : PBITS_F1;     // its 16-byte loads need a 16-byte aligned input
+    else pp->kind = g.s_first ? PBITS_GEN : PBITS_STRIDED;
+    // one-wave blocks for the 16-byte-load kernel (as k_planar_flat MODE 2), 256 threads for the others; k_pbits_gen: one lane per
+    // group of 8 samples of Y, or of both chroma planes
+    const int T = tune_block_threads(t, pp->kind == PBITS_F1 ? 64 : 256);
+    const int K = pp->kind == PBITS_F1 ? PBITS_K : pp->kind == PBITS_STRIDED ? 4 : 1;
+    const int64_t units = pp->kind == PBITS_F1 ? n / 4 : pp->kind == PBITS_STRIDED ? n : (n + 7) / 8 + (L.chroma_samples + 7) / 8;
+    if (flat_blocks(units, K, T) > 0x7FFFFFFF) return set_error(CSIC_EINVAL_SIZE, "frame too large for one launch");
+    plane_flat(units, K, T, nframes, pp);
+    return CSIC_OK;
+}
+
+void planar_bits_kernel_name(BitsKind kind, const csic_params &p, const Geometry &g, const Tune &t, char *buf, size_t len)
+{
+    csic_planar_layout L;
+    planar_layout(g, &p, &L);
+    const char *rn = p.rounding == CSIC_ROUND_FLOOR_HW ? "floor" : "trunc";
+    const char *nt = !t.no_nt ? "nt" : "cached";
+    switch (kind) {
+    case PBITS_F1: snprintf(buf, len, "k_pbits_f1<%s,h%d,v%d,%s>", rn, L.hold_h, L.hold_v, nt); break;
+    case PBITS_STRIDED: snprintf(buf, len, "k_pbits_strided<%s,f%d,h%d,%s>", rn, g.f, L.hold_h, nt); break;
+    case PBITS_GEN:
+        snprintf(buf, len, "k_pbits_gen<%s,%s,h%d,v%d>", rn, p.sampling == CSIC_SAMPLING_AVG ? "avg" : "hold", L.hold_h, L.hold_v);
+        break;
+    }
+}
+
+int plan_reconstruct(const Geometry &g, const Tune &t, int32_t module_width, int K, int nframes, ReconPlan *pp)
+{
+    pp->fast = module_width % 4 == 0 && t.variant != 9;
+    plane_flat(((int64_t)g.Wo * g.Ho + 3) / 4, K, tune_block_threads(t, 64), nframes < 65535 ? nframes : 65535, pp);
+    pp->bdx = pp->bdy = pp->row_step = 0;                       // the reconstruct kernels read none of KArgs
+    return CSIC_OK;
+}
+
+void reconstruct_kernel_name(int src_format, int out_format, bool fast, const Tune &t, char *buf, size_t len)
+{
+    snprintf(buf, len, "%s<%s,%s,%s>", src_format == CSIC_FMT_PLANAR_BITS ? "k_rbits" : "k_recon", out_format == CSIC_FMT_ARGB8888 ? "argb" : "ycc",
+             fast ? "fast" : "slow", !t.no_nt ? "nt" : "cached");
+}
+
+int plan_decode(const csic_params &p, const Geometry &g, const Tune &t, int src_format, uintptr_t align_bits, int nframes, DecodePlan *pp)
+{
+    const bool planar = src_format == CSIC_FMT_PLANAR || src_format == CSIC_FMT_PLANAR_BITS;
+    const int64_t out_px = (int64_t)g.W * g.H;
+    const int nz = nframes < 65535 ? nframes : 65535, T = tune_block_threads(t, 256);
+    pp->recon_fast = false;
+    if (t.variant == 9 || t.force_generic || t.no_vec || (align_bits & 15u)) pp->kind = DEC_GEN;
+    // the reconstruct kernels store 16 bytes at a time from each frame's base: frames after the first start 4 W H bytes further on
+    else if (g.f == 1 && planar && (nframes == 1 || out_px % 4 == 0)) pp->kind = DEC_RECON;
+    // width % 4 == 0 is all a planar source needs too: the module width is W or out_width, a multiple of NP (4 at factor 1, 2 at 2, 1
+    // above), and so is every piece's first stream position
+    else if (g.W % 4 != 0 || out_px > ((int64_t)1 << 30)) pp->kind = DEC_GEN;
+    else pp->kind = DEC_FAST;
+    switch (pp->kind) {
+    case DEC_RECON: {
+        csic_planar_layout L;
+        planar_layout(g, &p, &L);
+        ReconPlan rp;
+        plan_reconstruct(g, t, L.module_width, src_format == CSIC_FMT_PLANAR_BITS ? RBITS_K : RECON_K, nframes, &rp);
+        static_cast<PlaneLaunch &>(*pp) = rp;
+        pp->recon_fast = rp.fast;
+        return CSIC_OK;
+    }
+    // a lane takes dec_pieces_per_lane 16-byte pieces of the output, W / 4 of them to a row of the source
+    case DEC_FAST: plane_flat((int64_t)(g.W / 4) * g.Ho, dec_pieces_per_lane(g.f), T, nz, pp); break;
+    case DEC_GEN: plane_flat(out_px, 1, T, nz, pp); break;     // one output pixel per lane
+    }
+    pp->bdx = pp->bdy = pp->row_step = 0;                       // DecArgs carries T only
+    return CSIC_OK;
+}
+
+void decode_kernel_name(const DecodePlan &pp, const Geometry &g, const Tune &t, int src_format, int out_format, char *buf, size_t len)
+{
+    // an ARGB source runs the YCbCr -> YCbCr instantiation (a copy): the name is the kernel's, as a profiler shows it
+    const char *fmt = out_format == CSIC_FMT_ARGB8888 && src_format != CSIC_FMT_ARGB8888 ? "argb" : "ycc";
+    const char *src = src_format == CSIC_FMT_PLANAR_BITS ? "bits" : src_format == CSIC_FMT_PLANAR ? "planar" : "ycc";
+    switch (pp.kind) {
+    case DEC_RECON: reconstruct_kernel_name(src_format, out_format, pp.recon_fast, t, buf, len); break;
+    case DEC_FAST: snprintf(buf, len, "k_decode<%s,%s,f%d,%s>", src, fmt, g.f, !t.no_nt ? "nt" : "cached"); break;
+    case DEC_GEN: snprintf(buf, len, "k_decode_gen<%s,%s>", src, fmt); break;
     }
 }
 

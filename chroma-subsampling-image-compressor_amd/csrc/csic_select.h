@@ -1,8 +1,10 @@
 // csic_select.h -- the host-only planner: which packed kernel a parameter set takes (select_kernel), what it is called
 // (kernel_name) and with what grid, block and kernel arguments it is launched (plan_launch); which kernel the measurement units
-// take (measure_kind, measure_kernel_name).  Pure integer arithmetic on csic_params, Geometry and the tuning knobs: no HIP header,
-// no device; csic_kernels.hip turns a KernelId into a function pointer (resolve), csic_measure.h a kind into one
-// (measure_kernel), and tests/cpp/launch_table.cpp prints the whole table on a machine without a GPU.
+// take (measure_kind, measure_kernel_name); and the same three decisions for the plane units (plan_planar, plan_planar_bits,
+// plan_reconstruct, plan_decode and their name functions).  Pure integer arithmetic on csic_params, Geometry, the layouts of
+// csic_internal.h and the tuning knobs: no HIP header, no device; csic_kernels.hip turns a KernelId into a function pointer
+// (resolve), csic_measure.h and the plane units a kind into one, and tests/cpp/launch_table.cpp prints the whole table on a
+// machine without a GPU.
 #pragma once
 #include "csic_internal.h"
 
@@ -45,7 +47,7 @@ struct Constraints {
     bool no_vec;         // pointers or pitches that are only 4-byte aligned: no 16-byte vector kernels
 };
 
-// FAM_PLANAR: out_format CSIC_FMT_PLANAR / CSIC_FMT_PLANAR_BITS -- no packed kernel; csic_planar.hip / csic_planar_bits.hip pick theirs.
+// FAM_PLANAR: out_format CSIC_FMT_PLANAR / CSIC_FMT_PLANAR_BITS -- no packed kernel; plan_planar / plan_planar_bits below pick theirs.
 enum Family { FAM_F1X4, FAM_DEC, FAM_DEC2V1, FAM_DEC2V2, FAM_GENERIC, FAM_AVG, FAM_AVG_GENERIC, FAM_DECFLAT, FAM_FLATGEN, FAM_F1FLAT, FAM_PLANAR };
 
 constexpr int DEC_K = 4;     // output pixels per lane of k_dec / k_decflat / k_flatgen
@@ -82,6 +84,9 @@ Selection select_kernel(const csic_params &p, const Geometry &g, const Tune &t, 
 void kernel_name(const KernelId &id, const Geometry &g, char *buf, size_t len);
 // The geometry half of the kernel arguments (what does not depend on the kernel family or the launch shape).
 void fill_base_args(const Geometry &g, int32_t ip, int32_t op, KArgs *a);
+// Threads per block of the kernels that take CSIC_TUNE_BLOCK_THREADS: 64 / 128 / 256 as tuned, `dflt` (the kernel's own; 0 = "not
+// tuned") otherwise.  The one statement of that rule.
+int tune_block_threads(const Tune &t, int dflt);
 // Kernel, grid, block and arguments for `nframes` frames (<= 65535, the grid z limit) whose base pointers OR to `align_bits`,
 // rows `in_pitch` / `out_pitch` pixels apart (0 = packed); the pointers in lp->args stay null.  Returns a csic status.
 int plan_launch(const csic_params &p, const Geometry &g, const Tune &t, uintptr_t align_bits, int nframes, int32_t in_pitch,
@@ -103,5 +108,50 @@ constexpr int64_t CSTAT_BLOCK_SAMPLES = 65536;  // consecutive samples of one pl
 CodeStatsKind code_stats_kind(int src_format, const Tune &t);
 // "k_cstat_bytes<nt>", "k_cstat_bits<q6,5,5,nt>" (the Q of the Y, Cb and Cr launches), "k_cstat_gen<planar>" / "<bits>"
 void code_stats_kernel_name(CodeStatsKind kind, int src_format, const csic_params &p, const Tune &t, char *buf, size_t len);
+
+// ---- the plane units (csic_planar.hip, csic_planar_bits.hip, csic_decode.hip; reconstruct_device of csic_hip_common.h) ------
+// Per-lane constants that planner and kernels share: groups of 4 positions per lane of k_planar_flat, k_pbits_f1, k_recon and
+// k_rbits, and the 16-byte pieces per lane of k_decode at a factor.
+constexpr int PLANAR_K = 4, PBITS_K = 4, RBITS_K = 4;
+#ifndef CSIC_RECON_K
+#define CSIC_RECON_K 4
+#endif
+constexpr int RECON_K = CSIC_RECON_K;
+constexpr int dec_pieces_per_lane(int f) { return f == 1 ? 4 : f == 2 ? 2 : 1; }
+
+// One kernel each.  PLANAR_FLAT_* are k_planar_flat's MODE 0 / 2 / 1 (PLANAR_FLAT_4PL, 4 consecutive positions per lane, is the first
+// form of PLANAR_STRIDED: CSIC_TUNE_VARIANT 10, A/B); DEC_RECON is csic_reconstruct_device / csic_reconstruct_bits_device.
+enum PlanarKind { PLANAR_FLAT_GEN, PLANAR_STRIDED, PLANAR_FLAT_F1X4, PLANAR_AVG_F1, PLANAR_AVG_GEN, PLANAR_FLAT_4PL, PLANAR_AVG_TILE };
+enum BitsKind { PBITS_GEN, PBITS_F1, PBITS_STRIDED };
+enum DecodeKind { DEC_GEN, DEC_FAST, DEC_RECON };
+
+// The launch half of a plane unit's plan.  grid.z is nframes (at most 65535: the units cut longer calls into batches, which differ
+// in z only).  T is the threads per block that PExtra / BExtra / DecArgs carry; bdx, bdy and row_step are what the unit sets in
+// KArgs (0 where it sets none: reconstruct and decode).
+struct PlaneLaunch {
+    Dim3 grid, block;
+    int32_t T, bdx, bdy, row_step;
+};
+struct PlanarPlan : PlaneLaunch { PlanarKind kind; KArgs args; };   // args: complete but for the pointers (PLANAR_AVG_TILE: the packed twin's)
+struct BitsPlan : PlaneLaunch { BitsKind kind; };
+struct ReconPlan : PlaneLaunch { bool fast; };
+struct DecodePlan : PlaneLaunch { DecodeKind kind; bool recon_fast; };   // DEC_RECON: the reconstruct launch, and its kernel's FAST
+
+// Forward to CSIC_FMT_PLANAR over `nframes` <= 65535 frames.  `align_bits` (the OR of the frame pointers, as plan_launch takes it)
+// is NOT consulted: the 16-byte-load kernels are taken at any 4-byte alignment.  PLANAR_AVG_TILE launches as the k_avg
+// of the plan's packed twin does (plan_launch); CSIC_EHIP if that twin turns out not to be FAM_AVG.
+int plan_planar(const csic_params &p, const Geometry &g, const Tune &t, uintptr_t align_bits, int nframes, PlanarPlan *pp);
+// Forward to CSIC_FMT_PLANAR_BITS; `in_align_bits`: the input pointer (k_pbits_f1's 16-byte loads need it 16-byte aligned).
+// CSIC_EINVAL_SIZE for a frame of more than 2^31 - 1 blocks.
+int plan_planar_bits(const csic_params &p, const Geometry &g, const Tune &t, uintptr_t in_align_bits, int nframes, BitsPlan *pp);
+// Either reconstruct: `module_width` of the source's layout, K = RECON_K / RBITS_K groups per lane.
+int plan_reconstruct(const Geometry &g, const Tune &t, int32_t module_width, int K, int nframes, ReconPlan *pp);
+// csic_decode_device from `src_format` (any CSIC_FMT_*); align_bits: the output pointer, OR-ed with the source pointer for a packed source.
+int plan_decode(const csic_params &p, const Geometry &g, const Tune &t, int src_format, uintptr_t align_bits, int nframes, DecodePlan *pp);
+// "k_planar_flat<floor,f1x4,h2,v2,nt>", "k_pbits_gen<trunc,avg,h1,v1>", "k_recon<argb,fast,nt>", "k_decode<bits,ycc,f2,cached>", ...
+void planar_kernel_name(PlanarKind kind, const csic_params &p, const Geometry &g, const Tune &t, char *buf, size_t len);
+void planar_bits_kernel_name(BitsKind kind, const csic_params &p, const Geometry &g, const Tune &t, char *buf, size_t len);
+void reconstruct_kernel_name(int src_format, int out_format, bool fast, const Tune &t, char *buf, size_t len);
+void decode_kernel_name(const DecodePlan &pp, const Geometry &g, const Tune &t, int src_format, int out_format, char *buf, size_t len);
 
 } // namespace csic

@@ -15,6 +15,10 @@
 // its distinct parameter sets, one line per unit:
 //       measure WxH a:b f order sampling in rounding [| g1] -> dist|ssim kind name
 // (neither the output format nor, of the knobs, anything but force_generic enters that choice)
+// Last come the plane units (plan_planar, plan_planar_bits, plan_reconstruct, plan_decode), one section each, the same head fields
+// with the plane format as `out` (what reconstruct and decode READ; `to-` is what they write):
+//       planar|bits|recon|decode <head> [to-argb|to-ycc] -> status name g=grid b=block a=bdx,bdy,row_step T=threads [h=hash]
+// (h: the KArgs of the packed twin whose k_avg launch k_planar_avg_tile follows; --full adds the kind's number)
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -165,23 +169,34 @@ static void note_measure(const Case &c, const Geometry &g)
     }
 }
 
-static void emit(const Case &c)
+static const char *format_word(int fmt)
 {
-    Geometry g;
-    if (derive_geometry(&c.p, &g) != CSIC_OK) { std::fprintf(stderr, "bad case: %s\n", csic_last_error()); std::exit(2); }
-    if (g_print && !g_fields) note_measure(c, g);
-    const Result r = run_case(c, g);
-    ++g_cases;
+    return fmt == CSIC_FMT_ARGB8888 ? "argb" : fmt == CSIC_FMT_YCBCR888X ? "ycc" : fmt == CSIC_FMT_PLANAR ? "planar" : "bits";
+}
+
+// the head fields of a line; validates the case and derives its geometry
+static void case_head(const Case &c, Geometry *g, char *head, size_t len)
+{
+    if (derive_geometry(&c.p, g) != CSIC_OK) { std::fprintf(stderr, "bad case: %s\n", csic_last_error()); std::exit(2); }
     const csic_params &p = c.p;
     // knobs and launch settings are printed only where they differ from the default (no knob, one frame, aligned, packed)
-    char head[256], knobs[96] = "", at[96] = "";
+    char knobs[96] = "", at[96] = "";
     if (c.t.variant || c.t.force_generic || c.t.no_vec || c.t.no_nt || c.t.block_threads)
         std::snprintf(knobs, sizeof knobs, " | v%d g%d n%d c%d b%d", c.t.variant, c.t.force_generic, c.t.no_vec, c.t.no_nt, c.t.block_threads);
     if (c.nframes != 1 || c.align || c.ip || c.op) std::snprintf(at, sizeof at, " | n%d a%u p%d,%d", c.nframes, c.align, c.ip, c.op);
-    std::snprintf(head, sizeof head, "%dx%d %d:%d f%d o%d%d%d %s %s %s %s%s%s", p.width, p.height, p.chroma_a, p.chroma_b, p.factor, p.op[0],
-                  p.op[1], p.op[2], p.sampling == CSIC_SAMPLING_AVG ? "avg" : "hold",
-                  p.out_format == CSIC_FMT_ARGB8888 ? "argb" : p.out_format == CSIC_FMT_YCBCR888X ? "ycc" : p.out_format == CSIC_FMT_PLANAR ? "planar" : "bits",
+    std::snprintf(head, len, "%dx%d %d:%d f%d o%d%d%d %s %s %s %s%s%s", p.width, p.height, p.chroma_a, p.chroma_b, p.factor, p.op[0],
+                  p.op[1], p.op[2], p.sampling == CSIC_SAMPLING_AVG ? "avg" : "hold", format_word(p.out_format),
                   p.in_format == CSIC_FMT_ARGB8888 ? "argb" : "ycc", p.rounding == CSIC_ROUND_FLOOR_HW ? "floor" : "trunc", knobs, at);
+}
+
+static void emit(const Case &c)
+{
+    Geometry g;
+    char head[256];
+    case_head(c, &g, head, sizeof head);
+    if (g_print && !g_fields) note_measure(c, g);
+    const Result r = run_case(c, g);
+    ++g_cases;
     if (r.status != CSIC_OK) {
         if (g_print) std::printf("%s -> %d\n", head, r.status);
         return;
@@ -435,6 +450,228 @@ static void sweep_errors()
     c.p.out_format = CSIC_FMT_PLANAR_BITS; emit(c);
 }
 
+// ---- the plane units: planar and bit-plane forward, reconstruct, decode ------------------------------------------------
+// The plane format travels in p.out_format: what the forward units write, what reconstruct and decode read (decode also reads
+// the packed formats); `to` is the packed format those two write.
+enum Unit { U_PLANAR, U_BITS, U_RECON, U_DECODE };
+static const char *const UNIT_WORD[] = {"planar", "bits", "recon", "decode"};
+
+#define REQUIRE_COVER(blocks, per_block, work) REQUIRE((uint64_t)(blocks) * (uint64_t)(per_block) >= (uint64_t)(work))
+
+static void emit_plane(Unit u, const Case &c, int to = CSIC_FMT_ARGB8888)
+{
+    Geometry g;
+    char head[256], name[96] = "", hash[16] = "";
+    case_head(c, &g, head, sizeof head);
+    ++g_cases;
+    const csic_params &p = c.p;
+    csic_planar_layout L;
+    planar_layout(g, &p, &L);
+    const int64_t n = (int64_t)g.Wo * g.Ho, out_px = (int64_t)g.W * g.H;
+    const bool flat_src = p.out_format == CSIC_FMT_PLANAR || p.out_format == CSIC_FMT_PLANAR_BITS;
+    PlaneLaunch l{};
+    int status = CSIC_OK, kind = 0;
+    bool ok = true, rows = false, tile = false;                // a row-tiled kind; k_avg's launch
+    switch (u) {
+    case U_PLANAR: {
+        PlanarPlan pp;
+        if ((status = plan_planar(p, g, c.t, c.align, c.nframes, &pp)) != CSIC_OK) break;
+        l = pp; kind = pp.kind;
+        planar_kernel_name(pp.kind, p, g, c.t, name, sizeof name);
+        REQUIRE(pp.args.bdx == l.bdx && pp.args.bdy == l.bdy && pp.args.row_step == l.row_step);
+        REQUIRE(l.bdx == (int32_t)l.block.x && l.bdy == (int32_t)l.block.y);
+        if (pp.kind == PLANAR_AVG_TILE) {
+            // k_avg's launch: everything check_invariants asks of FAM_AVG
+            tile = true;
+            LaunchPlan lp{};
+            lp.id.fam = FAM_AVG; lp.id.tiles = g.f <= 2 ? 2 : 1;
+            lp.grid = l.grid; lp.block = l.block; lp.args = pp.args;
+            ok = check_invariants(c, g, lp) && ok;
+            REQUIRE(l.T == 256);
+            std::snprintf(hash, sizeof hash, " h=%08x", args_hash(pp.args));
+        } else if (pp.kind == PLANAR_AVG_F1 || pp.kind == PLANAR_AVG_GEN) {
+            rows = true;
+            REQUIRE(l.T == 256 && l.block.x * l.block.y <= 256);
+            REQUIRE_COVER(l.grid.x, l.block.x * (pp.kind == PLANAR_AVG_F1 ? 2 : 1), pp.kind == PLANAR_AVG_F1 ? g.W / 4 : g.Wo);
+            if (pp.kind == PLANAR_AVG_F1) REQUIRE(g.f == 1 && g.W % 4 == 0 && g.H % g.v == 0);
+        } else {
+            REQUIRE_COVER(l.grid.x, (uint64_t)l.T * 4 * (pp.kind == PLANAR_STRIDED ? 1 : PLANAR_K), n);
+            if (pp.kind != PLANAR_FLAT_GEN) REQUIRE(L.module_width % 4 == 0);
+        }
+        break;
+    }
+    case U_BITS: {
+        BitsPlan bp;
+        if ((status = plan_planar_bits(p, g, c.t, c.align, c.nframes, &bp)) != CSIC_OK) break;
+        l = bp; kind = bp.kind;
+        planar_bits_kernel_name(bp.kind, p, g, c.t, name, sizeof name);
+        REQUIRE(l.bdx == (int32_t)l.block.x && l.bdy == 1 && l.row_step == 1);
+        if (bp.kind == PBITS_F1) { REQUIRE((c.align & 15u) == 0 && L.module_width % 128 == 0 && g.f == 1); REQUIRE_COVER(l.grid.x, l.T * PBITS_K, n / 4); }
+        else if (bp.kind == PBITS_STRIDED) { REQUIRE(L.module_width % 128 == 0 && !g.s_first); REQUIRE_COVER(l.grid.x, l.T * 4, n); }
+        else REQUIRE_COVER(l.grid.x, l.T, (n + 7) / 8 + (L.chroma_samples + 7) / 8);
+        break;
+    }
+    case U_RECON: {
+        ReconPlan rp;
+        const int K = p.out_format == CSIC_FMT_PLANAR_BITS ? RBITS_K : RECON_K;
+        if ((status = plan_reconstruct(g, c.t, L.module_width, K, c.nframes, &rp)) != CSIC_OK) break;
+        l = rp; kind = rp.fast;
+        reconstruct_kernel_name(p.out_format, to, rp.fast, c.t, name, sizeof name);
+        if (rp.fast) REQUIRE(L.module_width % 4 == 0);
+        REQUIRE_COVER(l.grid.x, (uint64_t)l.T * K * 4, n);
+        break;
+    }
+    case U_DECODE: {
+        DecodePlan dp;
+        if ((status = plan_decode(p, g, c.t, p.out_format, c.align, c.nframes, &dp)) != CSIC_OK) break;
+        l = dp; kind = dp.kind;
+        decode_kernel_name(dp, g, c.t, p.out_format, to, name, sizeof name);
+        if (dp.kind == DEC_FAST) {
+            REQUIRE((c.align & 15u) == 0 && g.W % 4 == 0 && out_px <= (1ll << 30));
+            REQUIRE_COVER(l.grid.x, l.T * dec_pieces_per_lane(g.f), (int64_t)(g.W / 4) * g.Ho);
+        } else if (dp.kind == DEC_RECON) {
+            REQUIRE(g.f == 1 && flat_src && (c.nframes == 1 || out_px % 4 == 0) && (c.align & 15u) == 0);
+            REQUIRE_COVER(l.grid.x, (uint64_t)l.T * (p.out_format == CSIC_FMT_PLANAR_BITS ? RBITS_K : RECON_K) * 4, n);
+        } else {
+            REQUIRE_COVER(l.grid.x, l.T, out_px);
+        }
+        break;
+    }
+    }
+    if (status != CSIC_OK) {
+        if (g_print) std::printf("%s %s -> %d\n", UNIT_WORD[u], head, status);
+        return;
+    }
+    // every plane launch, whatever the rules are
+    REQUIRE(l.T == 64 || l.T == 128 || l.T == 256);
+    // (reconstruct and decode are planned once per call: z is the first batch's)
+    const int nz = (u == U_RECON || u == U_DECODE) && c.nframes > 65535 ? 65535 : c.nframes;
+    REQUIRE(l.grid.x >= 1 && l.grid.y >= 1 && l.grid.y <= 65535 && l.grid.z == (uint32_t)nz && l.block.z == 1);
+    if (rows) REQUIRE(l.row_step == (int32_t)(l.grid.y * l.block.y));
+    else if (!tile) REQUIRE(l.block.x * l.block.y == (uint32_t)l.T && l.grid.y == 1 && l.block.y == 1);
+    if (u == U_RECON || u == U_DECODE) REQUIRE(l.bdx == 0 && l.bdy == 0 && l.row_step == 0);
+    if (!ok) { std::fprintf(stderr, "  in: %s %s -> %s\n", UNIT_WORD[u], head, name); ++g_failed; }
+    if (!g_print) return;
+    std::printf("%s %s", UNIT_WORD[u], head);
+    if (u == U_RECON || u == U_DECODE) std::printf(" to-%s", format_word(to));
+    std::printf(" -> 0 %s g=%u,%u,%u b=%u,%u,%u a=%d,%d,%d T=%d%s", name, l.grid.x, l.grid.y, l.grid.z, l.block.x, l.block.y, l.block.z, l.bdx,
+                l.bdy, l.row_step, l.T, hash);
+    if (g_fields) std::printf(" k%d", kind);
+    std::printf("\n");
+}
+
+static Case plane_case(Shape s, int ch, int f, int order, bool avg, int fmt, int tune = -1, int nframes = 1, unsigned align = 0)
+{
+    Case c = make(s, ch, f, order, avg);
+    c.p.out_format = fmt;
+    if (tune >= 0) c.t = tune_set(tune);
+    c.nframes = nframes; c.align = align;
+    return c;
+}
+
+// One case on each side of every comparison of the plane units' rules, on the smallest shapes that flip it (nothing is allocated).
+// 64x40: every module width a multiple of 4; 201x27: none, and W H no multiple of 4; 66x40: W % 4 != 0 with an even output width.
+static void sweep_planes()
+{
+    const int PL = CSIC_FMT_PLANAR, PB = CSIC_FMT_PLANAR_BITS;
+    const Shape A{64, 40}, B{201, 27}, C{66, 40};
+    // planar forward.  HOLD: module width % 4, factor 1 with W % 4, factors >= 2 in both order classes
+    for (Shape s : {A, B, C})
+        for (int f : {1, 2, 4})
+            for (int o = 0; o < (f == 1 ? 1 : 2); ++o) emit_plane(U_PLANAR, plane_case(s, 2, f, o, false, PL));
+    for (int ch : {0, 3}) emit_plane(U_PLANAR, plane_case(A, ch, 2, 0, false, PL));          // the other holds
+    // the group count at a block's edge: 1024 groups and one position (4 blocks of 256 threads and 1), 1024 groups in 4 one-wave blocks
+    for (Shape s : {Shape{4097, 1}, Shape{64, 64}}) emit_plane(U_PLANAR, plane_case(s, 2, 1, 0, false, PL));
+    // AVG: whole tiles, H % v != 0, no whole tile; every factor
+    for (Shape s : {A, Shape{64, 41}, Shape{3, 5}})
+        for (int f : FACTORS) emit_plane(U_PLANAR, plane_case(s, 2, f, 0, true, PL));
+    // the variants (9 general, 10 four positions per lane, 12 the tile body at factor 1), cached accesses, block threads
+    for (int k : {9, 10, 12, 15, 16, 17, 18})
+        for (int f : {1, 2})
+            for (int avg = 0; avg < 2; ++avg) emit_plane(U_PLANAR, plane_case(A, 2, f, 0, avg != 0, PL, k));
+    { Case c = plane_case(A, 2, 1, 0, true, PL, 12); c.t.no_nt = 1; emit_plane(U_PLANAR, c); }    // variant 12 AND cached: avg_f1 again
+    // batches (k_avg's XCD rotation needs more than one frame); the table path's 4-byte-aligned frames: the same kernels as aligned
+    // ones, 16-byte loads included -- the packed path drops to 4-byte kernels there
+    for (int nf : {3, 65535})
+        for (int avg = 0; avg < 2; ++avg)
+            for (int f : {1, 2}) emit_plane(U_PLANAR, plane_case(Shape{1922, 1082}, 2, f, 0, avg != 0, PL, -1, nf));
+    for (int avg = 0; avg < 2; ++avg) emit_plane(U_PLANAR, plane_case(A, 2, 1, 0, avg != 0, PL, -1, 3, 4));
+    // the row-tiled kernels: block width around 256 lanes (avg_f1: 2 tiles of 4 pixels per lane; avg_gen, variant 9: a pixel), and
+    // the grid-y clamp at 65535 block rows, on both sides
+    for (int w : {2040, 2048, 2052, 2056}) emit_plane(U_PLANAR, plane_case(Shape{w, 8}, 2, 1, 0, true, PL));
+    for (int w : {255, 256, 257}) emit_plane(U_PLANAR, plane_case(Shape{w, 8}, 2, 1, 0, true, PL, 9));
+    for (int h : {65534, 65535, 65536, 70000}) {
+        emit_plane(U_PLANAR, plane_case(Shape{2048, 2 * h}, 2, 1, 0, true, PL));
+        emit_plane(U_PLANAR, plane_case(Shape{256, h}, 2, 1, 0, true, PL, 9));
+    }
+    // bit-plane forward: module width % 128 (chroma first at factor 2: the output width), factor 1, factor 2 in both order classes,
+    // factor 4, AVG, variant 9, a 4-byte-aligned input, block threads, a batch
+    for (Shape s : {Shape{128, 8}, Shape{132, 8}, Shape{256, 8}, Shape{264, 8}}) {
+        for (int f : {1, 2, 4})
+            for (int o = 0; o < (f == 1 ? 1 : 2); ++o) emit_plane(U_BITS, plane_case(s, 2, f, o, false, PB));
+        emit_plane(U_BITS, plane_case(s, 2, 1, 0, true, PB));
+    }
+    for (int f : {1, 2}) {
+        for (int k : {9, 15, 16, 17, 18}) emit_plane(U_BITS, plane_case(Shape{256, 8}, 2, f, 0, false, PB, k));
+        emit_plane(U_BITS, plane_case(Shape{256, 8}, 2, f, 0, false, PB, -1, 1, 4));
+        emit_plane(U_BITS, plane_case(Shape{256, 8}, 2, f, 0, false, PB, -1, 3));
+        emit_plane(U_BITS, plane_case(Shape{256, 40}, 2, f, 0, false, PB));                 // several blocks of either fast kernel
+    }
+    // k_pbits_gen's groups of 8 samples at 4:4:4 (as many chroma samples as positions): exactly one block of them, and 2 more
+    for (int w : {128, 129}) emit_plane(U_BITS, plane_case(Shape{w, 8}, 0, 1, 0, true, PB));
+    // reconstruct, both sources and both outputs: module width % 4, variant 9, cached accesses, block threads, a batch
+    for (int src : {PL, PB})
+        for (int to : {(int)CSIC_FMT_ARGB8888, (int)CSIC_FMT_YCBCR888X}) {
+            for (Shape s : {A, B, C})
+                for (int f : {1, 2})
+                    for (int o = 0; o < (f == 1 ? 1 : 2); ++o) emit_plane(U_RECON, plane_case(s, 2, f, o, false, src), to);
+            for (int k : {9, 15, 16, 17, 18}) emit_plane(U_RECON, plane_case(A, 2, 2, 0, false, src, k), to);
+            emit_plane(U_RECON, plane_case(B, 2, 1, 0, false, src, -1, 3), to);
+        }
+    // 1024 groups and one position; calls of more than 65535 frames go in batches: z is the first one's
+    emit_plane(U_RECON, plane_case(Shape{4097, 1}, 2, 1, 0, false, PL));
+    for (int nf : {65534, 65536}) {
+        emit_plane(U_RECON, plane_case(A, 2, 1, 0, false, PL, -1, nf));
+        emit_plane(U_DECODE, plane_case(A, 2, 2, 0, false, PL, -1, nf));
+    }
+    // decode from the three sources (and once from ARGB): every clause of the kind both ways -- variant 9, force-generic, no-vector,
+    // 4-byte-aligned pointers; factor 1 from planes (reconstruct) against packed; W H % 4 with 1 and 3 frames; W % 4; factors 1 - 8;
+    // W H on both sides of 2^30; block threads
+    for (int src : {(int)CSIC_FMT_YCBCR888X, PL, PB}) {
+        for (Shape s : {A, B, C, Shape{64, 41}})
+            for (int f : FACTORS)
+                for (int nf : {1, 3}) emit_plane(U_DECODE, plane_case(s, 2, f, 0, false, src, -1, nf));
+        for (int f : {1, 2}) {
+            for (int k : {9, 13, 14, 15, 16, 17, 18}) emit_plane(U_DECODE, plane_case(A, 2, f, 0, false, src, k));
+            emit_plane(U_DECODE, plane_case(A, 2, f, 0, false, src, -1, 1, 4));
+            emit_plane(U_DECODE, plane_case(A, 2, f, 1, false, src), CSIC_FMT_YCBCR888X);
+            for (Shape s : {Shape{32768, 32768}, Shape{32768, 32769}}) emit_plane(U_DECODE, plane_case(s, 2, f, 0, false, src));
+        }
+    }
+    emit_plane(U_DECODE, plane_case(A, 2, 2, 0, false, CSIC_FMT_ARGB8888));
+}
+
+// the whole cross product for the plane units: every knob setting, then batches and 4-byte-aligned pointers
+static void sweep_planes_full()
+{
+    for (int s = 0; s < NSHAPES; ++s)
+        for (int ch = 0; ch < 6; ++ch)
+            for (int f : FACTORS)
+                for (int o = 0; o < 7; ++o)
+                    for (int fmt : {(int)CSIC_FMT_YCBCR888X, (int)CSIC_FMT_PLANAR, (int)CSIC_FMT_PLANAR_BITS}) {
+                        const auto each = [&](Unit u, int to) {
+                            for (int k = 0; k < NTUNES; ++k) emit_plane(u, plane_case(SHAPES[s], ch, f, o % 6, o == 6, fmt, k), to);
+                            for (int nf : {1, 3, 65535})
+                                for (unsigned al : {0u, 4u})
+                                    if (nf != 1 || al) emit_plane(u, plane_case(SHAPES[s], ch, f, o % 6, o == 6, fmt, -1, nf, al), to);
+                        };
+                        for (int to : {(int)CSIC_FMT_ARGB8888, (int)CSIC_FMT_YCBCR888X}) each(U_DECODE, to);
+                        if (fmt == CSIC_FMT_YCBCR888X) continue;
+                        each(fmt == CSIC_FMT_PLANAR ? U_PLANAR : U_BITS, 0);
+                        each(U_RECON, CSIC_FMT_ARGB8888);
+                    }
+}
+
 int main(int argc, char **argv)
 {
     bool full = false;
@@ -448,6 +685,8 @@ int main(int argc, char **argv)
     sweep_limits();
     sweep_errors();
     for (const std::string &line : g_measure) std::printf("%s\n", line.c_str());
+    if (full) sweep_planes_full();
+    sweep_planes();
     std::fprintf(stderr, "launch_table: %ld cases, %ld with a broken invariant\n", g_cases, g_failed);
     return g_failed ? 1 : 0;
 }

@@ -1,7 +1,8 @@
-"""The launch table of the packed kernels, on the CPU: tests/cpp/launch_table.cpp (g++, host only) prints, for a structured sweep
-of parameter sets, knobs, batch sizes, alignments and pitches, which kernel csrc/csic_select.cpp picks and with what grid, block
-and KArgs; the output must equal tests/data/launch_table.txt.  A change of a selection or geometry rule therefore shows, in the
-diff of that file, exactly which shapes moved to which kernel and geometry:
+"""The launch table of the packed kernels and of the plane units (planar and bit-plane forward, reconstruct, decode), on the CPU:
+tests/cpp/launch_table.cpp (g++, host only) prints, for a structured sweep of parameter sets, knobs, batch sizes, alignments and
+pitches, which kernel csrc/csic_select.cpp picks and with what grid, block and KArgs; the output must equal
+tests/data/launch_table.txt.  A change of a selection or geometry rule therefore shows, in the diff of that file, exactly which
+shapes moved to which kernel and geometry:
 
     python tests/test_launch_table.py --write      # regenerate the fixture after an intended change
 
@@ -36,9 +37,11 @@ def test_launch_table_matches_the_committed_fixture(tmp_path):
         f"{len(moved)} of {len(want)} launches changed ({len(got)} printed); first ones:\n" + "\n".join(moved[:10]) +
         "\nif intended: python tests/test_launch_table.py --write, and review the diff of tests/data/launch_table.txt")
     assert os.path.getsize(FIXTURE) < 348 * 1024          # stays below the largest committed file
-    # the sweep reaches every packed family and both sides of the launch-time fall-backs
+    # the sweep reaches every packed family and both sides of the launch-time fall-backs, and every kernel of the plane units
     text = "\n".join(got)
-    for name in ("k_f1flat<", "k_f1x4<", "k_dec<", "k_decflat<", "k_dec2v<", "k_flatgen<", "k_generic<", "k_avg<", "k_avg_generic<"):
+    for name in ("k_f1flat<", "k_f1x4<", "k_dec<", "k_decflat<", "k_dec2v<", "k_flatgen<", "k_generic<", "k_avg<", "k_avg_generic<",
+                 "k_planar_flat<", "k_planar_strided<", "k_planar_avg_f1<", "k_planar_avg_gen<", "k_planar_avg_tile<", "k_pbits_gen<",
+                 "k_pbits_f1<", "k_pbits_strided<", "k_recon<", "k_rbits<", "k_decode<", "k_decode_gen<"):
         assert f" {name}" in text, name
 
 

@@ -6,7 +6,8 @@ name formatting, not fill_base_args), builds tests/cpp/launch_table.cpp against 
   killed      a line of the committed table moves, or an invariant of the program breaks;
   SURVIVED    the committed table does not move although the whole cross product (launch_table --full) does: add a case;
   unseen      neither moves: the mutant is equivalent on the parameter domain (factors 1 / 2 / 4 / 8, holds 1 / 2 / 4, ...) or
-              sits in a value nothing reads; each one is listed for a reader to judge (profiles/r07_planner_refactor.md does)."""
+              sits in a value nothing reads; each one is listed for a reader to judge (profiles/r07_planner_refactor.md does, and
+              profiles/r17_planner_planes.md for the plane units' planning functions)."""
 import concurrent.futures as cf
 import hashlib
 import os
@@ -36,7 +37,7 @@ skip_fn = False
 mutants = []
 for i in range(start, len(lines)):
     l = lines[i]
-    if l.startswith("void kernel_name") or l.startswith("void fill_base_args"):
+    if l.startswith("void fill_base_args") or re.match(r"void \w*kernel_name\(", l):        # every name function, the plane units' too
         skip_fn = True
     elif skip_fn and l.startswith("}"):
         skip_fn = False
