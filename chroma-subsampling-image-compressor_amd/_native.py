@@ -99,6 +99,11 @@ class CsicDeltaLayout(C.Structure):
     _fields_ = [("groups", C.c_int64 * 3), ("map_offset", C.c_int64 * 3), ("map_bytes", C.c_int64), ("map_stride", C.c_int64)]
 
 
+class CsicMcLayout(C.Structure):
+    _fields_ = [("groups", C.c_int64 * 3), ("width", C.c_int64 * 3), ("table_offset", C.c_int64 * 3), ("map_offset", C.c_int64 * 3),
+                ("map_bytes", C.c_int64), ("map_stride", C.c_int64), ("workspace_frame_bytes", C.c_int64)]
+
+
 class CsicContainerInfo(C.Structure):
     _fields_ = [("params", CsicParams), ("version", C.c_int32), ("nframes", C.c_int32), ("payload_bytes", C.c_int64),
                 ("file_bytes", C.c_int64)]
@@ -148,6 +153,10 @@ PROTOTYPES = {
                                                  C.c_int32, C.c_int32, C.c_int32]),
     "csic_container_gop": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
     "csic_container_inter_groups": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.c_int32]),
+    "csic_container_write_seq_ex": (C.c_int, [C.c_char_p, C.POINTER(CsicParams), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "csic_container_write_coded_seq_ex": (C.c_int, [C.c_char_p, C.POINTER(CsicParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t,
+                                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "csic_container_motion": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
     "csic_pack_layout_of": (C.c_int, [C.POINTER(CsicParams), C.POINTER(CsicPackLayout)]),
     "csic_pack_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "csic_unpack_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -168,6 +177,12 @@ PROTOTYPES = {
     "csic_delta_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "csic_undelta_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "csic_delta_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "csic_mc_layout_of": (C.c_int, [C.POINTER(CsicParams), C.POINTER(CsicMcLayout)]),
+    "csic_mc_delta_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "csic_mc_undelta_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "csic_mc_delta_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "csic_mc_undelta_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "csic_mc_kernel_name": (C.c_char_p, [C.c_void_p]),
     "csic_distortion_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
     "csic_distortion_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "csic_distortion_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_uint64)]),

@@ -11,7 +11,7 @@ HIP launch.
 Two leading verbs go past what the reference's app does (it only ever writes the reconstructed pixels as a PNG):
 
     python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ... [--coding raw|groups|rice]
-    python -m csic_amd.app compress   --inputs a.png,b.png,... --gop K --coding groups|rice --output x.csic ...
+    python -m csic_amd.app compress   --inputs a.png,b.png,... --gop K [--motion R] --coding groups|rice --output x.csic ...
     python -m csic_amd.app decompress --input x.csic --output x.png [--frame K | --output-pattern frame_%03d.png]
 
     python -m csic_amd.app inspect    --input x.csic
@@ -28,13 +28,13 @@ from __future__ import annotations
 
 import os
 import sys
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 
 from .compressor import ImageCompressorTop, Plan
 from . import _native as N
-from .container import (container_coded_sizes, container_info, container_inter_groups, delta_layout, read_container, write_container,
+from .container import (container_coded_sizes, container_info, container_inter_groups, delta_layout, mc_layout, read_container, write_container,
                         write_container_coded)
 from .model import Image, ImageProcessorModel
 from .params import PixelFormat, ProcessingStep, Sampling
@@ -122,9 +122,10 @@ class ImageCompressionApp:
                          yTargetBits: int, cbTargetBits: int, crTargetBits: int,
                          spatialFactorToUse: int,
                          op1: ProcessingStep, op2: ProcessingStep, op3: ProcessingStep,
-                         sampling: Sampling = Sampling.HOLD_DECIMATE, *, device: int = 0, coding: str = "rice", gop: int = 16) -> int:
+                         sampling: Sampling = Sampling.HOLD_DECIMATE, *, device: int = 0, coding: str = "rice", gop: int = 16,
+                         motion: Optional[int] = None) -> int:
         """PNGs of equal size -> one CSIC_FMT_PLANAR_BITS plan -> csic_delta_device -> the device coder -> a version-5 .csic container
-        (csic_container_write_coded_seq).  Returns the bytes written."""
+        (csic_container_write_coded_seq); with a `motion` range csic_mc_delta_device and version 6.  Returns the bytes written."""
         if coding not in ("groups", "rice"):
             raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: a sequence takes --coding groups or rice, got {coding!r}")
         paths = list(inputImagePaths)
@@ -145,10 +146,11 @@ class ImageCompressionApp:
             argb = np.stack([np.ascontiguousarray(im.argb, dtype=np.uint32).reshape(-1) for im in images])
             d_in = torch.from_numpy(argb.reshape(-1).view(np.int32)).to(f"cuda:{device}")
             bits = plan.process_device(d_in, None, n).reshape(n, plan.frame_bytes)
-            diff, maps = plan.delta_device(bits, n, gop)
+            diff, maps = plan.delta_device(bits, n, gop) if motion is None else plan.mc_delta_device(bits, n, gop, motion)
             pack = plan.pack_device if coding == "groups" else plan.rice_pack_device
             coded, sizes = pack(diff, n)
-            write_container_coded(outputPath, plan.c_params, coded.cpu().numpy(), sizes.cpu().numpy(), coding=coding, maps=maps.cpu().numpy(), gop=gop)
+            write_container_coded(outputPath, plan.c_params, coded.cpu().numpy(), sizes.cpu().numpy(), coding=coding, maps=maps.cpu().numpy(), gop=gop,
+                                  motion=motion)
         finally:
             top.close()
         return os.path.getsize(outputPath)
@@ -314,9 +316,18 @@ def _main_sequence(argsMap: Dict[str, str]) -> int:
         paths, argsMap["--output"], int(argsMap.get("--a", "4")), int(argsMap.get("--b", "4")), int(argsMap.get("--yq", "8")),
         int(argsMap.get("--cbq", "8")), int(argsMap.get("--crq", "8")), int(argsMap.get("--sf", "8")),
         ProcessingStep.parse(argsMap.get("--op1", "spatial")), ProcessingStep.parse(argsMap.get("--op2", "color")),
-        ProcessingStep.parse(argsMap.get("--op3", "chroma")), sampling, coding=coding, gop=int(argsMap.get("--gop", "16")))
+        ProcessingStep.parse(argsMap.get("--op3", "chroma")), sampling, coding=coding, gop=int(argsMap.get("--gop", "16")),
+        motion=int(argsMap["--motion"]) if "--motion" in argsMap else None)
     print(f"Compression complete. {len(paths)} frames, {sum(os.path.getsize(p) for p in paths)} -> {size} bytes. Output saved to: {argsMap['--output']}")
     return 0
+
+
+def _vector_of(s: int, w: int, R: int) -> str:
+    """The candidate a table word stands for: the (dy, dx) of [-R, R]^2 with dy * w + dx == s that has the lowest rank -- by
+    (|dx| + |dy|, dy, dx), the encoder's order; in narrow planes several have the same offset -- or the bare offset if there is none
+    (a file not written by this encoder)."""
+    hits = [(abs(dx) + abs(dy), dy, dx) for dy in range(-R, R + 1) for dx in range(-R, R + 1) if dy * w + dx == s]
+    return f"({min(hits)[1]}, {min(hits)[2]})" if hits else f"offset {s}"
 
 
 def _main_inspect(args: List[str]) -> int:
@@ -344,6 +355,27 @@ def _main_inspect(args: List[str]) -> int:
             share = ", ".join(f"{name} {int(inter[k][i]) / groups[i]:.3f}" for i, name in enumerate(("Y", "Cb", "Cr")))
             print(f"  frame {k} ({'key' if k % info.gop == 0 else 'delta'}): stored in {int(stored)} bytes, {int(stored) / info.payload_bytes:.4f} of raw, "
                   f"inter groups {share}")
+    elif info.version == 6:
+        print(f"Frame coding: {({1: 'groups', 3: 'rice'}).get(info.coding, 'raw')}, motion-compensated delta with gop {info.gop}, range {info.motion}")
+        ml = mc_layout(p)
+        sizes = container_coded_sizes(inputPath)
+        with open(inputPath, "rb") as fh:
+            at = 88 + 8 * info.nframes
+            for k, stored in enumerate(sizes):
+                print(f"  frame {k} ({'key' if k % info.gop == 0 else 'delta'}): stored in {int(stored)} bytes, {int(stored) / info.payload_bytes:.4f} of raw")
+                if k % info.gop:
+                    fh.seek(at)
+                    m = np.frombuffer(fh.read(ml.map_bytes), dtype=np.uint8)
+                    for i, name in enumerate(("Y", "Cb", "Cr")):
+                        words = m[ml.table_offset[i]:ml.table_offset[i] + 64].view("<i4")
+                        sec = m[ml.map_offset[i]:ml.map_offset[i] + (ml.groups[i] + 1) // 2]
+                        nib = np.stack([sec & 15, sec >> 4], axis=1).reshape(-1)[:ml.groups[i]]
+                        w, G = int(ml.width[i]), max(int(ml.groups[i]), 1)
+                        cells = [f"intra {np.count_nonzero(nib == 0) / G:.3f}"]
+                        for t in range(1, int(words[0]) + 1):
+                            cells.append(f"{_vector_of(int(words[t]), w, info.motion)} {np.count_nonzero(nib == t) / G:.3f}")
+                        print(f"    {name} table: " + ", ".join(cells))
+                at += int(stored)
     else:
         print(f"Frame coding: {({3: 'groups', 4: 'rice'}).get(info.version, 'raw')}")
         for k, stored in enumerate(container_coded_sizes(inputPath)):

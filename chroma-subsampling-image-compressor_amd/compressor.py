@@ -19,7 +19,8 @@ from typing import Tuple
 import numpy as np
 
 from . import _native as N
-from .container import delta_host, delta_layout, pack_frame_host, rice_pack_host, rice_unpack_host, undelta_host, unpack_frame_host
+from .container import (delta_host, delta_layout, mc_delta_host, mc_layout, mc_undelta_host, pack_frame_host, rice_pack_host, rice_unpack_host,
+                        undelta_host, unpack_frame_host)
 from .params import (ImageProcessorParams, PixelFormat, ProcessingStep, Rounding, Sampling, make_c_params)
 
 
@@ -571,6 +572,66 @@ class Plan:
     def undelta(self, diff, maps, gop: int, out=None) -> np.ndarray:
         """csic_undelta_host: the inverse; damaged maps raise CsicIOError."""
         return undelta_host(self.c_params, diff, maps, gop, out)
+
+    # -- motion-compensated delta coding of sequences of PLANAR_BITS frames (csic_mc_*) ------------------
+    @property
+    def mc_layout(self) -> N.CsicMcLayout:
+        """csic_mc_layout of these parameters: groups, row widths, the map's table and section offsets, map_bytes, map_stride,
+        workspace_frame_bytes."""
+        return mc_layout(self.c_params)
+
+    @property
+    def mc_kernel_name(self) -> str:
+        return N.lib().csic_mc_kernel_name(self._h).decode()
+
+    def _mc_buffers(self, d_a, nframes, d_b, d_maps, what):
+        """As _delta_buffers with the maps of this layer; the two sides must be apart."""
+        import torch
+        fb, ms = self.planar_bits_layout.frame_bytes, self.mc_layout.map_stride
+        self._pack_check(d_a, nframes * fb, what)
+        if d_b is None:
+            d_b = torch.empty((nframes, fb), dtype=torch.uint8, device=d_a.device)
+        else:
+            self._pack_check(d_b, nframes * fb, "the output frames")
+        if d_maps is None:
+            d_maps = torch.zeros((nframes, ms), dtype=torch.uint8, device=d_a.device)
+        else:
+            self._pack_check(d_maps, nframes * ms, "d_maps")
+        return d_b, d_maps
+
+    def mc_delta_device(self, d_frames, nframes: int = 1, gop: int = 1, motion: int = 2, d_diff=None, d_maps=None, d_workspace=None):
+        """As delta_device with displacements of up to `motion` samples either way (0..7): returns (diff, maps), the difference frames
+        -- not in place: `d_diff` must lie apart from `d_frames` -- and the maps, uint8 (nframes, mc_layout.map_stride).  `d_workspace`:
+        nframes * mc_layout.workspace_frame_bytes bytes for the vote counters, allocated unless given.  Asynchronous on torch's current
+        stream."""
+        import torch
+        d_diff, d_maps = self._mc_buffers(d_frames, nframes, d_diff, d_maps, "d_frames")
+        wsb = nframes * self.mc_layout.workspace_frame_bytes
+        if d_workspace is None:
+            d_workspace = torch.empty((wsb,), dtype=torch.uint8, device=d_frames.device)
+        else:
+            self._pack_check(d_workspace, wsb, "d_workspace")
+        N.check(N.lib().csic_mc_delta_device(self._h, C.c_void_p(d_frames.data_ptr()), int(nframes), int(gop), int(motion), C.c_void_p(d_diff.data_ptr()),
+                                             C.c_void_p(d_maps.data_ptr()), C.c_void_p(d_workspace.data_ptr()), wsb, self._stream()))
+        return d_diff, d_maps
+
+    def mc_undelta_device(self, d_diff, d_maps, nframes: int = 1, gop: int = 1, d_frames=None):
+        """The inverse of mc_delta_device, one launch per step of a run.  The device does not validate the maps: check untrusted ones
+        with mc_undelta() first."""
+        if d_maps is None:
+            raise N.IllegalArgumentException(N.EINVAL_NULL, "requirement failed: d_maps is None")
+        d_frames, _ = self._mc_buffers(d_diff, nframes, d_frames, d_maps, "d_diff")
+        N.check(N.lib().csic_mc_undelta_device(self._h, C.c_void_p(d_diff.data_ptr()), C.c_void_p(d_maps.data_ptr()), int(nframes), int(gop),
+                                               C.c_void_p(d_frames.data_ptr()), self._stream()))
+        return d_frames
+
+    def mc_delta(self, frames, gop: int, motion: int, out=None):
+        """csic_mc_delta_host: frame buffers in host memory (nframes, frame_bytes) -> (diff, maps).  Needs no GPU."""
+        return mc_delta_host(self.c_params, frames, gop, motion, out)
+
+    def mc_undelta(self, diff, maps, gop: int, out=None) -> np.ndarray:
+        """csic_mc_undelta_host: the inverse; damaged maps raise CsicIOError."""
+        return mc_undelta_host(self.c_params, diff, maps, gop, out)
 
     # -- compute ----------------------------------------------------------------------------------
     def _stream(self):

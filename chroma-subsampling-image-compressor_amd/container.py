@@ -25,7 +25,10 @@ def container_info(path: str) -> N.CsicContainerInfo:
     if info.coding is None:                           # version 5 names its coding in the word behind the parameters (checked: 1 or 3)
         with open(path, "rb") as fh:
             fh.seek(80)
-            info.coding = int.from_bytes(fh.read(4), "little")
+            info.coding = int.from_bytes(fh.read(4), "little") & 0xFF      # (version 6 keeps its range + 1 in bits 8..)
+    motion = C.c_int32()
+    N.check(N.lib().csic_container_motion(os.fsencode(path), C.byref(motion)))
+    info.motion = motion.value                        # csic_container_motion: the range of a version-6 file, -1 otherwise
     return info
 
 
@@ -154,14 +157,58 @@ def undelta_host(c_params: N.CsicParams, diff, maps, gop: int, out=None) -> np.n
     return frames
 
 
-def write_container(path: str, c_params: N.CsicParams, frames, coding="raw", gop=None) -> None:
+def mc_layout(c_params: N.CsicParams) -> N.CsicMcLayout:
+    """csic_mc_layout_of: groups, row widths, the tables' and the nibble sections' offsets, map_bytes, map_stride and the device codec's
+    workspace bytes per frame."""
+    lay = N.CsicMcLayout()
+    N.check(N.lib().csic_mc_layout_of(C.byref(c_params), C.byref(lay)))
+    return lay
+
+
+def mc_delta_host(c_params: N.CsicParams, frames, gop: int, motion: int, out=None):
+    """csic_mc_delta_host: PLANAR_BITS frame buffers (nframes, frame_bytes) -> (diff, maps) with displacements of up to `motion`
+    samples either way: the difference frames, an array of the same shape (zero outside the payload ranges, or `out` -- not `frames`:
+    there is no in-place form), and the maps, uint8 (nframes, map_stride) with map_bytes of each row written."""
+    q, lay = _bits_params(c_params)
+    ml = mc_layout(q)
+    a = _frames_2d(frames, lay.frame_bytes)
+    diff = np.zeros_like(a) if out is None else out
+    maps = np.zeros((a.shape[0], ml.map_stride), dtype=np.uint8)
+    N.check(N.lib().csic_mc_delta_host(C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], int(gop), int(motion), diff.ctypes.data_as(C.c_void_p),
+                                       maps.ctypes.data_as(C.c_void_p)))
+    return diff, maps
+
+
+def mc_undelta_host(c_params: N.CsicParams, diff, maps, gop: int, out=None) -> np.ndarray:
+    """csic_mc_undelta_host: the inverse of mc_delta_host.  The maps are untrusted: a damaged table, a nibble above its table, a set
+    padding nibble or a non-zero map of a key frame raises CsicIOError (CSIC_EFORMAT) and nothing is written."""
+    q, lay = _bits_params(c_params)
+    ml = mc_layout(q)
+    d = _frames_2d(diff, lay.frame_bytes)
+    m = np.ascontiguousarray(maps).view(np.uint8).reshape(d.shape[0], -1)
+    if m.shape[1] != ml.map_stride:
+        raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: maps must be (nframes, {ml.map_stride}), got {m.shape}")
+    frames = np.zeros_like(d) if out is None else out
+    N.check(N.lib().csic_mc_undelta_host(C.byref(q), d.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), d.shape[0], int(gop),
+                                         frames.ctypes.data_as(C.c_void_p)))
+    return frames
+
+
+def write_container(path: str, c_params: N.CsicParams, frames, coding="raw", gop=None, motion=None) -> None:
     """frames: the PLANAR_BITS frame buffers of `c_params` (its out_format does not matter), frame_bytes each -- one buffer, an
     array (nframes, frame_bytes), or a list of buffers.  Only the planes' payload bytes reach the file.  coding = "raw" (version 1,
     the bytes as they are), "groups" (version 3, every frame group-coded on the host: csic_container_write_ex) or "rice" (version 4,
     every frame Rice-coded on the host).  With a `gop` the frames are a sequence: version 5, delta and packing on the host
-    (csic_container_write_seq; coding "groups" or "rice")."""
+    (csic_container_write_seq; coding "groups" or "rice"); with a `motion` range (0..7) as well, version 6 through the
+    motion-compensated layer (csic_container_write_seq_ex)."""
     q, lay = _bits_params(c_params)
     coding = _coding(coding)
+    if motion is not None and gop is None:
+        raise N.IllegalArgumentException(N.EINVAL_NULL, "requirement failed: motion needs a gop")
+    if motion is not None:
+        a = _frames_2d(frames, lay.frame_bytes)
+        N.check(N.lib().csic_container_write_seq_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], coding, int(gop), int(motion)))
+        return
     if gop is not None:
         a = _frames_2d(frames, lay.frame_bytes)
         N.check(N.lib().csic_container_write_seq(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], coding, int(gop)))
@@ -177,12 +224,13 @@ def write_container(path: str, c_params: N.CsicParams, frames, coding="raw", gop
         N.check(N.lib().csic_container_write_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.size // lay.frame_bytes, coding))
 
 
-def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, coding="groups", maps=None, gop=None) -> None:
+def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, coding="groups", maps=None, gop=None, motion=None) -> None:
     """Version 3 (coding "groups") or 4 ("rice") from frames that are packed already (csic_container_write_coded_ex): `coded` is an
     array (nframes, stride) -- what Plan.pack_device / Plan.rice_pack_device returns, copied to the host -- or a list of coded frames;
     sizes[k] is frame k's coded_bytes.  Every frame is validated before anything is written.  With `maps` and `gop` -- what
     Plan.delta_device returned, copied to the host: uint8 (nframes, map_stride) -- the coded frames are difference frames and the file is
-    version 5 (csic_container_write_coded_seq)."""
+    version 5 (csic_container_write_coded_seq); with `motion` too the maps are Plan.mc_delta_device's and the file is version 6
+    (csic_container_write_coded_seq_ex)."""
     if (maps is None) != (gop is None):
         raise N.IllegalArgumentException(N.EINVAL_NULL, "requirement failed: maps and gop go together")
     q, _ = _bits_params(c_params)
@@ -203,6 +251,11 @@ def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, codin
         m = np.ascontiguousarray(maps).view(np.uint8)
         if m.size == 0 or m.size % sz.size != 0:
             raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: {m.size} bytes of maps for {sz.size} frames")
+        if motion is not None:
+            N.check(N.lib().csic_container_write_coded_seq_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1],
+                                                              sz.ctypes.data_as(C.POINTER(C.c_uint64)), m.ctypes.data_as(C.c_void_p), m.size // sz.size,
+                                                              int(sz.size), coding, int(gop), int(motion)))
+            return
         N.check(N.lib().csic_container_write_coded_seq(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1],
                                                        sz.ctypes.data_as(C.POINTER(C.c_uint64)), m.ctypes.data_as(C.c_void_p), m.size // sz.size,
                                                        int(sz.size), coding, int(gop)))

@@ -5,6 +5,7 @@
 // version 4 is the same layout with the frames Rice-coded (csic_rice_host.cpp).  What differs between the two is one row of codec_of;
 // the little-endian dwords are csic_group_host.h's.  Version 5 holds a sequence through the temporal layer (csic_delta_host.cpp): the word
 // behind the coding is the gop, a key frame's record is its coded frame, a delta frame's its map and then its coded difference frame.
+// Version 6 is version 5 through the motion-compensated layer (csic_mc_host.cpp): its maps, and the range + 1 in bits 8.. of the coding word.
 #include <zlib.h>
 
 #include <cstdio>
@@ -17,7 +18,7 @@
 namespace csic {
 
 constexpr size_t CONTAINER_HEADER = 80, CONTAINER_CRC_FROM = 16;
-constexpr uint32_t CONTAINER_VERSION = 1, CONTAINER_VERSION_CODED = 3, CONTAINER_VERSION_RICE = 4, CONTAINER_VERSION_SEQ = 5;
+constexpr uint32_t CONTAINER_VERSION = 1, CONTAINER_VERSION_CODED = 3, CONTAINER_VERSION_RICE = 4, CONTAINER_VERSION_SEQ = 5, CONTAINER_VERSION_MC = 6;
 constexpr size_t CODED_BODY = 8;                  // versions 3, 4 and 5: coding, reserved (5: gop); then the table of sizes
 static const unsigned char CONTAINER_MAGIC[4] = {0x43, 0x53, 0x49, 0x43};   // "CSIC"
 
@@ -89,6 +90,7 @@ struct CodedBody {
     int coding = CSIC_CODING_RAW;
     int32_t gop = 1;
     int64_t map_bytes = 0;
+    int32_t motion = -1;           // version 6: the range
 };
 static int64_t map_bytes_of(const PackGeometry &G)
 {
@@ -109,8 +111,9 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Ric
     if (fread(h, 1, sizeof h, f) != sizeof h) return set_error(CSIC_EIO, "cannot read %s", path);
     if (std::memcmp(h, CONTAINER_MAGIC, 4) != 0) return set_error(CSIC_EFORMAT, "%s is not a .csic file (bad magic)", path);
     const uint32_t version = get_u32(h + 4), nframes = get_u32(h + 8);
-    if (version != CONTAINER_VERSION && version != CONTAINER_VERSION_CODED && version != CONTAINER_VERSION_RICE && version != CONTAINER_VERSION_SEQ)
-        return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1, 3, 4 and 5 are)", path, version);
+    if (version != CONTAINER_VERSION && version != CONTAINER_VERSION_CODED && version != CONTAINER_VERSION_RICE && version != CONTAINER_VERSION_SEQ &&
+        version != CONTAINER_VERSION_MC)
+        return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1, 3, 4, 5 and 6 are)", path, version);
     if (nframes < 1 || nframes > 65535) return set_error(CSIC_EFORMAT, "%s: nframes must be in 1..65535. Got %u", path, nframes);
     int32_t fields[16];
     for (int i = 0; i < 16; ++i) fields[i] = (int32_t)get_u32(h + 16 + 4 * i);
@@ -128,13 +131,26 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Ric
         std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
         if (fread(t.data(), 1, t.size(), f) != t.size()) return set_error(CSIC_EIO, "cannot read %s", path);
         int coding = version == CONTAINER_VERSION_RICE ? CSIC_CODING_RICE : CSIC_CODING_GROUPS;
-        if (version == CONTAINER_VERSION_SEQ) {
-            const uint32_t c = get_u32(t.data()), gop = get_u32(t.data() + 4);
-            if (c != CSIC_CODING_GROUPS && c != CSIC_CODING_RICE) return set_error(CSIC_EFORMAT, "%s: coding %u is not one version 5 holds (1 or 3)", path, c);
+        if (version == CONTAINER_VERSION_SEQ || version == CONTAINER_VERSION_MC) {
+            uint32_t c = get_u32(t.data());
+            const uint32_t gop = get_u32(t.data() + 4);
+            if (version == CONTAINER_VERSION_MC) {                 // coding | (range + 1) << 8, every other bit zero
+                const uint32_t field = c >> 8;
+                if (field < 1 || field > (uint32_t)MC_MAX_RANGE + 1)
+                    return set_error(CSIC_EFORMAT, "%s: motion field %u of the coding word %#x is not a range + 1 of 1..%d", path, field, c, MC_MAX_RANGE + 1);
+                cb.motion = (int32_t)field - 1;
+                c &= 0xFFu;
+            }
+            if (c != CSIC_CODING_GROUPS && c != CSIC_CODING_RICE) return set_error(CSIC_EFORMAT, "%s: coding %u is not one version %u holds (1 or 3)", path, c, version);
             if (gop < 1 || gop > 65535) return set_error(CSIC_EFORMAT, "%s: gop must be in 1..65535. Got %u", path, gop);
             coding = (int)c;
             cb.gop = (int32_t)gop;
             cb.map_bytes = map_bytes_of(G->pk);
+            if (version == CONTAINER_VERSION_MC) {
+                McGeometry M;
+                if (mc_geometry(&p, &M) != CSIC_OK) return set_error(CSIC_EFORMAT, "%s: the stored parameters have no motion-compensated layout", path);
+                cb.map_bytes = M.layout.map_bytes;
+            }
         } else if (get_u32(t.data()) != (uint32_t)coding || get_u32(t.data() + 4) != 0)
             return set_error(CSIC_EFORMAT, "%s: coding %u (reserved word %u) is not what version %u holds (%d, 0)", path, get_u32(t.data()), get_u32(t.data() + 4),
                              version, coding);
@@ -186,15 +202,15 @@ static int writer_params(const csic_params *p, int32_t nframes, csic_params *q, 
 }
 
 // A version-3 or version-4 file from coded frames in memory: frame k is frames[k][0, sizes[k]).  With a gop (> 0) a version-5 file:
-// maps[k][0, map_bytes) stands in front of every delta frame.
+// maps[k][0, map_bytes) stands in front of every delta frame.  With a motion range (>= 0) a version-6 file: the maps are csic_mc_*'s.
 static int write_coded_file(const char *path, const csic_params &q, const unsigned char *const *frames, const uint64_t *sizes, int32_t nframes, const Codec &codec,
-                            int32_t gop = 0, const unsigned char *const *maps = nullptr, size_t map_bytes = 0)
+                            int32_t gop = 0, const unsigned char *const *maps = nullptr, size_t map_bytes = 0, int32_t motion = -1)
 {
     const auto map_of = [&](int32_t k) { return gop > 0 && k % gop ? map_bytes : (size_t)0; };
     unsigned char h[CONTAINER_HEADER];
-    fill_header(h, gop > 0 ? CONTAINER_VERSION_SEQ : codec.version, q, nframes);
+    fill_header(h, gop > 0 ? (motion >= 0 ? CONTAINER_VERSION_MC : CONTAINER_VERSION_SEQ) : codec.version, q, nframes);
     std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
-    put_u32(t.data(), (uint32_t)codec.coding);
+    put_u32(t.data(), (uint32_t)codec.coding | (motion >= 0 ? (uint32_t)(motion + 1) << 8 : 0u));
     put_u32(t.data() + 4, (uint32_t)gop);
     for (int32_t k = 0; k < nframes; ++k) put_u64(t.data() + CODED_BODY + 8 * (size_t)k, sizes[k] + map_of(k));
     uLong crc = crc32(0L, h + CONTAINER_CRC_FROM, (uInt)(CONTAINER_HEADER - CONTAINER_CRC_FROM));
@@ -371,7 +387,8 @@ static int seq_check(int32_t coding, int32_t gop)
     return CSIC_OK;
 }
 
-int csic_container_write_seq(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding, int32_t gop)
+// motion < 0: version 5 through csic_delta_*; otherwise version 6 through csic_mc_* at that range
+static int write_seq(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding, int32_t gop, int32_t motion)
 {
     if (!path || !p || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
     int st = seq_check(coding, gop);
@@ -379,15 +396,19 @@ int csic_container_write_seq(const char *path, const csic_params *p, const void 
     csic_params q;
     RiceGeometry G;
     DeltaGeometry D;
+    McGeometry M;
     if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = delta_geometry(&q, &D)) != CSIC_OK) return st;
+    if (motion >= 0 && (st = mc_geometry(&q, &M)) != CSIC_OK) return st;
     const Codec codec = codec_of(G, coding);
     try {
-        const size_t fb = (size_t)G.pk.bits.frame_bytes, mb = (size_t)D.layout.map_bytes;
+        const size_t fb = (size_t)G.pk.bits.frame_bytes, mb = (size_t)(motion >= 0 ? M.layout.map_bytes : D.layout.map_bytes);
         const unsigned char *x = static_cast<const unsigned char *>(frames);
         std::vector<unsigned char> diff(fb), maps((size_t)nframes * mb), all;
         std::vector<uint64_t> sizes((size_t)nframes);
         for (int32_t k = 0; k < nframes; ++k) {
-            delta_frame(D, x + (size_t)k * fb, k % gop ? x + (size_t)(k - 1) * fb : nullptr, diff.data(), maps.data() + (size_t)k * mb);
+            const unsigned char *prev = k % gop ? x + (size_t)(k - 1) * fb : nullptr;
+            if (motion >= 0) mc_delta_frame(M, x + (size_t)k * fb, prev, motion, diff.data(), maps.data() + (size_t)k * mb);
+            else delta_frame(D, x + (size_t)k * fb, prev, diff.data(), maps.data() + (size_t)k * mb);
             const size_t at = all.size();
             all.resize(at + codec.bound);
             st = codec.pack(G, diff.data(), all.data() + at, codec.bound, &sizes[k]);
@@ -397,9 +418,55 @@ int csic_container_write_seq(const char *path, const csic_params *p, const void 
         std::vector<const unsigned char *> ptrs((size_t)nframes), mptrs((size_t)nframes);
         size_t at = 0;
         for (int32_t k = 0; k < nframes; ++k) { ptrs[k] = all.data() + at; at += (size_t)sizes[k]; mptrs[k] = maps.data() + (size_t)k * mb; }
-        st = write_coded_file(path, q, ptrs.data(), sizes.data(), nframes, codec, gop, mptrs.data(), mb);
+        st = write_coded_file(path, q, ptrs.data(), sizes.data(), nframes, codec, gop, mptrs.data(), mb, motion);
     } catch (const std::bad_alloc &) {
         return set_error(CSIC_ENOMEM, "out of host memory coding %d frames for %s", nframes, path);
+    }
+    if (st != CSIC_OK) return st;
+    clear_error();
+    return CSIC_OK;
+}
+
+int csic_container_write_seq(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding, int32_t gop)
+{
+    return write_seq(path, p, frames, nframes, coding, gop, -1);
+}
+
+int csic_container_write_seq_ex(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding, int32_t gop, int32_t range)
+{
+    const int st = mc_check_range(range);
+    return st != CSIC_OK ? st : write_seq(path, p, frames, nframes, coding, gop, range);
+}
+
+static int write_coded_seq(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
+                           const void *maps, size_t map_stride, int32_t nframes, int32_t coding, int32_t gop, int32_t motion)
+{
+    if (!path || !p || !coded || !sizes || !maps) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    int st = seq_check(coding, gop);
+    if (st != CSIC_OK) return st;
+    csic_params q;
+    RiceGeometry G;
+    DeltaGeometry D;
+    McGeometry M;
+    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = delta_geometry(&q, &D)) != CSIC_OK) return st;
+    if (motion >= 0 && (st = mc_geometry(&q, &M)) != CSIC_OK) return st;
+    const size_t mb = (size_t)(motion >= 0 ? M.layout.map_bytes : D.layout.map_bytes);
+    if (map_stride < mb)
+        return set_error(CSIC_EINVAL_SIZE, "a map of these parameters has %zu bytes: a map_stride of %zu cannot hold it", mb, map_stride);
+    const Codec codec = codec_of(G, coding);
+    try {
+        std::vector<const unsigned char *> ptrs((size_t)nframes), mptrs((size_t)nframes);
+        for (int32_t k = 0; k < nframes; ++k) {
+            if (sizes[k] > stride_bytes)
+                return set_error(CSIC_EINVAL_SIZE, "frame %d: %llu coded bytes do not fit the stride of %zu", k, (unsigned long long)sizes[k], stride_bytes);
+            ptrs[k] = static_cast<const unsigned char *>(coded) + (size_t)k * stride_bytes;
+            mptrs[k] = static_cast<const unsigned char *>(maps) + (size_t)k * map_stride;
+            if ((st = codec.check(G, ptrs[k], (size_t)sizes[k])) != CSIC_OK) return st;
+            if ((st = motion >= 0 ? mc_check_map(M, mptrs[k], k % gop == 0, k) : delta_check_map(D, mptrs[k], k % gop == 0, k)) != CSIC_OK) return st;
+        }
+        st = write_coded_file(path, q, ptrs.data(), sizes, nframes, codec, gop, mptrs.data(), mb, motion);
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory writing %s", path);
     }
     if (st != CSIC_OK) return st;
     clear_error();
@@ -409,30 +476,31 @@ int csic_container_write_seq(const char *path, const csic_params *p, const void 
 int csic_container_write_coded_seq(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
                                    const void *maps, size_t map_stride, int32_t nframes, int32_t coding, int32_t gop)
 {
-    if (!path || !p || !coded || !sizes || !maps) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    int st = seq_check(coding, gop);
-    if (st != CSIC_OK) return st;
-    csic_params q;
-    RiceGeometry G;
-    DeltaGeometry D;
-    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = delta_geometry(&q, &D)) != CSIC_OK) return st;
-    if (map_stride < (size_t)D.layout.map_bytes)
-        return set_error(CSIC_EINVAL_SIZE, "a map of these parameters has %lld bytes: a map_stride of %zu cannot hold it", (long long)D.layout.map_bytes, map_stride);
-    const Codec codec = codec_of(G, coding);
+    return write_coded_seq(path, p, coded, stride_bytes, sizes, maps, map_stride, nframes, coding, gop, -1);
+}
+
+int csic_container_write_coded_seq_ex(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
+                                      const void *maps, size_t map_stride, int32_t nframes, int32_t coding, int32_t gop, int32_t range)
+{
+    const int st = mc_check_range(range);
+    return st != CSIC_OK ? st : write_coded_seq(path, p, coded, stride_bytes, sizes, maps, map_stride, nframes, coding, gop, range);
+}
+
+int csic_container_motion(const char *path, int32_t *range)
+{
+    if (!path || !range) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    FileCloser fc{fopen(path, "rb")};
+    if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
     try {
-        std::vector<const unsigned char *> ptrs((size_t)nframes), mptrs((size_t)nframes);
-        for (int32_t k = 0; k < nframes; ++k) {
-            if (sizes[k] > stride_bytes)
-                return set_error(CSIC_EINVAL_SIZE, "frame %d: %llu coded bytes do not fit the stride of %zu", k, (unsigned long long)sizes[k], stride_bytes);
-            ptrs[k] = static_cast<const unsigned char *>(coded) + (size_t)k * stride_bytes;
-            mptrs[k] = static_cast<const unsigned char *>(maps) + (size_t)k * map_stride;
-            if ((st = codec.check(G, ptrs[k], (size_t)sizes[k])) != CSIC_OK || (st = delta_check_map(D, mptrs[k], k % gop == 0, k)) != CSIC_OK) return st;
-        }
-        st = write_coded_file(path, q, ptrs.data(), sizes, nframes, codec, gop, mptrs.data(), (size_t)D.layout.map_bytes);
+        RiceGeometry G;
+        csic_container_info ci;
+        CodedBody body;
+        const int st = read_header(fc.f, path, &ci, &G, nullptr, nullptr, &body);
+        if (st != CSIC_OK) return st;
+        *range = body.motion;
     } catch (const std::bad_alloc &) {
-        return set_error(CSIC_ENOMEM, "out of host memory writing %s", path);
+        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
     }
-    if (st != CSIC_OK) return st;
     clear_error();
     return CSIC_OK;
 }
@@ -464,6 +532,7 @@ int csic_container_inter_groups(const char *path, uint64_t *counts, int32_t n)
     try {
         RiceGeometry G;
         DeltaGeometry D;
+        McGeometry M;
         csic_container_info ci;
         CodedBody body;
         std::vector<uint64_t> table;
@@ -472,11 +541,19 @@ int csic_container_inter_groups(const char *path, uint64_t *counts, int32_t n)
         if (n != 3 * ci.nframes) return set_error(CSIC_EINVAL_SIZE, "expected room for %d counts, got %d", 3 * ci.nframes, n);
         std::vector<uint64_t> got((size_t)n, 0);
         if (body.map_bytes > 0 && (st = delta_geometry(&ci.params, &D)) != CSIC_OK) return st;
+        if (body.motion >= 0 && (st = mc_geometry(&ci.params, &M)) != CSIC_OK) return st;
         std::vector<unsigned char> map((size_t)body.map_bytes);
         long long at = ftello(fc.f);                   // where the records begin
         for (int32_t k = 0; k < ci.nframes; ++k) {
             if (body.map_bytes > 0 && k % body.gop) {
                 if (fseeko(fc.f, at, SEEK_SET) != 0 || fread(map.data(), 1, map.size(), fc.f) != map.size()) return set_error(CSIC_EIO, "cannot read %s", path);
+                if (body.motion >= 0) {                     // version 6: the nibbles that are not 0
+                    if ((st = mc_check_map(M, map.data(), false, k)) != CSIC_OK) return st;
+                    for (int pl = 0; pl < 3; ++pl)
+                        for (int64_t g = 0; g < M.layout.groups[pl]; ++g) got[3 * (size_t)k + pl] += nibble_at(map.data() + M.layout.map_offset[pl], g) != 0;
+                    at += (long long)table[k];
+                    continue;
+                }
                 if ((st = delta_check_map(D, map.data(), false, k)) != CSIC_OK) return st;
                 for (int pl = 0; pl < 3; ++pl)
                     for (int64_t b = 0; b < 4 * ((D.layout.groups[pl] + 31) / 32); ++b) got[3 * (size_t)k + pl] += (uint64_t)__builtin_popcount(map[D.layout.map_offset[pl] + b]);
@@ -504,7 +581,9 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
     if (st != CSIC_OK) return st;
     const PackGeometry &G = C.pk;
     DeltaGeometry D;
+    McGeometry M;
     if (ci.version == (int32_t)CONTAINER_VERSION_SEQ && (st = delta_geometry(&ci.params, &D)) != CSIC_OK) return st;
+    if (ci.version == (int32_t)CONTAINER_VERSION_MC && (st = mc_geometry(&ci.params, &M)) != CSIC_OK) return st;
     const csic_planar_bits_layout &L = G.bits;
     const size_t need = (size_t)ci.nframes * (size_t)L.frame_bytes;
     if (frames_bytes != need)
@@ -518,7 +597,7 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
     uLong crc = crc_long(0L, h.data() + CONTAINER_CRC_FROM, (int64_t)(h.size() - CONTAINER_CRC_FROM));
     unsigned char *base = static_cast<unsigned char *>(frames);
     std::memset(base, 0, need);
-    std::vector<unsigned char> coded;
+    std::vector<unsigned char> coded, diff;
     const Codec codec = codec_of(C, body.coding);     // (unused by version 1)
     for (int32_t k = 0; k < ci.nframes && st == CSIC_OK; ++k) {
         unsigned char *fr = base + (int64_t)k * L.frame_bytes;
@@ -533,6 +612,12 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
             if (fread(coded.data(), 1, coded.size(), fc.f) != coded.size()) return set_error(CSIC_EIO, "cannot read %s", path);
             crc = crc_long(crc, coded.data(), (int64_t)coded.size());
             const size_t map = k % body.gop ? (size_t)body.map_bytes : 0;      // version 5: a delta frame's map first (read_header: the record holds it)
+            if (map && body.motion >= 0) {                 // version 6: a group reads other groups of the previous frame, so not in place
+                diff.assign((size_t)L.frame_bytes, 0);
+                if ((st = mc_check_map(M, coded.data(), false, k)) == CSIC_OK) st = codec.unpack(C, coded.data() + map, coded.size() - map, diff.data());
+                if (st == CSIC_OK) mc_undelta_frame(M, diff.data(), coded.data(), fr - L.frame_bytes, fr);
+                continue;
+            }
             if (map) st = delta_check_map(D, coded.data(), false, k);
             if (st == CSIC_OK) st = codec.unpack(C, coded.data() + map, coded.size() - map, fr);
             if (st == CSIC_OK && map) undelta_frame(D, fr, coded.data(), fr - L.frame_bytes, fr);      // the difference frame -> the frame, in place

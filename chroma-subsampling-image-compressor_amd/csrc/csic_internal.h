@@ -71,6 +71,25 @@ int delta_check_map(const DeltaGeometry &G, const unsigned char *map, bool key, 
 // buffers other than diff == frames exactly
 int delta_check_call(const DeltaGeometry &G, const void *frames, const void *diff, const void *maps, int32_t nframes, int32_t gop);
 
+// csic_mc_host.cpp: the motion-compensated temporal layer (csic.h: csic_mc_*), the same for it.  mc_candidates writes the (2 range + 1)^2
+// candidates in rank order and returns their number; neither frame function works in place.  mc_check_call is delta_check_call without
+// the in-place exception, mc_check_range the refusal of a range outside 0..MC_MAX_RANGE.
+constexpr int MC_MAX_RANGE = 7, MC_MAX_CANDIDATES = (2 * MC_MAX_RANGE + 1) * (2 * MC_MAX_RANGE + 1);
+constexpr int MC_TABLE_WORDS = 16, MC_TABLE_BYTES = 4 * MC_TABLE_WORDS;
+constexpr int MC_COUNTERS = 256;              // vote counters per frame and plane in the device codec's workspace (>= MC_MAX_CANDIDATES)
+struct McGeometry {
+    PackGeometry pk;
+    csic_mc_layout layout;
+};
+struct McCandidate { int dy, dx; };
+int mc_geometry(const csic_params *p, McGeometry *G);
+int mc_candidates(int range, McCandidate *out);
+void mc_delta_frame(const McGeometry &G, const unsigned char *cur, const unsigned char *prev, int range, unsigned char *diff, unsigned char *map);
+void mc_undelta_frame(const McGeometry &G, const unsigned char *diff, const unsigned char *map, const unsigned char *prev, unsigned char *cur);
+int mc_check_map(const McGeometry &G, const unsigned char *map, bool key, int frame);
+int mc_check_call(const McGeometry &G, const void *frames, const void *diff, const void *maps, int32_t nframes, int32_t gop);
+int mc_check_range(int32_t range);
+
 // Exact unsigned division by a run-time constant without a divide (k_generic's stream-index arithmetic): for
 // 1 <= d < 2^31 and every n < 2^31,  n / d == (uint64(n) * m) >> k  with  k = 31 + ceil(log2 d),  m = ceil(2^k / d) < 2^32.
 // (Error term e = m*d - 2^k < d <= 2^ceil(log2 d), and n * e < 2^31 * 2^ceil(log2 d) = 2^k.)  Host side, csic_host.cpp;

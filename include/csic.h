@@ -811,7 +811,8 @@ const char *csic_rice_kernel_name(const csic_plan *plan);
  * frames into a sequence of DIFFERENCE frames of the same layout, which either coding then codes as it codes any frame, and one small
  * map per frame.  It is lossless.  Prediction across the groups of a frame would need a scan over a plane; across frames the
  * dependency is per sample -- sample i of frame k depends on sample i of frame k - 1 only -- so encode and decode stay one lane per
- * group.  There is no motion compensation: content that stays in place gains, a pan gains nothing and loses the map at most.
+ * group.  There is no motion compensation here: content that stays in place gains, a pan gains nothing and loses the map at most; the
+ * layer for content that moves is csic_mc_*, below.
  *
  * Input: frames x_0 .. x_(n - 1) of one parameter set and gop >= 1.  Frame k is a KEY frame iff k % gop == 0; every other frame is a
  * DELTA frame against x_(k - 1), the source frame itself (the coding is lossless: the decoder has it exactly).  Planes, q_p, n_p and the
@@ -869,6 +870,94 @@ int  csic_delta_device(csic_plan *plan, const void *d_frames, int32_t nframes, i
 int  csic_undelta_device(csic_plan *plan, const void *d_diff, const void *d_maps, int32_t nframes, int32_t gop, void *d_frames,
                          void *hip_stream);
 const char *csic_delta_kernel_name(const csic_plan *plan);
+
+/* ---- motion-compensated delta coding of frame sequences (csic_mc_*) -----------------------------------------------------------------
+ * A second temporal layer beside csic_delta_*, for content that moves: the same inputs, the same kind of outputs -- a sequence of
+ * DIFFERENCE frames of the CSIC_FMT_PLANAR_BITS layout, which either coding codes as it codes any frame, and one map per frame -- but
+ * a group is predicted from the previous frame DISPLACED by one of up to 15 offsets that the frame's plane has chosen for itself.  It
+ * is lossless.  The map costs 4 bits per group where csic_delta_*'s costs 1, so content that stays put is better off there: the layer
+ * is opt-in.
+ *
+ * Planes, q_p, n_p, the groups of 32 (G_p), key and delta frames and gop are those of csic_delta_*.  Plane p has a row width w_p:
+ * y_width for Y, chroma_width for Cb and Cr (csic_planar_layout).
+ *
+ * DISPLACEMENT.  A displacement is a flat signed sample offset s (int32).  With r the previous source frame's codes of the plane, the
+ * reference of sample i is  ref_s(i) = r[clamp(i + s, 0, n_p - 1)],  i + s computed in 64 bits.  Rows wrap into their neighbours at
+ * the plane's edges; that is accepted, because the coding is lossless whatever the predictor.
+ *
+ * CANDIDATES.  The range R is 0 .. 7.  The candidates are all (dy, dx) of [-R, R]^2, ranked by (|dx| + |dy|, dy, dx) ascending -- rank
+ * 0 is the zero vector, then (-1, 0), (0, -1), (0, 1), (1, 0), (-2, 0), (-1, -1), ... --, each with s = dy * w_p + dx.
+ *
+ * COST AND VOTE.  cost_s(g) is cost() of csic_delta_* over d_i = (c_i - ref_s(i)) mod 2^q on the group's real slots.  Every group of
+ * a delta frame votes for the lowest-ranked candidate that attains its minimal cost.
+ *
+ * TABLE.  Each plane of each delta frame has a table of 16 int32 words: word 0 is T, the number of entries; word 1 is 0, the zero
+ * vector, always; words 2 .. T hold s of the non-zero candidates that got votes, ordered by votes descending, then rank ascending, at
+ * most 14 of them (T = 1 + min(14, their number)); unused words are 0.
+ *
+ * CHOICE.  A group takes the lowest t of 1 .. T whose cost_(word t)(g) is minimal over the table.  It is INTER with nibble t iff that
+ * cost is below cost(c), the cost of its own codes; a tie is intra, nibble 0, as in csic_delta_*.  The group of the difference frame
+ * holds d (against word t) where it is inter and c where it is intra; the bits behind a plane's last sample are 0, bytes outside the
+ * three payload ranges are not written.  For a key frame D_k = x_k.
+ *
+ * MAP.  Three tables of 64 bytes at byte offsets 0, 64 and 128 (Y, Cb, Cr; little endian), followed by three nibble sections of
+ * 4 * ceil(G_p / 8) bytes each: group g is nibble g % 8 of dword g / 8, least significant first; padding nibbles are 0.  map_bytes is
+ * 192 + the sections, map_stride map_bytes rounded up to a multiple of 256: the distance between the maps of consecutive frames in a
+ * buffer of maps, which needs (nframes - 1) * map_stride + map_bytes bytes; bytes of a map behind its map_bytes are not touched.  The
+ * map of a key frame is all zeros.
+ *
+ * INVERSE, frame after frame from each key frame: c_i = (d_i + r[clamp(i + word t)]) mod 2^q where the group's nibble is t >= 1,
+ * c_i = d_i where it is 0; r is the decoded previous frame.
+ *
+ * Worked vectors, the Y plane of an 8 x 1 frame (w = 8, n = 8, one group), q = 3, r = 1,2,3,4,5,6,7,0 (bytes as for csic_delta_*):
+ *     a pan, R = 1      c = 1,1,2,3,4,5,6,7 = r one sample to the right, the edge repeated.  Candidate (0, -1), s = -1, rank 2, gives
+ *                       d = 0 x 8 at cost 0 and is the only one that does: it gets the vote.  Table 2, 0, -1, 0 x 13 (bytes 02 00 00 00
+ *                       00 00 00 00 ff ff ff ff 00 ...).  Word 1: d = 0,7,7,7,7,7,7,7, cost 1; word 2: cost 0; cost(c) = 12: inter,
+ *                       nibble 2, section 02 00 00 00, D = 00 00 00
+ *     the same, R = 0   the zero vector alone: table 1, 0 x 15; cost 1 < 12: nibble 1, section 01 00 00 00, D = f8 ff ff
+ *     clamping          c = 1 x 8, R = 1: (-1, 0), s = -8, rank 1, reads r[0] = 1 everywhere, d = 0 x 8, cost 0; so do (-1, -1) and
+ *                       (-1, 1) at ranks 5 and 6: the lowest rank gets the vote.  Table 2, 0, -8, 0 x 13; cost(c) = 0: a tie, intra,
+ *                       nibble 0, section 00 00 00 00, D = 49 92 24 (the codes)
+ *     identical frames  c = r, R = 1: the zero vector gets the vote, table 1, 0 x 15, nibble 1, D = 00 00 00 -- what csic_delta_*
+ *                       stores, with R = 0 always: at R = 0 the inter / intra choices are exactly csic_delta_*'s
+ *
+ * Host codec (no GPU; parameters and statuses as for csic_delta_*):
+ *   csic_mc_layout_of    : groups, row widths, the tables' and the sections' offsets, map_bytes, map_stride and the device codec's
+ *                          workspace bytes per frame of these parameters.
+ *   csic_mc_delta_host   : frames (frame_bytes apart) -> diff (frame_bytes apart) and maps (map_stride apart), range R.
+ *   csic_mc_undelta_host : the inverse.  The maps are untrusted: T > 15, a nibble above T, a non-zero unused table word, word 1 != 0
+ *                          when T >= 1, a set padding nibble or a non-zero map of a key frame gives CSIC_EFORMAT; a refused call writes
+ *                          nothing.  Any int32 displacement is valid, because it clamps.
+ * Device codec (gfx950): asynchronous on `hip_stream`, no allocation, no synchronisation, hipGraph-capturable.
+ *   csic_mc_delta_device   : d_frames -> d_diff and d_maps; the source is only read.  The reference is the SOURCE frame, so all frames
+ *                            are independent: frames on grid z.  d_workspace: at least nframes * workspace_frame_bytes bytes, 256-byte
+ *                            aligned, the vote counters; its contents before and after are of no interest.
+ *   csic_mc_undelta_device : the inverse.  Frame k needs all of frame k - 1: one launch per step of a run, min(gop, nframes) launches
+ *                            in a line, grid z over the runs; no workspace.  It does NOT validate: any nibble reads one of the 16
+ *                            words, any word clamps; a key frame's map is ignored.
+ *   csic_mc_kernel_name    : "k_mc_delta<q6,5,5,nt>", as csic_delta_kernel_name.
+ * For all four calls: nframes outside 1..65535, gop < 1, ANY overlap of the frames, the difference frames and the maps -- in place is
+ * NOT allowed: a group reads other groups of the previous frame -- and, on the device, a buffer that is not 256-byte aligned or a
+ * workspace that is too small are CSIC_EINVAL_SIZE; so is a range outside 0..7.  NULL arguments: CSIC_EINVAL_NULL; parameters the
+ * container does not take: csic_validate's status -- all before any device is touched.  CSIC_TUNE_NONTEMPORAL applies to the accesses
+ * that stream -- a frame's own groups and the difference frames --; the reference windows are read several times and stay cached. */
+typedef struct csic_mc_layout {
+    int64_t groups[3];             /* G_p                                                              */
+    int64_t width[3];              /* w_p                                                              */
+    int64_t table_offset[3];       /* 0, 64, 128: byte offsets of the tables inside a map              */
+    int64_t map_offset[3];         /* byte offsets of the nibble sections inside a map                 */
+    int64_t map_bytes;             /* 192 + sum_p 4 * ceil(G_p / 8)                                    */
+    int64_t map_stride;            /* multiple of 256: the distance of maps in a buffer of maps        */
+    int64_t workspace_frame_bytes; /* csic_mc_delta_device's workspace, per frame                      */
+} csic_mc_layout;
+int  csic_mc_layout_of(const csic_params *p, csic_mc_layout *layout);
+int  csic_mc_delta_host(const csic_params *p, const void *frames, int32_t nframes, int32_t gop, int32_t range, void *diff, void *maps);
+int  csic_mc_undelta_host(const csic_params *p, const void *diff, const void *maps, int32_t nframes, int32_t gop, void *frames);
+int  csic_mc_delta_device(csic_plan *plan, const void *d_frames, int32_t nframes, int32_t gop, int32_t range, void *d_diff, void *d_maps,
+                          void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int  csic_mc_undelta_device(csic_plan *plan, const void *d_diff, const void *d_maps, int32_t nframes, int32_t gop, void *d_frames,
+                            void *hip_stream);
+const char *csic_mc_kernel_name(const csic_plan *plan);
 
 /* ---- .csic files: the compressed frames on disk (host only, usable without a GPU) --------------------------------------------
  * A container holds `nframes` CSIC_FMT_PLANAR_BITS frames of one parameter set: the only thing this library writes to a file that
@@ -948,7 +1037,19 @@ const char *csic_delta_kernel_name(const csic_plan *plan);
  *   csic_container_coded_sizes gives the table (maps included).
  * CSIC_EFORMAT for a version-5 file, beyond the cases of versions 3 / 4 (with the sizes of the file's coding; a delta record holds
  * map_bytes more): a coding other than 1 or 3, a gop out of range, a delta record shorter than map_bytes + fixed_bytes, a padding bit
- * that is set in a map, any coded frame the coding's host decoder refuses.  Versions 1, 3 and 4 keep their behaviour. */
+ * that is set in a map, any coded frame the coding's host decoder refuses.  Versions 1, 3 and 4 keep their behaviour.
+ *
+ * Version 6 is version 5 through the motion-compensated layer (csic_mc_*): the same layout, the maps are csic_mc_layout_of's (map_bytes
+ * of that layout in front of every delta frame's coded difference frame), and the word at 80 is  coding | (R + 1) << 8  with R the range
+ * 0 .. 7 and every other bit zero; the word at 84 is the gop.  A motion field of 0 -- what a version-5 body has there -- or above 8 is
+ * CSIC_EFORMAT, so a version-5 body behind a version-6 header is refused at the header.
+ *   csic_container_write_seq_ex       : csic_container_write_seq with csic_mc_delta_host at `range`: version 6.  range outside 0 .. 7:
+ *                                       CSIC_EINVAL_SIZE.
+ *   csic_container_write_coded_seq_ex : csic_container_write_coded_seq with the maps of csic_mc_delta_device, validated as
+ *                                       csic_mc_undelta_host validates them: version 6.
+ *   csic_container_motion             : the range of a version-6 file, -1 for every other version.
+ *   csic_container_read, _info_of, _coded_sizes and _gop read version 6 as they read version 5; csic_container_inter_groups counts the
+ *   nibbles that are not 0.  CSIC_EFORMAT beyond version 5's cases: the motion field, and whatever csic_mc_undelta_host refuses of a map. */
 typedef struct csic_container_info {
     csic_params params;            /* out_format = CSIC_FMT_PLANAR_BITS, in_format = CSIC_FMT_ARGB8888 */
     int32_t version, nframes;
@@ -969,6 +1070,11 @@ int  csic_container_write_coded_seq(const char *path, const csic_params *p, cons
                                     const void *maps, size_t map_stride, int32_t nframes, int32_t coding, int32_t gop);
 int  csic_container_gop(const char *path, int32_t *gop);
 int  csic_container_inter_groups(const char *path, uint64_t *counts, int32_t n);
+int  csic_container_write_seq_ex(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding, int32_t gop,
+                                 int32_t range);
+int  csic_container_write_coded_seq_ex(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
+                                       const void *maps, size_t map_stride, int32_t nframes, int32_t coding, int32_t gop, int32_t range);
+int  csic_container_motion(const char *path, int32_t *range);
 
 /* ---- host-frame pipeline (the step either side of the hot path) -----------------------------------
  * Replaces the reference's per-image  readImage -> per-pixel poke ... peek -> writeImage  flow

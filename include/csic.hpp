@@ -243,11 +243,52 @@ inline std::vector<uint8_t> undelta(const csic_params &p, const void *diff, cons
     check(csic_undelta_host(&p, diff, maps, nframes, gop, frames.data()));
     return frames;
 }
+// The motion-compensated temporal layer (csic.h: csic_mc_*), host codec: as delta / undelta with a range of 0..7 and the maps of
+// csic_mc_layout_of; the difference frames never share memory with the frames.
+inline csic_mc_layout mcLayout(const csic_params &p)
+{
+    csic_mc_layout layout;
+    check(csic_mc_layout_of(&p, &layout));
+    return layout;
+}
+inline DeltaFrames mcDelta(const csic_params &p, const void *frames, int nframes, int gop, int range)
+{
+    csic_params q = p;
+    q.out_format = CSIC_FMT_PLANAR_BITS;
+    csic_planar_bits_layout layout;
+    check(csic_planar_bits_layout_of(&q, &layout));
+    DeltaFrames d;
+    d.diff.assign((size_t)(nframes > 0 ? nframes : 0) * (size_t)layout.frame_bytes, 0);
+    d.maps.assign((size_t)(nframes > 0 ? nframes : 0) * (size_t)mcLayout(p).map_stride, 0);
+    check(csic_mc_delta_host(&p, frames, nframes, gop, range, d.diff.data(), d.maps.data()));
+    return d;
+}
+inline std::vector<uint8_t> mcUndelta(const csic_params &p, const void *diff, const void *maps, int nframes, int gop)
+{
+    csic_params q = p;
+    q.out_format = CSIC_FMT_PLANAR_BITS;
+    csic_planar_bits_layout layout;
+    check(csic_planar_bits_layout_of(&q, &layout));
+    std::vector<uint8_t> frames((size_t)(nframes > 0 ? nframes : 0) * (size_t)layout.frame_bytes, 0);
+    check(csic_mc_undelta_host(&p, diff, maps, nframes, gop, frames.data()));
+    return frames;
+}
 // version 5: the frames as a sequence, delta and packing on the host (coding CSIC_CODING_GROUPS or CSIC_CODING_RICE); readContainer
 // returns the frames themselves
 inline void writeContainerSeq(const std::string &file, const csic_params &p, const void *frames, int nframes, int coding, int gop)
 {
     check(csic_container_write_seq(file.c_str(), &p, frames, nframes, coding, gop));
+}
+// version 6: the same through the motion-compensated layer at `range` (0..7); containerMotion: a file's range, -1 below version 6
+inline void writeContainerSeq(const std::string &file, const csic_params &p, const void *frames, int nframes, int coding, int gop, int range)
+{
+    check(csic_container_write_seq_ex(file.c_str(), &p, frames, nframes, coding, gop, range));
+}
+inline int containerMotion(const std::string &file)
+{
+    int32_t range = -1;
+    check(csic_container_motion(file.c_str(), &range));
+    return range;
 }
 inline int containerGop(const std::string &file)
 {
@@ -429,6 +470,20 @@ public:
         check(csic_undelta_device(plan_, d_diff, d_maps, nframes, gop, d_frames, hip_stream));
     }
     const char *deltaKernelName() { return csic_delta_kernel_name(plan_); }
+    // the motion-compensated layer, host and device (d_workspace: nframes * mcLayout().workspace_frame_bytes bytes; never in place)
+    csic_mc_layout mcLayout() const { return csic::mcLayout(params_); }
+    DeltaFrames mcDelta(const void *frames, int nframes, int gop, int range) const { return csic::mcDelta(params_, frames, nframes, gop, range); }
+    std::vector<uint8_t> mcUndelta(const void *diff, const void *maps, int nframes, int gop) const { return csic::mcUndelta(params_, diff, maps, nframes, gop); }
+    void mcDeltaDevice(const void *d_frames, int nframes, int gop, int range, void *d_diff, void *d_maps, void *d_workspace, size_t workspace_bytes,
+                       void *hip_stream)
+    {
+        check(csic_mc_delta_device(plan_, d_frames, nframes, gop, range, d_diff, d_maps, d_workspace, workspace_bytes, hip_stream));
+    }
+    void mcUndeltaDevice(const void *d_diff, const void *d_maps, int nframes, int gop, void *d_frames, void *hip_stream)
+    {
+        check(csic_mc_undelta_device(plan_, d_diff, d_maps, nframes, gop, d_frames, hip_stream));
+    }
+    const char *mcKernelName() { return csic_mc_kernel_name(plan_); }
 
 private:
     csic_params params_;
