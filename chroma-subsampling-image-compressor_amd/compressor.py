@@ -530,10 +530,11 @@ class Plan:
     def delta_kernel_name(self) -> str:
         return N.lib().csic_delta_kernel_name(self._h).decode()
 
-    def _delta_buffers(self, d_a, nframes, d_b, d_maps, what):
-        """The frames of one side checked, the other side's and the maps allocated unless given (`d_b` may be `d_a`: in place)."""
+    def _temporal_buffers(self, ms, d_a, nframes, d_b, d_maps, what):
+        """Both temporal layers: the frames of one side checked, the other side's and the maps (`ms`: the layer's map_stride) allocated
+        unless given (csic_delta_*: `d_b` may be `d_a`, in place; csic_mc_*: the library refuses that)."""
         import torch
-        fb, ms = self.planar_bits_layout.frame_bytes, self.delta_layout.map_stride
+        fb = self.planar_bits_layout.frame_bytes
         self._pack_check(d_a, nframes * fb, what)
         if d_b is None:
             d_b = torch.empty((nframes, fb), dtype=torch.uint8, device=d_a.device)
@@ -550,7 +551,7 @@ class Plan:
         uint8 tensor (nframes, frame_bytes) of which only the payload ranges are written -- `d_diff` may be `d_frames` itself, in place --
         and the maps, uint8 (nframes, map_stride) with map_bytes of each row written.  Either coder then packs `diff` as it packs
         frames.  Asynchronous on torch's current stream."""
-        d_diff, d_maps = self._delta_buffers(d_frames, nframes, d_diff, d_maps, "d_frames")
+        d_diff, d_maps = self._temporal_buffers(self.delta_layout.map_stride, d_frames, nframes, d_diff, d_maps, "d_frames")
         N.check(N.lib().csic_delta_device(self._h, C.c_void_p(d_frames.data_ptr()), int(nframes), int(gop), C.c_void_p(d_diff.data_ptr()),
                                           C.c_void_p(d_maps.data_ptr()), self._stream()))
         return d_diff, d_maps
@@ -560,7 +561,7 @@ class Plan:
         ones with undelta() first."""
         if d_maps is None:
             raise N.IllegalArgumentException(N.EINVAL_NULL, "requirement failed: d_maps is None")
-        d_frames, _ = self._delta_buffers(d_diff, nframes, d_frames, d_maps, "d_diff")
+        d_frames, _ = self._temporal_buffers(self.delta_layout.map_stride, d_diff, nframes, d_frames, d_maps, "d_diff")
         N.check(N.lib().csic_undelta_device(self._h, C.c_void_p(d_diff.data_ptr()), C.c_void_p(d_maps.data_ptr()), int(nframes), int(gop),
                                             C.c_void_p(d_frames.data_ptr()), self._stream()))
         return d_frames
@@ -584,28 +585,13 @@ class Plan:
     def mc_kernel_name(self) -> str:
         return N.lib().csic_mc_kernel_name(self._h).decode()
 
-    def _mc_buffers(self, d_a, nframes, d_b, d_maps, what):
-        """As _delta_buffers with the maps of this layer; the two sides must be apart."""
-        import torch
-        fb, ms = self.planar_bits_layout.frame_bytes, self.mc_layout.map_stride
-        self._pack_check(d_a, nframes * fb, what)
-        if d_b is None:
-            d_b = torch.empty((nframes, fb), dtype=torch.uint8, device=d_a.device)
-        else:
-            self._pack_check(d_b, nframes * fb, "the output frames")
-        if d_maps is None:
-            d_maps = torch.zeros((nframes, ms), dtype=torch.uint8, device=d_a.device)
-        else:
-            self._pack_check(d_maps, nframes * ms, "d_maps")
-        return d_b, d_maps
-
     def mc_delta_device(self, d_frames, nframes: int = 1, gop: int = 1, motion: int = 2, d_diff=None, d_maps=None, d_workspace=None):
         """As delta_device with displacements of up to `motion` samples either way (0..7): returns (diff, maps), the difference frames
         -- not in place: `d_diff` must lie apart from `d_frames` -- and the maps, uint8 (nframes, mc_layout.map_stride).  `d_workspace`:
         nframes * mc_layout.workspace_frame_bytes bytes for the vote counters, allocated unless given.  Asynchronous on torch's current
         stream."""
         import torch
-        d_diff, d_maps = self._mc_buffers(d_frames, nframes, d_diff, d_maps, "d_frames")
+        d_diff, d_maps = self._temporal_buffers(self.mc_layout.map_stride, d_frames, nframes, d_diff, d_maps, "d_frames")
         wsb = nframes * self.mc_layout.workspace_frame_bytes
         if d_workspace is None:
             d_workspace = torch.empty((wsb,), dtype=torch.uint8, device=d_frames.device)
@@ -620,7 +606,7 @@ class Plan:
         with mc_undelta() first."""
         if d_maps is None:
             raise N.IllegalArgumentException(N.EINVAL_NULL, "requirement failed: d_maps is None")
-        d_frames, _ = self._mc_buffers(d_diff, nframes, d_frames, d_maps, "d_diff")
+        d_frames, _ = self._temporal_buffers(self.mc_layout.map_stride, d_diff, nframes, d_frames, d_maps, "d_diff")
         N.check(N.lib().csic_mc_undelta_device(self._h, C.c_void_p(d_diff.data_ptr()), C.c_void_p(d_maps.data_ptr()), int(nframes), int(gop),
                                                C.c_void_p(d_frames.data_ptr()), self._stream()))
         return d_frames

@@ -128,33 +128,41 @@ def _frames_2d(frames, frame_bytes: int) -> np.ndarray:
     return a.reshape(-1, frame_bytes)
 
 
-def delta_host(c_params: N.CsicParams, frames, gop: int, out=None):
-    """csic_delta_host: PLANAR_BITS frame buffers (nframes, frame_bytes) -> (diff, maps): the difference frames, an array of the same
-    shape (zero outside the payload ranges, or `out` -- which may be `frames` itself, in place), and the maps, uint8 (nframes,
-    map_stride) with map_bytes of each row written."""
+def _temporal_forward(c_params: N.CsicParams, frames, out, layout_of, entry, *args):
+    """Both layers' `*_delta_host`: `entry(params, frames, nframes, *args, diff, maps)` with the maps of `layout_of`."""
     q, lay = _bits_params(c_params)
-    ml = delta_layout(q)
+    ml = layout_of(q)
     a = _frames_2d(frames, lay.frame_bytes)
     diff = np.zeros_like(a) if out is None else out
     maps = np.zeros((a.shape[0], ml.map_stride), dtype=np.uint8)
-    N.check(N.lib().csic_delta_host(C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], int(gop), diff.ctypes.data_as(C.c_void_p),
-                                    maps.ctypes.data_as(C.c_void_p)))
+    N.check(entry(C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], *args, diff.ctypes.data_as(C.c_void_p), maps.ctypes.data_as(C.c_void_p)))
     return diff, maps
 
 
-def undelta_host(c_params: N.CsicParams, diff, maps, gop: int, out=None) -> np.ndarray:
-    """csic_undelta_host: the inverse of delta_host.  The maps are untrusted: a set padding bit or a non-zero map of a key frame raises
-    CsicIOError (CSIC_EFORMAT) and nothing is written."""
+def _temporal_inverse(c_params: N.CsicParams, diff, maps, gop, out, layout_of, entry) -> np.ndarray:
+    """Both layers' `*_undelta_host`: `entry(params, diff, maps, nframes, gop, frames)` with the maps of `layout_of`."""
     q, lay = _bits_params(c_params)
-    ml = delta_layout(q)
+    ml = layout_of(q)
     d = _frames_2d(diff, lay.frame_bytes)
     m = np.ascontiguousarray(maps).view(np.uint8).reshape(d.shape[0], -1)
     if m.shape[1] != ml.map_stride:
         raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: maps must be (nframes, {ml.map_stride}), got {m.shape}")
     frames = np.zeros_like(d) if out is None else out
-    N.check(N.lib().csic_undelta_host(C.byref(q), d.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), d.shape[0], int(gop),
-                                      frames.ctypes.data_as(C.c_void_p)))
+    N.check(entry(C.byref(q), d.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), d.shape[0], int(gop), frames.ctypes.data_as(C.c_void_p)))
     return frames
+
+
+def delta_host(c_params: N.CsicParams, frames, gop: int, out=None):
+    """csic_delta_host: PLANAR_BITS frame buffers (nframes, frame_bytes) -> (diff, maps): the difference frames, an array of the same
+    shape (zero outside the payload ranges, or `out` -- which may be `frames` itself, in place), and the maps, uint8 (nframes,
+    map_stride) with map_bytes of each row written."""
+    return _temporal_forward(c_params, frames, out, delta_layout, N.lib().csic_delta_host, int(gop))
+
+
+def undelta_host(c_params: N.CsicParams, diff, maps, gop: int, out=None) -> np.ndarray:
+    """csic_undelta_host: the inverse of delta_host.  The maps are untrusted: a set padding bit or a non-zero map of a key frame raises
+    CsicIOError (CSIC_EFORMAT) and nothing is written."""
+    return _temporal_inverse(c_params, diff, maps, gop, out, delta_layout, N.lib().csic_undelta_host)
 
 
 def mc_layout(c_params: N.CsicParams) -> N.CsicMcLayout:
@@ -169,29 +177,18 @@ def mc_delta_host(c_params: N.CsicParams, frames, gop: int, motion: int, out=Non
     """csic_mc_delta_host: PLANAR_BITS frame buffers (nframes, frame_bytes) -> (diff, maps) with displacements of up to `motion`
     samples either way: the difference frames, an array of the same shape (zero outside the payload ranges, or `out` -- not `frames`:
     there is no in-place form), and the maps, uint8 (nframes, map_stride) with map_bytes of each row written."""
-    q, lay = _bits_params(c_params)
-    ml = mc_layout(q)
-    a = _frames_2d(frames, lay.frame_bytes)
-    diff = np.zeros_like(a) if out is None else out
-    maps = np.zeros((a.shape[0], ml.map_stride), dtype=np.uint8)
-    N.check(N.lib().csic_mc_delta_host(C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], int(gop), int(motion), diff.ctypes.data_as(C.c_void_p),
-                                       maps.ctypes.data_as(C.c_void_p)))
-    return diff, maps
+    return _temporal_forward(c_params, frames, out, mc_layout, N.lib().csic_mc_delta_host, int(gop), int(motion))
 
 
 def mc_undelta_host(c_params: N.CsicParams, diff, maps, gop: int, out=None) -> np.ndarray:
     """csic_mc_undelta_host: the inverse of mc_delta_host.  The maps are untrusted: a damaged table, a nibble above its table, a set
     padding nibble or a non-zero map of a key frame raises CsicIOError (CSIC_EFORMAT) and nothing is written."""
-    q, lay = _bits_params(c_params)
-    ml = mc_layout(q)
-    d = _frames_2d(diff, lay.frame_bytes)
-    m = np.ascontiguousarray(maps).view(np.uint8).reshape(d.shape[0], -1)
-    if m.shape[1] != ml.map_stride:
-        raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: maps must be (nframes, {ml.map_stride}), got {m.shape}")
-    frames = np.zeros_like(d) if out is None else out
-    N.check(N.lib().csic_mc_undelta_host(C.byref(q), d.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), d.shape[0], int(gop),
-                                         frames.ctypes.data_as(C.c_void_p)))
-    return frames
+    return _temporal_inverse(c_params, diff, maps, gop, out, mc_layout, N.lib().csic_mc_undelta_host)
+
+
+def _seq_entry(plain, ex, gop, motion):
+    """-> (the writer of a sequence file, its arguments behind the coding): version 5, or with a `motion` range the _ex form, version 6."""
+    return (plain, (int(gop),)) if motion is None else (ex, (int(gop), int(motion)))
 
 
 def write_container(path: str, c_params: N.CsicParams, frames, coding="raw", gop=None, motion=None) -> None:
@@ -205,13 +202,10 @@ def write_container(path: str, c_params: N.CsicParams, frames, coding="raw", gop
     coding = _coding(coding)
     if motion is not None and gop is None:
         raise N.IllegalArgumentException(N.EINVAL_NULL, "requirement failed: motion needs a gop")
-    if motion is not None:
-        a = _frames_2d(frames, lay.frame_bytes)
-        N.check(N.lib().csic_container_write_seq_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], coding, int(gop), int(motion)))
-        return
     if gop is not None:
         a = _frames_2d(frames, lay.frame_bytes)
-        N.check(N.lib().csic_container_write_seq(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], coding, int(gop)))
+        write, layer = _seq_entry(N.lib().csic_container_write_seq, N.lib().csic_container_write_seq_ex, gop, motion)
+        N.check(write(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], coding, *layer))
         return
     if isinstance(frames, (list, tuple)):
         frames = np.stack([np.ascontiguousarray(f).reshape(-1).view(np.uint8) for f in frames])
@@ -251,14 +245,9 @@ def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, codin
         m = np.ascontiguousarray(maps).view(np.uint8)
         if m.size == 0 or m.size % sz.size != 0:
             raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: {m.size} bytes of maps for {sz.size} frames")
-        if motion is not None:
-            N.check(N.lib().csic_container_write_coded_seq_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1],
-                                                              sz.ctypes.data_as(C.POINTER(C.c_uint64)), m.ctypes.data_as(C.c_void_p), m.size // sz.size,
-                                                              int(sz.size), coding, int(gop), int(motion)))
-            return
-        N.check(N.lib().csic_container_write_coded_seq(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1],
-                                                       sz.ctypes.data_as(C.POINTER(C.c_uint64)), m.ctypes.data_as(C.c_void_p), m.size // sz.size,
-                                                       int(sz.size), coding, int(gop)))
+        write, layer = _seq_entry(N.lib().csic_container_write_coded_seq, N.lib().csic_container_write_coded_seq_ex, gop, motion)
+        N.check(write(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1], sz.ctypes.data_as(C.POINTER(C.c_uint64)),
+                      m.ctypes.data_as(C.c_void_p), m.size // sz.size, int(sz.size), coding, *layer))
         return
     N.check(N.lib().csic_container_write_coded_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1],
                                                   sz.ctypes.data_as(C.POINTER(C.c_uint64)), int(sz.size), coding))

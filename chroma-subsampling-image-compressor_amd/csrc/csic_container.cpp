@@ -6,6 +6,7 @@
 // the little-endian dwords are csic_group_host.h's.  Version 5 holds a sequence through the temporal layer (csic_delta_host.cpp): the word
 // behind the coding is the gop, a key frame's record is its coded frame, a delta frame's its map and then its coded difference frame.
 // Version 6 is version 5 through the motion-compensated layer (csic_mc_host.cpp): its maps, and the range + 1 in bits 8.. of the coding word.
+// What differs between those two is one row of layer_of.
 #include <zlib.h>
 
 #include <cstdio>
@@ -77,6 +78,57 @@ static Codec codec_of(const RiceGeometry &R, int coding)
     return rows[coding == CSIC_CODING_RICE];
 }
 
+// What depends on the temporal layer of a sequence file, for one parameter set: the version, the bytes of a delta frame's map, the
+// frame codec both ways, the check of a map nobody vouches for, the inter groups of one plane's section of a map, and whether the
+// inverse may run in place.  One row per layer; a file picks its row once.  motion < 0: version 5 through csic_delta_*; otherwise
+// version 6 through csic_mc_* at that range.  version 0: no layer (every frame stands alone).
+struct Layer {
+    uint32_t version = 0;
+    int32_t motion = -1;
+    int64_t map_bytes = 0;
+    bool in_place = true;
+    DeltaGeometry D;               // the geometry of the file's own layer only
+    McGeometry M;
+    void (*forward)(const Layer &L, const unsigned char *cur, const unsigned char *prev, unsigned char *diff, unsigned char *map) = nullptr;
+    void (*inverse)(const Layer &L, const unsigned char *diff, const unsigned char *map, const unsigned char *prev, unsigned char *cur) = nullptr;
+    int (*check)(const Layer &L, const unsigned char *map, bool key, int frame) = nullptr;
+    uint64_t (*inter)(const Layer &L, const unsigned char *map, int pl) = nullptr;
+};
+static int layer_of(const csic_params &q, int32_t motion, Layer *L)
+{
+    L->motion = motion;
+    if (motion < 0) {
+        const int st = delta_geometry(&q, &L->D);
+        if (st != CSIC_OK) return st;
+        L->version = CONTAINER_VERSION_SEQ;
+        L->map_bytes = L->D.layout.map_bytes;
+        L->in_place = true;
+        L->forward = [](const Layer &l, const unsigned char *c, const unsigned char *p, unsigned char *d, unsigned char *m) { delta_frame(l.D, c, p, d, m); };
+        L->inverse = [](const Layer &l, const unsigned char *d, const unsigned char *m, const unsigned char *p, unsigned char *c) { undelta_frame(l.D, d, m, p, c); };
+        L->check = [](const Layer &l, const unsigned char *m, bool key, int frame) { return delta_check_map(l.D, m, key, frame); };
+        L->inter = [](const Layer &l, const unsigned char *m, int pl) {                 // the set bits
+            uint64_t got = 0;
+            for (int64_t g = 0; g < l.D.layout.groups[pl]; ++g) got += (m[l.D.layout.map_offset[pl] + (g >> 3)] >> (g & 7)) & 1;
+            return got;
+        };
+        return CSIC_OK;
+    }
+    const int st = mc_geometry(&q, &L->M);
+    if (st != CSIC_OK) return st;
+    L->version = CONTAINER_VERSION_MC;
+    L->map_bytes = L->M.layout.map_bytes;
+    L->in_place = false;                              // a group reads other groups of the previous frame
+    L->forward = [](const Layer &l, const unsigned char *c, const unsigned char *p, unsigned char *d, unsigned char *m) { mc_delta_frame(l.M, c, p, l.motion, d, m); };
+    L->inverse = [](const Layer &l, const unsigned char *d, const unsigned char *m, const unsigned char *p, unsigned char *c) { mc_undelta_frame(l.M, d, m, p, c); };
+    L->check = [](const Layer &l, const unsigned char *m, bool key, int frame) { return mc_check_map(l.M, m, key, frame); };
+    L->inter = [](const Layer &l, const unsigned char *m, int pl) {                     // the nibbles that are not 0
+        uint64_t got = 0;
+        for (int64_t g = 0; g < l.M.layout.groups[pl]; ++g) got += nibble_at(m + l.M.layout.map_offset[pl], g) != 0;
+        return got;
+    };
+    return CSIC_OK;
+}
+
 struct FileCloser {
     FILE *f;
     ~FileCloser() { if (f) fclose(f); }
@@ -85,19 +137,13 @@ struct FileCloser {
 // Reads and checks everything but the CRC (and, version 3, the coded frames themselves): header fields, parameters, the table of
 // sizes, the file's length.  `sizes` (may be NULL) receives the stored bytes of each frame; the file pointer is left behind the
 // header (version 1) or the table (version 3).  *stored_crc may be NULL.
-// What a coded file's body says in front of its table: the coding, the gop (1 below version 5) and the bytes of a delta frame's map.
+// What a coded file's body says in front of its table: the coding, the gop (1 below version 5) and the temporal layer (none below
+// version 5: no maps, motion -1).
 struct CodedBody {
     int coding = CSIC_CODING_RAW;
     int32_t gop = 1;
-    int64_t map_bytes = 0;
-    int32_t motion = -1;           // version 6: the range
+    Layer layer;
 };
-static int64_t map_bytes_of(const PackGeometry &G)
-{
-    int64_t b = 0;
-    for (int pl = 0; pl < 3; ++pl) b += 4 * ((G.layout.groups[pl] + 31) / 32);
-    return b;
-}
 
 static int read_header(FILE *f, const char *path, csic_container_info *info, RiceGeometry *G, uint32_t *stored_crc, std::vector<uint64_t> *sizes,
                        CodedBody *body = nullptr)
@@ -134,23 +180,20 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Ric
         if (version == CONTAINER_VERSION_SEQ || version == CONTAINER_VERSION_MC) {
             uint32_t c = get_u32(t.data());
             const uint32_t gop = get_u32(t.data() + 4);
+            int32_t motion = -1;
             if (version == CONTAINER_VERSION_MC) {                 // coding | (range + 1) << 8, every other bit zero
                 const uint32_t field = c >> 8;
                 if (field < 1 || field > (uint32_t)MC_MAX_RANGE + 1)
                     return set_error(CSIC_EFORMAT, "%s: motion field %u of the coding word %#x is not a range + 1 of 1..%d", path, field, c, MC_MAX_RANGE + 1);
-                cb.motion = (int32_t)field - 1;
+                motion = (int32_t)field - 1;
                 c &= 0xFFu;
             }
             if (c != CSIC_CODING_GROUPS && c != CSIC_CODING_RICE) return set_error(CSIC_EFORMAT, "%s: coding %u is not one version %u holds (1 or 3)", path, c, version);
             if (gop < 1 || gop > 65535) return set_error(CSIC_EFORMAT, "%s: gop must be in 1..65535. Got %u", path, gop);
             coding = (int)c;
             cb.gop = (int32_t)gop;
-            cb.map_bytes = map_bytes_of(G->pk);
-            if (version == CONTAINER_VERSION_MC) {
-                McGeometry M;
-                if (mc_geometry(&p, &M) != CSIC_OK) return set_error(CSIC_EFORMAT, "%s: the stored parameters have no motion-compensated layout", path);
-                cb.map_bytes = M.layout.map_bytes;
-            }
+            const int st = layer_of(p, motion, &cb.layer);
+            if (st != CSIC_OK) return motion < 0 ? st : set_error(CSIC_EFORMAT, "%s: the stored parameters have no motion-compensated layout", path);
         } else if (get_u32(t.data()) != (uint32_t)coding || get_u32(t.data() + 4) != 0)
             return set_error(CSIC_EFORMAT, "%s: coding %u (reserved word %u) is not what version %u holds (%d, 0)", path, get_u32(t.data()), get_u32(t.data() + 4),
                              version, coding);
@@ -160,7 +203,7 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Ric
         if (sizes) sizes->resize(nframes);
         for (uint32_t k = 0; k < nframes; ++k) {
             const uint64_t sz = get_u64(t.data() + CODED_BODY + 8 * (size_t)k);
-            const uint64_t map = k % (uint32_t)cb.gop ? (uint64_t)cb.map_bytes : 0, lo = codec.lo + map, hi = codec.hi + map;     // a delta record: map, then coded frame
+            const uint64_t map = k % (uint32_t)cb.gop ? (uint64_t)cb.layer.map_bytes : 0, lo = codec.lo + map, hi = codec.hi + map;     // a delta record: map, then coded frame
             if (sz < lo || sz > hi || sz % 4 != 0)
                 return set_error(CSIC_EFORMAT, "%s: frame %u is stored in %llu bytes; these parameters code to %llu .. %llu, in dwords", path, k,
                                  (unsigned long long)sz, (unsigned long long)lo, (unsigned long long)hi);
@@ -202,15 +245,16 @@ static int writer_params(const csic_params *p, int32_t nframes, csic_params *q, 
 }
 
 // A version-3 or version-4 file from coded frames in memory: frame k is frames[k][0, sizes[k]).  With a gop (> 0) a version-5 file:
-// maps[k][0, map_bytes) stands in front of every delta frame.  With a motion range (>= 0) a version-6 file: the maps are csic_mc_*'s.
+// maps[k][0, map_bytes) of the layer stands in front of every delta frame, and the version is the layer's.
 static int write_coded_file(const char *path, const csic_params &q, const unsigned char *const *frames, const uint64_t *sizes, int32_t nframes, const Codec &codec,
-                            int32_t gop = 0, const unsigned char *const *maps = nullptr, size_t map_bytes = 0, int32_t motion = -1)
+                            int32_t gop = 0, const unsigned char *const *maps = nullptr, const Layer &layer = Layer())
 {
+    const size_t map_bytes = (size_t)layer.map_bytes;
     const auto map_of = [&](int32_t k) { return gop > 0 && k % gop ? map_bytes : (size_t)0; };
     unsigned char h[CONTAINER_HEADER];
-    fill_header(h, gop > 0 ? (motion >= 0 ? CONTAINER_VERSION_MC : CONTAINER_VERSION_SEQ) : codec.version, q, nframes);
+    fill_header(h, gop > 0 ? layer.version : codec.version, q, nframes);
     std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
-    put_u32(t.data(), (uint32_t)codec.coding | (motion >= 0 ? (uint32_t)(motion + 1) << 8 : 0u));
+    put_u32(t.data(), (uint32_t)codec.coding | (uint32_t)(layer.motion + 1) << 8);
     put_u32(t.data() + 4, (uint32_t)gop);
     for (int32_t k = 0; k < nframes; ++k) put_u64(t.data() + CODED_BODY + 8 * (size_t)k, sizes[k] + map_of(k));
     uLong crc = crc32(0L, h + CONTAINER_CRC_FROM, (uInt)(CONTAINER_HEADER - CONTAINER_CRC_FROM));
@@ -233,6 +277,28 @@ static int write_coded_file(const char *path, const csic_params &q, const unsign
     return CSIC_OK;
 }
 
+// What the readers of one thing of a file share: the NULLs, the file opened, its header read and checked, then
+// take(file, info, table of sizes, body) with an allocation failure caught; the error state is cleared on success.
+template <class Take> static int with_header(const char *path, const void *out, Take take)
+{
+    if (!path || !out) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
+    FileCloser fc{fopen(path, "rb")};
+    if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
+    try {
+        RiceGeometry G;
+        csic_container_info ci;
+        std::vector<uint64_t> table;
+        CodedBody body;
+        int st = read_header(fc.f, path, &ci, &G, nullptr, &table, &body);
+        if (st == CSIC_OK) st = take(fc.f, ci, table, body);
+        if (st != CSIC_OK) return st;
+    } catch (const std::bad_alloc &) {
+        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
+    }
+    clear_error();
+    return CSIC_OK;
+}
+
 } // namespace csic
 
 using namespace csic;
@@ -241,40 +307,16 @@ extern "C" {
 
 int csic_container_info_of(const char *path, csic_container_info *info)
 {
-    if (!path || !info) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    FileCloser fc{fopen(path, "rb")};
-    if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
-    try {
-        RiceGeometry G;
-        csic_container_info ci;
-        const int st = read_header(fc.f, path, &ci, &G, nullptr, nullptr);
-        if (st != CSIC_OK) return st;
-        *info = ci;
-    } catch (const std::bad_alloc &) {
-        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
-    }
-    clear_error();
-    return CSIC_OK;
+    return with_header(path, info, [&](FILE *, const csic_container_info &ci, const std::vector<uint64_t> &, const CodedBody &) { *info = ci; return (int)CSIC_OK; });
 }
 
 int csic_container_coded_sizes(const char *path, uint64_t *sizes, int32_t n)
 {
-    if (!path || !sizes) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    FileCloser fc{fopen(path, "rb")};
-    if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
-    try {
-        RiceGeometry G;
-        csic_container_info ci;
-        std::vector<uint64_t> table;
-        const int st = read_header(fc.f, path, &ci, &G, nullptr, &table);
-        if (st != CSIC_OK) return st;
+    return with_header(path, sizes, [&](FILE *, const csic_container_info &ci, const std::vector<uint64_t> &table, const CodedBody &) {
         if (n != ci.nframes) return set_error(CSIC_EINVAL_SIZE, "expected room for %d sizes, got %d", ci.nframes, n);
         std::memcpy(sizes, table.data(), table.size() * sizeof(uint64_t));
-    } catch (const std::bad_alloc &) {
-        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
-    }
-    clear_error();
-    return CSIC_OK;
+        return (int)CSIC_OK;
+    });
 }
 
 int csic_container_write(const char *path, const csic_params *p, const void *frames, int32_t nframes)
@@ -395,20 +437,16 @@ static int write_seq(const char *path, const csic_params *p, const void *frames,
     if (st != CSIC_OK) return st;
     csic_params q;
     RiceGeometry G;
-    DeltaGeometry D;
-    McGeometry M;
-    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = delta_geometry(&q, &D)) != CSIC_OK) return st;
-    if (motion >= 0 && (st = mc_geometry(&q, &M)) != CSIC_OK) return st;
+    Layer layer;
+    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = layer_of(q, motion, &layer)) != CSIC_OK) return st;
     const Codec codec = codec_of(G, coding);
     try {
-        const size_t fb = (size_t)G.pk.bits.frame_bytes, mb = (size_t)(motion >= 0 ? M.layout.map_bytes : D.layout.map_bytes);
+        const size_t fb = (size_t)G.pk.bits.frame_bytes, mb = (size_t)layer.map_bytes;
         const unsigned char *x = static_cast<const unsigned char *>(frames);
         std::vector<unsigned char> diff(fb), maps((size_t)nframes * mb), all;
         std::vector<uint64_t> sizes((size_t)nframes);
         for (int32_t k = 0; k < nframes; ++k) {
-            const unsigned char *prev = k % gop ? x + (size_t)(k - 1) * fb : nullptr;
-            if (motion >= 0) mc_delta_frame(M, x + (size_t)k * fb, prev, motion, diff.data(), maps.data() + (size_t)k * mb);
-            else delta_frame(D, x + (size_t)k * fb, prev, diff.data(), maps.data() + (size_t)k * mb);
+            layer.forward(layer, x + (size_t)k * fb, k % gop ? x + (size_t)(k - 1) * fb : nullptr, diff.data(), maps.data() + (size_t)k * mb);
             const size_t at = all.size();
             all.resize(at + codec.bound);
             st = codec.pack(G, diff.data(), all.data() + at, codec.bound, &sizes[k]);
@@ -418,7 +456,7 @@ static int write_seq(const char *path, const csic_params *p, const void *frames,
         std::vector<const unsigned char *> ptrs((size_t)nframes), mptrs((size_t)nframes);
         size_t at = 0;
         for (int32_t k = 0; k < nframes; ++k) { ptrs[k] = all.data() + at; at += (size_t)sizes[k]; mptrs[k] = maps.data() + (size_t)k * mb; }
-        st = write_coded_file(path, q, ptrs.data(), sizes.data(), nframes, codec, gop, mptrs.data(), mb, motion);
+        st = write_coded_file(path, q, ptrs.data(), sizes.data(), nframes, codec, gop, mptrs.data(), layer);
     } catch (const std::bad_alloc &) {
         return set_error(CSIC_ENOMEM, "out of host memory coding %d frames for %s", nframes, path);
     }
@@ -446,11 +484,9 @@ static int write_coded_seq(const char *path, const csic_params *p, const void *c
     if (st != CSIC_OK) return st;
     csic_params q;
     RiceGeometry G;
-    DeltaGeometry D;
-    McGeometry M;
-    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = delta_geometry(&q, &D)) != CSIC_OK) return st;
-    if (motion >= 0 && (st = mc_geometry(&q, &M)) != CSIC_OK) return st;
-    const size_t mb = (size_t)(motion >= 0 ? M.layout.map_bytes : D.layout.map_bytes);
+    Layer layer;
+    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = layer_of(q, motion, &layer)) != CSIC_OK) return st;
+    const size_t mb = (size_t)layer.map_bytes;
     if (map_stride < mb)
         return set_error(CSIC_EINVAL_SIZE, "a map of these parameters has %zu bytes: a map_stride of %zu cannot hold it", mb, map_stride);
     const Codec codec = codec_of(G, coding);
@@ -462,9 +498,9 @@ static int write_coded_seq(const char *path, const csic_params *p, const void *c
             ptrs[k] = static_cast<const unsigned char *>(coded) + (size_t)k * stride_bytes;
             mptrs[k] = static_cast<const unsigned char *>(maps) + (size_t)k * map_stride;
             if ((st = codec.check(G, ptrs[k], (size_t)sizes[k])) != CSIC_OK) return st;
-            if ((st = motion >= 0 ? mc_check_map(M, mptrs[k], k % gop == 0, k) : delta_check_map(D, mptrs[k], k % gop == 0, k)) != CSIC_OK) return st;
+            if ((st = layer.check(layer, mptrs[k], k % gop == 0, k)) != CSIC_OK) return st;
         }
-        st = write_coded_file(path, q, ptrs.data(), sizes, nframes, codec, gop, mptrs.data(), mb, motion);
+        st = write_coded_file(path, q, ptrs.data(), sizes, nframes, codec, gop, mptrs.data(), layer);
     } catch (const std::bad_alloc &) {
         return set_error(CSIC_ENOMEM, "out of host memory writing %s", path);
     }
@@ -488,84 +524,32 @@ int csic_container_write_coded_seq_ex(const char *path, const csic_params *p, co
 
 int csic_container_motion(const char *path, int32_t *range)
 {
-    if (!path || !range) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    FileCloser fc{fopen(path, "rb")};
-    if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
-    try {
-        RiceGeometry G;
-        csic_container_info ci;
-        CodedBody body;
-        const int st = read_header(fc.f, path, &ci, &G, nullptr, nullptr, &body);
-        if (st != CSIC_OK) return st;
-        *range = body.motion;
-    } catch (const std::bad_alloc &) {
-        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
-    }
-    clear_error();
-    return CSIC_OK;
+    return with_header(path, range, [&](FILE *, const csic_container_info &, const std::vector<uint64_t> &, const CodedBody &body) { *range = body.layer.motion; return (int)CSIC_OK; });
 }
 
 int csic_container_gop(const char *path, int32_t *gop)
 {
-    if (!path || !gop) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    FileCloser fc{fopen(path, "rb")};
-    if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
-    try {
-        RiceGeometry G;
-        csic_container_info ci;
-        CodedBody body;
-        const int st = read_header(fc.f, path, &ci, &G, nullptr, nullptr, &body);
-        if (st != CSIC_OK) return st;
-        *gop = body.gop;
-    } catch (const std::bad_alloc &) {
-        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
-    }
-    clear_error();
-    return CSIC_OK;
+    return with_header(path, gop, [&](FILE *, const csic_container_info &, const std::vector<uint64_t> &, const CodedBody &body) { *gop = body.gop; return (int)CSIC_OK; });
 }
 
 int csic_container_inter_groups(const char *path, uint64_t *counts, int32_t n)
 {
-    if (!path || !counts) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    FileCloser fc{fopen(path, "rb")};
-    if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
-    try {
-        RiceGeometry G;
-        DeltaGeometry D;
-        McGeometry M;
-        csic_container_info ci;
-        CodedBody body;
-        std::vector<uint64_t> table;
-        int st = read_header(fc.f, path, &ci, &G, nullptr, &table, &body);
-        if (st != CSIC_OK) return st;
+    return with_header(path, counts, [&](FILE *f, const csic_container_info &ci, const std::vector<uint64_t> &table, const CodedBody &body) {
         if (n != 3 * ci.nframes) return set_error(CSIC_EINVAL_SIZE, "expected room for %d counts, got %d", 3 * ci.nframes, n);
+        const Layer &layer = body.layer;
         std::vector<uint64_t> got((size_t)n, 0);
-        if (body.map_bytes > 0 && (st = delta_geometry(&ci.params, &D)) != CSIC_OK) return st;
-        if (body.motion >= 0 && (st = mc_geometry(&ci.params, &M)) != CSIC_OK) return st;
-        std::vector<unsigned char> map((size_t)body.map_bytes);
-        long long at = ftello(fc.f);                   // where the records begin
-        for (int32_t k = 0; k < ci.nframes; ++k) {
-            if (body.map_bytes > 0 && k % body.gop) {
-                if (fseeko(fc.f, at, SEEK_SET) != 0 || fread(map.data(), 1, map.size(), fc.f) != map.size()) return set_error(CSIC_EIO, "cannot read %s", path);
-                if (body.motion >= 0) {                     // version 6: the nibbles that are not 0
-                    if ((st = mc_check_map(M, map.data(), false, k)) != CSIC_OK) return st;
-                    for (int pl = 0; pl < 3; ++pl)
-                        for (int64_t g = 0; g < M.layout.groups[pl]; ++g) got[3 * (size_t)k + pl] += nibble_at(map.data() + M.layout.map_offset[pl], g) != 0;
-                    at += (long long)table[k];
-                    continue;
-                }
-                if ((st = delta_check_map(D, map.data(), false, k)) != CSIC_OK) return st;
-                for (int pl = 0; pl < 3; ++pl)
-                    for (int64_t b = 0; b < 4 * ((D.layout.groups[pl] + 31) / 32); ++b) got[3 * (size_t)k + pl] += (uint64_t)__builtin_popcount(map[D.layout.map_offset[pl] + b]);
-            }
-            at += (long long)table[k];
+        std::vector<unsigned char> map((size_t)layer.map_bytes);
+        long long at = ftello(f);                      // where the records begin
+        for (int32_t k = 0; k < ci.nframes; at += (long long)table[k], ++k) {
+            if (layer.map_bytes <= 0 || k % body.gop == 0) continue;
+            if (fseeko(f, at, SEEK_SET) != 0 || fread(map.data(), 1, map.size(), f) != map.size()) return set_error(CSIC_EIO, "cannot read %s", path);
+            const int st = layer.check(layer, map.data(), false, k);
+            if (st != CSIC_OK) return st;
+            for (int pl = 0; pl < 3; ++pl) got[3 * (size_t)k + pl] = layer.inter(layer, map.data(), pl);
         }
         std::memcpy(counts, got.data(), got.size() * sizeof(uint64_t));
-    } catch (const std::bad_alloc &) {
-        return set_error(CSIC_ENOMEM, "out of host memory reading %s", path);
-    }
-    clear_error();
-    return CSIC_OK;
+        return (int)CSIC_OK;
+    });
 }
 
 static int container_read(const char *path, void *frames, size_t frames_bytes)
@@ -580,10 +564,7 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
     int st = read_header(fc.f, path, &ci, &C, &stored, &sizes, &body);
     if (st != CSIC_OK) return st;
     const PackGeometry &G = C.pk;
-    DeltaGeometry D;
-    McGeometry M;
-    if (ci.version == (int32_t)CONTAINER_VERSION_SEQ && (st = delta_geometry(&ci.params, &D)) != CSIC_OK) return st;
-    if (ci.version == (int32_t)CONTAINER_VERSION_MC && (st = mc_geometry(&ci.params, &M)) != CSIC_OK) return st;
+    const Layer &layer = body.layer;
     const csic_planar_bits_layout &L = G.bits;
     const size_t need = (size_t)ci.nframes * (size_t)L.frame_bytes;
     if (frames_bytes != need)
@@ -611,16 +592,15 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
             coded.resize((size_t)sizes[k]);            // within the coding's sizes: read_header checked the table
             if (fread(coded.data(), 1, coded.size(), fc.f) != coded.size()) return set_error(CSIC_EIO, "cannot read %s", path);
             crc = crc_long(crc, coded.data(), (int64_t)coded.size());
-            const size_t map = k % body.gop ? (size_t)body.map_bytes : 0;      // version 5: a delta frame's map first (read_header: the record holds it)
-            if (map && body.motion >= 0) {                 // version 6: a group reads other groups of the previous frame, so not in place
+            const size_t map = k % body.gop ? (size_t)layer.map_bytes : 0;     // versions 5, 6: a delta frame's map first (read_header: the record holds it)
+            unsigned char *d = fr;                         // the difference frame -> the frame, in place where the layer allows it
+            if (map && !layer.in_place) {
                 diff.assign((size_t)L.frame_bytes, 0);
-                if ((st = mc_check_map(M, coded.data(), false, k)) == CSIC_OK) st = codec.unpack(C, coded.data() + map, coded.size() - map, diff.data());
-                if (st == CSIC_OK) mc_undelta_frame(M, diff.data(), coded.data(), fr - L.frame_bytes, fr);
-                continue;
+                d = diff.data();
             }
-            if (map) st = delta_check_map(D, coded.data(), false, k);
-            if (st == CSIC_OK) st = codec.unpack(C, coded.data() + map, coded.size() - map, fr);
-            if (st == CSIC_OK && map) undelta_frame(D, fr, coded.data(), fr - L.frame_bytes, fr);      // the difference frame -> the frame, in place
+            if (map) st = layer.check(layer, coded.data(), false, k);
+            if (st == CSIC_OK) st = codec.unpack(C, coded.data() + map, coded.size() - map, d);
+            if (st == CSIC_OK && map) layer.inverse(layer, d, coded.data(), fr - L.frame_bytes, fr);
         }
     }
     if (st == CSIC_OK && (uint32_t)crc != stored)

@@ -18,37 +18,18 @@
 // has the group in registers before it stores.  Slots behind a plane's last sample take no part in the costs and are stored as zero
 // bits; the ragged group is loaded and stored byte by byte (pk_load_group, PkGroupOut).  Nothing is validated on the device and there
 // is nothing to clamp: any map bit decodes to valid codes.
-// Every global access goes through the accessors of csic_pack_common.h -- frames against frame_bytes -- and dt_map_* below -- maps
-// against map_bytes --, which the CSIC_DEBUG build checks.  CSIC_TUNE_NONTEMPORAL selects the accesses of the frames.
-#include "csic_pack_common.h"
+// Every global access goes through the accessors of csic_pack_common.h -- frames against frame_bytes -- and tp_map_* -- maps against
+// map_bytes --, which the CSIC_DEBUG build checks.  CSIC_TUNE_NONTEMPORAL selects the accesses of the frames.
+// Shared with csic_mc.hip, in csic_temporal_common.h: the argument (TpArgs), the frame and map accessors, the refusals and the filler
+// of the argument (tp_prepare); this unit keeps the run walk, the slot loops and the ballot.
+#include "csic_temporal_common.h"
 
 namespace csic {
 
-// PkArgs: bits = the source frames (k_delta reads, k_undelta writes); coded, ws, sizes and the coded frame's offsets are unused
-struct DtArgs : PkArgs {
-    uint8_t *diff;                 // difference frames, frame_bytes apart (k_delta writes, k_undelta reads)
-    uint8_t *maps;                 // maps, map_stride apart
-    int64_t map_stride, map_bytes;
-    uint32_t moff[3], mdw[3];      // byte offset and dwords of a plane's section of the map
-    int32_t nframes, gop;
-};
-
-__device__ __forceinline__ gpdst_t dt_frame(const DtArgs &a, uint8_t *first, uint32_t f) { return (gpdst_t)(uintptr_t)first + (int64_t)f * a.frame_bytes; }
-__device__ __forceinline__ gpdst_t dt_map(const DtArgs &a, uint32_t f) { return (gpdst_t)(uintptr_t)a.maps + (int64_t)f * a.map_stride; }
-// dword `dw` of a plane's section of a map
-__device__ __forceinline__ void dt_map_st4(const DtArgs &a, gpdst_t mb, int plane, uint32_t dw, uint32_t v)
-{
-    CSIC_CHECK(dw < a.mdw[plane]);
-    by_st4<false>(a.map_bytes, mb, (int64_t)a.moff[plane] + 4 * (int64_t)dw, v);
-}
-__device__ __forceinline__ uint32_t dt_map_ld4(const DtArgs &a, gpdst_t mb, int plane, uint32_t dw)
-{
-    CSIC_CHECK(dw < a.mdw[plane]);
-    return by_ld4<false>(a.map_bytes, mb, (int64_t)a.moff[plane] + 4 * (int64_t)dw);
-}
-
+// The slot loop fuses both costs -- of the codes, and of their differences against the previous frame's group -- in one pass (one
+// cut of c per slot, both candidates packed); k_mc_delta (csic_mc.hip) runs the same two loops apart, once per table entry.
 template <int Q, bool NT>
-__global__ void __launch_bounds__(PK_T) k_delta(DtArgs a)
+__global__ void __launch_bounds__(PK_T) k_delta(TpArgs a)
 {
     constexpr uint32_t MASK = (1u << Q) - 1u;
     const PkArgs &e = a;
@@ -65,7 +46,7 @@ __global__ void __launch_bounds__(PK_T) k_delta(DtArgs a)
         bool inter = false;
         if (mine) {
             uint32_t cur[Q];
-            pk_load_group<Q, NT>(e, dt_frame(a, a.bits, f), plane, g, cur);
+            pk_load_group<Q, NT>(e, tp_frame(a, a.bits, f), plane, g, cur);
             PkGroupOut<Q> oc, od;
             uint32_t cost_c = 0, cost_d = 0, pc = 0, pd = 0;
 #pragma unroll
@@ -84,17 +65,18 @@ __global__ void __launch_bounds__(PK_T) k_delta(DtArgs a)
             }
             inter = f > f0 && cost_d < cost_c;                              // a tie is intra
             if (inter) oc = od;
-            oc.template store<NT>(e, dt_frame(a, a.diff, f), plane, g);
+            oc.template store<NT>(e, tp_frame(a, a.diff, f), plane, g);
 #pragma unroll
             for (int i = 0; i < Q; ++i) prev[i] = cur[i];
         }
         const unsigned long long votes = __ballot(inter);
-        if ((t & 63u) < 2u && my_dw < a.mdw[plane]) dt_map_st4(a, dt_map(a, f), plane, my_dw, (uint32_t)(votes >> (32u * (t & 63u))));
+        if ((t & 63u) < 2u && my_dw < a.mdw[plane]) tp_map_st4(a, tp_map(a, f), plane, my_dw, (uint32_t)(votes >> (32u * (t & 63u))));
     }
 }
 
+// The add-back: k_delta's slot loop run the other way (same slots, same ragged-tail rule); k_mc_undelta's (csic_mc.hip) is the same.
 template <int Q, bool NT>
-__global__ void __launch_bounds__(PK_T) k_undelta(DtArgs a)
+__global__ void __launch_bounds__(PK_T) k_undelta(TpArgs a)
 {
     constexpr uint32_t MASK = (1u << Q) - 1u;
     const PkArgs &e = a;
@@ -107,8 +89,8 @@ __global__ void __launch_bounds__(PK_T) k_undelta(DtArgs a)
     for (int i = 0; i < Q; ++i) prev[i] = 0;
     for (uint32_t f = f0; f < f1; ++f) {
         uint32_t cur[Q];
-        pk_load_group<Q, NT>(e, dt_frame(a, a.diff, f), plane, g, cur);
-        const bool inter = f > f0 && ((dt_map_ld4(a, dt_map(a, f), plane, g >> 5) >> (g & 31u)) & 1u);   // a key frame's map is not read
+        pk_load_group<Q, NT>(e, tp_frame(a, a.diff, f), plane, g, cur);
+        const bool inter = f > f0 && ((tp_map_ld4(a, tp_map(a, f), plane, g >> 5) >> (g & 31u)) & 1u);   // a key frame's map is not read
         PkGroupOut<Q> out;
 #pragma unroll
         for (int j = 0; j < 32; ++j) {
@@ -117,7 +99,7 @@ __global__ void __launch_bounds__(PK_T) k_undelta(DtArgs a)
                 out.put(j, inter ? (d + pk_code<Q>(prev, j)) & MASK : d);
             }
         }
-        out.template store<NT>(e, dt_frame(a, a.bits, f), plane, g);
+        out.template store<NT>(e, tp_frame(a, a.bits, f), plane, g);
 #pragma unroll
         for (int i = 0; i < Q; ++i) prev[i] = out.d[i];
     }
@@ -129,35 +111,16 @@ __global__ void __launch_bounds__(PK_T) k_undelta(DtArgs a)
 static const auto delta_fn = [](auto q, auto nt) { return k_delta<CSIC_CONST(q), CSIC_CONST(nt)>; };
 static const auto undelta_fn = [](auto q, auto nt) { return k_undelta<CSIC_CONST(q), CSIC_CONST(nt)>; };
 
-// What both entry points refuse before any device is touched, then the arguments filled and one launch per run of planes of equal
-// width, grid z = the key-frame runs.
+// What both entry points refuse before any device is touched (tp_prepare), then one launch per run of planes of equal width, grid z =
+// the key-frame runs.
 template <class Choose>
 static int delta_call(csic_plan *plan, const void *d_frames, const void *d_diff, const void *d_maps, int32_t nframes, int32_t gop, void *hip_stream,
                       const char *entry, Choose choose)
 {
-    if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
-    if (!d_frames || !d_diff || !d_maps) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
     DeltaGeometry G;
-    int st = delta_geometry(&plan->p, &G);
-    if (st == CSIC_OK) st = delta_check_call(G, d_frames, d_diff, d_maps, nframes, gop);
+    TpArgs a;
+    int st = tp_prepare(plan, d_frames, d_diff, d_maps, nframes, gop, delta_geometry, true, 1, entry, &G, &a);
     if (st != CSIC_OK) return st;
-    if (((uintptr_t)d_frames | (uintptr_t)d_diff | (uintptr_t)d_maps) & 255u)
-        return set_error(CSIC_EINVAL_SIZE, "the frames, the difference frames and the maps must be 256-byte aligned");
-    DtArgs a;
-    const int64_t none[3] = {0, 0, 0};
-    st = pk_fill_args(plan, G.pk, none, none, 0, 0, entry, &a);
-    if (st != CSIC_OK) return st;
-    a.bits = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_frames));
-    a.diff = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_diff));
-    a.maps = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_maps));
-    a.map_stride = G.layout.map_stride;
-    a.map_bytes = G.layout.map_bytes;
-    for (int p = 0; p < 3; ++p) {
-        a.moff[p] = (uint32_t)G.layout.map_offset[p];
-        a.mdw[p] = (uint32_t)((G.layout.groups[p] + 31) / 32);
-    }
-    a.nframes = nframes;
-    a.gop = gop > nframes ? nframes : gop;                                  // (a run never passes the last frame: z gop + gop stays small)
     CSIC_DEVICE_SCOPE(plan->device);
     st = pk_launch_planes(plan, a, (nframes + a.gop - 1) / a.gop, static_cast<hipStream_t>(hip_stream), choose);
     if (st != CSIC_OK) return st;

@@ -1,7 +1,7 @@
 // csic_group_host.h -- what the host codecs of the group coding (csic_pack_host.cpp) and of the Rice coding (csic_rice_host.cpp) share,
 // header-only: the little-endian dword and bit-string accessors (csic_container.cpp uses the dwords too), the nibble read, the load of a
 // group with the ragged-tail rule and its folded residuals, the validation of a plane's nibble and anchors sections, and the body of the
-// extern "C" entry points.  The unfold u -> e is rice_unfold of csic_rice_decode.h, which the device codecs run as well.
+// extern "C" entry points.  The fold e -> u and the unfold u -> e are rice_fold and rice_unfold of csic_rice_decode.h.
 #pragma once
 #include <new>
 
@@ -38,7 +38,7 @@ inline int nibble_at(const unsigned char *nibbles, int64_t g) { return (nibbles[
 inline int load_group(const PackGeometry &G, const unsigned char *frame, int pl, int64_t g, uint32_t c[32], uint32_t u[32])
 {
     const int q = G.q[pl];
-    const uint32_t mask = (1u << q) - 1u, half = 1u << (q - 1);
+    const uint32_t mask = (1u << q) - 1u;
     for (int j = 0; j < 32; ++j) {
         const int64_t i = 32 * g + j;
         c[j] = i < G.n[pl] ? code_at(frame + G.src_offset[pl], G.src_bytes[pl], i, q) : c[j - 1];   // (i >= n only behind a real sample of this group)
@@ -46,8 +46,7 @@ inline int load_group(const PackGeometry &G, const unsigned char *frame, int pl,
     uint32_t any = 0;
     u[0] = 0;
     for (int j = 1; j < 32; ++j) {
-        const uint32_t e = (c[j] - c[j - 1]) & mask;
-        u[j] = e < half ? 2u * e : 2u * (mask + 1u - e) - 1u;
+        u[j] = rice_fold((c[j] - c[j - 1]) & mask, mask);
         any |= u[j];
     }
     int w = 0;

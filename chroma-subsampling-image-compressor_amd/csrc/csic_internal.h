@@ -67,13 +67,10 @@ int delta_geometry(const csic_params *p, DeltaGeometry *G);
 void delta_frame(const DeltaGeometry &G, const unsigned char *cur, const unsigned char *prev, unsigned char *diff, unsigned char *map);
 void undelta_frame(const DeltaGeometry &G, const unsigned char *diff, const unsigned char *map, const unsigned char *prev, unsigned char *cur);
 int delta_check_map(const DeltaGeometry &G, const unsigned char *map, bool key, int frame);
-// what the four csic_delta_* / csic_undelta_* entry points refuse (NULLs are the callers'): nframes, gop, and any overlap of the three
-// buffers other than diff == frames exactly
-int delta_check_call(const DeltaGeometry &G, const void *frames, const void *diff, const void *maps, int32_t nframes, int32_t gop);
 
 // csic_mc_host.cpp: the motion-compensated temporal layer (csic.h: csic_mc_*), the same for it.  mc_candidates writes the (2 range + 1)^2
-// candidates in rank order and returns their number; neither frame function works in place.  mc_check_call is delta_check_call without
-// the in-place exception, mc_check_range the refusal of a range outside 0..MC_MAX_RANGE.
+// candidates in rank order and returns their number; neither frame function works in place.  mc_check_range is the refusal of a range
+// outside 0..MC_MAX_RANGE.  What both layers refuse of a call is temporal_check_call of csic_temporal_host.h.
 constexpr int MC_MAX_RANGE = 7, MC_MAX_CANDIDATES = (2 * MC_MAX_RANGE + 1) * (2 * MC_MAX_RANGE + 1);
 constexpr int MC_TABLE_WORDS = 16, MC_TABLE_BYTES = 4 * MC_TABLE_WORDS;
 constexpr int MC_COUNTERS = 256;              // vote counters per frame and plane in the device codec's workspace (>= MC_MAX_CANDIDATES)
@@ -87,7 +84,6 @@ int mc_candidates(int range, McCandidate *out);
 void mc_delta_frame(const McGeometry &G, const unsigned char *cur, const unsigned char *prev, int range, unsigned char *diff, unsigned char *map);
 void mc_undelta_frame(const McGeometry &G, const unsigned char *diff, const unsigned char *map, const unsigned char *prev, unsigned char *cur);
 int mc_check_map(const McGeometry &G, const unsigned char *map, bool key, int frame);
-int mc_check_call(const McGeometry &G, const void *frames, const void *diff, const void *maps, int32_t nframes, int32_t gop);
 int mc_check_range(int32_t range);
 
 // Exact unsigned division by a run-time constant without a divide (k_generic's stream-index arithmetic): for

@@ -18,41 +18,32 @@
 //   k_mc_undelta<Q, NT> per group of frame run * gop + step; nothing is validated: a nibble reads one of the 16 words, a word clamps
 // mc_ref_group is the reference of one group under one displacement: where none of the 32 indices clamps and Q + 1 dwords lie inside the
 // plane, Q + 1 dwords from the unaligned bit offset and a funnel shift per dword; edge and ragged groups go sample by sample.
-// Invariants: every global access goes through the accessors of csic_pack_common.h -- frames against frame_bytes -- and mc_map_* /
-// mc_votes below -- maps against map_bytes, counters against their number --, which the CSIC_DEBUG build checks; the two sides of a call
+// Invariants: every global access goes through the accessors of csic_pack_common.h -- frames against frame_bytes --, tp_map_* /
+// mc_table_* -- maps against map_bytes, a dword against its section or table -- and mc_votes below -- counters against their number --,
+// which the CSIC_DEBUG build checks; the two sides of a call
 // never share memory (a group reads other groups of the previous frame).  CSIC_TUNE_NONTEMPORAL selects the accesses that stream (a
 // frame's own groups, the difference frames); the reference is read through the cache.  Design, bank layout, registers, measurements
 // and what is untuned: DESIGN.md section 4.12.
-#include "csic_pack_common.h"
+// Shared with csic_delta.hip, in csic_temporal_common.h: the argument's base (TpArgs), the frame and map accessors, the refusals and the
+// filler of the argument (tp_prepare); this unit keeps the search, the vote, the table, the displaced reference and its slot loops.
+#include "csic_temporal_common.h"
 
 namespace csic {
 
 constexpr int MC_ROW_DWORDS = 9, MC_WIN_DWORDS = (PK_T + 1) * MC_ROW_DWORDS;   // 256 rows and the 2 R codes behind them, in a row of their own
 static_assert(2 * MC_MAX_RANGE <= 32 && MC_MAX_CANDIDATES <= MC_COUNTERS && MC_COUNTERS <= PK_T, "the window's last row, the counters");
 
-// PkArgs: bits = the source frames (k_mc_search, k_mc_delta read; k_mc_undelta writes); coded, ws, sizes and the coded frame's offsets
-// are unused
-struct McArgs : PkArgs {
-    uint8_t *diff;                 // difference frames, frame_bytes apart (k_mc_delta writes, k_mc_undelta reads)
-    uint8_t *maps;                 // maps, map_stride apart
+struct McArgs : TpArgs {           // moff, mdw: a plane's nibble section
     uint32_t *votes;               // the workspace: [frame][plane][MC_COUNTERS]
-    int64_t map_stride, map_bytes;
-    uint32_t toff[3], moff[3], mdw[3];   // byte offset of a plane's table; byte offset and dwords of its nibble section
+    uint32_t toff[3];              // byte offset of a plane's table
     int32_t width[3];              // w_p
-    int32_t nframes, gop, range;
+    int32_t range;
     int32_t step;                  // k_mc_undelta: the frame of a run this launch decodes
 };
 
-__device__ __forceinline__ gpdst_t mc_frame(const McArgs &a, uint8_t *first, uint32_t f) { return (gpdst_t)(uintptr_t)first + (int64_t)f * a.frame_bytes; }
-__device__ __forceinline__ gpdst_t mc_map(const McArgs &a, uint32_t f) { return (gpdst_t)(uintptr_t)a.maps + (int64_t)f * a.map_stride; }
-__device__ __forceinline__ void mc_map_st4(const McArgs &a, gpdst_t mb, int64_t off, uint32_t v) { by_st4<false>(a.map_bytes, mb, off, v); }
-__device__ __forceinline__ uint32_t mc_map_ld4(const McArgs &a, gpdst_t mb, int64_t off) { return by_ld4<false>(a.map_bytes, mb, off); }
 // word t of a plane's table
-__device__ __forceinline__ uint32_t mc_table_word(const McArgs &a, gpdst_t mb, int plane, uint32_t t)
-{
-    CSIC_CHECK(t < (uint32_t)MC_TABLE_WORDS);
-    return mc_map_ld4(a, mb, (int64_t)a.toff[plane] + 4 * (int64_t)t);
-}
+__device__ __forceinline__ uint32_t mc_table_word(const McArgs &a, gpdst_t mb, int plane, uint32_t t) { return tp_map_word_ld4(a, mb, a.toff[plane], MC_TABLE_WORDS, t); }
+__device__ __forceinline__ void mc_table_st4(const McArgs &a, gpdst_t mb, int plane, uint32_t t, uint32_t v) { tp_map_word_st4(a, mb, a.toff[plane], MC_TABLE_WORDS, t, v); }
 // counter k of a frame's plane
 __device__ __forceinline__ gout_t mc_votes(const McArgs &a, uint32_t f, int plane, uint32_t k)
 {
@@ -97,6 +88,8 @@ template <int Q> __device__ __forceinline__ void mc_ref_group(const PkArgs &e, g
     }
 }
 
+// The pricing loop is k_mc_delta's loop of the differences without the packing; its reference is a row of the LDS window, one code
+// to a byte, not a group's dwords.
 template <int Q, bool NT>
 __global__ void __launch_bounds__(PK_T) k_mc_search(McArgs a)
 {
@@ -109,13 +102,13 @@ __global__ void __launch_bounds__(PK_T) k_mc_search(McArgs a)
     const bool mine = g < G;                                                // lanes behind the last group stay for the stage
     const int64_t n = e.n[plane];
     const int R = a.range, w = a.width[plane];
-    const gpdst_t pf = mc_frame(a, a.bits, f - 1u);
+    const gpdst_t pf = tp_frame(a, a.bits, f - 1u);
     const uint8_t *s_codes = reinterpret_cast<const uint8_t *>(s_win);
     if (t < (uint32_t)MC_COUNTERS) s_hist[t] = 0;
     uint32_t cur[Q];
 #pragma unroll
     for (int i = 0; i < Q; ++i) cur[i] = 0;
-    if (mine) pk_load_group<Q, NT>(e, mc_frame(a, a.bits, f), plane, g, cur);
+    if (mine) pk_load_group<Q, NT>(e, tp_frame(a, a.bits, f), plane, g, cur);
     uint32_t best_cost = ~0u, best_key = ~0u, best_at = 0;
     for (int dy = -R; dy <= R; ++dy) {                                      // block-uniform
         __syncthreads();                                                    // the window before is read (first: s_hist is zero)
@@ -199,7 +192,7 @@ __global__ void __launch_bounds__(64) k_mc_table(McArgs a)
         }
         if (lane == 0u) word = T;
     }
-    if (lane < (uint32_t)MC_TABLE_WORDS) mc_map_st4(a, mc_map(a, f), (int64_t)a.toff[plane] + 4 * (int64_t)lane, word);
+    if (lane < (uint32_t)MC_TABLE_WORDS) mc_table_st4(a, tp_map(a, f), plane, lane, word);
 }
 
 template <int Q, bool NT>
@@ -211,11 +204,11 @@ __global__ void __launch_bounds__(PK_T) k_mc_delta(McArgs a)
     const uint32_t G = e.groups[plane], g0 = blockIdx.x * PK_T, t = threadIdx.x, g = g0 + t, f = blockIdx.z;
     if (g0 >= G) return;                                                    // block-uniform
     const int64_t n = e.n[plane];
-    const gpdst_t mb = mc_map(a, f);
+    const gpdst_t mb = tp_map(a, f);
     uint32_t nib = 0;
     if (g < G) {                                                            // lanes behind the last group stay for the shuffles
         uint32_t cur[Q];
-        pk_load_group<Q, NT>(e, mc_frame(a, a.bits, f), plane, g, cur);
+        pk_load_group<Q, NT>(e, tp_frame(a, a.bits, f), plane, g, cur);
         PkGroupOut<Q> out;
         uint32_t cost_c = 0, pc = 0;
 #pragma unroll
@@ -228,7 +221,7 @@ __global__ void __launch_bounds__(PK_T) k_mc_delta(McArgs a)
             }
         }
         if (f % (uint32_t)a.gop != 0u) {
-            const gpdst_t pf = mc_frame(a, a.bits, f - 1u);
+            const gpdst_t pf = tp_frame(a, a.bits, f - 1u);
             const uint32_t T = min(mc_table_word(a, mb, plane, 0), (uint32_t)MC_TABLE_WORDS - 1u);   // (k_mc_table wrote 1 .. 15)
             uint32_t best = ~0u, best_t = 0;
             PkGroupOut<Q> keep;
@@ -258,14 +251,15 @@ __global__ void __launch_bounds__(PK_T) k_mc_delta(McArgs a)
                 out = keep;
             }
         }
-        out.template store<NT>(e, mc_frame(a, a.diff, f), plane, g);
+        out.template store<NT>(e, tp_frame(a, a.diff, f), plane, g);
     }
     uint32_t v = nib;
 #pragma unroll
     for (int k = 1; k < 8; ++k) v |= (uint32_t)__shfl_down((int)nib, k, 64) << (4 * k);   // (lanes 8 i .. 8 i + 7 are in one wave)
-    if ((t & 7u) == 0u && (g >> 3) < a.mdw[plane]) mc_map_st4(a, mb, (int64_t)a.moff[plane] + 4 * (int64_t)(g >> 3), v);
+    if ((t & 7u) == 0u && (g >> 3) < a.mdw[plane]) tp_map_st4(a, mb, plane, g >> 3, v);
 }
 
+// The add-back: the loop of the differences run the other way (same slots, same ragged-tail rule), as in k_undelta (csic_delta.hip).
 template <int Q, bool NT>
 __global__ void __launch_bounds__(PK_T) k_mc_undelta(McArgs a)
 {
@@ -276,13 +270,12 @@ __global__ void __launch_bounds__(PK_T) k_mc_undelta(McArgs a)
     if (g >= G || f >= (uint32_t)a.nframes) return;
     const int64_t n = e.n[plane];
     uint32_t cur[Q], r[Q];
-    pk_load_group<Q, NT>(e, mc_frame(a, a.diff, f), plane, g, cur);
+    pk_load_group<Q, NT>(e, tp_frame(a, a.diff, f), plane, g, cur);
     uint32_t nib = 0;
     if (a.step > 0) {                                                       // a key frame's map is not read
-        const gpdst_t mb = mc_map(a, f);
-        CSIC_CHECK((g >> 3) < a.mdw[plane]);
-        nib = (mc_map_ld4(a, mb, (int64_t)a.moff[plane] + 4 * (int64_t)(g >> 3)) >> (4u * (g & 7u))) & 15u;
-        if (nib) mc_ref_group<Q>(e, mc_frame(a, a.bits, f - 1u), plane, 32 * (int64_t)g + (int32_t)mc_table_word(a, mb, plane, nib), r);
+        const gpdst_t mb = tp_map(a, f);
+        nib = (tp_map_ld4(a, mb, plane, g >> 3) >> (4u * (g & 7u))) & 15u;
+        if (nib) mc_ref_group<Q>(e, tp_frame(a, a.bits, f - 1u), plane, 32 * (int64_t)g + (int32_t)mc_table_word(a, mb, plane, nib), r);
     }
     if (!nib) {
 #pragma unroll
@@ -292,7 +285,7 @@ __global__ void __launch_bounds__(PK_T) k_mc_undelta(McArgs a)
 #pragma unroll
     for (int j = 0; j < 32; ++j)
         if (32 * (int64_t)g + j < n) out.put(j, (pk_code<Q>(cur, j) + pk_code<Q>(r, j)) & MASK);
-    out.template store<NT>(e, mc_frame(a, a.bits, f), plane, g);
+    out.template store<NT>(e, tp_frame(a, a.bits, f), plane, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -302,34 +295,17 @@ static const auto mc_search_fn = [](auto q, auto nt) { return k_mc_search<CSIC_C
 static const auto mc_delta_fn = [](auto q, auto nt) { return k_mc_delta<CSIC_CONST(q), CSIC_CONST(nt)>; };
 static const auto mc_undelta_fn = [](auto q, auto nt) { return k_mc_undelta<CSIC_CONST(q), CSIC_CONST(nt)>; };
 
-// What both entry points refuse before any device is touched, then the arguments filled.
+// What both entry points refuse before any device is touched and the common arguments (tp_prepare), then this layer's own.
 static int mc_prepare(csic_plan *plan, const void *d_frames, const void *d_diff, const void *d_maps, int32_t nframes, int32_t gop, const char *entry,
                       McGeometry *G, McArgs *a)
 {
-    if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
-    if (!d_frames || !d_diff || !d_maps) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
-    int st = mc_geometry(&plan->p, G);
-    if (st == CSIC_OK) st = mc_check_call(*G, d_frames, d_diff, d_maps, nframes, gop);
+    const int st = tp_prepare(plan, d_frames, d_diff, d_maps, nframes, gop, mc_geometry, false, 4, entry, G, a);
     if (st != CSIC_OK) return st;
-    if (((uintptr_t)d_frames | (uintptr_t)d_diff | (uintptr_t)d_maps) & 255u)
-        return set_error(CSIC_EINVAL_SIZE, "the frames, the difference frames and the maps must be 256-byte aligned");
-    const int64_t none[3] = {0, 0, 0};
-    st = pk_fill_args(plan, G->pk, none, none, 0, 0, entry, a);
-    if (st != CSIC_OK) return st;
-    a->bits = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_frames));
-    a->diff = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_diff));
-    a->maps = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_maps));
     a->votes = nullptr;
-    a->map_stride = G->layout.map_stride;
-    a->map_bytes = G->layout.map_bytes;
     for (int p = 0; p < 3; ++p) {
         a->toff[p] = (uint32_t)G->layout.table_offset[p];
-        a->moff[p] = (uint32_t)G->layout.map_offset[p];
-        a->mdw[p] = (uint32_t)((G->layout.groups[p] + 7) / 8);
         a->width[p] = (int32_t)G->layout.width[p];
     }
-    a->nframes = nframes;
-    a->gop = gop > nframes ? nframes : gop;                                 // (a run never passes the last frame: z gop + step stays small)
     a->range = 0;
     a->step = 0;
     return CSIC_OK;

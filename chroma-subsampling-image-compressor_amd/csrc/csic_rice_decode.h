@@ -4,7 +4,8 @@
 // frame, tests/cpp/rice_fuzz.cpp on exactly-sized heap blocks of random bytes under the sanitizers.  Nothing here trusts the bits: every
 // word index is compared with nwords first (a word behind the segment reads as 0), a unary run ends at `uend` at the latest, and every
 // loop is bounded by the segment's length.  rice_unfold, the inverse of the fold of a residual, is the one definition for both codings:
-// the group coding's codecs (csic_pack.hip, csic_pack_host.cpp) call it as well.
+// the group coding's codecs (csic_pack.hip, csic_pack_host.cpp) call it as well; rice_fold is the host codecs' one statement of the fold
+// (csic_group_host.h's load_group, csic_temporal_host.h's group_cost).
 #pragma once
 #include <cstdint>
 
@@ -93,7 +94,9 @@ CSIC_RICE_HD uint32_t rice_next_u(const uint32_t *seg, uint32_t nwords, uint32_t
     return u & ((1u << q) - 1u);
 }
 
-// a folded residual u -> e, the difference to the code before, modulo mask + 1
+// a difference e to the code before, modulo mask + 1 -> its folded, centred residual u (the host codecs' one statement of the fold)
+CSIC_RICE_HD uint32_t rice_fold(uint32_t e, uint32_t mask) { return e <= (mask >> 1) ? 2u * e : 2u * (mask + 1u - e) - 1u; }
+// a folded residual u -> e, the inverse
 CSIC_RICE_HD uint32_t rice_unfold(uint32_t u, uint32_t mask) { return ((u & 1u) ? ~(u >> 1) : (u >> 1)) & mask; }
 
 } // namespace csic

@@ -221,25 +221,25 @@ inline csic_delta_layout deltaLayout(const csic_params &p)
     check(csic_delta_layout_of(&p, &layout));
     return layout;
 }
-inline DeltaFrames delta(const csic_params &p, const void *frames, int nframes, int gop)
+// nframes zeroed frame buffers of these parameters: the buffer both layers' host codecs write frames or difference frames into
+inline std::vector<uint8_t> zeroedFrames(const csic_params &p, int nframes)
 {
     csic_params q = p;
     q.out_format = CSIC_FMT_PLANAR_BITS;
     csic_planar_bits_layout layout;
     check(csic_planar_bits_layout_of(&q, &layout));
-    DeltaFrames d;
-    d.diff.assign((size_t)(nframes > 0 ? nframes : 0) * (size_t)layout.frame_bytes, 0);
+    return std::vector<uint8_t>((size_t)(nframes > 0 ? nframes : 0) * (size_t)layout.frame_bytes, 0);
+}
+inline DeltaFrames delta(const csic_params &p, const void *frames, int nframes, int gop)
+{
+    DeltaFrames d{zeroedFrames(p, nframes), {}};
     d.maps.assign((size_t)(nframes > 0 ? nframes : 0) * (size_t)deltaLayout(p).map_stride, 0);
     check(csic_delta_host(&p, frames, nframes, gop, d.diff.data(), d.maps.data()));
     return d;
 }
 inline std::vector<uint8_t> undelta(const csic_params &p, const void *diff, const void *maps, int nframes, int gop)
 {
-    csic_params q = p;
-    q.out_format = CSIC_FMT_PLANAR_BITS;
-    csic_planar_bits_layout layout;
-    check(csic_planar_bits_layout_of(&q, &layout));
-    std::vector<uint8_t> frames((size_t)(nframes > 0 ? nframes : 0) * (size_t)layout.frame_bytes, 0);
+    std::vector<uint8_t> frames = zeroedFrames(p, nframes);
     check(csic_undelta_host(&p, diff, maps, nframes, gop, frames.data()));
     return frames;
 }
@@ -253,23 +253,14 @@ inline csic_mc_layout mcLayout(const csic_params &p)
 }
 inline DeltaFrames mcDelta(const csic_params &p, const void *frames, int nframes, int gop, int range)
 {
-    csic_params q = p;
-    q.out_format = CSIC_FMT_PLANAR_BITS;
-    csic_planar_bits_layout layout;
-    check(csic_planar_bits_layout_of(&q, &layout));
-    DeltaFrames d;
-    d.diff.assign((size_t)(nframes > 0 ? nframes : 0) * (size_t)layout.frame_bytes, 0);
+    DeltaFrames d{zeroedFrames(p, nframes), {}};
     d.maps.assign((size_t)(nframes > 0 ? nframes : 0) * (size_t)mcLayout(p).map_stride, 0);
     check(csic_mc_delta_host(&p, frames, nframes, gop, range, d.diff.data(), d.maps.data()));
     return d;
 }
 inline std::vector<uint8_t> mcUndelta(const csic_params &p, const void *diff, const void *maps, int nframes, int gop)
 {
-    csic_params q = p;
-    q.out_format = CSIC_FMT_PLANAR_BITS;
-    csic_planar_bits_layout layout;
-    check(csic_planar_bits_layout_of(&q, &layout));
-    std::vector<uint8_t> frames((size_t)(nframes > 0 ? nframes : 0) * (size_t)layout.frame_bytes, 0);
+    std::vector<uint8_t> frames = zeroedFrames(p, nframes);
     check(csic_mc_undelta_host(&p, diff, maps, nframes, gop, frames.data()));
     return frames;
 }
