@@ -695,7 +695,7 @@ def test_avg_extension_wide_ragged_rows(csic, oracle, W, H):
     import torch
     n = 3
     host = oracle.synth_frame(n * W * H, W + 7 * H)
-    for (a, b), f in itertools.product([(4, 4), (2, 2), (2, 0), (1, 1), (1, 0)], (1, 2, 4, 8)):
+    for (a, b), f in itertools.product([(4, 4), (2, 2), (2, 0), (1, 1), (1, 0), (4, 0)], (1, 2, 4, 8)):
         wants = [oracle.process(_oparams(oracle, W, H, a, b, (8, 7, 6), f), host[k * W * H:(k + 1) * W * H], form="avg") for k in range(n)]
         with _avg_plan(csic, W, H, a, b, (8, 7, 6), f) as pl:
             assert pl.kernel_name.startswith("k_avg<"), pl.kernel_name
