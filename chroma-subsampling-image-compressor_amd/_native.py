@@ -30,6 +30,7 @@ SSIM_WINDOW, SSIM_ONE = 8, 65536        # csic_ssim_*: window edge in pixels, SS
 STATS_KINDS, STATS_PLANES, STATS_BINS = 2, 3, 256     # csic_code_stats_*: codes / residuals; Y, Cb, Cr; bins per histogram
 CODING_RAW, CODING_GROUPS = 0, 1        # csic_pack_* / .csic: the planes as they are (version 1), group-coded (version 3)
 CODING_RICE = 3                         # csic_rice_* / .csic version 4: Rice-coded (id 2 was never written)
+CODING_RANS = 5                         # csic_rans_* / .csic version 7: rANS-coded (id 4 was never written)
 
 
 class IllegalArgumentException(ValueError):
@@ -92,6 +93,11 @@ class CsicPackLayout(C.Structure):
 
 class CsicRiceLayout(C.Structure):
     _fields_ = [("groups", C.c_int64 * 3), ("blocks", C.c_int64 * 3), ("modes_offset", C.c_int64 * 3), ("anchors_offset", C.c_int64 * 3),
+                ("directory_offset", C.c_int64), ("payload_offset", C.c_int64), ("fixed_bytes", C.c_int64), ("bound_bytes", C.c_int64)]
+
+
+class CsicRansLayout(C.Structure):
+    _fields_ = [("groups", C.c_int64 * 3), ("blocks", C.c_int64 * 3), ("tables_offset", C.c_int64 * 3), ("anchors_offset", C.c_int64 * 3),
                 ("directory_offset", C.c_int64), ("payload_offset", C.c_int64), ("fixed_bytes", C.c_int64), ("bound_bytes", C.c_int64)]
 
 
@@ -171,6 +177,13 @@ PROTOTYPES = {
     "csic_rice_pack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "csic_rice_unpack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "csic_rice_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "csic_rans_layout_of": (C.c_int, [C.POINTER(CsicParams), C.POINTER(CsicRansLayout)]),
+    "csic_rans_pack_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "csic_rans_unpack_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "csic_rans_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
+    "csic_rans_pack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "csic_rans_unpack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "csic_rans_kernel_name": (C.c_char_p, [C.c_void_p]),
     "csic_delta_layout_of": (C.c_int, [C.POINTER(CsicParams), C.POINTER(CsicDeltaLayout)]),
     "csic_delta_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "csic_undelta_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),

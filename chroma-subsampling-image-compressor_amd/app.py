@@ -10,8 +10,8 @@ HIP launch.
 
 Two leading verbs go past what the reference's app does (it only ever writes the reconstructed pixels as a PNG):
 
-    python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ... [--coding raw|groups|rice]
-    python -m csic_amd.app compress   --inputs a.png,b.png,... --gop K [--motion R] --coding groups|rice --output x.csic ...
+    python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ... [--coding raw|groups|rice|rans]
+    python -m csic_amd.app compress   --inputs a.png,b.png,... --gop K [--motion R] --coding groups|rice|rans --output x.csic ...
     python -m csic_amd.app decompress --input x.csic --output x.png [--frame K | --output-pattern frame_%03d.png]
 
     python -m csic_amd.app inspect    --input x.csic
@@ -34,7 +34,7 @@ import numpy as np
 
 from .compressor import ImageCompressorTop, Plan
 from . import _native as N
-from .container import (container_coded_sizes, container_info, container_inter_groups, delta_layout, mc_layout, read_container, write_container,
+from .container import (container_coded_sizes, container_info, container_inter_groups, delta_layout, mc_layout, rans_layout, read_container, write_container,
                         write_container_coded)
 from .model import Image, ImageProcessorModel
 from .params import PixelFormat, ProcessingStep, Sampling
@@ -94,9 +94,9 @@ class ImageCompressionApp:
                       op1: ProcessingStep, op2: ProcessingStep, op3: ProcessingStep,
                       sampling: Sampling = Sampling.HOLD_DECIMATE, *, device: int = 0, coding: str = "raw") -> int:
         """PNG -> CSIC_FMT_PLANAR_BITS plan -> .csic container.  Returns the bytes written (coding "raw": 80 + payload_bytes;
-        "groups" / "rice": the frame is coded on the device and goes out through csic_container_write_coded_ex)."""
-        if coding not in ("raw", "groups", "rice"):
-            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: --coding must be raw, groups or rice, got {coding!r}")
+        "groups" / "rice" / "rans": the frame is coded on the device and goes out through csic_container_write_coded_ex)."""
+        if coding not in ("raw", "groups", "rice", "rans"):
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: --coding must be rans, raw, groups or rice, got {coding!r}")
         inputImage = ImageProcessorModel.readImage(inputImagePath)
         top = ImageCompressorTop(inputImage.width, inputImage.height, chromaParamA, chromaParamB, yTargetBits, cbTargetBits,
                                  crTargetBits, spatialFactorToUse, op1, op2, op3, device=device, sampling=sampling)
@@ -106,7 +106,7 @@ class ImageCompressionApp:
             if coding != "raw":
                 import torch
                 d_in = torch.from_numpy(np.ascontiguousarray(inputImage.argb, dtype=np.uint32).reshape(-1).view(np.int32)).to(f"cuda:{device}")
-                pack = plan.pack_device if coding == "groups" else plan.rice_pack_device
+                pack = {"groups": plan.pack_device, "rice": plan.rice_pack_device, "rans": plan.rans_pack_device}[coding]
                 coded, sizes = pack(plan.process_device(d_in))
                 write_container_coded(outputPath, plan.c_params, coded.cpu().numpy(), sizes.cpu().numpy(), coding=coding)
             else:
@@ -125,9 +125,10 @@ class ImageCompressionApp:
                          sampling: Sampling = Sampling.HOLD_DECIMATE, *, device: int = 0, coding: str = "rice", gop: int = 16,
                          motion: Optional[int] = None) -> int:
         """PNGs of equal size -> one CSIC_FMT_PLANAR_BITS plan -> csic_delta_device -> the device coder -> a version-5 .csic container
-        (csic_container_write_coded_seq); with a `motion` range csic_mc_delta_device and version 6.  Returns the bytes written."""
-        if coding not in ("groups", "rice"):
-            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: a sequence takes --coding groups or rice, got {coding!r}")
+        (csic_container_write_coded_seq); with a `motion` range csic_mc_delta_device and version 6; coding "rans": version 7 either way.
+        Returns the bytes written."""
+        if coding not in ("groups", "rice", "rans"):
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: a sequence takes --coding rans, groups or rice, got {coding!r}")
         paths = list(inputImagePaths)
         if not paths:
             raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: no input image")
@@ -147,7 +148,7 @@ class ImageCompressionApp:
             d_in = torch.from_numpy(argb.reshape(-1).view(np.int32)).to(f"cuda:{device}")
             bits = plan.process_device(d_in, None, n).reshape(n, plan.frame_bytes)
             diff, maps = plan.delta_device(bits, n, gop) if motion is None else plan.mc_delta_device(bits, n, gop, motion)
-            pack = plan.pack_device if coding == "groups" else plan.rice_pack_device
+            pack = {"groups": plan.pack_device, "rice": plan.rice_pack_device, "rans": plan.rans_pack_device}[coding]
             coded, sizes = pack(diff, n)
             write_container_coded(outputPath, plan.c_params, coded.cpu().numpy(), sizes.cpu().numpy(), coding=coding, maps=maps.cpu().numpy(), gop=gop,
                                   motion=motion)
@@ -261,7 +262,7 @@ def _args_map(args: List[str]) -> Dict[str, str]:
 
 def _main_container(verb: str, args: List[str]) -> int:
     """`compress` / `decompress`: the keys of the verb-less CLI with its defaults, plus --output and (compress) --sampling avg and
-    --coding raw|groups|rice."""
+    --coding raw|groups|rice|rans."""
     argsMap = _args_map(args)
     if verb == "compress" and "--inputs" in argsMap:
         return _main_sequence(argsMap)
@@ -285,8 +286,8 @@ def _main_container(verb: str, args: List[str]) -> int:
         return 0
     sampling = Sampling.AVG if argsMap.get("--sampling", "hold").lower() == "avg" else Sampling.HOLD_DECIMATE
     coding = argsMap.get("--coding", "raw").lower()
-    if coding not in ("raw", "groups", "rice"):
-        print(f"[ERROR] --coding must be raw, groups or rice, got {coding}")
+    if coding not in ("raw", "groups", "rice", "rans"):
+        print(f"[ERROR] --coding must be rans, raw, groups or rice, got {coding}")
         return 2
     size = ImageCompressionApp.compressImage(
         inputPath, outputPath, int(argsMap.get("--a", "4")), int(argsMap.get("--b", "4")), int(argsMap.get("--yq", "8")),
@@ -298,7 +299,7 @@ def _main_container(verb: str, args: List[str]) -> int:
 
 
 def _main_sequence(argsMap: Dict[str, str]) -> int:
-    """`compress --inputs a.png,b.png,... --gop K --coding groups|rice --output x.csic`: frames of equal size as one version-5 container."""
+    """`compress --inputs a.png,b.png,... --gop K --coding groups|rice|rans --output x.csic`: frames of equal size as one version-5 container (--motion: 6; rans: 7)."""
     if "--output" not in argsMap:
         print("[ERROR] compress needs --inputs and --output")
         return 2
@@ -308,8 +309,8 @@ def _main_sequence(argsMap: Dict[str, str]) -> int:
             print(f"[ERROR] Input not found: {p}")
             return 1
     coding = argsMap.get("--coding", "rice").lower()
-    if coding not in ("groups", "rice") or not paths:
-        print(f"[ERROR] a sequence needs at least one input and --coding groups or rice, got {coding}")
+    if coding not in ("groups", "rice", "rans") or not paths:
+        print(f"[ERROR] a sequence needs at least one input and --coding rans, groups or rice, got {coding}")
         return 2
     sampling = Sampling.AVG if argsMap.get("--sampling", "hold").lower() == "avg" else Sampling.HOLD_DECIMATE
     size = ImageCompressionApp.compressSequence(
@@ -376,6 +377,22 @@ def _main_inspect(args: List[str]) -> int:
                             cells.append(f"{_vector_of(int(words[t]), w, info.motion)} {np.count_nonzero(nib == t) / G:.3f}")
                         print(f"    {name} table: " + ", ".join(cells))
                 at += int(stored)
+    elif info.version == 7:
+        with open(inputPath, "rb") as fh:
+            fh.seek(84)
+            gop = int.from_bytes(fh.read(4), "little")         # 0: every frame stands alone
+            layer = "" if gop == 0 else f", temporal delta with gop {gop}" if info.motion < 0 else f", motion-compensated delta with gop {gop}, range {info.motion}"
+            print(f"Frame coding: rans{layer}")
+            sizes = container_coded_sizes(inputPath)
+            for k, stored in enumerate(sizes):
+                kind = "" if gop == 0 else " (key)" if k % gop == 0 else " (delta)"
+                print(f"  frame {k}{kind}: stored in {int(stored)} bytes, {int(stored) / info.payload_bytes:.4f} of raw")
+            rl = rans_layout(p)                                 # frame 0 is a key frame: its record is its coded frame
+            fh.seek(88 + 8 * info.nframes + rl.directory_offset)
+            directory = np.frombuffer(fh.read(4 * (sum(rl.blocks) + 1)), dtype="<u4")
+            for i, name in enumerate(("Y", "Cb", "Cr")):
+                b0 = sum(rl.blocks[:i])
+                print(f"    frame 0, {name}: {int(np.count_nonzero(directory[b0:b0 + rl.blocks[i]] >> 31))} of {rl.blocks[i]} blocks raw")
     else:
         print(f"Frame coding: {({3: 'groups', 4: 'rice'}).get(info.version, 'raw')}")
         for k, stored in enumerate(container_coded_sizes(inputPath)):

@@ -19,8 +19,8 @@ from typing import Tuple
 import numpy as np
 
 from . import _native as N
-from .container import (delta_host, delta_layout, mc_delta_host, mc_layout, mc_undelta_host, pack_frame_host, rice_pack_host, rice_unpack_host,
-                        undelta_host, unpack_frame_host)
+from .container import (delta_host, delta_layout, mc_delta_host, mc_layout, mc_undelta_host, pack_frame_host, rans_pack_host, rans_unpack_host,
+                        rice_pack_host, rice_unpack_host, undelta_host, unpack_frame_host)
 from .params import (ImageProcessorParams, PixelFormat, ProcessingStep, Rounding, Sampling, make_c_params)
 
 
@@ -519,6 +519,41 @@ class Plan:
     def rice_unpack(self, coded, out=None) -> np.ndarray:
         """csic_rice_unpack_host: Rice-coded bytes -> a PLANAR_BITS frame buffer."""
         return rice_unpack_host(self.c_params, coded, out)
+
+    # -- lossless rANS coding of PLANAR_BITS frames (csic_rans_*) ---------------------------------------
+    @property
+    def rans_layout(self) -> N.CsicRansLayout:
+        """csic_rans_layout of these parameters: groups, blocks, section offsets, fixed_bytes, bound_bytes."""
+        lay = N.CsicRansLayout()
+        N.check(N.lib().csic_rans_layout_of(C.byref(self.c_params), C.byref(lay)))
+        return lay
+
+    @property
+    def rans_kernel_name(self) -> str:
+        return N.lib().csic_rans_kernel_name(self._h).decode()
+
+    def rans_workspace_bytes(self, nframes: int = 1) -> int:
+        b = C.c_size_t()
+        N.check(N.lib().csic_rans_workspace_bytes(self._h, int(nframes), C.byref(b)))
+        return b.value
+
+    def rans_pack_device(self, d_bits, nframes: int = 1, d_coded=None):
+        """As pack_device, in the rANS coding: returns (coded, sizes), a uint8 tensor (nframes, rans_layout.bound_bytes) whose row k
+        holds frame k's coded bytes in [0, sizes[k]), and an int64 tensor of the sizes.  Asynchronous on torch's current stream."""
+        return self._pack_device(d_bits, nframes, d_coded, self.rans_layout.bound_bytes, self.rans_workspace_bytes, N.lib().csic_rans_pack_device)
+
+    def rans_unpack_device(self, d_coded, nframes: int = 1, d_bits=None):
+        """The inverse of rans_pack_device, one pass without a workspace.  The device does not validate: check untrusted bytes with
+        rans_unpack() first."""
+        return self._unpack_device(d_coded, nframes, d_bits, self.rans_layout.bound_bytes, None, N.lib().csic_rans_unpack_device)
+
+    def rans_pack(self, bits_frame) -> np.ndarray:
+        """csic_rans_pack_host: one PLANAR_BITS frame buffer in host memory -> its rANS-coded bytes.  Needs no GPU."""
+        return rans_pack_host(self.c_params, bits_frame)
+
+    def rans_unpack(self, coded, out=None) -> np.ndarray:
+        """csic_rans_unpack_host: rANS-coded bytes -> a PLANAR_BITS frame buffer."""
+        return rans_unpack_host(self.c_params, coded, out)
 
     # -- temporal delta coding of sequences of PLANAR_BITS frames (csic_delta_*) -------------------------
     @property

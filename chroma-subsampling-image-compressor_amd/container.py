@@ -1,6 +1,6 @@
 """.csic files: CSIC_FMT_PLANAR_BITS frames on disk (csic_container_*; byte layout in include/csic.h), raw (version 1), group-coded
-(version 3), Rice-coded (version 4) or as a sequence through the temporal layer (version 5), the host codecs of both codings
-(csic_pack_host / csic_unpack_host, csic_rice_pack_host / csic_rice_unpack_host) and the host codec of the temporal layer
+(version 3), Rice-coded (version 4), rANS-coded (version 7) or as a sequence through the temporal layer (versions 5, 6, 7), the host
+codecs of the three codings (csic_pack_host / csic_unpack_host, csic_rice_*_host, csic_rans_*_host) and the host codec of the temporal layer
 (csic_delta_host / csic_undelta_host).  Host only: nothing here needs a GPU."""
 from __future__ import annotations
 
@@ -22,7 +22,7 @@ def container_info(path: str) -> N.CsicContainerInfo:
     N.check(N.lib().csic_container_gop(os.fsencode(path), C.byref(gop)))
     info.gop = gop.value                              # csic_container_gop: 1 below version 5 (every frame stands alone)
     info.coding = {1: N.CODING_RAW, 3: N.CODING_GROUPS, 4: N.CODING_RICE}.get(info.version)
-    if info.coding is None:                           # version 5 names its coding in the word behind the parameters (checked: 1 or 3)
+    if info.coding is None:                           # versions 5, 6, 7 name their coding in the word behind the parameters (checked by the library)
         with open(path, "rb") as fh:
             fh.seek(80)
             info.coding = int.from_bytes(fh.read(4), "little") & 0xFF      # (version 6 keeps its range + 1 in bits 8..)
@@ -44,9 +44,9 @@ def _bits_params(c_params: N.CsicParams):
 
 def _coding(coding) -> int:
     if isinstance(coding, str):
-        names = {"raw": N.CODING_RAW, "groups": N.CODING_GROUPS, "rice": N.CODING_RICE}
+        names = {"raw": N.CODING_RAW, "groups": N.CODING_GROUPS, "rice": N.CODING_RICE, "rans": N.CODING_RANS}
         if coding.lower() not in names:
-            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: coding must be 'raw', 'groups' or 'rice', got {coding!r}")
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: coding must be 'raw', 'groups', 'rice' or 'rans', got {coding!r}")
         return names[coding.lower()]
     return int(coding)
 
@@ -110,6 +110,23 @@ def rice_pack_host(c_params: N.CsicParams, bits_frame) -> np.ndarray:
 def rice_unpack_host(c_params: N.CsicParams, coded, out=None) -> np.ndarray:
     """csic_rice_unpack_host: Rice-coded bytes -> a PLANAR_BITS frame buffer, as unpack_frame_host.  Damaged input raises CsicIOError."""
     return _unpack_host(c_params, coded, out, N.lib().csic_rice_unpack_host)
+
+
+def rans_layout(c_params: N.CsicParams) -> N.CsicRansLayout:
+    """csic_rans_layout_of: groups, blocks, section offsets, fixed_bytes and bound_bytes of a rANS-coded frame of these parameters."""
+    lay = N.CsicRansLayout()
+    N.check(N.lib().csic_rans_layout_of(C.byref(c_params), C.byref(lay)))
+    return lay
+
+
+def rans_pack_host(c_params: N.CsicParams, bits_frame) -> np.ndarray:
+    """csic_rans_pack_host: one PLANAR_BITS frame buffer (frame_bytes) -> its rANS-coded bytes, a uint8 array of coded_bytes."""
+    return _pack_host(c_params, bits_frame, rans_layout, N.lib().csic_rans_pack_host)
+
+
+def rans_unpack_host(c_params: N.CsicParams, coded, out=None) -> np.ndarray:
+    """csic_rans_unpack_host: rANS-coded bytes -> a PLANAR_BITS frame buffer, as unpack_frame_host.  Damaged input raises CsicIOError."""
+    return _unpack_host(c_params, coded, out, N.lib().csic_rans_unpack_host)
 
 
 def delta_layout(c_params: N.CsicParams) -> N.CsicDeltaLayout:
@@ -195,9 +212,9 @@ def write_container(path: str, c_params: N.CsicParams, frames, coding="raw", gop
     """frames: the PLANAR_BITS frame buffers of `c_params` (its out_format does not matter), frame_bytes each -- one buffer, an
     array (nframes, frame_bytes), or a list of buffers.  Only the planes' payload bytes reach the file.  coding = "raw" (version 1,
     the bytes as they are), "groups" (version 3, every frame group-coded on the host: csic_container_write_ex) or "rice" (version 4,
-    every frame Rice-coded on the host).  With a `gop` the frames are a sequence: version 5, delta and packing on the host
+    every frame Rice-coded on the host) or "rans" (version 7, every frame rANS-coded on the host).  With a `gop` the frames are a sequence: version 5, delta and packing on the host
     (csic_container_write_seq; coding "groups" or "rice"); with a `motion` range (0..7) as well, version 6 through the
-    motion-compensated layer (csic_container_write_seq_ex)."""
+    motion-compensated layer (csic_container_write_seq_ex); a sequence coded with "rans" is version 7 with either layer."""
     q, lay = _bits_params(c_params)
     coding = _coding(coding)
     if motion is not None and gop is None:
@@ -219,7 +236,7 @@ def write_container(path: str, c_params: N.CsicParams, frames, coding="raw", gop
 
 
 def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, coding="groups", maps=None, gop=None, motion=None) -> None:
-    """Version 3 (coding "groups") or 4 ("rice") from frames that are packed already (csic_container_write_coded_ex): `coded` is an
+    """Version 3 (coding "groups"), 4 ("rice") or 7 ("rans") from frames that are packed already (csic_container_write_coded_ex): `coded` is an
     array (nframes, stride) -- what Plan.pack_device / Plan.rice_pack_device returns, copied to the host -- or a list of coded frames;
     sizes[k] is frame k's coded_bytes.  Every frame is validated before anything is written.  With `maps` and `gop` -- what
     Plan.delta_device returned, copied to the host: uint8 (nframes, map_stride) -- the coded frames are difference frames and the file is

@@ -6,7 +6,8 @@
 // the little-endian dwords are csic_group_host.h's.  Version 5 holds a sequence through the temporal layer (csic_delta_host.cpp): the word
 // behind the coding is the gop, a key frame's record is its coded frame, a delta frame's its map and then its coded difference frame.
 // Version 6 is version 5 through the motion-compensated layer (csic_mc_host.cpp): its maps, and the range + 1 in bits 8.. of the coding word.
-// What differs between those two is one row of layer_of.
+// What differs between those two is one row of layer_of.  Version 7 holds everything that is rANS-coded (csic_rans_host.cpp): the third row
+// of codec_of, the coding word and the gop as in version 6 -- a range field of 0 for no motion layer, a gop of 0 for frames that stand alone.
 #include <zlib.h>
 
 #include <cstdio>
@@ -19,8 +20,9 @@
 namespace csic {
 
 constexpr size_t CONTAINER_HEADER = 80, CONTAINER_CRC_FROM = 16;
-constexpr uint32_t CONTAINER_VERSION = 1, CONTAINER_VERSION_CODED = 3, CONTAINER_VERSION_RICE = 4, CONTAINER_VERSION_SEQ = 5, CONTAINER_VERSION_MC = 6;
-constexpr size_t CODED_BODY = 8;                  // versions 3, 4 and 5: coding, reserved (5: gop); then the table of sizes
+constexpr uint32_t CONTAINER_VERSION = 1, CONTAINER_VERSION_CODED = 3, CONTAINER_VERSION_RICE = 4, CONTAINER_VERSION_SEQ = 5, CONTAINER_VERSION_MC = 6,
+                   CONTAINER_VERSION_RANS = 7;
+constexpr size_t CODED_BODY = 8;                  // versions 3 to 7: coding, reserved (5, 6, 7: gop); then the table of sizes
 static const unsigned char CONTAINER_MAGIC[4] = {0x43, 0x53, 0x49, 0x43};   // "CSIC"
 
 static void put_u64(unsigned char *p, uint64_t v) { put_u32(p, (uint32_t)v); put_u32(p + 4, (uint32_t)(v >> 32)); }
@@ -53,6 +55,16 @@ static csic_params params_of_fields(const int32_t f[16])
     return p;
 }
 
+// the geometries of the three codings of one parameter set: the Rice coding's (with the group coding's as .pk) and the rANS coding's
+struct FileGeometry : RiceGeometry {
+    RansGeometry rans;
+};
+static int file_geometry(const csic_params *p, FileGeometry *G)
+{
+    const int st = rice_geometry(p, G);
+    return st != CSIC_OK ? st : rans_geometry(p, &G->rans);
+}
+
 // What depends on the coding of a coded file, for one parameter set (R.pk is the group coding's geometry): a coded frame's least and
 // most bytes and its bound_bytes, and the host codec.  One row per coding; a file picks its row once.
 struct Codec {
@@ -60,22 +72,29 @@ struct Codec {
     uint32_t version;
     uint64_t lo, hi;
     size_t bound;
-    int (*check)(const RiceGeometry &R, const unsigned char *c, size_t n);
-    int (*pack)(const RiceGeometry &R, const unsigned char *frame, unsigned char *c, size_t cap, uint64_t *n);
-    int (*unpack)(const RiceGeometry &R, const unsigned char *c, size_t n, unsigned char *frame);
+    int (*check)(const FileGeometry &R, const unsigned char *c, size_t n);
+    int (*pack)(const FileGeometry &R, const unsigned char *frame, unsigned char *c, size_t cap, uint64_t *n);
+    int (*unpack)(const FileGeometry &R, const unsigned char *c, size_t n, unsigned char *frame);
 };
-static Codec codec_of(const RiceGeometry &R, int coding)
+static Codec codec_of(const FileGeometry &R, int coding)
 {
     const csic_pack_layout &P = R.pk.layout;
     const csic_rice_layout &L = R.layout;
-    const Codec rows[2] = {
+    const csic_rans_layout &A = R.rans.layout;
+    const Codec rows[3] = {
         {CSIC_CODING_GROUPS, CONTAINER_VERSION_CODED, (uint64_t)P.fixed_bytes, (uint64_t)(P.fixed_bytes + 4 * R.pk.max_payload_dwords), (size_t)P.bound_bytes,
-         [](const RiceGeometry &G, const unsigned char *c, size_t n) { return pack_check_coded(G.pk, c, n); },
-         [](const RiceGeometry &G, const unsigned char *f, unsigned char *c, size_t cap, uint64_t *n) { return pack_frame(G.pk, f, c, cap, n); },
-         [](const RiceGeometry &G, const unsigned char *c, size_t n, unsigned char *f) { return unpack_frame(G.pk, c, n, f); }},
+         [](const FileGeometry &G, const unsigned char *c, size_t n) { return pack_check_coded(G.pk, c, n); },
+         [](const FileGeometry &G, const unsigned char *f, unsigned char *c, size_t cap, uint64_t *n) { return pack_frame(G.pk, f, c, cap, n); },
+         [](const FileGeometry &G, const unsigned char *c, size_t n, unsigned char *f) { return unpack_frame(G.pk, c, n, f); }},
         {CSIC_CODING_RICE, CONTAINER_VERSION_RICE, (uint64_t)L.fixed_bytes, (uint64_t)(L.fixed_bytes + 4 * R.max_payload_dwords), (size_t)L.bound_bytes,
-         rice_check_coded, rice_pack_frame, rice_unpack_frame}};
-    return rows[coding == CSIC_CODING_RICE];
+         [](const FileGeometry &G, const unsigned char *c, size_t n) { return rice_check_coded(G, c, n); },
+         [](const FileGeometry &G, const unsigned char *f, unsigned char *c, size_t cap, uint64_t *n) { return rice_pack_frame(G, f, c, cap, n); },
+         [](const FileGeometry &G, const unsigned char *c, size_t n, unsigned char *f) { return rice_unpack_frame(G, c, n, f); }},
+        {CSIC_CODING_RANS, CONTAINER_VERSION_RANS, (uint64_t)A.fixed_bytes, (uint64_t)(A.fixed_bytes + 4 * R.rans.max_payload_dwords), (size_t)A.bound_bytes,
+         [](const FileGeometry &G, const unsigned char *c, size_t n) { return rans_check_coded(G.rans, c, n); },
+         [](const FileGeometry &G, const unsigned char *f, unsigned char *c, size_t cap, uint64_t *n) { return rans_pack_frame(G.rans, f, c, cap, n); },
+         [](const FileGeometry &G, const unsigned char *c, size_t n, unsigned char *f) { return rans_unpack_frame(G.rans, c, n, f); }}};
+    return rows[coding == CSIC_CODING_RANS ? 2 : coding == CSIC_CODING_RICE];
 }
 
 // What depends on the temporal layer of a sequence file, for one parameter set: the version, the bytes of a delta frame's map, the
@@ -145,7 +164,7 @@ struct CodedBody {
     Layer layer;
 };
 
-static int read_header(FILE *f, const char *path, csic_container_info *info, RiceGeometry *G, uint32_t *stored_crc, std::vector<uint64_t> *sizes,
+static int read_header(FILE *f, const char *path, csic_container_info *info, FileGeometry *G, uint32_t *stored_crc, std::vector<uint64_t> *sizes,
                        CodedBody *body = nullptr)
 {
     CodedBody cb;
@@ -158,13 +177,13 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Ric
     if (std::memcmp(h, CONTAINER_MAGIC, 4) != 0) return set_error(CSIC_EFORMAT, "%s is not a .csic file (bad magic)", path);
     const uint32_t version = get_u32(h + 4), nframes = get_u32(h + 8);
     if (version != CONTAINER_VERSION && version != CONTAINER_VERSION_CODED && version != CONTAINER_VERSION_RICE && version != CONTAINER_VERSION_SEQ &&
-        version != CONTAINER_VERSION_MC)
-        return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1, 3, 4, 5 and 6 are)", path, version);
+        version != CONTAINER_VERSION_MC && version != CONTAINER_VERSION_RANS)
+        return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1, 3, 4, 5, 6 and 7 are)", path, version);
     if (nframes < 1 || nframes > 65535) return set_error(CSIC_EFORMAT, "%s: nframes must be in 1..65535. Got %u", path, nframes);
     int32_t fields[16];
     for (int i = 0; i < 16; ++i) fields[i] = (int32_t)get_u32(h + 16 + 4 * i);
     const csic_params p = params_of_fields(fields);
-    if (p.out_format != CSIC_FMT_PLANAR_BITS || rice_geometry(&p, G) != CSIC_OK)
+    if (p.out_format != CSIC_FMT_PLANAR_BITS || file_geometry(&p, G) != CSIC_OK)
         return set_error(CSIC_EFORMAT, "%s: the stored parameters are not a valid PLANAR_BITS parameter set", path);
     const csic_planar_bits_layout &L = G->pk.bits;
     if (version == CONTAINER_VERSION) {
@@ -177,7 +196,19 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Ric
         std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
         if (fread(t.data(), 1, t.size(), f) != t.size()) return set_error(CSIC_EIO, "cannot read %s", path);
         int coding = version == CONTAINER_VERSION_RICE ? CSIC_CODING_RICE : CSIC_CODING_GROUPS;
-        if (version == CONTAINER_VERSION_SEQ || version == CONTAINER_VERSION_MC) {
+        if (version == CONTAINER_VERSION_RANS) {                   // 5 | (range + 1) << 8 with a field of 0 for no motion layer; gop 0: no layer at all
+            const uint32_t c = get_u32(t.data()), field = c >> 8, gop = get_u32(t.data() + 4);
+            if ((c & 0xFFu) != CSIC_CODING_RANS) return set_error(CSIC_EFORMAT, "%s: coding %u is not the one version %u holds (5)", path, c & 0xFFu, version);
+            if (field > (uint32_t)MC_MAX_RANGE + 1 || gop > 65535 || (gop == 0 && field != 0))
+                return set_error(CSIC_EFORMAT, "%s: motion field %u and gop %u of a version-%u file: the field is a range + 1 of 1..%d or 0, the gop at most 65535, and a range needs a gop",
+                                 path, field, gop, version, MC_MAX_RANGE + 1);
+            coding = CSIC_CODING_RANS;
+            if (gop > 0) {
+                cb.gop = (int32_t)gop;
+                const int st = layer_of(p, (int32_t)field - 1, &cb.layer);
+                if (st != CSIC_OK) return set_error(CSIC_EFORMAT, "%s: the stored parameters have no layout in the file's temporal layer", path);
+            }
+        } else if (version == CONTAINER_VERSION_SEQ || version == CONTAINER_VERSION_MC) {
             uint32_t c = get_u32(t.data());
             const uint32_t gop = get_u32(t.data() + 4);
             int32_t motion = -1;
@@ -234,11 +265,11 @@ static void fill_header(unsigned char h[CONTAINER_HEADER], uint32_t version, con
 }
 
 // the parameters a file stores, and their geometry; nframes checked
-static int writer_params(const csic_params *p, int32_t nframes, csic_params *q, RiceGeometry *G)
+static int writer_params(const csic_params *p, int32_t nframes, csic_params *q, FileGeometry *G)
 {
     *q = *p;
     q->out_format = CSIC_FMT_PLANAR_BITS;
-    const int st = rice_geometry(q, G);           // csic_validate first: refuses in_format != ARGB for PLANAR_BITS
+    const int st = file_geometry(q, G);           // csic_validate first: refuses in_format != ARGB for PLANAR_BITS
     if (st != CSIC_OK) return st;
     if (nframes < 1 || nframes > 65535) return set_error(CSIC_EINVAL_SIZE, "nframes must be in 1..65535. Got %d", nframes);
     return CSIC_OK;
@@ -252,7 +283,7 @@ static int write_coded_file(const char *path, const csic_params &q, const unsign
     const size_t map_bytes = (size_t)layer.map_bytes;
     const auto map_of = [&](int32_t k) { return gop > 0 && k % gop ? map_bytes : (size_t)0; };
     unsigned char h[CONTAINER_HEADER];
-    fill_header(h, gop > 0 ? layer.version : codec.version, q, nframes);
+    fill_header(h, gop > 0 && codec.coding != CSIC_CODING_RANS ? layer.version : codec.version, q, nframes);       // (version 7: with or without a layer)
     std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
     put_u32(t.data(), (uint32_t)codec.coding | (uint32_t)(layer.motion + 1) << 8);
     put_u32(t.data() + 4, (uint32_t)gop);
@@ -285,7 +316,7 @@ template <class Take> static int with_header(const char *path, const void *out, 
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
     try {
-        RiceGeometry G;
+        FileGeometry G;
         csic_container_info ci;
         std::vector<uint64_t> table;
         CodedBody body;
@@ -323,7 +354,7 @@ int csic_container_write(const char *path, const csic_params *p, const void *fra
 {
     if (!path || !p || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
     csic_params q;
-    RiceGeometry C;
+    FileGeometry C;
     const int st = writer_params(p, nframes, &q, &C);
     if (st != CSIC_OK) return st;
     const PackGeometry &G = C.pk;
@@ -355,10 +386,10 @@ int csic_container_write_ex(const char *path, const csic_params *p, const void *
 {
     if (coding == CSIC_CODING_RAW) return csic_container_write(path, p, frames, nframes);
     if (!path || !p || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE)
-        return set_error(CSIC_EINVAL_FORMAT, "coding must be CSIC_CODING_RAW(0), CSIC_CODING_GROUPS(1) or CSIC_CODING_RICE(3). Got %d", coding);
+    if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE && coding != CSIC_CODING_RANS)
+        return set_error(CSIC_EINVAL_FORMAT, "coding must be CSIC_CODING_RAW(0), CSIC_CODING_GROUPS(1), CSIC_CODING_RICE(3) or CSIC_CODING_RANS(5). Got %d", coding);
     csic_params q;
-    RiceGeometry G;
+    FileGeometry G;
     int st = writer_params(p, nframes, &q, &G);
     if (st != CSIC_OK) return st;
     const Codec codec = codec_of(G, coding);
@@ -389,10 +420,10 @@ int csic_container_write_coded_ex(const char *path, const csic_params *p, const 
                                   int32_t nframes, int32_t coding)
 {
     if (!path || !p || !coded || !sizes) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE)
-        return set_error(CSIC_EINVAL_FORMAT, "coded frames are CSIC_CODING_GROUPS(1) or CSIC_CODING_RICE(3). Got %d", coding);
+    if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE && coding != CSIC_CODING_RANS)
+        return set_error(CSIC_EINVAL_FORMAT, "coded frames are CSIC_CODING_GROUPS(1), CSIC_CODING_RICE(3) or CSIC_CODING_RANS(5). Got %d", coding);
     csic_params q;
-    RiceGeometry G;
+    FileGeometry G;
     int st = writer_params(p, nframes, &q, &G);
     if (st != CSIC_OK) return st;
     const Codec codec = codec_of(G, coding);
@@ -423,8 +454,8 @@ int csic_container_write_coded(const char *path, const csic_params *p, const voi
 // csic_container_write_seq and csic_container_write_coded_seq: what they refuse of coding and gop
 static int seq_check(int32_t coding, int32_t gop)
 {
-    if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE)
-        return set_error(CSIC_EINVAL_FORMAT, "a sequence is coded with CSIC_CODING_GROUPS(1) or CSIC_CODING_RICE(3). Got %d", coding);
+    if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE && coding != CSIC_CODING_RANS)
+        return set_error(CSIC_EINVAL_FORMAT, "a sequence is coded with CSIC_CODING_GROUPS(1), CSIC_CODING_RICE(3) or CSIC_CODING_RANS(5). Got %d", coding);
     if (gop < 1 || gop > 65535) return set_error(CSIC_EINVAL_SIZE, "gop must be in 1..65535. Got %d", gop);
     return CSIC_OK;
 }
@@ -436,7 +467,7 @@ static int write_seq(const char *path, const csic_params *p, const void *frames,
     int st = seq_check(coding, gop);
     if (st != CSIC_OK) return st;
     csic_params q;
-    RiceGeometry G;
+    FileGeometry G;
     Layer layer;
     if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = layer_of(q, motion, &layer)) != CSIC_OK) return st;
     const Codec codec = codec_of(G, coding);
@@ -483,7 +514,7 @@ static int write_coded_seq(const char *path, const csic_params *p, const void *c
     int st = seq_check(coding, gop);
     if (st != CSIC_OK) return st;
     csic_params q;
-    RiceGeometry G;
+    FileGeometry G;
     Layer layer;
     if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = layer_of(q, motion, &layer)) != CSIC_OK) return st;
     const size_t mb = (size_t)layer.map_bytes;
@@ -556,7 +587,7 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
 {
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) return set_error(CSIC_EIO, "cannot open %s", path);
-    RiceGeometry C;
+    FileGeometry C;
     csic_container_info ci;
     uint32_t stored = 0;
     std::vector<uint64_t> sizes;

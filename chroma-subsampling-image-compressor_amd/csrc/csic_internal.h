@@ -56,6 +56,21 @@ int rice_pack_frame(const RiceGeometry &G, const unsigned char *frame, unsigned 
 int rice_unpack_frame(const RiceGeometry &G, const unsigned char *coded, size_t coded_bytes, unsigned char *frame);
 int rice_check_coded(const RiceGeometry &G, const unsigned char *coded, size_t coded_bytes);
 
+// csic_rans_host.cpp: the rANS coding (csic.h: csic_rans_*), the same three for it.  `pk` gives the PLANAR_BITS frame, n, q, the payload
+// ranges and the groups; the blocks are the rANS coding's own (1024 groups, csic_rans_decode.h) and so are all section offsets.
+struct RansGeometry {
+    PackGeometry pk;
+    csic_rans_layout layout;
+    int64_t block0[3], nblocks;               // a plane's first block number; blocks per frame (NB)
+    int64_t max_payload_dwords;               // the raw chunks of all blocks
+};
+int rans_geometry(const csic_params *p, RansGeometry *G);
+int rans_pack_frame(const RansGeometry &G, const unsigned char *frame, unsigned char *coded, size_t capacity, uint64_t *coded_bytes);
+int rans_unpack_frame(const RansGeometry &G, const unsigned char *coded, size_t coded_bytes, unsigned char *frame);
+int rans_check_coded(const RansGeometry &G, const unsigned char *coded, size_t coded_bytes);
+// the scaling rule of csic.h: counts c[0, nsym) with sum N > 0 -> frequencies f[0, nsym) with sum M
+void rans_scale_counts(const uint32_t *c, int nsym, uint64_t N, uint16_t *f);
+
 // csic_delta_host.cpp: the temporal layer (csic.h: csic_delta_*).  `pk` is the group coding's geometry of the same parameters; `layout`
 // is the map's.  delta_frame writes the difference frame of `cur` against `prev` (NULL: a key frame) and its map; undelta_frame is the
 // inverse; both allow diff == cur.  delta_check_map is what csic_undelta_host and the container ask of a map nobody vouches for.

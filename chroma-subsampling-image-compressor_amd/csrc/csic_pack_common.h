@@ -1,5 +1,5 @@
-// csic_pack_common.h -- what the device codecs of the group coding (csic_pack.hip) and of the Rice coding (csic_rice.hip) share, and the
-// temporal layer in front of them (csic_delta.hip) with both.
+// csic_pack_common.h -- what the device codecs of the group coding (csic_pack.hip), of the Rice coding (csic_rice.hip) and of the rANS
+// coding (csic_rans.hip) share, and the temporal layer in front of them (csic_delta.hip) with them.
 // Device: the kernels' argument, the checked accessors of the PLANAR_BITS and the coded frames, the block scan, the load of a group's
 // dwords with the ragged-tail rule, the cut of one code and the fold of one residual, and from them the load of a group with its folded
 // residuals, the store of a block's nibble and anchors sections, the reads of a group's nibble and anchor, and the
@@ -144,6 +144,26 @@ __device__ __forceinline__ uint32_t pk_fold_group(const PkArgs &e, gpdst_t fb, i
     return any ? 32u - (uint32_t)__builtin_clz(any) : 0u;
 }
 
+// The block's 256 anchors (one per thread in LDS, 0 behind the plane's last group, published by a barrier) -> the 8 Q dwords of the
+// plane's anchors section that the block owns; threads 64 .. 64 + 8 Q store one each.  Every thread of the block may call it.
+template <int Q>
+__device__ __forceinline__ void pk_store_anchors(const PkArgs &e, gpdst_t cb, int plane, const uint32_t *s_a)
+{
+    const uint32_t t = threadIdx.x;
+    if (t >= 64u && t < 64u + 8u * Q) {
+        // wave 1: dword a of the block's anchors = bits [32 a, 32 a + 32) of 256 codes at Q bits
+        const uint32_t a = t - 64u, dw = blockIdx.x * (8u * Q) + a;
+        if (dw < e.adw[plane]) {
+            uint32_t v = 0;
+            for (uint32_t i = 32u * a / Q; i * Q < 32u * a + 32u; ++i) {    // (i < 256: the block's string is 256 Q bits)
+                const int sh = (int)(i * Q) - (int)(32u * a);
+                v |= sh >= 0 ? s_a[i] << sh : s_a[i] >> -sh;
+            }
+            pk_coded_st4(e, cb, (int64_t)e.aoff[plane] + 4 * (int64_t)dw, v);
+        }
+    }
+}
+
 // The block's nibbles and anchors (one per thread in LDS, 0 behind the plane's last group: the sections' padding, and published by a
 // barrier) -> the dwords of the plane's nibble and anchors sections.  A block's first group g0 is a multiple of 256: both strings start
 // on a dword.  Every thread of the block calls it.
@@ -159,17 +179,8 @@ __device__ __forceinline__ void pk_store_sections(const PkArgs &e, gpdst_t cb, i
             for (int k = 0; k < 8; ++k) v |= s_nib[8u * t + (uint32_t)k] << (4 * k);
             pk_coded_st4(e, cb, (int64_t)e.woff[plane] + 4 * (int64_t)(g0 / 8u + t), v);
         }
-    } else if (t >= 64u && t < 64u + 8u * Q) {
-        // wave 1: dword a of the block's anchors = bits [32 a, 32 a + 32) of 256 codes at Q bits
-        const uint32_t a = t - 64u, dw = blockIdx.x * (8u * Q) + a;
-        if (dw < e.adw[plane]) {
-            uint32_t v = 0;
-            for (uint32_t i = 32u * a / Q; i * Q < 32u * a + 32u; ++i) {    // (i < 256: the block's string is 256 Q bits)
-                const int sh = (int)(i * Q) - (int)(32u * a);
-                v |= sh >= 0 ? s_a[i] << sh : s_a[i] >> -sh;
-            }
-            pk_coded_st4(e, cb, (int64_t)e.aoff[plane] + 4 * (int64_t)dw, v);
-        }
+    } else {
+        pk_store_anchors<Q>(e, cb, plane, s_a);
     }
 }
 
@@ -235,17 +246,17 @@ inline size_t pk_workspace_need(int32_t nframes, uint32_t nblocks) { return ((si
 // Below, Args is the argument struct of a coding's kernels: PkArgs, or a struct derived from it; fill(plan, &args) fills it from the
 // plan's parameters.
 // What the four device entry points refuse before any device is touched, then the arguments filled; `has_ws` is false for the one
-// entry point without a workspace.
+// entry point without a workspace.  need(nframes, nblocks) is the coding's workspace size: one uint32 per block unless it says more.
 int pk_check_buffers(const csic_plan *plan, const void *d_bits, const void *d_coded, int32_t nframes, bool has_ws, const void *d_workspace);
 template <class Args>
 int pk_prepare(const csic_plan *plan, const void *d_bits, const void *d_coded, int32_t nframes, bool has_ws, const void *d_workspace,
-               size_t workspace_bytes, int (*fill)(const csic_plan *, Args *), Args *e)
+               size_t workspace_bytes, int (*fill)(const csic_plan *, Args *), Args *e, size_t (*need)(int32_t, uint32_t) = pk_workspace_need)
 {
     int st = pk_check_buffers(plan, d_bits, d_coded, nframes, has_ws, d_workspace);
     if (st == CSIC_OK) st = fill(plan, e);
     if (st != CSIC_OK) return st;
-    if (has_ws && workspace_bytes < pk_workspace_need(nframes, e->nblocks))
-        return set_error(CSIC_EINVAL_SIZE, "workspace of %zu bytes, %d frames need %zu", workspace_bytes, nframes, pk_workspace_need(nframes, e->nblocks));
+    if (has_ws && workspace_bytes < need(nframes, e->nblocks))
+        return set_error(CSIC_EINVAL_SIZE, "workspace of %zu bytes, %d frames need %zu", workspace_bytes, nframes, need(nframes, e->nblocks));
     e->bits = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_bits));
     e->coded = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_coded));
     e->ws = const_cast<uint32_t *>(static_cast<const uint32_t *>(d_workspace));
@@ -253,20 +264,23 @@ int pk_prepare(const csic_plan *plan, const void *d_bits, const void *d_coded, i
 }
 
 // *_workspace_bytes of both codings
-template <class Args> int pk_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes, int (*fill)(const csic_plan *, Args *))
+template <class Args>
+int pk_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes, int (*fill)(const csic_plan *, Args *), size_t (*need)(int32_t, uint32_t) = pk_workspace_need)
 {
     if (!plan || !bytes) return set_error(CSIC_EINVAL_NULL, "plan or bytes is NULL");
     if (nframes < 1 || nframes > 65535) return set_error(CSIC_EINVAL_SIZE, "nframes must be 1..65535. Got %d", nframes);
     Args e;
     const int st = fill(plan, &e);
     if (st != CSIC_OK) return st;
-    *bytes = pk_workspace_need(nframes, e.nblocks);
+    *bytes = need(nframes, e.nblocks);
     clear_error();
     return CSIC_OK;
 }
 
-// One launch per run of planes of equal width; choose(Q, NT) maps the two constants to the kernel.
-template <class Args, class Choose> int pk_launch_planes(const csic_plan *plan, Args &e, int nframes, hipStream_t stream, Choose choose)
+// One launch per run of planes of equal width; choose(Q, NT) maps the two constants to the kernel.  A block of `threads` threads takes
+// `block_groups` consecutive groups of one plane (the group and Rice codings: 256 and 256; the rANS coding's wave per block: 1024 and 64).
+template <class Args, class Choose>
+int pk_launch_planes(const csic_plan *plan, Args &e, int nframes, hipStream_t stream, Choose choose, uint32_t block_groups = PK_T, uint32_t threads = PK_T)
 {
     for (int p0 = 0; p0 < 3;) {
         int p1 = p0 + 1;
@@ -278,7 +292,7 @@ template <class Args, class Choose> int pk_launch_planes(const csic_plan *plan, 
             void (*const fn)(Args) = with_const<true, false>(!plan->tune.no_nt, [&](auto nt) {
                 return with_const<1, 2, 3, 4, 5, 6, 7, 8>(e.q[p0], [&](auto q) -> void (*)(Args) { return choose(q, nt); });
             });
-            const int st = launch(fn, dim3((gmax + PK_T - 1) / PK_T, (unsigned)(p1 - p0), (unsigned)nframes), dim3(PK_T, 1, 1), stream, e);
+            const int st = launch(fn, dim3((gmax + block_groups - 1) / block_groups, (unsigned)(p1 - p0), (unsigned)nframes), dim3(threads, 1, 1), stream, e);
             if (st != CSIC_OK) return st;
         }
         p0 = p1;

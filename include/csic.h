@@ -806,6 +806,101 @@ int  csic_rice_pack_device(csic_plan *plan, const void *d_bits, int32_t nframes,
 int  csic_rice_unpack_device(csic_plan *plan, const void *d_coded, int32_t nframes, void *d_bits, void *hip_stream);
 const char *csic_rice_kernel_name(const csic_plan *plan);
 
+/* ---- lossless rANS coding of the bit planes (csic_rans_*) -------------------------------------------------------------------------
+ * A Golomb-Rice code spends at least one bit on every sample of a group that is not all zero; where the entropy of the residuals is
+ * below one bit per sample the Rice coding cannot follow it.  This coding (CSIC_CODING_RANS) is a table-driven range coder (rANS) with
+ * one static frequency table per plane and frame: it reaches the `ideal` figure of csic_code_stats_* up to its tables and stream
+ * flushes.  It is interleaved over the 64 lanes of a wave and cut into independent blocks behind a directory, so there is still no
+ * serial bit stream across the frame.  Coding ids 2 and 4 were never written and stay refused.
+ *
+ * Carried over from the group coding, word for word: the input is one CSIC_FMT_PLANAR_BITS frame; planes, q_p, n_p, the groups of 32
+ * (G_p of them), anchor_g, e_j, s_j and the folded u_j (slots j = 1 .. 31) are as above; the last group is completed with the plane's
+ * last real code (so its slots behind the last sample hold u_j = 0, and are coded); bits beyond sample n_p - 1 are never read into a
+ * value; bit order is LSB first, every section starts at a multiple of 4 and every padding bit is 0.
+ *
+ * Model, per plane and frame.  M = 4096.  N = 31 G_p coded slots; c_s = how many of them hold the value s, s = 0 .. 2^q - 1.  The
+ * frequencies f_s, with sum_s f_s = M exactly, f_s >= 1 where c_s > 0 and f_s = 0 where c_s = 0, come from the scaling rule:
+ *     1. f_s = 0 if c_s = 0, else max(1, floor(c_s M / N)).
+ *     2. d = M - sum_s f_s.  If d > 0, d is added to f_t, t = the s with the largest c_s (the smallest such s on a tie).
+ *     3. If d < 0, -d times: 1 is taken off f_t, t = the s with the currently largest f_s (the smallest such s on a tie).  (That f_t is
+ *        above M / 2^q >= 16: no frequency falls below 1.)
+ * cum_s = sum of f_r over r < s.  The rule is the encoder's; decoding depends only on the stored table.
+ *
+ * State.  A stream's state x is 32 bits, L = 2^16 <= x < 2^32, renormalised in 16-bit words.
+ *     decode a symbol   slot = x & (M - 1); s = the symbol with cum_s <= slot < cum_s + f_s; x = f_s (x >> 12) + slot - cum_s;
+ *                       then, if x < L, x = (x << 16) | the stream's next word
+ *     encode a symbol   (the exact inverse) if x >= f_s << 20: emit the word x & 0xffff, x = x >> 16;
+ *                       then x = ((x / f_s) << 12) + (x mod f_s) + cum_s
+ * At most one word moves per symbol.  A symbol with f_s = M codes in zero bits: x does not change.  The encoder starts every stream at
+ * x = L and codes the stream's symbols in the reverse of the decode order; what it ends with is the stream's stored state.
+ *
+ * Blocks and interleave.  Plane p has B_p = ceil(G_p / 1024) blocks of 1024 consecutive groups; a frame's blocks are numbered Y, then
+ * Cb, then Cr; NB = sum_p B_p.  A block has 64 streams; stream l owns those of the groups 1024 b + 64 i + l, i = 0 .. 15, that exist:
+ * min(64, groups of the block) streams own a group.  Decode runs the steps t = 0 .. 495 with i = t / 31 and j = 1 + t mod 31: at step t
+ * every stream whose group i exists decodes slot j of that group; the streams that renormalise at that step then take their words from
+ * the block's word string, one each, in ascending stream order.  Every stream starts from its stored state and ends at exactly L.
+ *
+ * Sections, in this order:
+ *     1. tables of Y, Cb, Cr    2^q_p uint16: f_0, f_1, ...
+ *     2. anchors of Y, Cb, Cr   exactly as in the group coding
+ *     3. directory              NB + 1 uint32: bits 0 .. 30 of dir[i] = the dword offset of block i's chunk from payload_offset, bit
+ *                               31 set = the chunk is raw; dir[0] has offset 0; dir[NB] = the number of payload dwords, bit 31 clear
+ *     4. payload                one chunk per block, back to back
+ *          rANS chunk   the stored states of the streams that own a group, one uint32 each in stream order, then the word string
+ *                       (uint16 each, word k in bytes [2 k, 2 k + 2) behind the states), zero-padded to a dword
+ *          raw chunk    for each group of the block in order 31 q bits, u_j at bits [(j - 1) q, j q) of the group's run; runs
+ *                       bit-contiguous, zero-padded to a dword: ceil(31 q groups / 32) dwords
+ *     The encoder takes the raw chunk iff it is strictly smaller than the rANS chunk: no chunk is longer than its block's raw chunk.
+ *     fixed_bytes = the sum of sections 1 to 3              coded_bytes = fixed_bytes + 4 * dir[NB]
+ *     bound_bytes = the next multiple of 256 at or above fixed_bytes + the raw chunks of all blocks
+ * Worked vector, one plane alone: q = 3, codes 1,2,3,4,5,6,7,0 -> u_1 .. u_7 = 2, the other 24 slots 0; f_0 = 3172, f_2 = 924; one
+ * stream with the stored state 0x00e98cc8, which takes its one word 0x9dd4 at step t = 3; the raw chunk would be 3 dwords:
+ *     table 64 0c 00 00 9c 03 00 00 00 00 00 00 00 00 00 00, anchors 01 00 00 00, directory 00 00 00 00 02 00 00 00,
+ *     payload c8 8c e9 00 d4 9d 00 00
+ *
+ * Host codec (no GPU; parameters and statuses as for csic_pack_*):
+ *   csic_rans_layout_of   : groups, blocks, section offsets and sizes of a coded frame of these parameters.
+ *   csic_rans_pack_host   : as csic_pack_host, capacity rule included.
+ *   csic_rans_unpack_host : as csic_unpack_host.  The input is untrusted; CSIC_EFORMAT, nothing written, for: a table that does not
+ *                         sum to M; a padding bit that is not 0 (anchors, a raw chunk, the padding word of a word string); dir[0] with
+ *                         an offset other than 0; offsets that decrease; a flag on dir[NB]; a raw chunk that is not exactly its size; a
+ *                         rANS chunk shorter than its states or longer than the block's raw chunk; a stored state below L; a word
+ *                         string that is not consumed exactly (one zero padding word allowed); a stream that does not end at L;
+ *                         coded_bytes other than fixed_bytes + 4 dir[NB].  Whether the table is the scaling rule's, or the raw
+ *                         decision the encoder's, is not checked.
+ * Device codec (gfx950), with the argument lists, alignment rules, refusals before any device is touched, asynchrony and
+ * capturability of csic_rice_*:
+ *   csic_rans_workspace_bytes : what csic_rans_pack_device needs: per frame two uint32 per block and 256 uint32 per plane.
+ *   csic_rans_pack_device : in stream order a kernel that clears the counts, a histogram pass (which stores the anchors), one
+ *                         table launch, a sizing pass (one wave per block runs the encoder without
+ *                         storing), the scan of the group coding over the blocks' sizes, and the emit pass (one wave per block
+ *                         assembles its chunk in LDS, words placed from the end, and stores it and its directory entry).
+ *   csic_rans_unpack_device : ONE pass, no workspace: one wave per block builds the slot table in LDS, takes its chunk and walks the
+ *                         496 steps.  It does NOT validate: directory offsets are clamped to bound_bytes, a chunk to its block's raw
+ *                         size, table entries so that no slot leaves the table, a word behind the chunk reads as 0.  Whatever the
+ *                         bytes, nothing outside a frame's bound_bytes is read and nothing outside the three payload ranges written.
+ *                         Validate untrusted input on the host.
+ *   csic_rans_kernel_name : "k_rans<q6,5,5,nt>". */
+#define CSIC_CODING_RANS   5   /* the rANS coding above; ids 2 and 4 are never written    */
+typedef struct csic_rans_layout {
+    int64_t groups[3];             /* G_p                                                              */
+    int64_t blocks[3];             /* B_p, blocks of 1024 groups                                       */
+    int64_t tables_offset[3];      /* byte offsets of the sections inside a coded frame               */
+    int64_t anchors_offset[3];
+    int64_t directory_offset;      /* sum_p B_p + 1 uint32                                             */
+    int64_t payload_offset;        /* = fixed_bytes                                                    */
+    int64_t fixed_bytes;
+    int64_t bound_bytes;           /* multiple of 256: the distance of coded frames in device memory   */
+} csic_rans_layout;
+int  csic_rans_layout_of(const csic_params *p, csic_rans_layout *layout);
+int  csic_rans_pack_host(const csic_params *p, const void *bits_frame, void *coded, size_t capacity, uint64_t *coded_bytes);
+int  csic_rans_unpack_host(const csic_params *p, const void *coded, size_t coded_bytes, void *bits_frame);
+int  csic_rans_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes);
+int  csic_rans_pack_device(csic_plan *plan, const void *d_bits, int32_t nframes, void *d_coded, uint64_t *d_sizes,
+                           void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int  csic_rans_unpack_device(csic_plan *plan, const void *d_coded, int32_t nframes, void *d_bits, void *hip_stream);
+const char *csic_rans_kernel_name(const csic_plan *plan);
+
 /* ---- temporal delta coding of frame sequences (csic_delta_*) ------------------------------------------------------------------------
  * Both codings above code every frame on its own.  This layer sits in front of them: it turns a sequence of CSIC_FMT_PLANAR_BITS
  * frames into a sequence of DIFFERENCE frames of the same layout, which either coding then codes as it codes any frame, and one small
@@ -981,7 +1076,7 @@ const char *csic_mc_kernel_name(const csic_plan *plan);
  *                            when the parameters are invalid or p->in_format is not ARGB; nframes outside 1 .. 65535: CSIC_EINVAL_SIZE.
  *   csic_container_info_of : header, parameters and length of a file (everything csic_container_read checks except the CRC).
  *   csic_container_read    : frames_bytes must equal nframes * frame_bytes (CSIC_EINVAL_SIZE otherwise; ask csic_container_info_of).
- * CSIC_EFORMAT: bad magic, a version other than 1, 3, 4 or 5, nframes out of range, parameters that fail csic_validate (or are not
+ * CSIC_EFORMAT: bad magic, a version other than 1, 3, 4, 5, 6 or 7, nframes out of range, parameters that fail csic_validate (or are not
  * PLANAR_BITS), a length other than 80 + nframes * payload_bytes, a CRC mismatch.  CSIC_EIO: the file cannot be opened, read or
  * written.  NULL arguments: CSIC_EINVAL_NULL.
  *
@@ -994,7 +1089,8 @@ const char *csic_mc_kernel_name(const csic_plan *plan);
  *         88 + 8 * nframes             the coded frames back to back, each exactly its coded_bytes
  *
  *   csic_container_write_ex    : coding = CSIC_CODING_RAW writes what csic_container_write writes, byte for byte; CSIC_CODING_GROUPS
- *                                packs every frame on the host (csic_pack_host) and writes version 3; another coding: CSIC_EINVAL_FORMAT.
+ *                                packs every frame on the host (csic_pack_host) and writes version 3; CSIC_CODING_RICE and
+ *                                CSIC_CODING_RANS: versions 4 and 7 below; another coding (2 and 4 among them): CSIC_EINVAL_FORMAT.
  *   csic_container_write_coded : version 3 from frames that are packed already (csic_pack_device's output copied to the host, say):
  *                                frame k is coded[k * stride_bytes, + sizes[k]).  Every frame is validated as csic_unpack_host would
  *                                before anything is written (CSIC_EFORMAT); sizes[k] > stride_bytes: CSIC_EINVAL_SIZE.
@@ -1009,9 +1105,10 @@ const char *csic_mc_kernel_name(const csic_plan *plan);
  * (csic_rice_*).  A version / coding pair other than 3 / 1 or 4 / 3 is CSIC_EFORMAT; a version-4 file is refused in the cases of a
  * version-3 file, with the Rice coding's sizes (fixed_bytes .. fixed_bytes + 4 sum_p B_p (248 q_p + 1)) and csic_rice_unpack_host.
  *   csic_container_write_ex       : CSIC_CODING_RICE packs every frame on the host (csic_rice_pack_host) and writes version 4.
- *   csic_container_write_coded_ex : csic_container_write_coded for either coding (CSIC_CODING_GROUPS or CSIC_CODING_RICE; another:
- *                                   CSIC_EINVAL_FORMAT); csic_container_write_coded keeps meaning CSIC_CODING_GROUPS.
- *   csic_container_read, csic_container_info_of, csic_container_coded_sizes read versions 1, 3 and 4.
+ *   csic_container_write_coded_ex : csic_container_write_coded for any of the three codings (CSIC_CODING_GROUPS, CSIC_CODING_RICE, or
+ *                                   CSIC_CODING_RANS: version 7 below; another: CSIC_EINVAL_FORMAT); csic_container_write_coded keeps
+ *                                   meaning CSIC_CODING_GROUPS.
+ *   csic_container_read, csic_container_info_of, csic_container_coded_sizes read every version: 1, 3, 4, 5, 6 and 7.
  *
  * Version 5 holds a SEQUENCE: the frames go through the temporal layer (csic_delta_*) and their difference frames through one of the
  * two codings.  Bytes 0 .. 79 are as in version 1 with version = 5, the CRC covers [16, end of file), and the body is
@@ -1023,14 +1120,15 @@ const char *csic_mc_kernel_name(const csic_plan *plan);
  *                                      3 / 4; a delta frame is its map (map_bytes of csic_delta_layout_of) followed by the coded frame
  *                                      of its difference frame
  *
- *   csic_container_write_seq       : delta (csic_delta_host) and packing on the host, version 5.  coding other than GROUPS or RICE:
- *                                    CSIC_EINVAL_FORMAT; gop outside 1 .. 65535: CSIC_EINVAL_SIZE.
+ *   csic_container_write_seq       : delta (csic_delta_host) and packing on the host, version 5 (CSIC_CODING_RANS: version 7 below).
+ *                                    coding other than GROUPS, RICE or RANS: CSIC_EINVAL_FORMAT; gop outside 1 .. 65535: CSIC_EINVAL_SIZE.
  *   csic_container_write_coded_seq : version 5 from what the device made: coded difference frames coded[k * stride_bytes, + sizes[k])
  *                                    (sizes[k] is the coded frame's bytes, without the map) and the maps, map_stride apart (the maps of
  *                                    key frames are read too: they must be zero).  Every coded frame and every map is validated
  *                                    before anything is written (CSIC_EFORMAT); sizes[k] > stride_bytes or map_stride < map_bytes:
  *                                    CSIC_EINVAL_SIZE.
- *   csic_container_gop             : the gop of a version-5 file; 1 for versions 1, 3 and 4 (every frame stands alone).
+ *   csic_container_gop             : the gop of a version-5, -6 or -7 file; 1 for versions 1, 3 and 4 and for a version-7 file whose
+ *                                    stored gop is 0 (every frame stands alone).
  *   csic_container_inter_groups    : counts[3 k + p] = the groups of plane p of frame k that are inter, the popcount of that section of
  *                                    the map; n must be 3 * nframes (CSIC_EINVAL_SIZE otherwise).  All zeros for versions 1, 3 and 4.
  *   csic_container_read resolves the chains on the host and returns the frames themselves; csic_container_info_of reports version 5;
@@ -1047,9 +1145,36 @@ const char *csic_mc_kernel_name(const csic_plan *plan);
  *                                       CSIC_EINVAL_SIZE.
  *   csic_container_write_coded_seq_ex : csic_container_write_coded_seq with the maps of csic_mc_delta_device, validated as
  *                                       csic_mc_undelta_host validates them: version 6.
- *   csic_container_motion             : the range of a version-6 file, -1 for every other version.
+ *   csic_container_motion             : the range of a version-6 file or of a version-7 file with a motion layer, -1 otherwise.
  *   csic_container_read, _info_of, _coded_sizes and _gop read version 6 as they read version 5; csic_container_inter_groups counts the
- *   nibbles that are not 0.  CSIC_EFORMAT beyond version 5's cases: the motion field, and whatever csic_mc_undelta_host refuses of a map. */
+ *   nibbles that are not 0.  CSIC_EFORMAT beyond version 5's cases: the motion field, and whatever csic_mc_undelta_host refuses of a map.
+ *
+ * Version 7 holds everything that is rANS-coded (csic_rans_*, CSIC_CODING_RANS): frames that stand alone, a sequence through the
+ * temporal layer, or a sequence through the motion-compensated layer.  Bytes 0 .. 79 are as in version 1 with version = 7, the CRC
+ * covers [16, end of file), and the body is
+ *
+ *         80     4                     uint32  5 | F << 8 : the coding id and the motion field F, every other bit zero.  F = 0: no
+ *                                      motion layer; F = R + 1 for the range R = 0 .. 7 of csic_mc_*
+ *         84     4                     uint32 gop, 0 .. 65535.  0: every frame stands alone, no record holds a map, and F is 0
+ *         88     8 * nframes           uint64 stored bytes of each frame's record
+ *         88 + 8 * nframes             the records back to back.  gop = 0: each record is the frame's coded frame (csic_rans_pack_host's
+ *                                      bytes).  gop >= 1: as in versions 5 (F = 0: the maps of csic_delta_layout_of) and 6 (F >= 1: the
+ *                                      maps of csic_mc_layout_of): a key frame's record is its coded frame, a delta frame's its map
+ *                                      followed by the coded frame of its difference frame
+ *
+ *   csic_container_write_ex, csic_container_write_coded_ex          : coding = CSIC_CODING_RANS writes gop = 0, F = 0.
+ *   csic_container_write_seq, csic_container_write_coded_seq        : coding = CSIC_CODING_RANS writes the gop and F = 0.
+ *   csic_container_write_seq_ex, csic_container_write_coded_seq_ex  : coding = CSIC_CODING_RANS writes the gop and F = range + 1.
+ *       The refusals are those of the same calls with the other codings; the _coded writers validate every coded frame as
+ *       csic_rans_unpack_host would, and every map as its layer's decoder would, before anything is written.
+ *   csic_container_read, _info_of, _coded_sizes read version 7 as they read versions 3 to 6; csic_container_gop gives the stored gop,
+ *   or 1 when it is 0; csic_container_motion gives F - 1 (so -1 without a motion layer); csic_container_inter_groups counts as for
+ *   version 5 (F = 0) or 6 (F >= 1), and gives all zeros when the gop is 0.
+ * CSIC_EFORMAT for a version-7 file, beyond the cases of versions 3 to 6 (with the rANS coding's sizes: fixed_bytes .. fixed_bytes + the
+ * raw chunks of all blocks, plus map_bytes for a delta record): a coding id other than 5 in the low byte; F above 8 or any higher bit
+ * set; a gop above 65535; F other than 0 with a gop of 0; any coded frame csic_rans_unpack_host refuses; a record that holds a map
+ * where the gop says it has none, or none where it has one (refused by its size or by the decoders).  Coding id 5 under versions 3,
+ * 4, 5 or 6 is CSIC_EFORMAT as well: those versions keep their codings, their bytes and their refusals. */
 typedef struct csic_container_info {
     csic_params params;            /* out_format = CSIC_FMT_PLANAR_BITS, in_format = CSIC_FMT_ARGB8888 */
     int32_t version, nframes;

@@ -130,8 +130,8 @@ inline void writeContainer(const std::string &file, const csic_params &p, const 
 {
     check(csic_container_write_ex(file.c_str(), &p, frames, nframes, coding));
 }
-// version 3 (CSIC_CODING_GROUPS) or 4 (CSIC_CODING_RICE) from frames that are packed already (csic_pack_device's / csic_rice_pack_device's
-// output on the host): frame k at coded + k * stride_bytes
+// version 3 (CSIC_CODING_GROUPS), 4 (CSIC_CODING_RICE) or 7 (CSIC_CODING_RANS) from frames that are packed already (csic_pack_device's /
+// csic_rice_pack_device's / csic_rans_pack_device's output on the host): frame k at coded + k * stride_bytes
 inline void writeContainerCoded(const std::string &file, const csic_params &p, const void *coded, size_t stride_bytes,
                                 const std::vector<uint64_t> &sizes, int coding = CSIC_CODING_GROUPS)
 {
@@ -206,6 +206,32 @@ inline std::vector<uint8_t> riceUnpack(const csic_params &p, const void *coded, 
     check(csic_planar_bits_layout_of(&q, &layout));
     std::vector<uint8_t> frame((size_t)layout.frame_bytes, 0);
     check(csic_rice_unpack_host(&p, coded, codedBytes, frame.data()));
+    return frame;
+}
+
+// The same for the rANS coding (csic.h: csic_rans_*).
+inline csic_rans_layout ransLayout(const csic_params &p)
+{
+    csic_rans_layout layout;
+    check(csic_rans_layout_of(&p, &layout));
+    return layout;
+}
+inline std::vector<uint8_t> ransPack(const csic_params &p, const void *bitsFrame)
+{
+    std::vector<uint8_t> coded((size_t)ransLayout(p).bound_bytes);
+    uint64_t size = 0;
+    check(csic_rans_pack_host(&p, bitsFrame, coded.data(), coded.size(), &size));
+    coded.resize((size_t)size);
+    return coded;
+}
+inline std::vector<uint8_t> ransUnpack(const csic_params &p, const void *coded, size_t codedBytes)
+{
+    csic_params q = p;
+    q.out_format = CSIC_FMT_PLANAR_BITS;
+    csic_planar_bits_layout layout;
+    check(csic_planar_bits_layout_of(&q, &layout));
+    std::vector<uint8_t> frame((size_t)layout.frame_bytes, 0);
+    check(csic_rans_unpack_host(&p, coded, codedBytes, frame.data()));
     return frame;
 }
 
@@ -448,6 +474,25 @@ public:
         check(csic_rice_unpack_device(plan_, d_coded, nframes, d_bits, hip_stream));
     }
     const char *riceKernelName() { return csic_rice_kernel_name(plan_); }
+    // the rANS coding of this plan's PLANAR_BITS frames, host and device; ransUnpackDevice is one pass and takes no workspace
+    csic_rans_layout ransLayout() const { return csic::ransLayout(params_); }
+    std::vector<uint8_t> ransPack(const void *bitsFrame) const { return csic::ransPack(params_, bitsFrame); }
+    std::vector<uint8_t> ransUnpack(const void *coded, size_t codedBytes) const { return csic::ransUnpack(params_, coded, codedBytes); }
+    size_t ransWorkspaceBytes(int nframes = 1)
+    {
+        size_t bytes = 0;
+        check(csic_rans_workspace_bytes(plan_, nframes, &bytes));
+        return bytes;
+    }
+    void ransPackDevice(const void *d_bits, int nframes, void *d_coded, uint64_t *d_sizes, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+    {
+        check(csic_rans_pack_device(plan_, d_bits, nframes, d_coded, d_sizes, d_workspace, workspace_bytes, hip_stream));
+    }
+    void ransUnpackDevice(const void *d_coded, int nframes, void *d_bits, void *hip_stream)
+    {
+        check(csic_rans_unpack_device(plan_, d_coded, nframes, d_bits, hip_stream));
+    }
+    const char *ransKernelName() { return csic_rans_kernel_name(plan_); }
     // the temporal layer over this plan's PLANAR_BITS frames, host and device (no workspace; d_diff may be d_frames, in place)
     csic_delta_layout deltaLayout() const { return csic::deltaLayout(params_); }
     DeltaFrames delta(const void *frames, int nframes, int gop) const { return csic::delta(params_, frames, nframes, gop); }
