@@ -31,6 +31,7 @@ STATS_KINDS, STATS_PLANES, STATS_BINS = 2, 3, 256     # csic_code_stats_*: codes
 CODING_RAW, CODING_GROUPS = 0, 1        # csic_pack_* / .csic: the planes as they are (version 1), group-coded (version 3)
 CODING_RICE = 3                         # csic_rice_* / .csic version 4: Rice-coded (id 2 was never written)
 CODING_RANS = 5                         # csic_rans_* / .csic version 7: rANS-coded (id 4 was never written)
+QSWEEP_WIDTHS, QSWEEP_MAX_CANDIDATES, QSWEEP_MAX_TRIES = 8, 512, 4      # csic_qsweep_*: widths 1..8; (y, cb, cr) sets; encodes at most
 
 
 class IllegalArgumentException(ValueError):
@@ -108,6 +109,15 @@ class CsicDeltaLayout(C.Structure):
 class CsicMcLayout(C.Structure):
     _fields_ = [("groups", C.c_int64 * 3), ("width", C.c_int64 * 3), ("table_offset", C.c_int64 * 3), ("map_offset", C.c_int64 * 3),
                 ("map_bytes", C.c_int64), ("map_stride", C.c_int64), ("workspace_frame_bytes", C.c_int64)]
+
+
+class CsicQsweepResult(C.Structure):
+    _fields_ = [("sse", C.c_uint64 * QSWEEP_WIDTHS * STATS_PLANES), ("hist", C.c_uint64 * STATS_BINS * QSWEEP_WIDTHS * STATS_PLANES)]
+
+
+class CsicQsweepCandidate(C.Structure):
+    _fields_ = [("distortion", C.c_uint64), ("est_bytes", C.c_uint64), ("y_bits", C.c_int32), ("cb_bits", C.c_int32),
+                ("cr_bits", C.c_int32), ("reserved", C.c_int32)]
 
 
 class CsicContainerInfo(C.Structure):
@@ -208,6 +218,14 @@ PROTOTYPES = {
     "csic_code_stats_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p]),
     "csic_code_stats_kernel_name": (C.c_char_p, [C.c_void_p, C.c_int32]),
     "csic_code_stats_block_samples": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
+    "csic_qsweep_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
+    "csic_qsweep_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "csic_qsweep_hist_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "csic_qsweep_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    "csic_qsweep_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "csic_qsweep_block_samples": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "csic_qsweep_rank": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                   C.POINTER(CsicQsweepCandidate), C.POINTER(C.c_int32)]),
     "csic_plan_preferred_pitch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "csic_debug_build": (C.c_int, []),
     "csic_debug_probe_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -11,6 +11,7 @@ HIP launch.
 Two leading verbs go past what the reference's app does (it only ever writes the reconstructed pixels as a PNG):
 
     python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ... [--coding raw|groups|rice|rans]
+    python -m csic_amd.app compress   --input x.png --output x.csic --target-bytes N [--coding raw|groups|rice|rans] [--yq 8 --cbq 8 --crq 8: upper bounds]
     python -m csic_amd.app compress   --inputs a.png,b.png,... --gop K [--motion R] --coding groups|rice|rans --output x.csic ...
     python -m csic_amd.app decompress --input x.csic --output x.png [--frame K | --output-pattern frame_%03d.png]
 
@@ -98,6 +99,13 @@ class ImageCompressionApp:
         if coding not in ("raw", "groups", "rice", "rans"):
             raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: --coding must be rans, raw, groups or rice, got {coding!r}")
         inputImage = ImageProcessorModel.readImage(inputImagePath)
+        return ImageCompressionApp._compressFrame(inputImage, outputPath, chromaParamA, chromaParamB, yTargetBits, cbTargetBits, crTargetBits,
+                                                  spatialFactorToUse, op1, op2, op3, sampling, device, coding)
+
+    @staticmethod
+    def _compressFrame(inputImage, outputPath, chromaParamA, chromaParamB, yTargetBits, cbTargetBits, crTargetBits, spatialFactorToUse,
+                       op1, op2, op3, sampling, device, coding) -> int:
+        """compressImage behind its argument check and its PNG reader."""
         top = ImageCompressorTop(inputImage.width, inputImage.height, chromaParamA, chromaParamB, yTargetBits, cbTargetBits,
                                  crTargetBits, spatialFactorToUse, op1, op2, op3, device=device, sampling=sampling)
         try:
@@ -115,6 +123,59 @@ class ImageCompressionApp:
         finally:
             top.close()
         return os.path.getsize(outputPath)
+
+    @staticmethod
+    def compressImageToSize(inputImagePath: str, outputPath: str,
+                            chromaParamA: int, chromaParamB: int,
+                            yMaxBits: int, cbMaxBits: int, crMaxBits: int,
+                            spatialFactorToUse: int,
+                            op1: ProcessingStep, op2: ProcessingStep, op3: ProcessingStep,
+                            sampling: Sampling = Sampling.HOLD_DECIMATE, *, targetBytes: int, coding: str = "rans",
+                            weights=(1, 1, 1), device: int = 0) -> dict:
+        """PNG -> a .csic container of at most targetBytes bytes, with the bit widths (each at most yMaxBits / cbMaxBits / crMaxBits)
+        of least distortion that the budget allows.  The procedure:
+          1. Sweep the quantiser axis once (csic_qsweep_*), rank the bit sets (csic_qsweep_rank: ascending weighted distortion
+             w_y sse_Y + w_cb sse_Cb + w_cr sse_Cr, then est_bytes) and set r = 1.
+          2. Walk the candidates in rank order and skip those with est_bytes * r > targetBytes.
+          3. If none is left before any encode, refuse with IllegalArgumentException and write no file.
+          4. Encode the candidate with the device coder and the container writer, as compressImage does.
+          5. If the file is <= targetBytes, it is done.
+          6. Otherwise set r = max(r, size / est_bytes) and continue the walk behind that candidate.
+          7. Make at most CSIC_QSWEEP_MAX_TRIES = 4 encodes; after that, or when the walk ends, remove the file and raise
+             CsicRuntimeError ("not reachable in 4 tries").
+        With coding "raw" est_bytes is the file's size, so the first candidate that fits is written in one try.
+        Returns {"bits": (y, cb, cr), "est_bytes", "bytes", "tries", "psnr": (Y, Cb, Cr) from the sweep's table}."""
+        if coding not in ("raw", "groups", "rice", "rans"):
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: --coding must be rans, raw, groups or rice, got {coding!r}")
+        targetBytes = int(targetBytes)
+        if targetBytes < 80:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: --target-bytes must be at least the 80 bytes of a header, got {targetBytes}")
+        inputImage = ImageProcessorModel.readImage(inputImagePath)
+        top = ImageCompressorTop(inputImage.width, inputImage.height, chromaParamA, chromaParamB, 8, 8, 8, spatialFactorToUse, op1, op2, op3,
+                                 device=device, sampling=sampling)
+        try:
+            sweep = top.qsweep(inputImage.argb)
+        finally:
+            top.close()
+        ranked = sweep.rank(coding, weights, (yMaxBits, cbMaxBits, crMaxBits))
+        r, tries = 1.0, 0
+        for _, est, bits in ranked:
+            if est * r > targetBytes:
+                continue
+            if tries == N.QSWEEP_MAX_TRIES:
+                break
+            size = ImageCompressionApp._compressFrame(inputImage, outputPath, chromaParamA, chromaParamB, *bits, spatialFactorToUse, op1, op2, op3,
+                                                      sampling, device, coding)
+            tries += 1
+            if size <= targetBytes:
+                return {"bits": bits, "est_bytes": est, "bytes": size, "tries": tries,
+                        "psnr": tuple(sweep.psnr(p, q) for p, q in enumerate(bits))}
+            r = max(r, size / est)
+        if tries == 0:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: no bit set is estimated to fit {targetBytes} bytes "
+                                             f"(the smallest estimate is {min(e for _, e, _ in ranked)} bytes)")
+        os.remove(outputPath)
+        raise N.CsicRuntimeError(N.EINVAL_SIZE, f"{targetBytes} bytes not reachable in {N.QSWEEP_MAX_TRIES} tries ({tries} encodes made)")
 
     @staticmethod
     def compressSequence(inputImagePaths, outputPath: str,
@@ -265,6 +326,9 @@ def _main_container(verb: str, args: List[str]) -> int:
     --coding raw|groups|rice|rans."""
     argsMap = _args_map(args)
     if verb == "compress" and "--inputs" in argsMap:
+        if "--target-bytes" in argsMap:
+            print("[ERROR] --target-bytes takes one image (--input): sequences under a byte budget are not supported")
+            return 2
         return _main_sequence(argsMap)
     if verb == "decompress" and "--output-pattern" in argsMap and "--input" in argsMap:
         if not os.path.exists(argsMap["--input"]):
@@ -289,12 +353,46 @@ def _main_container(verb: str, args: List[str]) -> int:
     if coding not in ("raw", "groups", "rice", "rans"):
         print(f"[ERROR] --coding must be rans, raw, groups or rice, got {coding}")
         return 2
+    if "--target-bytes" in argsMap:
+        return _main_target(argsMap, inputPath, outputPath, sampling)
     size = ImageCompressionApp.compressImage(
         inputPath, outputPath, int(argsMap.get("--a", "4")), int(argsMap.get("--b", "4")), int(argsMap.get("--yq", "8")),
         int(argsMap.get("--cbq", "8")), int(argsMap.get("--crq", "8")), int(argsMap.get("--sf", "8")),
         ProcessingStep.parse(argsMap.get("--op1", "spatial")), ProcessingStep.parse(argsMap.get("--op2", "color")),
         ProcessingStep.parse(argsMap.get("--op3", "chroma")), sampling, coding=coding)
     print(f"Compression complete. {os.path.getsize(inputPath)} -> {size} bytes. Output saved to: {outputPath}")
+    return 0
+
+
+def _main_target(argsMap: Dict[str, str], inputPath: str, outputPath: str, sampling: Sampling) -> int:
+    """`compress --input x.png --output x.csic --target-bytes N [--coding raw|groups|rice|rans]`: --yq / --cbq / --crq are upper bounds."""
+    coding = argsMap.get("--coding", "rans").lower()
+    if coding not in ("raw", "groups", "rice", "rans"):
+        print(f"[ERROR] --coding must be rans, raw, groups or rice, got {coding}")
+        return 2
+    try:
+        target = int(argsMap["--target-bytes"])
+    except ValueError:
+        print(f"[ERROR] --target-bytes must be a number of bytes, got {argsMap['--target-bytes']}")
+        return 2
+    if target < 80:
+        print(f"[ERROR] --target-bytes must be at least the 80 bytes of a header, got {target}")
+        return 2
+    try:
+        got = ImageCompressionApp.compressImageToSize(
+            inputPath, outputPath, int(argsMap.get("--a", "4")), int(argsMap.get("--b", "4")), int(argsMap.get("--yq", "8")),
+            int(argsMap.get("--cbq", "8")), int(argsMap.get("--crq", "8")), int(argsMap.get("--sf", "8")),
+            ProcessingStep.parse(argsMap.get("--op1", "spatial")), ProcessingStep.parse(argsMap.get("--op2", "color")),
+            ProcessingStep.parse(argsMap.get("--op3", "chroma")), sampling, targetBytes=target, coding=coding)
+    except (N.IllegalArgumentException, N.CsicRuntimeError) as e:
+        if isinstance(e, N.CsicRuntimeError) and e.status != N.EINVAL_SIZE:
+            raise
+        print(f"[ERROR] {e}")
+        return 1
+    y, cb, cr = got["bits"]
+    print(f"Compression complete. Bits Y/Cb/Cr {y}/{cb}/{cr}, estimated {got['est_bytes']} bytes, written {got['bytes']} bytes "
+          f"(target {target}) in {got['tries']} tries. PSNR Y/Cb/Cr {got['psnr'][0]:.2f}/{got['psnr'][1]:.2f}/{got['psnr'][2]:.2f} dB. "
+          f"Output saved to: {outputPath}")
     return 0
 
 

@@ -155,6 +155,64 @@ class CodeStats:
                 f"H0={self.bits_per_pixel(0):.4f}, H1={self.bits_per_pixel(1):.4f}, best={self.bits_per_pixel('best'):.4f} bits/px)")
 
 
+class QSweep:
+    """The quantiser sweep of one frame, or of several frames together (csic_qsweep_*; definition in include/csic.h): sse[p][q - 1]
+    is the sum of squared errors of plane p (Y, Cb, Cr: index or name) at bit width q and hist[p][q - 1] the 256 counts of the
+    left-predicted residuals of that plane at that width, both uint64 and exact; with several frames the leading axis is the
+    frame.  psnr(p, q) is the plane's PSNR at width q over all frames; est_bytes(bits, coding) and rank(coding, weights, max_bits)
+    are csic_qsweep_rank's figures."""
+
+    PLANES = ("Y", "Cb", "Cr")
+    CODINGS = {"raw": N.CODING_RAW, "groups": N.CODING_GROUPS, "rice": N.CODING_RICE, "rans": N.CODING_RANS}
+
+    def __init__(self, result, c_params: N.CsicParams):
+        raw = np.ascontiguousarray(result).view(np.uint64).reshape(-1, C.sizeof(N.CsicQsweepResult) // 8)
+        self._raw = raw
+        self.nframes = raw.shape[0]
+        nsse = N.STATS_PLANES * N.QSWEEP_WIDTHS
+        self.sse = raw[:, :nsse].reshape(-1, N.STATS_PLANES, N.QSWEEP_WIDTHS)
+        self.hist = raw[:, nsse:].reshape(-1, N.STATS_PLANES, N.QSWEEP_WIDTHS, N.STATS_BINS)
+        if self.nframes == 1:
+            self.sse, self.hist = self.sse[0], self.hist[0]
+        self.c_params = c_params
+        self.pixels = c_params.width * c_params.height
+
+    def _plane(self, plane) -> int:
+        return self.PLANES.index(plane) if isinstance(plane, str) else int(plane)
+
+    @classmethod
+    def _coding(cls, coding) -> int:
+        return cls.CODINGS[coding] if isinstance(coding, str) else int(coding)
+
+    def psnr(self, plane, q: int) -> float:
+        e = int(self._raw[:, self._plane(plane) * N.QSWEEP_WIDTHS + int(q) - 1].sum())
+        return math.inf if e == 0 else 10.0 * math.log10(255.0 * 255.0 * self.pixels * self.nframes / e)
+
+    def rank(self, coding="rans", weights=(1, 1, 1), max_bits=(8, 8, 8)):
+        """Every (y, cb, cr) with 1 <= q_p <= max_bits[p] in ascending order of (distortion, est_bytes, y, cb, cr): a list of
+        (distortion, est_bytes, (y, cb, cr)) (csic_qsweep_rank)."""
+        if any(not 0 <= int(v) <= 255 for v in tuple(weights) + tuple(max_bits)) or len(weights) != 3 or len(max_bits) != 3:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: weights and max_bits are three values in 0..255")
+        w = (C.c_uint8 * 3)(*[int(v) for v in weights])
+        mb = (C.c_uint8 * 3)(*[int(v) for v in max_bits])
+        out = (N.CsicQsweepCandidate * N.QSWEEP_MAX_CANDIDATES)()
+        n = C.c_int32(N.QSWEEP_MAX_CANDIDATES)
+        N.check(N.lib().csic_qsweep_rank(C.byref(self.c_params), self._raw.ctypes.data_as(C.c_void_p), self.nframes, self._coding(coding),
+                                         w, mb, out, C.byref(n)))
+        return [(c.distortion, c.est_bytes, (c.y_bits, c.cb_bits, c.cr_bits)) for c in out[:n.value]]
+
+    def est_bytes(self, bits, coding="rans") -> int:
+        """The size estimate of the bit set `bits` = (y, cb, cr) under `coding`; exact for "raw"."""
+        bits = tuple(int(b) for b in bits)
+        for _, est, b in self.rank(coding, (1, 1, 1), bits):
+            if b == bits:
+                return est
+        raise AssertionError("csic_qsweep_rank lists every bit set up to max_bits")
+
+    def __repr__(self) -> str:
+        return f"QSweep(nframes={self.nframes}, pixels={self.pixels}, psnr_y8={self.psnr(0, 8):.2f}, psnr_y1={self.psnr(0, 1):.2f})"
+
+
 class Plan:
     """One validated parameter set bound to one HIP device (csic_plan_create / csic_plan_destroy)."""
 
@@ -357,6 +415,88 @@ class Plan:
         wy, wx = self.ssim_windows
         out = [Ssim(row, wy * wx) for row in sums]
         return out[0] if single and n == 1 else out
+
+    # -- quantiser sweep (csic_qsweep_*) -----------------------------------------------------------
+    @property
+    def qsweep_kernel_name(self) -> str:
+        return N.lib().csic_qsweep_kernel_name(self._h).decode()
+
+    @property
+    def qsweep_block_samples(self) -> int:
+        """Consecutive samples of a plane that one block of the histogram kernel counts (csic_qsweep_block_samples)."""
+        b = C.c_int64()
+        N.check(N.lib().csic_qsweep_block_samples(self._h, C.byref(b)))
+        return b.value
+
+    def qsweep_workspace_bytes(self, nframes: int = 1) -> int:
+        b = C.c_size_t()
+        N.check(N.lib().csic_qsweep_workspace_bytes(self._h, int(nframes), C.byref(b)))
+        return b.value
+
+    def _qsweep_result(self, nframes: int, device, d_result):
+        import torch
+        words = C.sizeof(N.CsicQsweepResult) // 8
+        if d_result is None:
+            return torch.empty((nframes, words), dtype=torch.int64, device=device)
+        if d_result.numel() != nframes * words or d_result.element_size() != 8 or not d_result.is_contiguous():
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: d_result must be a contiguous 8-byte tensor of nframes * {words}")
+        return d_result
+
+    def qsweep_device(self, d_in, nframes: int = 1, d_result=None):
+        """d_in: contiguous 4-byte CUDA tensor of nframes * W * H input pixels.  Returns an int64 tensor (nframes, 6168) on the
+        device: each frame's csic_qsweep_result as 64-bit words (QSweep reads it).  Asynchronous on torch's current stream; the plan
+        keeps its workspace between calls (allocate it with a first call before capturing the call into a graph)."""
+        import torch
+        if not d_in.is_cuda or d_in.element_size() != 4 or not d_in.is_contiguous():
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_in must be a contiguous 4-byte CUDA tensor")
+        if d_in.device.index != self.device:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: tensor is on a different device than the plan")
+        if d_in.numel() != nframes * self.width * self.height:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: expected {nframes * self.width * self.height} input pixels, got {d_in.numel()}")
+        need = self.qsweep_workspace_bytes(nframes)
+        ws = getattr(self, "_qsweep_ws", None)
+        if ws is None or ws.numel() < need or ws.device != d_in.device:
+            ws = torch.empty(need, dtype=torch.uint8, device=d_in.device)
+            self._qsweep_ws = ws
+        d_result = self._qsweep_result(nframes, d_in.device, d_result)
+        N.check(N.lib().csic_qsweep_device(self._h, C.c_void_p(d_in.data_ptr()), int(nframes), C.c_void_p(d_result.data_ptr()),
+                                           C.c_void_p(ws.data_ptr()), ws.numel(), self._stream()))
+        return d_result
+
+    def qsweep_hist_device(self, d_planar, nframes: int = 1, d_result=None):
+        """d_planar: contiguous CUDA tensor of nframes CSIC_FMT_PLANAR frame buffers.  Fills `hist` of d_result (as qsweep_device
+        returns it; a new one is zeroed first) and leaves its `sse` as it was (csic_qsweep_hist_device)."""
+        import torch
+        if not d_planar.is_cuda or not d_planar.is_contiguous() or d_planar.numel() * d_planar.element_size() != nframes * self.planar_layout.frame_bytes:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_planar must be a contiguous CUDA tensor of nframes PLANAR frames")
+        if d_planar.device.index != self.device:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: tensor is on a different device than the plan")
+        if d_result is None:
+            d_result = torch.zeros((nframes, C.sizeof(N.CsicQsweepResult) // 8), dtype=torch.int64, device=d_planar.device)
+        d_result = self._qsweep_result(nframes, d_planar.device, d_result)
+        N.check(N.lib().csic_qsweep_hist_device(self._h, C.c_void_p(d_planar.data_ptr()), int(nframes), C.c_void_p(d_result.data_ptr()),
+                                                self._stream()))
+        return d_result
+
+    def qsweep_host(self, frames: np.ndarray, nframes: int = 1) -> np.ndarray:
+        """csic_qsweep_host: nframes * W * H host pixels -> uint64 array (nframes, 6168)."""
+        a = np.ascontiguousarray(frames, dtype=np.uint32).reshape(-1)
+        res = np.zeros((nframes, C.sizeof(N.CsicQsweepResult) // 8), dtype=np.uint64)
+        N.check(N.lib().csic_qsweep_host(self._h, a.ctypes.data_as(C.c_void_p), a.size, int(nframes), res.ctypes.data_as(C.c_void_p)))
+        return res
+
+    def qsweep(self, frames) -> QSweep:
+        """One frame ((H, W), or flat W * H) or a stack (n, H, W) -> QSweep.  numpy input goes through csic_qsweep_host, a CUDA
+        tensor through qsweep_device (synchronised here)."""
+        px = self.width * self.height
+        if _is_torch_tensor(frames):
+            n = frames.numel() // px if px else 0
+            res = self.qsweep_device(frames.contiguous().reshape(-1), n).cpu().numpy()
+        else:
+            a = np.asarray(frames)
+            n = a.size // px if px else 0
+            res = self.qsweep_host(a, n)
+        return QSweep(res, self.c_params)
 
     # -- code statistics (csic_code_stats_*) ------------------------------------------------------
     def _stats_format(self, src_format) -> int:
@@ -970,6 +1110,11 @@ class ImageCompressorTop:
         """How much of the structure of `argb` (one frame, or a stack (n, H, W)) these parameters keep: Ssim (list of them for a
         stack) -- the per-channel 8 x 8 block SSIM against the packed ARGB / YCbCr outputs."""
         return self.plan(PixelFormat.ARGB8888).ssim(argb)
+
+    def qsweep(self, argb) -> QSweep:
+        """Rate and distortion of every (y, cb, cr) bit set of these parameters on `argb` (one frame, or a stack (n, H, W)) from one
+        pass: QSweep (csic_qsweep_*).  The three bit widths this compressor was built with do not matter."""
+        return self.plan(PixelFormat.ARGB8888).qsweep(argb)
 
     def codeStats(self, argb):
         """What the samples of `argb`'s compressed frame really carry: CodeStats of its bit-packed planes (csic_code_stats_*).  A

@@ -70,27 +70,35 @@ __device__ __forceinline__ u32x4 in4n_or_1n(const KArgs &a, gin_t in, uint32_t o
 // One block per frame: frame blockIdx.x's nblk partials of MEAS_CH 64-bit words, summed in a fixed order (so that a result does
 // not depend on how the blocks were scheduled), -> sums[frame * MEAS_CH + channel].  The words are SSE partials (uint64_t) or
 // SSIM partials (int64_t, possibly negative): two's-complement addition is the same instruction for both, so one element type
-// serves.  `static`: each unit compiles its own copy into its own code object.
-static __global__ void __launch_bounds__(MEAS_T) k_sum_partials(const uint64_t *part, uint32_t nblk, uint64_t *sums)
+// serves.  CH words per partial, and frame z's sums at sums[z * STRIDE]: the two measurement units have CH = STRIDE = MEAS_CH, the
+// quantiser sweep (csic_qsweep.hip) 24 words into a larger per-frame result.
+template <int CH, int STRIDE>
+__device__ __forceinline__ void sum_partials(const uint64_t *part, uint32_t nblk, uint64_t *sums)
 {
     typedef const uint64_t CSIC_GLOBAL *gcpart_t;
     typedef uint64_t CSIC_GLOBAL *gsum_t;
-    const gcpart_t p = (gcpart_t)(uintptr_t)part + (uint64_t)blockIdx.x * nblk * MEAS_CH;
-    uint64_t t[MEAS_CH] = {0, 0, 0, 0, 0, 0};
+    const gcpart_t p = (gcpart_t)(uintptr_t)part + (uint64_t)blockIdx.x * nblk * CH;
+    uint64_t t[CH] = {};
     for (uint32_t b = threadIdx.x; b < nblk; b += MEAS_T)
 #pragma unroll
-        for (int ch = 0; ch < MEAS_CH; ++ch) t[ch] += p[(uint64_t)b * MEAS_CH + ch];
-    __shared__ uint64_t red[MEAS_T][MEAS_CH];
+        for (int ch = 0; ch < CH; ++ch) t[ch] += p[(uint64_t)b * CH + ch];
+    __shared__ uint64_t red[MEAS_T][CH];
 #pragma unroll
-    for (int ch = 0; ch < MEAS_CH; ++ch) red[threadIdx.x][ch] = t[ch];
+    for (int ch = 0; ch < CH; ++ch) red[threadIdx.x][ch] = t[ch];
     __syncthreads();
     for (int w = MEAS_T / 2; w > 0; w >>= 1) {
         if ((int)threadIdx.x < w)
 #pragma unroll
-            for (int ch = 0; ch < MEAS_CH; ++ch) red[threadIdx.x][ch] += red[threadIdx.x + w][ch];
+            for (int ch = 0; ch < CH; ++ch) red[threadIdx.x][ch] += red[threadIdx.x + w][ch];
         __syncthreads();
     }
-    if (threadIdx.x < (unsigned)MEAS_CH) ((gsum_t)(uintptr_t)sums)[(uint64_t)blockIdx.x * MEAS_CH + threadIdx.x] = red[0][threadIdx.x];
+    if (threadIdx.x < (unsigned)CH) ((gsum_t)(uintptr_t)sums)[(uint64_t)blockIdx.x * STRIDE + threadIdx.x] = red[0][threadIdx.x];
+}
+
+// `static`: each unit compiles its own copy into its own code object (csic_qsweep.hip, which has its own width, none).
+__attribute__((unused)) static __global__ void __launch_bounds__(MEAS_T) k_sum_partials(const uint64_t *part, uint32_t nblk, uint64_t *sums)
+{
+    sum_partials<MEAS_CH, MEAS_CH>(part, nblk, sums);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -377,6 +377,71 @@ int  csic_code_stats_host(csic_plan *plan, const void *src, size_t src_bytes, in
 const char *csic_code_stats_kernel_name(const csic_plan *plan, int32_t src_format);
 int  csic_code_stats_block_samples(const csic_plan *plan, int32_t src_format, int64_t *samples);   /* samples one block covers; needs no device */
 
+/* ---- quantiser sweep: rate and distortion of all 512 bit sets of a plan in one pass ---------------------------------------------
+ * The quantiser is three AND masks and commutes with every other stage (AVG applies it last), and the three YCbCr channels are
+ * independent: the Y error depends on y_bits alone, and so on.  So 8 widths x 3 planes = 24 sums and 24 histograms describe every
+ * (y_bits, cb_bits, cr_bits) of a plan.  Per frame, frames back to back:
+ *     sse[p][q-1]  = element 3 + p of csic_distortion_* for the same plan with plane p's bit width set to q (p = 0, 1, 2: Y, Cb, Cr;
+ *                    the other two widths do not matter): pairing, reference channels, ragged edges, orders and AVG as defined there.
+ *     hist[p][q-1] = kind 1 (residuals), plane p of csic_code_stats_* on the CSIC_FMT_PLANAR output of the same plan with that
+ *                    width: storage order, e_0 = c_0, no special case per row; bins >= 2^q are 0.
+ * The plan's own three bit widths and its out_format are ignored.  ARGB input only (CSIC_EINVAL_FORMAT otherwise), the scope of
+ * CSIC_FMT_PLANAR_BITS.  Every figure is an exact integer and does not depend on scheduling.
+ *
+ * csic_qsweep_workspace_bytes : the workspace csic_qsweep_device needs for `nframes` (1..65535) frames: one 192-byte partial per
+ *                               block of the SSE kernel, rounded up to 256 bytes, then nframes 8/8/8 CSIC_FMT_PLANAR frames.  Needs
+ *                               no device; query again after csic_plan_tune.
+ * csic_qsweep_device      : d_in -> d_result[nframes] (8-byte aligned) through d_workspace (256-byte aligned, at least the queried
+ *                           size).  Asynchronous on `hip_stream`, no allocation, no synchronisation, hipGraph-capturable: `hist` is
+ *                           cleared by a kernel, blocks count in LDS and add their non-zero bins with 64-bit atomics.  One pass over
+ *                           the input for the sums (k_qsweep_sse_fast for the plans k_dist_fast serves, k_qsweep_sse_gen otherwise),
+ *                           the plan's planar kernel at 8/8/8 into the workspace, and one pass over those planes (k_qsweep_hist).
+ *                           NULL arguments fail with CSIC_EINVAL_NULL; nframes outside 1..65535, a d_in that is not 4-byte, a d_result
+ *                           that is not 8-byte or a workspace that is not 256-byte aligned with CSIC_EINVAL_SIZE; a YCbCr input with
+ *                           CSIC_EINVAL_FORMAT -- all before any device is touched; then CSIC_ENODEVICE on a machine without a
+ *                           device, and CSIC_EINVAL_SIZE for a workspace smaller than the queried size.
+ * csic_qsweep_hist_device : the rate half alone, on given CSIC_FMT_PLANAR frames (256-byte aligned, frame_bytes apart, the low bits
+ *                           of a byte are cut per width, so the frame is an 8/8/8 one or carries junk there): writes `hist` of
+ *                           d_result[nframes] and leaves `sse` untouched.  Same refusals.
+ * csic_qsweep_host        : csic_qsweep_device from host memory (in_px = nframes * width * height); synchronous, allocates its staging.
+ * csic_qsweep_kernel_name : the SSE kernel csic_qsweep_device takes (static string; "" for a NULL plan).
+ * csic_qsweep_block_samples : consecutive samples of a plane that one block of k_qsweep_hist counts.  Needs no device.
+ *
+ * csic_qsweep_rank (host arithmetic, no device): sums the results of `nframes` frames and lists every (y, cb, cr) with
+ * 1 <= q_p <= max_bits[p] (max_bits NULL: 8, 8, 8; a value outside 1..8: CSIC_EINVAL_BITS), in ascending order of
+ * (distortion, est_bytes, y_bits, cb_bits, cr_bits).  On entry *n is the capacity of `out` (CSIC_EINVAL_SIZE when it is less than
+ * max_bits[0] * max_bits[1] * max_bits[2]), on return the number of candidates written.
+ *     distortion = w_0 sse_Y + w_1 sse_Cb + w_2 sse_Cr, exact uint64; weights 1..255 (NULL: 1, 1, 1; 0: CSIC_EINVAL_SIZE); a sum
+ *                  that leaves 64 bits and a frame of more than 2^30 pixels are refused with CSIC_EINVAL_SIZE.
+ *     est_bytes, coding = CSIC_CODING_GROUPS, CSIC_CODING_RICE or CSIC_CODING_RANS: with N_p the total of hist[p][q_p-1] (the
+ *                  plane's samples over all frames) and H its zero-order entropy (double precision, as in the derived figures of
+ *                  csic_code_stats_*), bits_p = min(N_p q_p, N_p H) and est_bytes = 80 + sum_p ceil(bits_p / 8).
+ *     est_bytes, coding = CSIC_CODING_RAW: the exact size of the file, 80 + nframes * payload_bytes of csic_planar_bits_layout_of
+ *                  for those widths.  Another coding: CSIC_EINVAL_FORMAT.
+ * p->y_bits, cb_bits, cr_bits and out_format are ignored; p->in_format must be ARGB (CSIC_EINVAL_FORMAT). */
+#define CSIC_QSWEEP_WIDTHS         8
+#define CSIC_QSWEEP_MAX_CANDIDATES 512
+#define CSIC_QSWEEP_MAX_TRIES      4     /* encodes the host layers' size-targeted compression makes at most */
+typedef struct csic_qsweep_result {
+    uint64_t sse[CSIC_STATS_PLANES][CSIC_QSWEEP_WIDTHS];                     /* plane p = Y, Cb, Cr; index q - 1 for width q = 1..8 */
+    uint64_t hist[CSIC_STATS_PLANES][CSIC_QSWEEP_WIDTHS][CSIC_STATS_BINS];   /* residual histogram of plane p at width q          */
+} csic_qsweep_result;
+typedef struct csic_qsweep_candidate {
+    uint64_t distortion;
+    uint64_t est_bytes;
+    int32_t y_bits, cb_bits, cr_bits;
+    int32_t reserved;                     /* 0 */
+} csic_qsweep_candidate;
+int  csic_qsweep_workspace_bytes(const csic_plan *plan, int32_t nframes, size_t *bytes);
+int  csic_qsweep_device(csic_plan *plan, const void *d_in, int32_t nframes, csic_qsweep_result *d_result,
+                        void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int  csic_qsweep_hist_device(csic_plan *plan, const void *d_planar, int32_t nframes, csic_qsweep_result *d_result, void *hip_stream);
+int  csic_qsweep_host(csic_plan *plan, const uint32_t *in, size_t in_px, int32_t nframes, csic_qsweep_result *result);
+const char *csic_qsweep_kernel_name(const csic_plan *plan);
+int  csic_qsweep_block_samples(const csic_plan *plan, int64_t *samples);
+int  csic_qsweep_rank(const csic_params *p, const csic_qsweep_result *r, int32_t nframes, int32_t coding, const uint8_t weights[3],
+                      const uint8_t max_bits[3], csic_qsweep_candidate *out, int32_t *n);
+
 const char *csic_strerror(int status);
 const char *csic_last_error(void);       /* thread-local; "" when the last call succeeded */
 

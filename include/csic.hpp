@@ -394,6 +394,18 @@ struct CodeStats {
     }
 };
 
+// The candidates of a quantiser sweep in rank order (csic.h: csic_qsweep_rank): `results` holds one csic_qsweep_result per frame,
+// weights are 1..255, max_bits 1..8; ascending (distortion, est_bytes, y_bits, cb_bits, cr_bits).
+inline std::vector<csic_qsweep_candidate> qsweepRank(const csic_params &p, const std::vector<csic_qsweep_result> &results, int coding = CSIC_CODING_RANS,
+                                                     const uint8_t (&weights)[3] = {1, 1, 1}, const uint8_t (&max_bits)[3] = {8, 8, 8})
+{
+    std::vector<csic_qsweep_candidate> out(CSIC_QSWEEP_MAX_CANDIDATES);
+    int32_t n = (int32_t)out.size();
+    check(csic_qsweep_rank(&p, results.data(), (int32_t)results.size(), coding, weights, max_bits, out.data(), &n));
+    out.resize((size_t)n);
+    return out;
+}
+
 // One validated parameter set bound to one device (csic_plan_create / csic_plan_destroy), for what works on compressed frames of
 // known parameters -- a container's, for instance -- rather than on an image.
 class Plan {
@@ -700,6 +712,29 @@ public:
         check(csic_ssim_device(plan(PixelFormat::ARGB8888), d_in, nframes, d_ssim, d_map, d_workspace, workspace_bytes, hip_stream));
     }
     const char *ssimKernelName() { return csic_ssim_kernel_name(plan(PixelFormat::ARGB8888)); }
+    // Rate and distortion of every (y, cb, cr) bit set of these parameters in one pass (csic.h: csic_qsweep_*): `nframes` ARGB frames
+    // back to back (host memory) -> one csic_qsweep_result per frame; csic::qsweepRank ranks them.  The three bit widths this object
+    // was built with do not matter.
+    std::vector<csic_qsweep_result> qsweep(const uint32_t *argb, int nframes = 1)
+    {
+        std::vector<csic_qsweep_result> out((size_t)(nframes > 0 ? nframes : 0));
+        const size_t px = (size_t)params_.width * (size_t)params_.height;
+        check(csic_qsweep_host(plan(PixelFormat::ARGB8888), argb, px * out.size(), nframes, out.data()));
+        return out;
+    }
+    // device-resident: d_result receives nframes results (8-byte aligned), d_workspace (256-byte aligned) at least
+    // qsweepWorkspaceBytes(nframes) bytes; asynchronous on `hip_stream`, no allocation, capturable.
+    size_t qsweepWorkspaceBytes(int nframes = 1)
+    {
+        size_t b = 0;
+        check(csic_qsweep_workspace_bytes(plan(PixelFormat::ARGB8888), nframes, &b));
+        return b;
+    }
+    void qsweepDevice(const void *d_in, int nframes, csic_qsweep_result *d_result, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+    {
+        check(csic_qsweep_device(plan(PixelFormat::ARGB8888), d_in, nframes, d_result, d_workspace, workspace_bytes, hip_stream));
+    }
+    const char *qsweepKernelName() { return csic_qsweep_kernel_name(plan(PixelFormat::ARGB8888)); }
     // What the samples of an ARGB frame's compressed form really carry: compresses to bit-packed planes, then measures them
     // (csic_code_stats_*), host memory in, CodeStats out.
     CodeStats codeStats(const std::vector<uint32_t> &argb)
