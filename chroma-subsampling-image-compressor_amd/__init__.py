@@ -14,7 +14,7 @@ from .pipeline import FramePipeline
 from .stages import (ChromaSubsampler, ColorQuantizer, PixelBundle, PixelYCbCrBundle, ReferenceModel, RGB2YCbCr,
                      SpatialDownsampler, YCbCrUtils, pack_ycc, unpack_ycc)
 from .container import (container_coded_sizes, container_info, container_inter_groups, delta_host, delta_layout, undelta_host,
-                        mc_delta_host, mc_layout, mc_undelta_host, pack_frame_host, pack_layout, read_container, rans_layout, rans_pack_host,
+                        mc_delta_host, mc_layout, mc_undelta_host, rows_host, rows_layout, unrows_host, pack_frame_host, pack_layout, read_container, rans_layout, rans_pack_host,
                         rans_unpack_host, rice_layout, rice_pack_host, rice_unpack_host, unpack_frame_host, write_container, write_container_coded)
 from .app import ImageCompressionApp
 from .distributed import MultiDeviceCompressor, Stripe, StripedImageCompressorTop, halo_stripe_for_rank, stripe_for_rank
@@ -27,5 +27,5 @@ __all__ = [
     "SpatialDownsampler", "YCbCrUtils", "pack_ycc", "unpack_ycc", "Stripe", "StripedImageCompressorTop", "MultiDeviceCompressor", "halo_stripe_for_rank", "stripe_for_rank",
     "container_info", "read_container", "write_container", "write_container_coded", "container_coded_sizes", "pack_layout", "pack_frame_host",
     "unpack_frame_host", "rice_layout", "rice_pack_host", "rice_unpack_host", "rans_layout", "rans_pack_host", "rans_unpack_host", "delta_layout", "delta_host", "undelta_host",
-    "mc_layout", "mc_delta_host", "mc_undelta_host", "container_inter_groups",
+    "mc_layout", "mc_delta_host", "mc_undelta_host", "rows_layout", "rows_host", "unrows_host", "container_inter_groups",
 ]

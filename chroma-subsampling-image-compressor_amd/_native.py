@@ -31,6 +31,7 @@ STATS_KINDS, STATS_PLANES, STATS_BINS = 2, 3, 256     # csic_code_stats_*: codes
 CODING_RAW, CODING_GROUPS = 0, 1        # csic_pack_* / .csic: the planes as they are (version 1), group-coded (version 3)
 CODING_RICE = 3                         # csic_rice_* / .csic version 4: Rice-coded (id 2 was never written)
 CODING_RANS = 5                         # csic_rans_* / .csic version 7: rANS-coded (id 4 was never written)
+ROWS_BAND = 16                         # CSIC_ROWS_BAND: the dependent steps of a band of the row-prediction layer (csic_rows_*)
 QSWEEP_WIDTHS, QSWEEP_MAX_CANDIDATES, QSWEEP_MAX_TRIES = 8, 512, 4      # csic_qsweep_*: widths 1..8; (y, cb, cr) sets; encodes at most
 
 
@@ -111,6 +112,11 @@ class CsicMcLayout(C.Structure):
                 ("map_bytes", C.c_int64), ("map_stride", C.c_int64), ("workspace_frame_bytes", C.c_int64)]
 
 
+class CsicRowsLayout(C.Structure):
+    _fields_ = [("groups", C.c_int64 * 3), ("width", C.c_int64 * 3), ("k", C.c_int64 * 3), ("band", C.c_int64 * 3), ("map_offset", C.c_int64 * 3),
+                ("map_bytes", C.c_int64), ("map_stride", C.c_int64)]
+
+
 class CsicQsweepResult(C.Structure):
     _fields_ = [("sse", C.c_uint64 * QSWEEP_WIDTHS * STATS_PLANES), ("hist", C.c_uint64 * STATS_BINS * QSWEEP_WIDTHS * STATS_PLANES)]
 
@@ -173,6 +179,10 @@ PROTOTYPES = {
     "csic_container_write_coded_seq_ex": (C.c_int, [C.c_char_p, C.POINTER(CsicParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t,
                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "csic_container_motion": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
+    "csic_container_write_rows": (C.c_int, [C.c_char_p, C.POINTER(CsicParams), C.c_void_p, C.c_int32, C.c_int32]),
+    "csic_container_write_coded_rows": (C.c_int, [C.c_char_p, C.POINTER(CsicParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t,
+                                                  C.c_int32, C.c_int32]),
+    "csic_container_rows": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
     "csic_pack_layout_of": (C.c_int, [C.POINTER(CsicParams), C.POINTER(CsicPackLayout)]),
     "csic_pack_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "csic_unpack_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -206,6 +216,12 @@ PROTOTYPES = {
     "csic_mc_delta_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "csic_mc_undelta_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "csic_mc_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "csic_rows_layout_of": (C.c_int, [C.POINTER(CsicParams), C.POINTER(CsicRowsLayout)]),
+    "csic_rows_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "csic_unrows_host": (C.c_int, [C.POINTER(CsicParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "csic_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "csic_unrows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "csic_rows_kernel_name": (C.c_char_p, [C.c_void_p]),
     "csic_distortion_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
     "csic_distortion_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "csic_distortion_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_uint64)]),

@@ -11,6 +11,7 @@ HIP launch.
 Two leading verbs go past what the reference's app does (it only ever writes the reconstructed pixels as a PNG):
 
     python -m csic_amd.app compress   --input x.png --output x.csic --a 2 --b 0 --yq 6 --cbq 5 --crq 5 --sf 2 ... [--coding raw|groups|rice|rans]
+    python -m csic_amd.app compress   --input x.png --output x.csic --coding groups|rice|rans --rows ...      (row prediction in front of the coder: version 8)
     python -m csic_amd.app compress   --input x.png --output x.csic --target-bytes N [--coding raw|groups|rice|rans] [--yq 8 --cbq 8 --crq 8: upper bounds]
     python -m csic_amd.app compress   --inputs a.png,b.png,... --gop K [--motion R] --coding groups|rice|rans --output x.csic ...
     python -m csic_amd.app decompress --input x.csic --output x.png [--frame K | --output-pattern frame_%03d.png]
@@ -35,8 +36,8 @@ import numpy as np
 
 from .compressor import ImageCompressorTop, Plan
 from . import _native as N
-from .container import (container_coded_sizes, container_info, container_inter_groups, delta_layout, mc_layout, rans_layout, read_container, write_container,
-                        write_container_coded)
+from .container import (container_coded_sizes, container_info, container_inter_groups, delta_layout, mc_layout, rans_layout, read_container, rows_layout,
+                        write_container, write_container_coded)
 from .model import Image, ImageProcessorModel
 from .params import PixelFormat, ProcessingStep, Sampling
 
@@ -93,18 +94,21 @@ class ImageCompressionApp:
                       yTargetBits: int, cbTargetBits: int, crTargetBits: int,
                       spatialFactorToUse: int,
                       op1: ProcessingStep, op2: ProcessingStep, op3: ProcessingStep,
-                      sampling: Sampling = Sampling.HOLD_DECIMATE, *, device: int = 0, coding: str = "raw") -> int:
+                      sampling: Sampling = Sampling.HOLD_DECIMATE, *, device: int = 0, coding: str = "raw", rows: bool = False) -> int:
         """PNG -> CSIC_FMT_PLANAR_BITS plan -> .csic container.  Returns the bytes written (coding "raw": 80 + payload_bytes;
-        "groups" / "rice" / "rans": the frame is coded on the device and goes out through csic_container_write_coded_ex)."""
+        "groups" / "rice" / "rans": the frame is coded on the device and goes out through csic_container_write_coded_ex).  rows: the
+        row-prediction layer (csic_rows_device) in front of the coder, version 8; it needs a coding other than "raw"."""
         if coding not in ("raw", "groups", "rice", "rans"):
             raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: --coding must be rans, raw, groups or rice, got {coding!r}")
+        if rows and coding == "raw":
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, "requirement failed: --rows needs --coding rans, groups or rice: the layer gains nothing without a coder")
         inputImage = ImageProcessorModel.readImage(inputImagePath)
         return ImageCompressionApp._compressFrame(inputImage, outputPath, chromaParamA, chromaParamB, yTargetBits, cbTargetBits, crTargetBits,
-                                                  spatialFactorToUse, op1, op2, op3, sampling, device, coding)
+                                                  spatialFactorToUse, op1, op2, op3, sampling, device, coding, rows)
 
     @staticmethod
     def _compressFrame(inputImage, outputPath, chromaParamA, chromaParamB, yTargetBits, cbTargetBits, crTargetBits, spatialFactorToUse,
-                       op1, op2, op3, sampling, device, coding) -> int:
+                       op1, op2, op3, sampling, device, coding, rows=False) -> int:
         """compressImage behind its argument check and its PNG reader."""
         top = ImageCompressorTop(inputImage.width, inputImage.height, chromaParamA, chromaParamB, yTargetBits, cbTargetBits,
                                  crTargetBits, spatialFactorToUse, op1, op2, op3, device=device, sampling=sampling)
@@ -115,8 +119,13 @@ class ImageCompressionApp:
                 import torch
                 d_in = torch.from_numpy(np.ascontiguousarray(inputImage.argb, dtype=np.uint32).reshape(-1).view(np.int32)).to(f"cuda:{device}")
                 pack = {"groups": plan.pack_device, "rice": plan.rice_pack_device, "rans": plan.rans_pack_device}[coding]
-                coded, sizes = pack(plan.process_device(d_in))
-                write_container_coded(outputPath, plan.c_params, coded.cpu().numpy(), sizes.cpu().numpy(), coding=coding)
+                bits = plan.process_device(d_in)
+                maps = None
+                if rows:                                    # the difference frame is what the coder packs
+                    bits, maps = plan.rows_device(bits.reshape(1, plan.frame_bytes))
+                coded, sizes = pack(bits)
+                write_container_coded(outputPath, plan.c_params, coded.cpu().numpy(), sizes.cpu().numpy(), coding=coding,
+                                      maps=None if maps is None else maps.cpu().numpy(), rows=rows)
             else:
                 bits = plan.process_host(inputImage.argb)
                 write_container(outputPath, plan.c_params, bits)
@@ -324,7 +333,11 @@ def _args_map(args: List[str]) -> Dict[str, str]:
 def _main_container(verb: str, args: List[str]) -> int:
     """`compress` / `decompress`: the keys of the verb-less CLI with its defaults, plus --output and (compress) --sampling avg and
     --coding raw|groups|rice|rans."""
-    argsMap = _args_map(args)
+    rows = verb == "compress" and "--rows" in args          # a flag without a value: taken out before the pairs are read
+    argsMap = _args_map([a for a in args if not (rows and a == "--rows")])
+    if rows and ("--inputs" in argsMap or "--gop" in argsMap or "--motion" in argsMap or "--target-bytes" in argsMap):
+        print("[ERROR] --rows takes one image (--input) and a coding: it does not combine with --inputs, --gop, --motion or --target-bytes")
+        return 2
     if verb == "compress" and "--inputs" in argsMap:
         if "--target-bytes" in argsMap:
             print("[ERROR] --target-bytes takes one image (--input): sequences under a byte budget are not supported")
@@ -353,13 +366,16 @@ def _main_container(verb: str, args: List[str]) -> int:
     if coding not in ("raw", "groups", "rice", "rans"):
         print(f"[ERROR] --coding must be rans, raw, groups or rice, got {coding}")
         return 2
+    if rows and coding == "raw":
+        print("[ERROR] --rows needs --coding rans, groups or rice: the layer gains nothing without a coder")
+        return 2
     if "--target-bytes" in argsMap:
         return _main_target(argsMap, inputPath, outputPath, sampling)
     size = ImageCompressionApp.compressImage(
         inputPath, outputPath, int(argsMap.get("--a", "4")), int(argsMap.get("--b", "4")), int(argsMap.get("--yq", "8")),
         int(argsMap.get("--cbq", "8")), int(argsMap.get("--crq", "8")), int(argsMap.get("--sf", "8")),
         ProcessingStep.parse(argsMap.get("--op1", "spatial")), ProcessingStep.parse(argsMap.get("--op2", "color")),
-        ProcessingStep.parse(argsMap.get("--op3", "chroma")), sampling, coding=coding)
+        ProcessingStep.parse(argsMap.get("--op3", "chroma")), sampling, coding=coding, rows=rows)
     print(f"Compression complete. {os.path.getsize(inputPath)} -> {size} bytes. Output saved to: {outputPath}")
     return 0
 
@@ -491,6 +507,14 @@ def _main_inspect(args: List[str]) -> int:
             for i, name in enumerate(("Y", "Cb", "Cr")):
                 b0 = sum(rl.blocks[:i])
                 print(f"    frame 0, {name}: {int(np.count_nonzero(directory[b0:b0 + rl.blocks[i]] >> 31))} of {rl.blocks[i]} blocks raw")
+    elif info.version == 8:
+        print(f"Frame coding: {({1: 'groups', 3: 'rice', 5: 'rans'})[info.coding]}, row prediction (bands of {N.ROWS_BAND} steps)")
+        groups = [int(g) for g in rows_layout(p).groups]
+        above = container_inter_groups(inputPath)
+        for k, stored in enumerate(container_coded_sizes(inputPath)):
+            print(f"  frame {k}: stored in {int(stored)} bytes, {int(stored) / info.payload_bytes:.4f} of raw")
+            for i, name in enumerate(("Y", "Cb", "Cr")):
+                print(f"    frame {k}, {name}: {int(above[k][i])} of {groups[i]} groups ({100.0 * int(above[k][i]) / max(groups[i], 1):.1f}%) predicted from the row above")
     else:
         print(f"Frame coding: {({3: 'groups', 4: 'rice'}).get(info.version, 'raw')}")
         for k, stored in enumerate(container_coded_sizes(inputPath)):

@@ -19,7 +19,7 @@ from typing import Tuple
 import numpy as np
 
 from . import _native as N
-from .container import (delta_host, delta_layout, mc_delta_host, mc_layout, mc_undelta_host, pack_frame_host, rans_pack_host, rans_unpack_host,
+from .container import (delta_host, delta_layout, mc_delta_host, mc_layout, mc_undelta_host, rows_host, rows_layout, unrows_host, pack_frame_host, rans_pack_host, rans_unpack_host,
                         rice_pack_host, rice_unpack_host, undelta_host, unpack_frame_host)
 from .params import (ImageProcessorParams, PixelFormat, ProcessingStep, Rounding, Sampling, make_c_params)
 
@@ -793,6 +793,44 @@ class Plan:
     def mc_undelta(self, diff, maps, gop: int, out=None) -> np.ndarray:
         """csic_mc_undelta_host: the inverse; damaged maps raise CsicIOError."""
         return mc_undelta_host(self.c_params, diff, maps, gop, out)
+
+    # -- row prediction of PLANAR_BITS frames in front of a coder (csic_rows_*) ----------------------------
+    @property
+    def rows_layout(self) -> N.CsicRowsLayout:
+        """csic_rows_layout of these parameters: groups, row widths, K, S, the map's section offsets, map_bytes, map_stride."""
+        return rows_layout(self.c_params)
+
+    @property
+    def rows_kernel_name(self) -> str:
+        return N.lib().csic_rows_kernel_name(self._h).decode()
+
+    def rows_device(self, d_frames, nframes: int = 1, d_diff=None, d_maps=None):
+        """d_frames: nframes PLANAR_BITS frame buffers on the device (frame_bytes each).  Returns (diff, maps): the difference frames, a
+        uint8 tensor (nframes, frame_bytes) of which only the payload ranges are written -- not in place: `d_diff` must lie apart from
+        `d_frames` -- and the maps, uint8 (nframes, rows_layout.map_stride) with map_bytes of each row written.  Any coder then packs
+        `diff` as it packs frames.  Asynchronous on torch's current stream."""
+        d_diff, d_maps = self._temporal_buffers(self.rows_layout.map_stride, d_frames, nframes, d_diff, d_maps, "d_frames")
+        N.check(N.lib().csic_rows_device(self._h, C.c_void_p(d_frames.data_ptr()), int(nframes), C.c_void_p(d_diff.data_ptr()),
+                                         C.c_void_p(d_maps.data_ptr()), self._stream()))
+        return d_diff, d_maps
+
+    def unrows_device(self, d_diff, d_maps, nframes: int = 1, d_frames=None):
+        """The inverse of rows_device (`d_frames` may be `d_diff`, in place).  The device does not validate the maps: check untrusted
+        ones with unrows() first."""
+        if d_maps is None:
+            raise N.IllegalArgumentException(N.EINVAL_NULL, "requirement failed: d_maps is None")
+        d_frames, _ = self._temporal_buffers(self.rows_layout.map_stride, d_diff, nframes, d_frames, d_maps, "d_diff")
+        N.check(N.lib().csic_unrows_device(self._h, C.c_void_p(d_diff.data_ptr()), C.c_void_p(d_maps.data_ptr()), int(nframes),
+                                           C.c_void_p(d_frames.data_ptr()), self._stream()))
+        return d_frames
+
+    def rows(self, frames, out=None):
+        """csic_rows_host: frame buffers in host memory (nframes, frame_bytes) -> (diff, maps).  Needs no GPU."""
+        return rows_host(self.c_params, frames, out)
+
+    def unrows(self, diff, maps, out=None) -> np.ndarray:
+        """csic_unrows_host: the inverse; damaged maps raise CsicIOError."""
+        return unrows_host(self.c_params, diff, maps, out)
 
     # -- compute ----------------------------------------------------------------------------------
     def _stream(self):

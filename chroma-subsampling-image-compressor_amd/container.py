@@ -1,7 +1,8 @@
 """.csic files: CSIC_FMT_PLANAR_BITS frames on disk (csic_container_*; byte layout in include/csic.h), raw (version 1), group-coded
 (version 3), Rice-coded (version 4), rANS-coded (version 7) or as a sequence through the temporal layer (versions 5, 6, 7), the host
 codecs of the three codings (csic_pack_host / csic_unpack_host, csic_rice_*_host, csic_rans_*_host) and the host codec of the temporal layer
-(csic_delta_host / csic_undelta_host).  Host only: nothing here needs a GPU."""
+(csic_delta_host / csic_undelta_host) and of the row-prediction layer (csic_rows_host / csic_unrows_host; version 8).  Host only: nothing
+here needs a GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -22,13 +23,16 @@ def container_info(path: str) -> N.CsicContainerInfo:
     N.check(N.lib().csic_container_gop(os.fsencode(path), C.byref(gop)))
     info.gop = gop.value                              # csic_container_gop: 1 below version 5 (every frame stands alone)
     info.coding = {1: N.CODING_RAW, 3: N.CODING_GROUPS, 4: N.CODING_RICE}.get(info.version)
-    if info.coding is None:                           # versions 5, 6, 7 name their coding in the word behind the parameters (checked by the library)
+    if info.coding is None:                           # versions 5 to 8 name their coding in the word behind the parameters (checked by the library)
         with open(path, "rb") as fh:
             fh.seek(80)
-            info.coding = int.from_bytes(fh.read(4), "little") & 0xFF      # (version 6 keeps its range + 1 in bits 8..)
+            info.coding = int.from_bytes(fh.read(4), "little") & 0xFF      # (version 6 keeps its range + 1 in bits 8.., version 8 its flag in bit 16)
     motion = C.c_int32()
     N.check(N.lib().csic_container_motion(os.fsencode(path), C.byref(motion)))
     info.motion = motion.value                        # csic_container_motion: the range of a version-6 file, -1 otherwise
+    rows = C.c_int32()
+    N.check(N.lib().csic_container_rows(os.fsencode(path), C.byref(rows)))
+    info.rows = bool(rows.value)                      # csic_container_rows: version 8, every frame through the row-prediction layer
     return info
 
 
@@ -165,7 +169,8 @@ def _temporal_inverse(c_params: N.CsicParams, diff, maps, gop, out, layout_of, e
     if m.shape[1] != ml.map_stride:
         raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: maps must be (nframes, {ml.map_stride}), got {m.shape}")
     frames = np.zeros_like(d) if out is None else out
-    N.check(entry(C.byref(q), d.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), d.shape[0], int(gop), frames.ctypes.data_as(C.c_void_p)))
+    N.check(entry(C.byref(q), d.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), d.shape[0], *([] if gop is None else [int(gop)]),
+                  frames.ctypes.data_as(C.c_void_p)))
     return frames
 
 
@@ -203,20 +208,48 @@ def mc_undelta_host(c_params: N.CsicParams, diff, maps, gop: int, out=None) -> n
     return _temporal_inverse(c_params, diff, maps, gop, out, mc_layout, N.lib().csic_mc_undelta_host)
 
 
+def rows_layout(c_params: N.CsicParams) -> N.CsicRowsLayout:
+    """csic_rows_layout_of: groups, row widths, K, the band length S, the sections' offsets, map_bytes and map_stride of a frame's map."""
+    lay = N.CsicRowsLayout()
+    N.check(N.lib().csic_rows_layout_of(C.byref(c_params), C.byref(lay)))
+    return lay
+
+
+def rows_host(c_params: N.CsicParams, frames, out=None):
+    """csic_rows_host: PLANAR_BITS frame buffers (nframes, frame_bytes) -> (diff, maps): the difference frames, an array of the same
+    shape (zero outside the payload ranges, or `out` -- not `frames`: there is no in-place form), and the maps, uint8 (nframes,
+    map_stride) with map_bytes of each row written."""
+    return _temporal_forward(c_params, frames, out, rows_layout, N.lib().csic_rows_host)
+
+
+def unrows_host(c_params: N.CsicParams, diff, maps, out=None) -> np.ndarray:
+    """csic_unrows_host: the inverse of rows_host (`out` may be `diff`, in place).  The maps are untrusted: a set padding bit, or a set
+    bit of a plane whose rows are shorter than a group, raises CsicIOError (CSIC_EFORMAT) and nothing is written."""
+    return _temporal_inverse(c_params, diff, maps, None, out, rows_layout, N.lib().csic_unrows_host)
+
+
 def _seq_entry(plain, ex, gop, motion):
     """-> (the writer of a sequence file, its arguments behind the coding): version 5, or with a `motion` range the _ex form, version 6."""
     return (plain, (int(gop),)) if motion is None else (ex, (int(gop), int(motion)))
 
 
-def write_container(path: str, c_params: N.CsicParams, frames, coding="raw", gop=None, motion=None) -> None:
+def write_container(path: str, c_params: N.CsicParams, frames, coding="raw", gop=None, motion=None, rows=False) -> None:
     """frames: the PLANAR_BITS frame buffers of `c_params` (its out_format does not matter), frame_bytes each -- one buffer, an
     array (nframes, frame_bytes), or a list of buffers.  Only the planes' payload bytes reach the file.  coding = "raw" (version 1,
     the bytes as they are), "groups" (version 3, every frame group-coded on the host: csic_container_write_ex) or "rice" (version 4,
     every frame Rice-coded on the host) or "rans" (version 7, every frame rANS-coded on the host).  With a `gop` the frames are a sequence: version 5, delta and packing on the host
     (csic_container_write_seq; coding "groups" or "rice"); with a `motion` range (0..7) as well, version 6 through the
-    motion-compensated layer (csic_container_write_seq_ex); a sequence coded with "rans" is version 7 with either layer."""
+    motion-compensated layer (csic_container_write_seq_ex); a sequence coded with "rans" is version 7 with either layer.  rows=True:
+    version 8, every frame through the row-prediction layer and then the coding, on the host (csic_container_write_rows); it takes a
+    coding other than "raw" and neither gop nor motion."""
     q, lay = _bits_params(c_params)
     coding = _coding(coding)
+    if rows:
+        if gop is not None or motion is not None:
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, "requirement failed: the row-prediction layer does not combine with gop or motion")
+        a = _frames_2d(frames, lay.frame_bytes)
+        N.check(N.lib().csic_container_write_rows(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[0], coding))
+        return
     if motion is not None and gop is None:
         raise N.IllegalArgumentException(N.EINVAL_NULL, "requirement failed: motion needs a gop")
     if gop is not None:
@@ -235,14 +268,17 @@ def write_container(path: str, c_params: N.CsicParams, frames, coding="raw", gop
         N.check(N.lib().csic_container_write_ex(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.size // lay.frame_bytes, coding))
 
 
-def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, coding="groups", maps=None, gop=None, motion=None) -> None:
+def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, coding="groups", maps=None, gop=None, motion=None, rows=False) -> None:
     """Version 3 (coding "groups"), 4 ("rice") or 7 ("rans") from frames that are packed already (csic_container_write_coded_ex): `coded` is an
     array (nframes, stride) -- what Plan.pack_device / Plan.rice_pack_device returns, copied to the host -- or a list of coded frames;
     sizes[k] is frame k's coded_bytes.  Every frame is validated before anything is written.  With `maps` and `gop` -- what
     Plan.delta_device returned, copied to the host: uint8 (nframes, map_stride) -- the coded frames are difference frames and the file is
     version 5 (csic_container_write_coded_seq); with `motion` too the maps are Plan.mc_delta_device's and the file is version 6
-    (csic_container_write_coded_seq_ex)."""
-    if (maps is None) != (gop is None):
+    (csic_container_write_coded_seq_ex).  rows=True: `maps` are Plan.rows_device's, there is no gop, and the file is version 8
+    (csic_container_write_coded_rows)."""
+    if rows and (maps is None or gop is not None or motion is not None):
+        raise N.IllegalArgumentException(N.EINVAL_FORMAT, "requirement failed: the row-prediction layer takes maps, and neither gop nor motion")
+    if not rows and (maps is None) != (gop is None):
         raise N.IllegalArgumentException(N.EINVAL_NULL, "requirement failed: maps and gop go together")
     q, _ = _bits_params(c_params)
     coding = _coding(coding)
@@ -262,7 +298,8 @@ def write_container_coded(path: str, c_params: N.CsicParams, coded, sizes, codin
         m = np.ascontiguousarray(maps).view(np.uint8)
         if m.size == 0 or m.size % sz.size != 0:
             raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: {m.size} bytes of maps for {sz.size} frames")
-        write, layer = _seq_entry(N.lib().csic_container_write_coded_seq, N.lib().csic_container_write_coded_seq_ex, gop, motion)
+        write, layer = (N.lib().csic_container_write_coded_rows, ()) if rows else \
+            _seq_entry(N.lib().csic_container_write_coded_seq, N.lib().csic_container_write_coded_seq_ex, gop, motion)
         N.check(write(os.fsencode(path), C.byref(q), a.ctypes.data_as(C.c_void_p), a.shape[1], sz.ctypes.data_as(C.POINTER(C.c_uint64)),
                       m.ctypes.data_as(C.c_void_p), m.size // sz.size, int(sz.size), coding, *layer))
         return
@@ -281,7 +318,7 @@ def container_coded_sizes(path: str) -> np.ndarray:
 
 def container_inter_groups(path: str) -> np.ndarray:
     """csic_container_inter_groups: uint64 (nframes, 3), the inter groups of each frame and plane (the popcounts of a version-5 file's
-    maps; zeros for key frames and for versions 1, 3 and 4)."""
+    maps; zeros for key frames and for versions 1, 3 and 4; for version 8 the groups predicted from the row above)."""
     info = container_info(path)
     counts = np.zeros((info.nframes, 3), dtype=np.uint64)
     N.check(N.lib().csic_container_inter_groups(os.fsencode(path), counts.ctypes.data_as(C.POINTER(C.c_uint64)), 3 * info.nframes))

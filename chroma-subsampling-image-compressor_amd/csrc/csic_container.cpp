@@ -8,6 +8,8 @@
 // Version 6 is version 5 through the motion-compensated layer (csic_mc_host.cpp): its maps, and the range + 1 in bits 8.. of the coding word.
 // What differs between those two is one row of layer_of.  Version 7 holds everything that is rANS-coded (csic_rans_host.cpp): the third row
 // of codec_of, the coding word and the gop as in version 6 -- a range field of 0 for no motion layer, a gop of 0 for frames that stand alone.
+// Version 8 holds frames that stand alone, each through the row-prediction layer (csic_rows_host.cpp) and any of the three codings: the
+// third row of layer_of, bit 16 of the coding word, and a map in front of EVERY frame's coded difference frame.
 #include <zlib.h>
 
 #include <cstdio>
@@ -21,8 +23,9 @@ namespace csic {
 
 constexpr size_t CONTAINER_HEADER = 80, CONTAINER_CRC_FROM = 16;
 constexpr uint32_t CONTAINER_VERSION = 1, CONTAINER_VERSION_CODED = 3, CONTAINER_VERSION_RICE = 4, CONTAINER_VERSION_SEQ = 5, CONTAINER_VERSION_MC = 6,
-                   CONTAINER_VERSION_RANS = 7;
-constexpr size_t CODED_BODY = 8;                  // versions 3 to 7: coding, reserved (5, 6, 7: gop); then the table of sizes
+                   CONTAINER_VERSION_RANS = 7, CONTAINER_VERSION_ROWS = 8;
+constexpr uint32_t ROWS_FLAG = 1u << 16;          // version 8: the coding word is coding | ROWS_FLAG
+constexpr size_t CODED_BODY = 8;                  // versions 3 to 8: coding, reserved (5, 6, 7: gop); then the table of sizes
 static const unsigned char CONTAINER_MAGIC[4] = {0x43, 0x53, 0x49, 0x43};   // "CSIC"
 
 static void put_u64(unsigned char *p, uint64_t v) { put_u32(p, (uint32_t)v); put_u32(p + 4, (uint32_t)(v >> 32)); }
@@ -100,14 +103,17 @@ static Codec codec_of(const FileGeometry &R, int coding)
 // What depends on the temporal layer of a sequence file, for one parameter set: the version, the bytes of a delta frame's map, the
 // frame codec both ways, the check of a map nobody vouches for, the inter groups of one plane's section of a map, and whether the
 // inverse may run in place.  One row per layer; a file picks its row once.  motion < 0: version 5 through csic_delta_*; otherwise
-// version 6 through csic_mc_* at that range.  version 0: no layer (every frame stands alone).
+// version 6 through csic_mc_* at that range.  version 0: no layer (every frame stands alone).  `rows`: version 8 through csic_rows_*,
+// where no frame has a previous one and every frame has a map (has_map).
 struct Layer {
     uint32_t version = 0;
     int32_t motion = -1;
     int64_t map_bytes = 0;
-    bool in_place = true;
+    bool in_place = true, rows = false;
     DeltaGeometry D;               // the geometry of the file's own layer only
     McGeometry M;
+    RowsGeometry W;
+    bool has_map(int32_t k, int32_t gop) const { return rows || (map_bytes > 0 && gop > 0 && k % gop != 0); }
     void (*forward)(const Layer &L, const unsigned char *cur, const unsigned char *prev, unsigned char *diff, unsigned char *map) = nullptr;
     void (*inverse)(const Layer &L, const unsigned char *diff, const unsigned char *map, const unsigned char *prev, unsigned char *cur) = nullptr;
     int (*check)(const Layer &L, const unsigned char *map, bool key, int frame) = nullptr;
@@ -148,6 +154,26 @@ static int layer_of(const csic_params &q, int32_t motion, Layer *L)
     return CSIC_OK;
 }
 
+static int rows_layer_of(const csic_params &q, Layer *L)
+{
+    const int st = rows_geometry(&q, &L->W);
+    if (st != CSIC_OK) return st;
+    L->version = CONTAINER_VERSION_ROWS;
+    L->motion = -1;
+    L->map_bytes = L->W.layout.map_bytes;
+    L->in_place = true;
+    L->rows = true;
+    L->forward = [](const Layer &l, const unsigned char *c, const unsigned char *, unsigned char *d, unsigned char *m) { rows_frame(l.W, c, d, m); };
+    L->inverse = [](const Layer &l, const unsigned char *d, const unsigned char *m, const unsigned char *, unsigned char *c) { unrows_frame(l.W, d, m, c); };
+    L->check = [](const Layer &l, const unsigned char *m, bool, int frame) { return rows_check_map(l.W, m, frame); };
+    L->inter = [](const Layer &l, const unsigned char *m, int pl) {                     // the set bits: the groups predicted from above
+        uint64_t got = 0;
+        for (int64_t g = 0; g < l.W.layout.groups[pl]; ++g) got += (m[l.W.layout.map_offset[pl] + (g >> 3)] >> (g & 7)) & 1;
+        return got;
+    };
+    return CSIC_OK;
+}
+
 struct FileCloser {
     FILE *f;
     ~FileCloser() { if (f) fclose(f); }
@@ -177,8 +203,8 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Fil
     if (std::memcmp(h, CONTAINER_MAGIC, 4) != 0) return set_error(CSIC_EFORMAT, "%s is not a .csic file (bad magic)", path);
     const uint32_t version = get_u32(h + 4), nframes = get_u32(h + 8);
     if (version != CONTAINER_VERSION && version != CONTAINER_VERSION_CODED && version != CONTAINER_VERSION_RICE && version != CONTAINER_VERSION_SEQ &&
-        version != CONTAINER_VERSION_MC && version != CONTAINER_VERSION_RANS)
-        return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1, 3, 4, 5, 6 and 7 are)", path, version);
+        version != CONTAINER_VERSION_MC && version != CONTAINER_VERSION_RANS && version != CONTAINER_VERSION_ROWS)
+        return set_error(CSIC_EFORMAT, "%s: container version %u is not supported (1, 3, 4, 5, 6, 7 and 8 are)", path, version);
     if (nframes < 1 || nframes > 65535) return set_error(CSIC_EFORMAT, "%s: nframes must be in 1..65535. Got %u", path, nframes);
     int32_t fields[16];
     for (int i = 0; i < 16; ++i) fields[i] = (int32_t)get_u32(h + 16 + 4 * i);
@@ -196,7 +222,15 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Fil
         std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
         if (fread(t.data(), 1, t.size(), f) != t.size()) return set_error(CSIC_EIO, "cannot read %s", path);
         int coding = version == CONTAINER_VERSION_RICE ? CSIC_CODING_RICE : CSIC_CODING_GROUPS;
-        if (version == CONTAINER_VERSION_RANS) {                   // 5 | (range + 1) << 8 with a field of 0 for no motion layer; gop 0: no layer at all
+        if (version == CONTAINER_VERSION_ROWS) {                   // coding | 1 << 16, every other bit zero; then a zero word
+            const uint32_t c = get_u32(t.data()), id = c & ~ROWS_FLAG;
+            if (!(c & ROWS_FLAG) || (id != CSIC_CODING_GROUPS && id != CSIC_CODING_RICE && id != CSIC_CODING_RANS) || get_u32(t.data() + 4) != 0)
+                return set_error(CSIC_EFORMAT, "%s: coding word %#x (then %u) is not what version %u holds (1, 3 or 5 with bit 16 set, then 0)", path, c,
+                                 get_u32(t.data() + 4), version);
+            coding = (int)id;
+            const int st = rows_layer_of(p, &cb.layer);
+            if (st != CSIC_OK) return set_error(CSIC_EFORMAT, "%s: the stored parameters have no layout in the row-prediction layer", path);
+        } else if (version == CONTAINER_VERSION_RANS) {                   // 5 | (range + 1) << 8 with a field of 0 for no motion layer; gop 0: no layer at all
             const uint32_t c = get_u32(t.data()), field = c >> 8, gop = get_u32(t.data() + 4);
             if ((c & 0xFFu) != CSIC_CODING_RANS) return set_error(CSIC_EFORMAT, "%s: coding %u is not the one version %u holds (5)", path, c & 0xFFu, version);
             if (field > (uint32_t)MC_MAX_RANGE + 1 || gop > 65535 || (gop == 0 && field != 0))
@@ -234,7 +268,7 @@ static int read_header(FILE *f, const char *path, csic_container_info *info, Fil
         if (sizes) sizes->resize(nframes);
         for (uint32_t k = 0; k < nframes; ++k) {
             const uint64_t sz = get_u64(t.data() + CODED_BODY + 8 * (size_t)k);
-            const uint64_t map = k % (uint32_t)cb.gop ? (uint64_t)cb.layer.map_bytes : 0, lo = codec.lo + map, hi = codec.hi + map;     // a delta record: map, then coded frame
+            const uint64_t map = cb.layer.has_map((int32_t)k, cb.gop) ? (uint64_t)cb.layer.map_bytes : 0, lo = codec.lo + map, hi = codec.hi + map;     // a delta record: map, then coded frame
             if (sz < lo || sz > hi || sz % 4 != 0)
                 return set_error(CSIC_EFORMAT, "%s: frame %u is stored in %llu bytes; these parameters code to %llu .. %llu, in dwords", path, k,
                                  (unsigned long long)sz, (unsigned long long)lo, (unsigned long long)hi);
@@ -281,11 +315,11 @@ static int write_coded_file(const char *path, const csic_params &q, const unsign
                             int32_t gop = 0, const unsigned char *const *maps = nullptr, const Layer &layer = Layer())
 {
     const size_t map_bytes = (size_t)layer.map_bytes;
-    const auto map_of = [&](int32_t k) { return gop > 0 && k % gop ? map_bytes : (size_t)0; };
+    const auto map_of = [&](int32_t k) { return layer.has_map(k, gop) ? map_bytes : (size_t)0; };
     unsigned char h[CONTAINER_HEADER];
-    fill_header(h, gop > 0 && codec.coding != CSIC_CODING_RANS ? layer.version : codec.version, q, nframes);       // (version 7: with or without a layer)
+    fill_header(h, layer.rows || (gop > 0 && codec.coding != CSIC_CODING_RANS) ? layer.version : codec.version, q, nframes);   // (version 7: with or without a layer)
     std::vector<unsigned char> t(CODED_BODY + 8 * (size_t)nframes);
-    put_u32(t.data(), (uint32_t)codec.coding | (uint32_t)(layer.motion + 1) << 8);
+    put_u32(t.data(), (uint32_t)codec.coding | (uint32_t)(layer.motion + 1) << 8 | (layer.rows ? ROWS_FLAG : 0u));
     put_u32(t.data() + 4, (uint32_t)gop);
     for (int32_t k = 0; k < nframes; ++k) put_u64(t.data() + CODED_BODY + 8 * (size_t)k, sizes[k] + map_of(k));
     uLong crc = crc32(0L, h + CONTAINER_CRC_FROM, (uInt)(CONTAINER_HEADER - CONTAINER_CRC_FROM));
@@ -460,16 +494,26 @@ static int seq_check(int32_t coding, int32_t gop)
     return CSIC_OK;
 }
 
+constexpr int32_t MOTION_ROWS = -2;                // write_seq, write_coded_seq: not a temporal layer but csic_rows_*, version 8 (gop 0)
+static int writer_layer(const csic_params &q, int32_t motion, Layer *L) { return motion == MOTION_ROWS ? rows_layer_of(q, L) : layer_of(q, motion, L); }
+// seq_check for the row-prediction layer: the coding alone
+static int rows_check(int32_t coding)
+{
+    if (coding != CSIC_CODING_GROUPS && coding != CSIC_CODING_RICE && coding != CSIC_CODING_RANS)
+        return set_error(CSIC_EINVAL_FORMAT, "the row-prediction layer sits in front of CSIC_CODING_GROUPS(1), CSIC_CODING_RICE(3) or CSIC_CODING_RANS(5). Got %d", coding);
+    return CSIC_OK;
+}
+
 // motion < 0: version 5 through csic_delta_*; otherwise version 6 through csic_mc_* at that range
 static int write_seq(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding, int32_t gop, int32_t motion)
 {
     if (!path || !p || !frames) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    int st = seq_check(coding, gop);
+    int st = motion == MOTION_ROWS ? rows_check(coding) : seq_check(coding, gop);
     if (st != CSIC_OK) return st;
     csic_params q;
     FileGeometry G;
     Layer layer;
-    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = layer_of(q, motion, &layer)) != CSIC_OK) return st;
+    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = writer_layer(q, motion, &layer)) != CSIC_OK) return st;
     const Codec codec = codec_of(G, coding);
     try {
         const size_t fb = (size_t)G.pk.bits.frame_bytes, mb = (size_t)layer.map_bytes;
@@ -477,7 +521,7 @@ static int write_seq(const char *path, const csic_params *p, const void *frames,
         std::vector<unsigned char> diff(fb), maps((size_t)nframes * mb), all;
         std::vector<uint64_t> sizes((size_t)nframes);
         for (int32_t k = 0; k < nframes; ++k) {
-            layer.forward(layer, x + (size_t)k * fb, k % gop ? x + (size_t)(k - 1) * fb : nullptr, diff.data(), maps.data() + (size_t)k * mb);
+            layer.forward(layer, x + (size_t)k * fb, gop > 0 && k % gop ? x + (size_t)(k - 1) * fb : nullptr, diff.data(), maps.data() + (size_t)k * mb);
             const size_t at = all.size();
             all.resize(at + codec.bound);
             st = codec.pack(G, diff.data(), all.data() + at, codec.bound, &sizes[k]);
@@ -511,12 +555,12 @@ static int write_coded_seq(const char *path, const csic_params *p, const void *c
                            const void *maps, size_t map_stride, int32_t nframes, int32_t coding, int32_t gop, int32_t motion)
 {
     if (!path || !p || !coded || !sizes || !maps) return set_error(CSIC_EINVAL_NULL, "argument is NULL");
-    int st = seq_check(coding, gop);
+    int st = motion == MOTION_ROWS ? rows_check(coding) : seq_check(coding, gop);
     if (st != CSIC_OK) return st;
     csic_params q;
     FileGeometry G;
     Layer layer;
-    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = layer_of(q, motion, &layer)) != CSIC_OK) return st;
+    if ((st = writer_params(p, nframes, &q, &G)) != CSIC_OK || (st = writer_layer(q, motion, &layer)) != CSIC_OK) return st;
     const size_t mb = (size_t)layer.map_bytes;
     if (map_stride < mb)
         return set_error(CSIC_EINVAL_SIZE, "a map of these parameters has %zu bytes: a map_stride of %zu cannot hold it", mb, map_stride);
@@ -529,7 +573,7 @@ static int write_coded_seq(const char *path, const csic_params *p, const void *c
             ptrs[k] = static_cast<const unsigned char *>(coded) + (size_t)k * stride_bytes;
             mptrs[k] = static_cast<const unsigned char *>(maps) + (size_t)k * map_stride;
             if ((st = codec.check(G, ptrs[k], (size_t)sizes[k])) != CSIC_OK) return st;
-            if ((st = layer.check(layer, mptrs[k], k % gop == 0, k)) != CSIC_OK) return st;
+            if ((st = layer.check(layer, mptrs[k], gop > 0 && k % gop == 0, k)) != CSIC_OK) return st;
         }
         st = write_coded_file(path, q, ptrs.data(), sizes, nframes, codec, gop, mptrs.data(), layer);
     } catch (const std::bad_alloc &) {
@@ -553,6 +597,22 @@ int csic_container_write_coded_seq_ex(const char *path, const csic_params *p, co
     return st != CSIC_OK ? st : write_coded_seq(path, p, coded, stride_bytes, sizes, maps, map_stride, nframes, coding, gop, range);
 }
 
+int csic_container_write_rows(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding)
+{
+    return write_seq(path, p, frames, nframes, coding, 0, MOTION_ROWS);
+}
+
+int csic_container_write_coded_rows(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
+                                    const void *maps, size_t map_stride, int32_t nframes, int32_t coding)
+{
+    return write_coded_seq(path, p, coded, stride_bytes, sizes, maps, map_stride, nframes, coding, 0, MOTION_ROWS);
+}
+
+int csic_container_rows(const char *path, int32_t *flag)
+{
+    return with_header(path, flag, [&](FILE *, const csic_container_info &, const std::vector<uint64_t> &, const CodedBody &body) { *flag = body.layer.rows ? 1 : 0; return (int)CSIC_OK; });
+}
+
 int csic_container_motion(const char *path, int32_t *range)
 {
     return with_header(path, range, [&](FILE *, const csic_container_info &, const std::vector<uint64_t> &, const CodedBody &body) { *range = body.layer.motion; return (int)CSIC_OK; });
@@ -572,7 +632,7 @@ int csic_container_inter_groups(const char *path, uint64_t *counts, int32_t n)
         std::vector<unsigned char> map((size_t)layer.map_bytes);
         long long at = ftello(f);                      // where the records begin
         for (int32_t k = 0; k < ci.nframes; at += (long long)table[k], ++k) {
-            if (layer.map_bytes <= 0 || k % body.gop == 0) continue;
+            if (!layer.has_map(k, body.gop)) continue;
             if (fseeko(f, at, SEEK_SET) != 0 || fread(map.data(), 1, map.size(), f) != map.size()) return set_error(CSIC_EIO, "cannot read %s", path);
             const int st = layer.check(layer, map.data(), false, k);
             if (st != CSIC_OK) return st;
@@ -623,7 +683,7 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
             coded.resize((size_t)sizes[k]);            // within the coding's sizes: read_header checked the table
             if (fread(coded.data(), 1, coded.size(), fc.f) != coded.size()) return set_error(CSIC_EIO, "cannot read %s", path);
             crc = crc_long(crc, coded.data(), (int64_t)coded.size());
-            const size_t map = k % body.gop ? (size_t)layer.map_bytes : 0;     // versions 5, 6: a delta frame's map first (read_header: the record holds it)
+            const size_t map = layer.has_map(k, body.gop) ? (size_t)layer.map_bytes : 0;     // versions 5 to 8: the map first (read_header: the record holds it)
             unsigned char *d = fr;                         // the difference frame -> the frame, in place where the layer allows it
             if (map && !layer.in_place) {
                 diff.assign((size_t)L.frame_bytes, 0);
@@ -631,7 +691,7 @@ static int container_read(const char *path, void *frames, size_t frames_bytes)
             }
             if (map) st = layer.check(layer, coded.data(), false, k);
             if (st == CSIC_OK) st = codec.unpack(C, coded.data() + map, coded.size() - map, d);
-            if (st == CSIC_OK && map) layer.inverse(layer, d, coded.data(), fr - L.frame_bytes, fr);
+            if (st == CSIC_OK && map) layer.inverse(layer, d, coded.data(), layer.rows ? nullptr : fr - L.frame_bytes, fr);
         }
     }
     if (st == CSIC_OK && (uint32_t)crc != stored)

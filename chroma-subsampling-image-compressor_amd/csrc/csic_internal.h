@@ -101,6 +101,18 @@ void mc_undelta_frame(const McGeometry &G, const unsigned char *diff, const unsi
 int mc_check_map(const McGeometry &G, const unsigned char *map, bool key, int frame);
 int mc_check_range(int32_t range);
 
+// csic_rows_host.cpp: the row-prediction layer (csic.h: csic_rows_*), the same for it: a frame stands alone, so there is no previous
+// frame and no gop.  rows_frame does not work in place, unrows_frame does.
+constexpr int ROWS_BAND = CSIC_ROWS_BAND;
+struct RowsGeometry {
+    PackGeometry pk;
+    csic_rows_layout layout;
+};
+int rows_geometry(const csic_params *p, RowsGeometry *G);
+void rows_frame(const RowsGeometry &G, const unsigned char *frame, unsigned char *diff, unsigned char *map);
+void unrows_frame(const RowsGeometry &G, const unsigned char *diff, const unsigned char *map, unsigned char *frame);
+int rows_check_map(const RowsGeometry &G, const unsigned char *map, int frame);
+
 // Exact unsigned division by a run-time constant without a divide (k_generic's stream-index arithmetic): for
 // 1 <= d < 2^31 and every n < 2^31,  n / d == (uint64(n) * m) >> k  with  k = 31 + ceil(log2 d),  m = ceil(2^k / d) < 2^32.
 // (Error term e = m*d - 2^k < d <= 2^ceil(log2 d), and n * e < 2^31 * 2^ceil(log2 d) = 2^k.)  Host side, csic_host.cpp;

@@ -85,7 +85,7 @@ inline int temporal_check_call(int64_t frame_bytes, int64_t map_stride, int64_t 
     const size_t fb = (size_t)nframes * (size_t)frame_bytes, mb = (size_t)(nframes - 1) * (size_t)map_stride + (size_t)map_bytes;
     if (!(in_place_ok && frames == diff) && overlap(frames, fb, diff, fb))
         return set_error(CSIC_EINVAL_SIZE, in_place_ok ? "the frames and the difference frames overlap: they must be the same buffer or apart"
-                                                       : "the frames and the difference frames overlap: a group reads other groups of the previous frame, so not even in place");
+                                                       : "the frames and the difference frames overlap: a group reads other groups of its reference, so not even in place");
     if (overlap(maps, mb, frames, fb) || overlap(maps, mb, diff, fb)) return set_error(CSIC_EINVAL_SIZE, "the maps overlap the frames");
     return CSIC_OK;
 }

@@ -969,7 +969,8 @@ const char *csic_rans_kernel_name(const csic_plan *plan);
 /* ---- temporal delta coding of frame sequences (csic_delta_*) ------------------------------------------------------------------------
  * Both codings above code every frame on its own.  This layer sits in front of them: it turns a sequence of CSIC_FMT_PLANAR_BITS
  * frames into a sequence of DIFFERENCE frames of the same layout, which either coding then codes as it codes any frame, and one small
- * map per frame.  It is lossless.  Prediction across the groups of a frame would need a scan over a plane; across frames the
+ * map per frame.  It is lossless.  Prediction across the groups of a frame would need a scan over a plane (csic_rows_*, below, predicts
+ * from the row above inside bands of 16 steps instead); across frames the
  * dependency is per sample -- sample i of frame k depends on sample i of frame k - 1 only -- so encode and decode stay one lane per
  * group.  There is no motion compensation here: content that stays in place gains, a pan gains nothing and loses the map at most; the
  * layer for content that moves is csic_mc_*, below.
@@ -1119,6 +1120,87 @@ int  csic_mc_undelta_device(csic_plan *plan, const void *d_diff, const void *d_m
                             void *hip_stream);
 const char *csic_mc_kernel_name(const csic_plan *plan);
 
+/* ---- row prediction of the bit planes (csic_rows_*) ---------------------------------------------------------------------------------
+ * Every coding above predicts a sample from its left neighbour inside a flat group of 32; none knows that a plane has rows.  This layer
+ * sits in front of them as csic_delta_* does: it turns a CSIC_FMT_PLANAR_BITS frame x into a DIFFERENCE frame D of the same layout,
+ * which any coding codes as it codes any frame, and one small map.  A group of D holds either the group's codes or -- where the row
+ * above predicts the group better than the left neighbour -- values whose LEFT residuals are the differences against the row above.  It
+ * is lossless.  A frame stands alone: there is no gop, and frames of a call are independent.
+ *
+ * Planes, q_p, n_p and the groups of 32 (G_p = ceil(n_p / 32)) are those of csic_pack_*; a plane's row width w is csic_mc_*'s w_p.
+ * Per plane:  K = floor(w / 32)  and  S = 32 * K * CSIC_ROWS_BAND.  A plane with K = 0 takes no part: its map bits are 0 and its D is
+ * x.  BANDS are the flat sample ranges [b S, (b + 1) S): they begin on group boundaries and, like csic_mc_*'s displacements, do not
+ * care about row ends.
+ *
+ * REFERENCE.   ref(i) = x[i - w] if i - w >= S * floor(i / S), else 0: the first w samples of a band restart.
+ *              u_i    = (x_i - ref(i)) mod 2^q
+ * CHOICE, per group g, over its real slots (slots behind the plane's last sample add nothing, as in csic_delta_*):
+ *     cost_left = csic_delta_*'s cost(x), the sum over the slots j >= 1 of the folded, centred left residuals of the codes
+ *     cost_up   = the sum over the slots j >= 1 of the folded, centred u_j -- u itself, not its left residual
+ *     t_g       = 1 iff cost_up < cost_left; a tie is 0 (a constant plane has an all-zero map).  Groups whose references are all 0
+ *                 follow the same rule.
+ * DIFFERENCE GROUP.  Where t_g = 0 it holds x.  Where t_g = 1 it holds v_j = (u_0 + ... + u_j) mod 2^q: every coding left-predicts
+ * inside a group, so the residual it sees at slot j >= 1 is exactly u_j and its anchor is u_0 -- the layer composes with
+ * CSIC_CODING_GROUPS, _RICE and _RANS unchanged.  Bits behind a plane's last sample are 0; bytes outside the payload ranges are not
+ * written.
+ * MAP.  csic_delta_*'s layout exactly: three sections of 4 * ceil(G_p / 32) bytes, bit g of a section (LSB first) is t_g, padding bits
+ * are 0; map_bytes is their sum, map_stride the next multiple of 256, the distance of the maps of consecutive frames.
+ * INVERSE, in increasing i.  t_g = 1: u_0 = v_0, u_j = (v_j - v_(j - 1)) mod 2^q, x_i = (u_i + ref(i)) mod 2^q.  t_g = 0: x = D.
+ *
+ * DECODING ORDER.  Inside a band, step s is the groups [s K, (s + 1) K).  Since 32 K <= w, a group of step s refers only to samples of
+ * steps s - 1 and s - 2: with delta = w - 32 K (0 .. 31), slots j >= delta of band-local group s K + k refer to group (s - 1) K + k,
+ * slots j < delta to the group before that one.  Bands are independent, a band is CSIC_ROWS_BAND dependent steps, and the encoder has
+ * no dependency at all: its references are source samples.
+ *
+ * Worked vectors, one plane alone, w = 32 and two rows unless said otherwise (bytes: the plane's payload in the bit layout):
+ *     a row repeated   q = 3, both rows 1,2,3,4,5,6,7,0 four times.  Group 0 has no reference: cost_up = 110 > cost_left = 62, it
+ *                      stays.  Group 1: u = 0 x 32, cost_up = 0 < 62 -> map 02 00 00 00, D = d1 58 1f x 4, then 00 x 12
+ *     a tie            q = 3, row 0 all 0, row 1 is 31 zeros and a 1: cost_up = 2 = cost_left -> map 00 00 00 00, D = x
+ *     the wrap         q = 3, row 0 is 7,3 sixteen times, row 1 is 0,4 sixteen times (2^q - 1 above a 0): u = 1 x 32, cost_up = 62 <
+ *                      cost_left = 217 -> v = 1,2,3,4,5,6,7,0 four times: group 1 of D = d1 58 1f x 4; back: (1 + 7) mod 8 = 0.
+ *                      (Group 0 is taken too, against references of 0: cost_up = 111 < 217, v = 7,2,1,4,3,6,5,0 four times; map 03.)
+ *     a ragged group   q = 2, n = 34: row 0 is 1,2,3,0 eight times, group 1 has the two samples 1,2.  u = 0,0, cost_up = 0 <
+ *                      cost_left = 2 -> bit 1 of the map; the 30 slots behind sample 33 take no part and are stored as zero bits.
+ *                      (Group 0: cost_up = 46 < 62, v = 1,3,2,2,3,1,0,0 eight times; map 03 00 00 00, D = ad 07 x 4, then 00.)
+ *     w = 33           q = 3, x_i = 5 (i mod 33) mod 8 for i < 66: K = 1, delta = 1.  Sample 32 ends row 0 and has no reference;
+ *                      sample 33 + j refers to sample j: slot 0 of group 1 is on its own, its slots j >= 1 refer to group 0, and group
+ *                      2 (samples 64, 65) refers to slots 31 of group 0 and 0 of group 1.  u = 0 from sample 32 on -> map 07 00 00 00
+ *                      (group 0, against 0: 112 < 155), D = e8 ad 85 cc e4 17 twice, then 00 x 13
+ *
+ * Host codec (no GPU; parameters and statuses as for csic_delta_*):
+ *   csic_rows_layout_of : groups, w, K, S, the sections' offsets, map_bytes and map_stride of these parameters.
+ *   csic_rows_host      : frames (frame_bytes apart) -> diff (frame_bytes apart) and maps (map_stride apart).
+ *   csic_unrows_host    : the inverse.  The maps are untrusted: a padding bit that is set, or a set bit in a plane with K = 0, gives
+ *                         CSIC_EFORMAT; a refused call writes nothing.
+ * Device codec (gfx950): asynchronous on `hip_stream`, no allocation, no synchronisation, no workspace, hipGraph-capturable; one launch
+ * per run of planes of one bit width, frames on grid z.
+ *   csic_rows_device    : d_frames -> d_diff and d_maps, one lane per group; the source is only read.
+ *   csic_unrows_device  : the inverse, one workgroup per band, lane k walks the band-local groups k, K + k, ... down the steps.  It
+ *                         does NOT validate and has nothing to clamp: any map bit decodes to valid codes; a bit of a plane with K = 0
+ *                         is ignored.
+ *   csic_rows_kernel_name : "k_rows<q6,5,5,nt>", as csic_delta_kernel_name.
+ * Forward calls: ANY overlap of the frames, the difference frames and the maps is CSIC_EINVAL_SIZE -- a group reads other groups of
+ * the source.  Inverse calls: diff == frames, exactly in place, is allowed, any other overlap is CSIC_EINVAL_SIZE.  nframes outside
+ * 1..65535 and, on the device, a buffer that is not 256-byte aligned: CSIC_EINVAL_SIZE.  NULL arguments: CSIC_EINVAL_NULL; parameters
+ * the container does not take: csic_validate's status -- all before any device is touched.  CSIC_TUNE_NONTEMPORAL applies to the
+ * accesses of the frames. */
+#define CSIC_ROWS_BAND 16
+typedef struct csic_rows_layout {
+    int64_t groups[3];             /* G_p                                                              */
+    int64_t width[3];              /* w_p                                                              */
+    int64_t k[3];                  /* K = floor(w_p / 32); 0: the plane takes no part                  */
+    int64_t band[3];               /* S = 32 * K * CSIC_ROWS_BAND samples                              */
+    int64_t map_offset[3];         /* byte offsets of the sections inside a map                        */
+    int64_t map_bytes;             /* sum_p 4 * ceil(G_p / 32)                                         */
+    int64_t map_stride;            /* multiple of 256: the distance of maps in a buffer of maps        */
+} csic_rows_layout;
+int  csic_rows_layout_of(const csic_params *p, csic_rows_layout *layout);
+int  csic_rows_host(const csic_params *p, const void *frames, int32_t nframes, void *diff, void *maps);
+int  csic_unrows_host(const csic_params *p, const void *diff, const void *maps, int32_t nframes, void *frames);
+int  csic_rows_device(csic_plan *plan, const void *d_frames, int32_t nframes, void *d_diff, void *d_maps, void *hip_stream);
+int  csic_unrows_device(csic_plan *plan, const void *d_diff, const void *d_maps, int32_t nframes, void *d_frames, void *hip_stream);
+const char *csic_rows_kernel_name(const csic_plan *plan);
+
 /* ---- .csic files: the compressed frames on disk (host only, usable without a GPU) --------------------------------------------
  * A container holds `nframes` CSIC_FMT_PLANAR_BITS frames of one parameter set: the only thing this library writes to a file that
  * is smaller than its input (a 6/5/5 4:2:0 frame: 1.06 bytes per pixel at factor 1; group-coded, version 3 below, less).  Version 1,
@@ -1141,7 +1223,7 @@ const char *csic_mc_kernel_name(const csic_plan *plan);
  *                            when the parameters are invalid or p->in_format is not ARGB; nframes outside 1 .. 65535: CSIC_EINVAL_SIZE.
  *   csic_container_info_of : header, parameters and length of a file (everything csic_container_read checks except the CRC).
  *   csic_container_read    : frames_bytes must equal nframes * frame_bytes (CSIC_EINVAL_SIZE otherwise; ask csic_container_info_of).
- * CSIC_EFORMAT: bad magic, a version other than 1, 3, 4, 5, 6 or 7, nframes out of range, parameters that fail csic_validate (or are not
+ * CSIC_EFORMAT: bad magic, a version other than 1, 3, 4, 5, 6, 7 or 8, nframes out of range, parameters that fail csic_validate (or are not
  * PLANAR_BITS), a length other than 80 + nframes * payload_bytes, a CRC mismatch.  CSIC_EIO: the file cannot be opened, read or
  * written.  NULL arguments: CSIC_EINVAL_NULL.
  *
@@ -1239,7 +1321,31 @@ const char *csic_mc_kernel_name(const csic_plan *plan);
  * raw chunks of all blocks, plus map_bytes for a delta record): a coding id other than 5 in the low byte; F above 8 or any higher bit
  * set; a gop above 65535; F other than 0 with a gop of 0; any coded frame csic_rans_unpack_host refuses; a record that holds a map
  * where the gop says it has none, or none where it has one (refused by its size or by the decoders).  Coding id 5 under versions 3,
- * 4, 5 or 6 is CSIC_EFORMAT as well: those versions keep their codings, their bytes and their refusals. */
+ * 4, 5 or 6 is CSIC_EFORMAT as well: those versions keep their codings, their bytes and their refusals.
+ *
+ * Version 8 holds frames that stand alone, each through the row-prediction layer (csic_rows_*) and then one of the three codings.
+ * Bytes 0 .. 79 are as in version 1 with version = 8, the CRC covers [16, end of file), and the body is
+ *
+ *         80     4                     uint32  coding | 1 << 16 : the coding id 1, 3 or 5, and bit 16, the layer; every other bit zero
+ *         84     4                     uint32  0
+ *         88     8 * nframes           uint64 stored bytes of each frame's record
+ *         88 + 8 * nframes             the records back to back: the frame's map (map_bytes of csic_rows_layout_of) followed by the
+ *                                      coded frame of its difference frame
+ *
+ *   csic_container_write_rows       : the layer (csic_rows_host) and the coding on the host.  coding CSIC_CODING_RAW -- the layer gains
+ *                                     nothing without a coder -- or any other than GROUPS, RICE, RANS: CSIC_EINVAL_FORMAT.
+ *   csic_container_write_coded_rows : version 8 from what the device made: coded difference frames coded[k * stride_bytes, + sizes[k])
+ *                                     (without the maps) and the maps, map_stride apart.  Every coded frame and every map is validated
+ *                                     before anything is written (CSIC_EFORMAT); sizes[k] > stride_bytes or map_stride < map_bytes:
+ *                                     CSIC_EINVAL_SIZE.
+ *   csic_container_rows             : *flag = 1 for a version-8 file, 0 for every other version.
+ *   csic_container_read resolves the layer on the host and returns the frames themselves; _info_of reports version 8; _coded_sizes
+ *   gives the table (maps included); _gop gives 1 and _motion -1; csic_container_inter_groups counts the groups predicted from the row
+ *   above, the popcount of each section of each frame's map.
+ * CSIC_EFORMAT for a version-8 file, beyond the cases of versions 3 / 4 / 7 without a gop (with the sizes of the file's coding plus
+ * map_bytes): a coding id other than 1, 3 or 5; any bit of the word at 80 other than the id and bit 16 -- a version-7 body behind a
+ * version-8 header is refused at the header --; a word at 84 that is not 0; a padding bit that is set in a map, or a set bit in the
+ * section of a plane with K = 0; any coded frame the coding's host decoder refuses.  Versions 1 to 7 keep their bytes and refusals. */
 typedef struct csic_container_info {
     csic_params params;            /* out_format = CSIC_FMT_PLANAR_BITS, in_format = CSIC_FMT_ARGB8888 */
     int32_t version, nframes;
@@ -1265,6 +1371,10 @@ int  csic_container_write_seq_ex(const char *path, const csic_params *p, const v
 int  csic_container_write_coded_seq_ex(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
                                        const void *maps, size_t map_stride, int32_t nframes, int32_t coding, int32_t gop, int32_t range);
 int  csic_container_motion(const char *path, int32_t *range);
+int  csic_container_write_rows(const char *path, const csic_params *p, const void *frames, int32_t nframes, int32_t coding);
+int  csic_container_write_coded_rows(const char *path, const csic_params *p, const void *coded, size_t stride_bytes, const uint64_t *sizes,
+                                     const void *maps, size_t map_stride, int32_t nframes, int32_t coding);
+int  csic_container_rows(const char *path, int32_t *flag);
 
 /* ---- host-frame pipeline (the step either side of the hot path) -----------------------------------
  * Replaces the reference's per-image  readImage -> per-pixel poke ... peek -> writeImage  flow

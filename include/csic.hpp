@@ -290,6 +290,39 @@ inline std::vector<uint8_t> mcUndelta(const csic_params &p, const void *diff, co
     check(csic_mc_undelta_host(&p, diff, maps, nframes, gop, frames.data()));
     return frames;
 }
+// The row-prediction layer (csic.h: csic_rows_*), host codec: every frame on its own, the maps of csic_rows_layout_of; the difference
+// frames never share memory with the frames (unrows may work in place through the C ABI).
+inline csic_rows_layout rowsLayout(const csic_params &p)
+{
+    csic_rows_layout layout;
+    check(csic_rows_layout_of(&p, &layout));
+    return layout;
+}
+inline DeltaFrames rows(const csic_params &p, const void *frames, int nframes)
+{
+    DeltaFrames d{zeroedFrames(p, nframes), {}};
+    d.maps.assign((size_t)(nframes > 0 ? nframes : 0) * (size_t)rowsLayout(p).map_stride, 0);
+    check(csic_rows_host(&p, frames, nframes, d.diff.data(), d.maps.data()));
+    return d;
+}
+inline std::vector<uint8_t> unrows(const csic_params &p, const void *diff, const void *maps, int nframes)
+{
+    std::vector<uint8_t> frames = zeroedFrames(p, nframes);
+    check(csic_unrows_host(&p, diff, maps, nframes, frames.data()));
+    return frames;
+}
+// version 8: every frame through the row-prediction layer and then `coding` (CSIC_CODING_GROUPS, _RICE or _RANS), on the host;
+// containerRows: whether a file uses the layer
+inline void writeContainerRows(const std::string &file, const csic_params &p, const void *frames, int nframes, int coding)
+{
+    check(csic_container_write_rows(file.c_str(), &p, frames, nframes, coding));
+}
+inline bool containerRows(const std::string &file)
+{
+    int32_t flag = 0;
+    check(csic_container_rows(file.c_str(), &flag));
+    return flag != 0;
+}
 // version 5: the frames as a sequence, delta and packing on the host (coding CSIC_CODING_GROUPS or CSIC_CODING_RICE); readContainer
 // returns the frames themselves
 inline void writeContainerSeq(const std::string &file, const csic_params &p, const void *frames, int nframes, int coding, int gop)
@@ -520,6 +553,10 @@ public:
     const char *deltaKernelName() { return csic_delta_kernel_name(plan_); }
     // the motion-compensated layer, host and device (d_workspace: nframes * mcLayout().workspace_frame_bytes bytes; never in place)
     csic_mc_layout mcLayout() const { return csic::mcLayout(params_); }
+    DeltaFrames rows(const void *frames, int nframes) const { return csic::rows(params_, frames, nframes); }
+    std::vector<uint8_t> unrows(const void *diff, const void *maps, int nframes) const { return csic::unrows(params_, diff, maps, nframes); }
+    void rowsDevice(const void *d_frames, int nframes, void *d_diff, void *d_maps, void *hip_stream) { check(csic_rows_device(plan_, d_frames, nframes, d_diff, d_maps, hip_stream)); }
+    void unrowsDevice(const void *d_diff, const void *d_maps, int nframes, void *d_frames, void *hip_stream) { check(csic_unrows_device(plan_, d_diff, d_maps, nframes, d_frames, hip_stream)); }
     DeltaFrames mcDelta(const void *frames, int nframes, int gop, int range) const { return csic::mcDelta(params_, frames, nframes, gop, range); }
     std::vector<uint8_t> mcUndelta(const void *diff, const void *maps, int nframes, int gop) const { return csic::mcUndelta(params_, diff, maps, nframes, gop); }
     void mcDeltaDevice(const void *d_frames, int nframes, int gop, int range, void *d_diff, void *d_maps, void *d_workspace, size_t workspace_bytes,
