@@ -1,7 +1,9 @@
 """The row-prediction layer (csic_rows_*; include/csic.h) stated in numpy, straight from the definition and independent of the C++: the
 reference of a sample (the sample one row above inside its band, else 0), the two costs of a group, the choice, the difference planes,
 the maps and the inverse.  A helper module without tests: tests/test_rows_host.py checks the host codec against it,
-tests/test_gpu_rows.py the device codec, tests/test_container_v8.py and tests/test_rows_sizes.py build files and sizes from it.
+tests/test_gpu_rows.py the device codec, tests/test_container_v8.py and tests/test_rows_sizes.py build files and sizes from it;
+tests/rows_planes.py builds planes to order with it (conditions: tests/test_rows_planes_host.py) and tests/test_gpu_rows_planes.py
+holds the device codec to it on those planes.
 
 A frame is three planes of codes (int64, values < 2^q); `widths` are the planes' row widths w_p."""
 import numpy as np

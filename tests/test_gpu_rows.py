@@ -11,7 +11,9 @@ are the smallest that reach each path of the kernels:
 
 with q over 1 .. 8 across the cases and CSIC_TUNE_NONTEMPORAL 1 and 0.  Per case: the difference frames inside the payload ranges and
 the maps inside map_bytes byte for byte, 0xEE everywhere else, the source only read; unrows restores the source apart and in place.
-Then one capture into a graph with one replay, the refusals, and the CLI.  Run with `-m gpu` on an MI355X."""
+Then one capture into a graph with one replay, the refusals, and the CLI.  The content here is loosely random; planes built to order
+-- every delta at every q, ties and choices decided by one, the group, block and lane-loop edges, maps no encoder wrote -- live in
+tests/rows_planes.py and run in tests/test_gpu_rows_planes.py against the numpy statement.  Run with `-m gpu` on an MI355X."""
 import ctypes as C
 import os
 
