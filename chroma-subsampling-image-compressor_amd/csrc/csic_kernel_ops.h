@@ -1,6 +1,6 @@
 // csic_kernel_ops.h -- device-side building blocks shared by the kernel translation units (csic_kernels.hip, csic_planar.hip,
-// csic_planar_bits.hip, csic_decode.hip, csic_code_stats.hip and, through csic_measure.h and csic_pack_common.h,
-// csic_distortion.hip, csic_ssim.hip, csic_pack.hip, csic_rice.hip and csic_delta.hip):
+// csic_planar_bits.hip, csic_decode.hip and, through csic_measure.h, csic_count.h and csic_pack_common.h,
+// csic_distortion.hip, csic_ssim.hip, csic_code_stats.hip, csic_qsweep.hip, csic_pack.hip, csic_rice.hip and csic_delta.hip):
 // the wave prologue, address-space-qualified pixel pointers, streaming (non-temporal) accesses, the ONE layer of range-checked
 // accessors every unit's global accesses go through (CSIC_RANGE_CHECK: live in the CSIC_DEBUG build, nothing otherwise), the
 // per-pixel arithmetic of the forward / inverse transforms and the quantiser, and one output pixel by the definition for both

@@ -11,11 +11,10 @@
 //                      input block, as k_dist_gen.
 //   k_qsweep_sum       one block per frame: the frame's partials of 24 words, summed in a fixed order (sum_partials, csic_measure.h),
 //                      -> the frame's sse[3][8].
-//   k_qsweep_hist<NT>  the walk of k_cstat_bytes over a CSIC_FMT_PLANAR frame -- a block counts 65 536 consecutive samples of its plane,
-//                      a wave a contiguous quarter, a lane chunks of 16 samples by one 16-byte load, 4 in flight, the predecessor of a
-//                      lane's first sample through one lane move, the plane's last block byte by byte where it ends -- but eight
-//                      residual bins are bumped per sample: width q's residual is ((b >> (8 - q)) - (prev >> (8 - q))) mod 2^q of the
-//                      8-bit sample b and its predecessor.
+//   k_qsweep_hist<NT>  csic_count.h's byte walk over the CSIC_FMT_PLANAR frame (the blocks, the LDS bins, the flush, the predecessor move
+//                      and the ragged end are that header's, shared with csic_code_stats.hip) under QhCount: eight residual bins are
+//                      bumped per sample, width q's residual being ((b >> (8 - q)) - (prev >> (8 - q))) mod 2^q of the 8-bit sample b
+//                      and its predecessor.
 //   k_qsweep_clear     zeroes the 6144 bins of every frame's hist (a kernel, not a memset of an interior pointer: DESIGN.md 4.13).
 // Both SSE kernels run with the masks at 0xFF: the output value o they see is the unquantised one.  At width q the output is o - t_q
 // with t_q = o & (0xFF >> q), constant over the n input pixels paired with o, and with e = ref - o their squared errors sum to
@@ -28,12 +27,12 @@
 // may be negative (|.| <= 127 * (2 * 64 * 255 + 64 * 127) < 2^23); it is added modulo 2^32 to a total that is not.  The block sum, the
 // partials and the frame's sums are 64-bit.  No atomics on this side: each block writes its own 192-byte partial with plain vector
 // stores.
-// Counting: 510 bins per wave in LDS (2^q bins of width q at offset 2^q - 2; padded to 512), 8 KiB per block, bumped with LDS atomics
-// (a block's 65 536 samples cannot overflow a bin); after one barrier thread t adds the four waves' bins t and t + 256 and, where the
-// sum is not zero, issues one 64-bit global atomic add.  No loop of any kernel has a length that depends on buffer contents.  Every
-// global access goes through the checked accessors of csic_kernel_ops.h or sits behind a CSIC_CHECK.
+// Counting: 510 of csic_count.h's 512 LDS bins per wave (2^q bins of width q at offset 2^q - 2).  No loop of any kernel has a length
+// that depends on buffer contents.  Every global access goes through the checked accessors of csic_kernel_ops.h or sits behind a
+// CSIC_CHECK.
 #include <cstdio>
 
+#include "csic_count.h"
 #include "csic_measure.h"
 
 namespace csic {
@@ -42,12 +41,8 @@ constexpr int QS_T = MEAS_T, QS_WAVES = QS_T / 64;
 constexpr int QS_W = CSIC_QSWEEP_WIDTHS, QS_CH = CSIC_STATS_PLANES * QS_W;           // 24 sums per frame
 constexpr int QS_RES_WORDS = (int)(sizeof(csic_qsweep_result) / sizeof(uint64_t));   // 6168
 constexpr int QS_HIST_WORDS = QS_CH * CSIC_STATS_BINS;                               // 6144
-constexpr int QS_K = 4;                                                              // 16-byte loads in flight per lane
-constexpr uint32_t QS_BLOCK = (uint32_t)CSTAT_BLOCK_SAMPLES, QS_WAVE = QS_BLOCK / QS_WAVES;
-constexpr int QS_LDS_BINS = 512;                                                     // 510 in use
-static_assert(QS_W == 8 && CSIC_STATS_BINS == 256 && QS_T == 256, "thread t flushes bins t and t + 256 of the 510");
+static_assert(QS_W == 8 && CSIC_STATS_BINS == 256 && QS_T == CNT_T, "the eight widths' 510 bins fit csic_count.h's 512");
 static_assert(QS_RES_WORDS == QS_CH + QS_HIST_WORDS && offsetof(csic_qsweep_result, hist) == QS_CH * sizeof(uint64_t), "sse, then hist");
-static_assert(QS_WAVE % (16 * 64 * QS_K) == 0, "a wave's span is whole rounds");
 
 struct QExtra {
     uint64_t *part;                  // workspace: nblk partials of QS_CH uint64 per frame, frames back to back
@@ -56,7 +51,6 @@ struct QExtra {
 };
 
 typedef uint64_t CSIC_GLOBAL *gqpart_t;
-typedef unsigned long long CSIC_GLOBAL *gqhist_t;
 
 // ------------------------------------------------------------------------------------------------
 // the 24 sums
@@ -242,121 +236,37 @@ static __global__ void __launch_bounds__(QS_T) k_qsweep_sum(const uint64_t *part
 // ------------------------------------------------------------------------------------------------
 // k_qsweep_hist
 // ------------------------------------------------------------------------------------------------
-struct QhArgs {
-    const uint8_t *src;            // CSIC_FMT_PLANAR frames, frame_bytes apart
-    unsigned long long *res;       // csic_qsweep_result per frame, as 64-bit words
-    int64_t frame_bytes;
-    int64_t off[3];                // plane offsets
-    uint32_t n[3];                 // samples per plane
+// csic_count.h's policy: the code of a byte is the byte; a sample bumps eight residual bins, width q's at 2^q - 2 (510 bins, the
+// last two of the 512 unused); LDS bin k is word hist[plane][q - 1][r] of the frame's csic_qsweep_result
+struct QhCount {
+    __device__ __forceinline__ uint32_t code(uint32_t byte) const { return byte; }
+    // 8-bit value b after 8-bit value prev (0 in front of sample 0)
+    __device__ __forceinline__ void bump(uint32_t *wh, uint32_t b, uint32_t prev) const
+    {
+#pragma unroll
+        for (int q = 1; q <= QS_W; ++q) {
+            const uint32_t r = ((b >> (8 - q)) - (prev >> (8 - q))) & ((1u << q) - 1u);
+            __hip_atomic_fetch_add(&wh[(1u << q) - 2u + r], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+    static constexpr uint32_t STRIDE = QS_RES_WORDS;
+    static __device__ __forceinline__ bool has_word(uint32_t k) { return k < 510u; }
+    static __device__ __forceinline__ uint32_t index(int plane, uint32_t k0, uint32_t t)
+    {
+        const uint32_t k = k0 + t;
+        const uint32_t q = 31u - (uint32_t)__builtin_clz(k + 2u), r = k + 2u - (1u << q);
+        CSIC_CHECK(q >= 1u && q <= 8u && r < (1u << q) && plane < CSIC_STATS_PLANES);
+        return (uint32_t)QS_CH + ((uint32_t)plane * QS_W + (q - 1u)) * CSIC_STATS_BINS + r;
+    }
 };
 
-template <bool NT> __device__ __forceinline__ u32x4 qh_ld16(const QhArgs &e, gcbyte_t fb, int64_t off) { return by_ld16<NT>(e.frame_bytes, fb, off); }
-__device__ __forceinline__ uint32_t qh_ld1(const QhArgs &e, gcbyte_t fb, int64_t off) { return by_ld1(e.frame_bytes, fb, off); }
-
-struct QhLds { uint32_t h[QS_WAVES][QS_LDS_BINS]; };
-
-// clears the block's histograms and returns this wave's set
-__device__ __forceinline__ uint32_t *qh_begin(QhLds &s)
-{
-    uint32_t *all = &s.h[0][0];
-#pragma unroll
-    for (int i = 0; i < QS_WAVES * QS_LDS_BINS / QS_T; ++i) all[i * QS_T + threadIdx.x] = 0;
-    __syncthreads();
-    return &s.h[threadIdx.x >> 6][0];
-}
-
-// one sample: 8-bit value b after 8-bit value prev (0 in front of sample 0); width q's bins sit at 2^q - 2
-__device__ __forceinline__ void qh_count(uint32_t *wh, uint32_t b, uint32_t prev)
-{
-#pragma unroll
-    for (int q = 1; q <= QS_W; ++q) {
-        const uint32_t r = ((b >> (8 - q)) - (prev >> (8 - q))) & ((1u << q) - 1u);
-        __hip_atomic_fetch_add(&wh[(1u << q) - 2u + r], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-}
-
-// the four waves' bins -> the frame's hist: thread t owns packed bins t and t + 256
-__device__ __forceinline__ void qh_flush(const QhArgs &e, QhLds &s, int plane)
-{
-    __syncthreads();
-    const gqhist_t res = (gqhist_t)(uintptr_t)e.res;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        const uint32_t k = threadIdx.x + (uint32_t)half * QS_T;
-        if (k >= 510u) continue;
-        uint32_t t = 0;
-#pragma unroll
-        for (int w = 0; w < QS_WAVES; ++w) t += s.h[w][k];
-        if (t) {
-            const uint32_t q = 31u - (uint32_t)__builtin_clz(k + 2u), r = k + 2u - (1u << q);
-            const uint32_t at = (uint32_t)QS_CH + ((uint32_t)plane * QS_W + (q - 1u)) * CSIC_STATS_BINS + r;
-            CSIC_CHECK(q >= 1u && q <= 8u && r < (1u << q) && plane < CSIC_STATS_PLANES && at < (uint32_t)QS_RES_WORDS && blockIdx.z < 65535u);
-            __hip_atomic_fetch_add(res + ((uint64_t)blockIdx.z * QS_RES_WORDS + at), (unsigned long long)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
-// The value in front of this lane's first sample of a step: `last` is the lane's own last value of the step, `carry` (wave-uniform)
-// what was in front of the wave's first sample of the step; afterwards carry is what is in front of the next step's.
-__device__ __forceinline__ uint32_t qh_pred(uint32_t last, uint32_t &carry)
-{
-    const uint32_t up = (uint32_t)__shfl_up((int)last, 1, 64);
-    const uint32_t pred = (threadIdx.x & 63u) == 0 ? carry : up;
-    carry = (uint32_t)__shfl((int)last, 63, 64);
-    return pred;
-}
-
-// chunk `ch` of a plane of n samples as four dwords: CHECK = the plane may end in or before it
-template <bool NT, bool CHECK>
-__device__ __forceinline__ u32x4 qh_chunk(const QhArgs &e, gcbyte_t fb, int64_t plane_off, uint32_t ch, uint32_t n)
-{
-    if (!CHECK || 16u * ch + 16u <= n) return qh_ld16<NT>(e, fb, plane_off + 16 * (int64_t)ch);
-    uint32_t w[4] = {0, 0, 0, 0};
-    for (uint32_t i = 16u * ch; i < n; ++i) w[(i >> 2) & 3u] |= qh_ld1(e, fb, plane_off + i) << (8u * (i & 3u));
-    return u32x4{w[0], w[1], w[2], w[3]};
-}
-
-template <bool NT, bool CHECK>
-__device__ __forceinline__ void qh_body(const QhArgs &e, gcbyte_t fb, uint32_t *wh, int plane, uint32_t i0)
-{
-    const uint32_t n = e.n[plane], lane = threadIdx.x & 63u;
-    const int64_t off = e.off[plane];
-    // in front of the wave's span: the byte before it, nothing at sample 0 (and nothing for a wave past the plane's end)
-    uint32_t carry = 0;
-    if (i0 > 0 && (!CHECK || i0 < n)) carry = qh_ld1(e, fb, off + i0 - 1);
-    for (uint32_t c0 = i0 / 16u; c0 < (i0 + QS_WAVE) / 16u; c0 += 64u * QS_K) {
-        if (CHECK && 16u * c0 >= n) break;                                  // wave-uniform
-        u32x4 v[QS_K];
-#pragma unroll
-        for (int k = 0; k < QS_K; ++k) v[k] = qh_chunk<NT, CHECK>(e, fb, off, c0 + 64u * (uint32_t)k + lane, n);
-#pragma unroll
-        for (int k = 0; k < QS_K; ++k) {
-            const uint32_t first = 16u * (c0 + 64u * (uint32_t)k + lane);
-            const uint32_t w[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-            uint32_t prev = qh_pred(w[3] >> 24, carry);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const uint32_t b = (w[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-                if (!CHECK || first + (uint32_t)j < n) qh_count(wh, b, prev);
-                prev = b;
-            }
-        }
-    }
-}
-
 template <bool NT>
-__global__ void __launch_bounds__(QS_T) k_qsweep_hist(QhArgs e)
+__global__ void __launch_bounds__(QS_T) k_qsweep_hist(CountArgs e)
 {
-    __shared__ QhLds lds;
     const int plane = (int)blockIdx.y;
-    const uint32_t b0 = blockIdx.x * QS_BLOCK;
-    if (b0 >= e.n[plane]) return;                                           // block-uniform, before any barrier
-    uint32_t *wh = qh_begin(lds);
-    const uint32_t i0 = b0 + (threadIdx.x >> 6) * QS_WAVE;
-    const gcbyte_t fb = frame_at_z(e.src, e.frame_bytes);
-    if (e.n[plane] - b0 >= QS_BLOCK) qh_body<NT, false>(e, fb, wh, plane, i0);
-    else                             qh_body<NT, true>(e, fb, wh, plane, i0);
-    qh_flush(e, lds, plane);
+    count_block<QhCount>(e, plane, [&](auto check, gcbyte_t fb, uint32_t *wh, uint32_t i0) {
+        count_bytes_body<NT, CSIC_CONST(check)>(e, fb, wh, plane, i0, QhCount{});
+    });
 }
 
 // grid (24, 1, nframes): one 256-bin histogram per block
@@ -364,7 +274,7 @@ static __global__ void __launch_bounds__(QS_T) k_qsweep_clear(unsigned long long
 {
     const uint32_t at = (uint32_t)QS_CH + blockIdx.x * (uint32_t)CSIC_STATS_BINS + threadIdx.x;
     CSIC_CHECK(at < (uint32_t)QS_RES_WORDS);
-    ((gqhist_t)(uintptr_t)res)[(uint64_t)blockIdx.z * QS_RES_WORDS + at] = 0ull;
+    ((gcount_t)(uintptr_t)res)[(uint64_t)blockIdx.z * QS_RES_WORDS + at] = 0ull;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -391,11 +301,8 @@ static int qs_check_format(const csic_plan *pl)
     return CSIC_OK;
 }
 
-static int qs_check_frames(int32_t nframes)
-{
-    if (nframes < 1 || nframes > 65535) return set_error(CSIC_EINVAL_SIZE, "nframes must be in 1..65535. Got %d", nframes);
-    return CSIC_OK;
-}
+static const char *const QS_FRAMES_FMT = "nframes must be in 1..65535. Got %d";
+static int qs_check_frames(int32_t nframes) { return count_check_frames(nframes, QS_FRAMES_FMT); }
 
 // k_qsweep_sse_fast: units per frame; k_qsweep_sse_gen: output pixels per frame (as DistUnit)
 static uint32_t qs_units(const Geometry &g, int kind)
@@ -436,29 +343,18 @@ static int qs_workspace(const csic_plan *pl, int32_t nframes, size_t *part_bytes
     return CSIC_OK;
 }
 
-static void qs_fill_hist_args(const csic_plan *pl, QhArgs *e)
-{
-    std::memset(e, 0, sizeof *e);
-    csic_planar_layout G;
-    planar_layout(pl->g, &pl->p, &G);
-    e->n[0] = (uint32_t)((int64_t)G.y_width * G.y_height);
-    e->n[1] = e->n[2] = (uint32_t)G.chroma_samples;
-    e->off[0] = G.y_offset; e->off[1] = G.cb_offset; e->off[2] = G.cr_offset;
-    e->frame_bytes = G.frame_bytes;
-}
-
 // the clear and k_qsweep_hist over nframes planar frames (arguments checked by the callers)
 static int qs_hist_launch(const csic_plan *pl, const void *d_planar, int32_t nframes, csic_qsweep_result *d_result, hipStream_t stream)
 {
-    QhArgs e;
-    qs_fill_hist_args(pl, &e);
+    CountArgs e;
+    count_fill_planar(pl, &e);
     e.src = static_cast<const uint8_t *>(d_planar);
     e.res = reinterpret_cast<unsigned long long *>(d_result);
     int st = launch(k_qsweep_clear, dim3(QS_CH, 1, (unsigned)nframes), dim3(QS_T, 1, 1), stream, e.res);
     if (st != CSIC_OK) return st;
     const uint32_t nmax = e.n[0] > e.n[1] ? e.n[0] : e.n[1];
     if (nmax == 0) return CSIC_OK;
-    const unsigned blocks = (unsigned)(((uint64_t)nmax + QS_BLOCK - 1) / QS_BLOCK);
+    const unsigned blocks = (unsigned)(((uint64_t)nmax + CNT_BLOCK - 1) / CNT_BLOCK);
     const auto fn = pl->tune.no_nt ? k_qsweep_hist<false> : k_qsweep_hist<true>;
     return launch(fn, dim3(blocks, CSIC_STATS_PLANES, (unsigned)nframes), dim3(QS_T, 1, 1), stream, e);
 }
@@ -489,7 +385,7 @@ const char *csic_qsweep_kernel_name(const csic_plan *plan)
 int csic_qsweep_block_samples(const csic_plan *plan, int64_t *samples)
 {
     if (!plan || !samples) return set_error(CSIC_EINVAL_NULL, "plan or samples is NULL");
-    *samples = QS_BLOCK;
+    *samples = CNT_BLOCK;
     clear_error();
     return CSIC_OK;
 }
@@ -498,16 +394,13 @@ int csic_qsweep_hist_device(csic_plan *plan, const void *d_planar, int32_t nfram
 {
     if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
     if (!d_planar || !d_result) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
-    int st = qs_check_frames(nframes);
-    if (st != CSIC_OK) return st;
-    if ((uintptr_t)d_planar & 255u) return set_error(CSIC_EINVAL_SIZE, "a planar frame buffer must be 256-byte aligned");
-    if ((uintptr_t)d_result & 7u) return set_error(CSIC_EINVAL_SIZE, "d_result must be 8-byte aligned");
-    st = qs_check_format(plan);
+    int st = count_check_buffers(nframes, QS_FRAMES_FMT, d_planar, d_result, "d_result must be 8-byte aligned");
+    if (st == CSIC_OK) st = qs_check_format(plan);
     if (st != CSIC_OK) return st;
     st = csic_device_count();
     if (st < 0) return st;
-    const Geometry &g = plan->g;
-    if ((int64_t)g.W * g.H >= ((int64_t)1 << 31)) return set_error(CSIC_EINVAL_SIZE, "frame too large for csic_qsweep_hist_device");
+    st = count_check_size(plan->g, "frame too large for csic_qsweep_hist_device");
+    if (st != CSIC_OK) return st;
     CSIC_DEVICE_SCOPE(plan->device);
     st = qs_hist_launch(plan, d_planar, nframes, d_result, static_cast<hipStream_t>(hip_stream));
     if (st != CSIC_OK) return st;
