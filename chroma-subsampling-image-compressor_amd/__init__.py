@@ -8,7 +8,7 @@ ImageCompressionApp).  There is no CPU compute path in here.
 from . import _native
 from ._native import CsicIOError, CsicRuntimeError, IllegalArgumentException
 from .params import ImageProcessorParams, PixelFormat, ProcessingStep, Rounding, Sampling, make_c_params
-from .compressor import CodeStats, Distortion, FrameGraph, ImageCompressorTop, ImageProcessor, Plan, QSweep, Ssim
+from .compressor import CodeStats, Distortion, FrameGraph, ImageCompressorTop, ImageProcessor, Plan, QSweep, Ssim, View
 from .model import Image, ImageProcessorModel
 from .pipeline import FramePipeline
 from .stages import (ChromaSubsampler, ColorQuantizer, PixelBundle, PixelYCbCrBundle, ReferenceModel, RGB2YCbCr,
@@ -22,7 +22,7 @@ from . import app, compressor, container, distributed, model, params, pipeline, 
 
 __all__ = [
     "CsicIOError", "CsicRuntimeError", "IllegalArgumentException", "ImageProcessorParams", "PixelFormat", "ProcessingStep",
-    "Rounding", "Sampling", "make_c_params", "ImageCompressorTop", "ImageProcessor", "Plan", "FrameGraph", "Distortion", "Ssim", "CodeStats", "QSweep", "Image", "ImageProcessorModel",
+    "Rounding", "Sampling", "make_c_params", "ImageCompressorTop", "ImageProcessor", "Plan", "FrameGraph", "Distortion", "Ssim", "CodeStats", "QSweep", "View", "Image", "ImageProcessorModel",
     "ImageCompressionApp", "FramePipeline", "ChromaSubsampler", "ColorQuantizer", "PixelBundle", "PixelYCbCrBundle", "ReferenceModel", "RGB2YCbCr",
     "SpatialDownsampler", "YCbCrUtils", "pack_ycc", "unpack_ycc", "Stripe", "StripedImageCompressorTop", "MultiDeviceCompressor", "halo_stripe_for_rank", "stripe_for_rank",
     "container_info", "read_container", "write_container", "write_container_coded", "container_coded_sizes", "pack_layout", "pack_frame_host",

@@ -131,6 +131,10 @@ class CsicContainerInfo(C.Structure):
                 ("file_bytes", C.c_int64)]
 
 
+class CsicView(C.Structure):
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("scale", C.c_int32)]
+
+
 class CsicFilesStats(C.Structure):
     _fields_ = [("frames", C.c_int64), ("wall_s", C.c_double), ("decode_s", C.c_double), ("encode_s", C.c_double),
                 ("gpu_wait_s", C.c_double), ("slot_wait_s", C.c_double), ("decode_threads", C.c_int32), ("encode_threads", C.c_int32),
@@ -163,6 +167,9 @@ PROTOTYPES = {
     "csic_decode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "csic_decode_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32]),
     "csic_decode_kernel_name": (C.c_char_p, [C.c_void_p, C.c_int32, C.c_int32]),
+    "csic_decode_view_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CsicView), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "csic_decode_view_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(CsicView), C.c_void_p, C.c_size_t, C.c_int32, C.c_int32]),
+    "csic_decode_view_kernel_name": (C.c_char_p, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CsicView)]),
     "csic_container_info_of": (C.c_int, [C.c_char_p, C.POINTER(CsicContainerInfo)]),
     "csic_container_write": (C.c_int, [C.c_char_p, C.POINTER(CsicParams), C.c_void_p, C.c_int32]),
     "csic_container_read": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t]),

@@ -15,6 +15,7 @@ Two leading verbs go past what the reference's app does (it only ever writes the
     python -m csic_amd.app compress   --input x.png --output x.csic --target-bytes N [--coding raw|groups|rice|rans] [--yq 8 --cbq 8 --crq 8: upper bounds]
     python -m csic_amd.app compress   --inputs a.png,b.png,... --gop K [--motion R] --coding groups|rice|rans --output x.csic ...
     python -m csic_amd.app decompress --input x.csic --output x.png [--frame K | --output-pattern frame_%03d.png]
+    python -m csic_amd.app decompress --input x.csic --output x.png [--window x,y,w,h] [--scale 1|2|4|8|16]    (a window of the frame, box-reduced: decompress --help)
 
     python -m csic_amd.app inspect    --input x.csic
 
@@ -34,7 +35,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from .compressor import ImageCompressorTop, Plan
+from .compressor import ImageCompressorTop, Plan, View
 from . import _native as N
 from .container import (container_coded_sizes, container_info, container_inter_groups, delta_layout, mc_layout, rans_layout, read_container, rows_layout,
                         write_container, write_container_coded)
@@ -227,24 +228,44 @@ class ImageCompressionApp:
         return os.path.getsize(outputPath)
 
     @staticmethod
-    def decompressImage(inputPath: str, outputImagePath: str, *, device: int = 0, frame: int = 0) -> None:
+    def viewOf(width: int, height: int, window=None, scale: int = 1) -> Optional[View]:
+        """The View of `decompress --window x,y,w,h --scale s` on a width x height frame: the window is in source pixels (default:
+        the whole frame), the output is (w // s) x (h // s) pixels and the remainder of the window is dropped.  None when neither is
+        given -- the plain decode.  A scale outside 1, 2, 4, 8, 16, a window outside the frame or smaller than one box is refused."""
+        if window is None and scale == 1:
+            return None
+        if scale not in (1, 2, 4, 8, 16):
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: --scale must be 1, 2, 4, 8 or 16, got {scale}")
+        x, y, w, h = (0, 0, width, height) if window is None else window
+        if x < 0 or y < 0 or w < 1 or h < 1 or x + w > width or y + h > height:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: --window {x},{y},{w},{h} does not lie inside the {width}x{height} frame")
+        if w < scale or h < scale:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: --window {x},{y},{w},{h} is smaller than one {scale}x{scale} box")
+        return View(x, y, w // scale, h // scale, scale)
+
+    @staticmethod
+    def decompressImage(inputPath: str, outputImagePath: str, *, device: int = 0, frame: int = 0, window=None, scale: int = 1) -> None:
         """.csic container -> plan from the stored parameters -> csic_decode_* -> PNG of width x height: frame `frame` of a container
-        that holds several (the first by default)."""
+        that holds several (the first by default).  With a window (x, y, w, h in source pixels) or a scale: csic_decode_view_*, a PNG
+        of (w // scale) x (h // scale) pixels (viewOf)."""
         c_params, nframes, frames = read_container(inputPath)
         if not 0 <= frame < nframes:
             raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: --frame must be in 0..{nframes - 1}, got {frame}")
+        view = ImageCompressionApp.viewOf(c_params.width, c_params.height, window, scale)
         with Plan(c_params, device) as plan:
-            argb = plan.decode_host(frames[frame])
+            argb = plan.decode_host(frames[frame]) if view is None else plan.decode_view_host(frames[frame], view)
         ImageProcessorModel.writeImage(Image(argb), outputImagePath)
 
     @staticmethod
-    def decompressImages(inputPath: str, outputPattern: str, *, device: int = 0) -> List[str]:
-        """Every frame of a container to outputPattern % k (a printf pattern such as "frame_%03d.png").  Returns the paths written."""
+    def decompressImages(inputPath: str, outputPattern: str, *, device: int = 0, window=None, scale: int = 1) -> List[str]:
+        """Every frame of a container to outputPattern % k (a printf pattern such as "frame_%03d.png"), whole or as the view of
+        `window` and `scale` (decompressImage).  Returns the paths written."""
         c_params, nframes, frames = read_container(inputPath)
         paths = [outputPattern % k for k in range(nframes)]
+        view = ImageCompressionApp.viewOf(c_params.width, c_params.height, window, scale)
         with Plan(c_params, device) as plan:
             for k, path in enumerate(paths):
-                ImageProcessorModel.writeImage(Image(plan.decode_host(frames[k])), path)
+                ImageProcessorModel.writeImage(Image(plan.decode_host(frames[k]) if view is None else plan.decode_view_host(frames[k], view)), path)
         return paths
 
     @staticmethod
@@ -330,6 +351,19 @@ def _args_map(args: List[str]) -> Dict[str, str]:
     return argsMap
 
 
+DECOMPRESS_HELP = """usage: python -m csic_amd.app decompress --input x.csic (--output x.png [--frame K] | --output-pattern frame_%03d.png)
+                                         [--window x,y,w,h] [--scale s]
+  --input           a .csic container of any version
+  --output          the PNG to write: frame 0, or frame K with --frame K
+  --output-pattern  a printf pattern: every frame of the container is written
+  --window x,y,w,h  decode only this rectangle of the frame, given in source pixels (default: the whole frame); a window outside
+                    the frame is refused
+  --scale s         reduce by an s x s box, s = 1, 2, 4, 8 or 16 (default 1): each output pixel is the rounded mean of the s x s
+                    decoded pixels under it.  The PNG is (w // s) x (h // s) pixels: the remainder of a window that is no multiple
+                    of s is dropped at its right and bottom edges; a window smaller than one box is refused
+Without --window and --scale the whole frame is decoded at its original size."""
+
+
 def _main_container(verb: str, args: List[str]) -> int:
     """`compress` / `decompress`: the keys of the verb-less CLI with its defaults, plus --output and (compress) --sampling avg and
     --coding raw|groups|rice|rans."""
@@ -343,11 +377,35 @@ def _main_container(verb: str, args: List[str]) -> int:
             print("[ERROR] --target-bytes takes one image (--input): sequences under a byte budget are not supported")
             return 2
         return _main_sequence(argsMap)
+    window, scale = None, 1
+    if verb == "decompress":
+        if "--help" in args:
+            print(DECOMPRESS_HELP)
+            return 0
+        try:
+            scale = int(argsMap.get("--scale", "1"))
+        except ValueError:
+            scale = 0
+        if "--window" in argsMap:
+            try:
+                window = tuple(int(x) for x in argsMap["--window"].split(","))
+            except ValueError:
+                window = ()
+        if scale not in (1, 2, 4, 8, 16):
+            print(f"[ERROR] --scale must be 1, 2, 4, 8 or 16, got {argsMap.get('--scale')}")
+            return 2
+        if window is not None and len(window) != 4:
+            print(f"[ERROR] --window must be x,y,w,h in source pixels, got {argsMap.get('--window')}")
+            return 2
     if verb == "decompress" and "--output-pattern" in argsMap and "--input" in argsMap:
         if not os.path.exists(argsMap["--input"]):
             print(f"[ERROR] Input not found: {argsMap['--input']}")
             return 1
-        paths = ImageCompressionApp.decompressImages(argsMap["--input"], argsMap["--output-pattern"])
+        try:
+            paths = ImageCompressionApp.decompressImages(argsMap["--input"], argsMap["--output-pattern"], window=window, scale=scale)
+        except N.IllegalArgumentException as e:
+            print(f"[ERROR] {e}")
+            return 1
         print(f"Decompression complete. {len(paths)} frames saved to: {argsMap['--output-pattern']}")
         return 0
     if "--input" not in argsMap or "--output" not in argsMap:
@@ -358,7 +416,14 @@ def _main_container(verb: str, args: List[str]) -> int:
         print(f"[ERROR] Input not found: {inputPath}")
         return 1
     if verb == "decompress":
-        ImageCompressionApp.decompressImage(inputPath, outputPath, frame=int(argsMap.get("--frame", "0")))
+        if window is None and scale == 1:
+            ImageCompressionApp.decompressImage(inputPath, outputPath, frame=int(argsMap.get("--frame", "0")))
+        else:
+            try:
+                ImageCompressionApp.decompressImage(inputPath, outputPath, frame=int(argsMap.get("--frame", "0")), window=window, scale=scale)
+            except N.IllegalArgumentException as e:
+                print(f"[ERROR] {e}")
+                return 1
         print(f"Decompression complete. Output saved to: {outputPath}")
         return 0
     sampling = Sampling.AVG if argsMap.get("--sampling", "hold").lower() == "avg" else Sampling.HOLD_DECIMATE

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Tuple
+from typing import NamedTuple, Tuple
 
 import numpy as np
 
@@ -26,6 +26,16 @@ from .params import (ImageProcessorParams, PixelFormat, ProcessingStep, Rounding
 
 def _is_torch_tensor(x) -> bool:
     return type(x).__module__.split(".")[0] == "torch"
+
+
+class View(NamedTuple):
+    """A window of a decoded frame for Plan.decode_view_* (csic_view): the source rectangle starts at (x0, y0) and covers width *
+    scale x height * scale decoded pixels; width and height count OUTPUT pixels; scale is 1, 2, 4, 8 or 16."""
+    x0: int
+    y0: int
+    width: int
+    height: int
+    scale: int = 1
 
 
 class Distortion:
@@ -967,6 +977,56 @@ class Plan:
             return self.decode_device(src, src_format, None, nframes, out_format)
         return self.decode_host(src, src_format, nframes, out_format)
 
+    # -- view decode (csic_decode_view_*) ---------------------------------------------------------
+    @staticmethod
+    def _c_view(view) -> "N.CsicView":
+        return N.CsicView(*(int(x) for x in View(*view)))
+
+    def decode_view_kernel_name(self, src_format: int, view, out_format: int = N.FMT_ARGB8888) -> str:
+        """The kernel decode_view_device takes for 16-byte aligned buffers (csic_decode_view_kernel_name); "" for a refused pair or view."""
+        return N.lib().csic_decode_view_kernel_name(self._h, int(src_format), int(out_format), C.byref(self._c_view(view))).decode()
+
+    def decode_view_device(self, d_src, view, src_format=None, d_out=None, nframes: int = 1, out_format: int = N.FMT_ARGB8888):
+        """A compressed frame -> the window `view` of its decode, reduced by a scale x scale box (csic_decode_view_device): view.width
+        x view.height packed pixels, each the rounded mean of the decoded pixels under its box; scale 1 is a crop.  d_src and
+        src_format as for decode_device.  Returns d_out shaped (view.height, view.width) or (nframes, ...), int32.  Asynchronous on
+        torch's current stream."""
+        import torch
+        view = View(*view)
+        src_format = self.c_params.out_format if src_format is None else int(src_format)
+        if src_format not in (N.FMT_ARGB8888, N.FMT_YCBCR888X, N.FMT_PLANAR, N.FMT_PLANAR_BITS):
+            raise N.IllegalArgumentException(N.EINVAL_FORMAT, f"requirement failed: unknown source format {src_format}")
+        if not d_src.is_cuda or not d_src.is_contiguous() or d_src.numel() * d_src.element_size() != nframes * self._decode_src_bytes(src_format):
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_src must be a contiguous CUDA tensor of nframes source frames")
+        if d_src.device.index != self.device:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: tensor is on a different device than the plan")
+        if view.width < 1 or view.height < 1:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, f"requirement failed: a view has at least one pixel, got {view.width} x {view.height}")
+        shape = (view.height, view.width) if nframes == 1 else (nframes, view.height, view.width)
+        if d_out is None:
+            d_out = torch.empty(shape, dtype=torch.int32, device=d_src.device)
+        elif d_out.numel() != nframes * view.width * view.height or d_out.element_size() != 4 or not d_out.is_contiguous() \
+                or d_out.device != d_src.device:
+            raise N.IllegalArgumentException(N.EINVAL_SIZE, "requirement failed: d_out has the wrong size/layout")
+        N.check(N.lib().csic_decode_view_device(self._h, C.c_void_p(d_src.data_ptr()), src_format, C.byref(self._c_view(view)),
+                                                C.c_void_p(d_out.data_ptr()), int(out_format), int(nframes), self._stream()))
+        return d_out
+
+    def decode_view_host(self, src: np.ndarray, view, src_format=None, nframes: int = 1, out_format: int = N.FMT_ARGB8888) -> np.ndarray:
+        """csic_decode_view_host: nframes source frames in host memory -> uint32 array (view.height, view.width) or (nframes, ...)."""
+        view = View(*view)
+        src_format = self.c_params.out_format if src_format is None else int(src_format)
+        a = np.ascontiguousarray(src).reshape(-1).view(np.uint8)
+        out = np.empty(nframes * max(view.width, 0) * max(view.height, 0), dtype=np.uint32)
+        N.check(N.lib().csic_decode_view_host(self._h, a.ctypes.data_as(C.c_void_p), a.size, src_format, C.byref(self._c_view(view)),
+                                              out.ctypes.data_as(C.c_void_p), out.size, int(out_format), int(nframes)))
+        return out.reshape((view.height, view.width) if nframes == 1 else (nframes, view.height, view.width))
+
+    def decode_view(self, src, view, src_format=None, nframes: int = 1, out_format: int = N.FMT_ARGB8888):
+        if _is_torch_tensor(src):
+            return self.decode_view_device(src, view, src_format, None, nframes, out_format)
+        return self.decode_view_host(src, view, src_format, nframes, out_format)
+
     def unpack_planar_bits(self, buf) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """One bit-packed planar frame buffer (bytes on the host) -> (Y (Ho, Wo), Cb, Cr) with the restored 8-bit values
         (code << (8 - q)): what split_planar gives for the PLANAR frame of the same parameters."""
@@ -1170,6 +1230,12 @@ class ImageCompressorTop:
         """One bit-packed planar frame buffer (what processPlanarBits returns: host bytes or a CUDA uint8 tensor) -> the ARGB frame
         of the ORIGINAL size, height x width: every reconstructed pixel replicated factor x factor times (csic_decode_*)."""
         return self.plan(PixelFormat.PLANAR_BITS).decode(buf)
+
+    def decodeView(self, buf, view):
+        """One bit-packed planar frame buffer -> the ARGB pixels of `view` (a View: x0, y0, width, height in output pixels, scale):
+        the window of decode(buf) that starts at (x0, y0), reduced by a scale x scale box (csic_decode_view_*).  The whole frame is
+        never written."""
+        return self.plan(PixelFormat.PLANAR_BITS).decode_view(buf, view)
 
     def close(self) -> None:
         for p in self._plans.values():

@@ -22,6 +22,8 @@
 //   At factor 1 a planar source IS a reconstruct: csic_reconstruct_bits_device / csic_reconstruct_device (k_rbits / k_recon) are
 //   called, and csic_decode_kernel_name says so.  (Not for a batch of frames whose W * H is not a multiple of 4: those kernels store
 //   16 bytes at a time from each frame's base, which only the first frame's alignment check covers.)
+//   k_view<LS, SRC, FMT, NT>, k_view_gen<SRC, FMT>   csic_decode_view_*: a window of the decoded frame under an s x s box, without the
+//                      frame -- described in front of them, below.
 // The planes are read through csic_plane_read.h (the chroma sample of a position, the window of a bit plane, the per-position read of
 // k_decode_gen), which k_recon and k_rbits use too.  Every global access goes through the accessors of csic_kernel_ops.h, which the
 // CSIC_DEBUG build range-checks; the forwards below name the limits: loads against the source frame's bytes, stores against the
@@ -205,6 +207,205 @@ __global__ void __launch_bounds__(256) k_decode_gen(DecArgs e)
 }
 
 // ------------------------------------------------------------------------------------------------
+// view decode: a window of the decoded frame, reduced by an s x s box (csic_decode_view_*, definition in include/csic.h)
+// ------------------------------------------------------------------------------------------------
+// An output pixel is the rounded mean of the s x s decoded pixels under its box.  decode replicates, so the box is walked over the
+// DISTINCT source positions it touches -- decimated rows (ys >> lf) .. ((ys + s - 1) >> lf) and the matching columns -- each
+// inverse-transformed once and weighted by the decoded pixels it stands for, wy * wx (the weights add up to s * s).  The four byte
+// sums ride in two registers as 16-bit pairs: at most 255 * 256 + 128 = 65 408 each.
+//   k_view<LS, SRC, FMT, NT>  the fast kernel: a lane owns 4 consecutive output pixels of a row and stores them as one 16-byte piece,
+//                      so a wave's store is one contiguous 1 KiB run.  Per decimated row the 4 boxes are walked in chunks of CH
+//                      positions; a chunk is three windows of the planes (Y, Cb, Cr: the codes of CH consecutive positions and of
+//                      their chroma samples), and the windows of all 4 boxes are loaded before the first inverse transform.  The
+//                      chroma half of the transform runs once per run of equal chroma samples inside a chunk.  Where the view's
+//                      origin is a multiple of f and s >= f no position straddles a box: the weights drop out (view_walk, WHOLE).
+//   k_view_gen<SRC, FMT>      the general kernel: one output pixel per lane straight from the definition, dec_pixel per position.
+struct ViewArgs {
+    DecArgs d;                     // the source side, as for k_decode (d.dst, d.T, d.P and the piece counts are not used)
+    uint32_t *dst;                 // vw * vh pixels per frame, back to back
+    int64_t view_px, units;        // vw * vh; lanes with work (plan_view)
+    int32_t x0, y0, vw, vh, ls;
+    int32_t ncx, ncy;              // decimated columns / rows a box can touch (plan_view)
+    int32_t whole;                 // every position a box touches lies inside it: origin % f == 0 and s >= f
+    int32_t U, T;                  // units per output row; threads per block
+    uint32_t mU, kU;               // exact t / U
+};
+
+__device__ __forceinline__ gout_t view_dst(const ViewArgs &v) { return (gout_t)(uintptr_t)v.dst + (int64_t)blockIdx.z * v.view_px; }
+
+// decoded pixels that decimated cell d -- [d f, d f + f) along one axis -- shares with the box [b, b + s)
+__device__ __forceinline__ uint32_t view_overlap(uint32_t d, uint32_t lf, uint32_t b, uint32_t s)
+{
+    return (uint32_t)max((int)min((d + 1u) << lf, b + s) - (int)max(d << lf, b), 0);
+}
+
+// the four byte sums of a box as 16-bit pairs: bytes 0 and 2 in `lo`, 1 and 3 in `hi`
+struct ViewSum { uint32_t lo, hi; };
+__device__ __forceinline__ void view_add(ViewSum &a, uint32_t px, uint32_t w)
+{
+    a.lo += (px & 0x00FF00FFu) * w;
+    a.hi += ((px >> 8) & 0x00FF00FFu) * w;
+}
+// (sum + s s / 2) >> 2 log2 s, byte by byte.  Each pair's upper sum shifts into bits the mask drops (2 LS <= 8).
+template <int LS> __device__ __forceinline__ uint32_t view_mean(const ViewSum &a)
+{
+    constexpr uint32_t half = LS == 0 ? 0u : (1u << (2 * LS - 1)) * 0x00010001u;
+    return (((a.lo + half) >> (2 * LS)) & 0x00FF00FFu) | ((((a.hi + half) >> (2 * LS)) & 0x00FF00FFu) << 8);
+}
+__device__ __forceinline__ uint32_t view_mean(const ViewSum &a, int ls)
+{
+    const uint32_t half = ls == 0 ? 0u : (1u << (2 * ls - 1)) * 0x00010001u;
+    return (((a.lo + half) >> (2 * ls)) & 0x00FF00FFu) | ((((a.hi + half) >> (2 * ls)) & 0x00FF00FFu) << 8);
+}
+
+template <int SRC, int FMT>
+__global__ void __launch_bounds__(256) k_view_gen(ViewArgs v)
+{
+    const DecArgs &e = v.d;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;    // view_px < 2^31
+    if (t >= v.view_px) return;
+    const uint32_t r = (uint32_t)(((uint64_t)t * v.mU) >> v.kU), c = (uint32_t)t - r * (uint32_t)v.U;
+    const uint32_t s = 1u << v.ls, lf = (uint32_t)e.lf;
+    const uint32_t ys = (uint32_t)v.y0 + r * s, xs = (uint32_t)v.x0 + c * s;
+    const gcbyte_t fb = dec_src(e);
+    ViewSum a = {0u, 0u};
+    for (uint32_t dr = ys >> lf; dr <= (ys + s - 1u) >> lf; ++dr) {
+        const uint32_t wy = view_overlap(dr, lf, ys, s);
+        for (uint32_t dc = xs >> lf; dc <= (xs + s - 1u) >> lf; ++dc)
+            view_add(a, dec_pixel<SRC, FMT>(e, fb, dr * (uint32_t)e.Wo + dc), wy * view_overlap(dc, lf, xs, s));
+    }
+    px_st1<false>(v.view_px, view_dst(v), t, view_mean(a, v.ls));
+}
+
+// CH consecutive stream positions from j0 on, none past jlast (positions past it repeat jlast's chroma and are weighted 0)
+template <int CH> struct ViewChunk {
+    uint32_t px[CH];            // packed sources: the pixels
+    uint32_t yw, bw, rw;        // planar sources: the windows that start at the first Y / Cb / Cr code
+    uint32_t k0, k[CH];         // the chroma sample of each position
+};
+
+template <int SRC, int CH>
+__device__ __forceinline__ ViewChunk<CH> view_load(const DecArgs &e, gcbyte_t fb, uint32_t j0, uint32_t jlast)
+{
+    ViewChunk<CH> g;
+    if (SRC == S_YCC) {
+#pragma unroll
+        for (int i = 0; i < CH; ++i) g.px[i] = dsrc4(e, fb, 4 * (int64_t)min(j0 + (uint32_t)i, jlast));
+        g.yw = g.bw = g.rw = g.k0 = 0;
+        return g;
+    }
+    const DecPlanes<SRC> s{e, fb};
+    const uint32_t imax = jlast - j0;                                     // the live positions are j0 .. j0 + imax
+    const uint32_t r0 = (uint32_t)(((uint64_t)j0 * e.mWm) >> e.kWm), cc0 = j0 - r0 * (uint32_t)e.Wm;
+    if (cc0 + min((uint32_t)(CH - 1), imax) < (uint32_t)e.Wm) {           // ... in one row of the chroma counters: one division for the chunk
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            g.k[i] = chroma_index<uint32_t>(e, r0, cc0 + min((uint32_t)i, imax));      // chroma samples <= positions < 2^31
+            g.px[i] = 0;
+        }
+    } else {                                                              // a chunk across rows of the counters (spatial before chroma, narrow frames)
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            const uint32_t j = j0 + min((uint32_t)i, imax);
+            const uint32_t r = (uint32_t)(((uint64_t)j * e.mWm) >> e.kWm), c = j - r * (uint32_t)e.Wm;
+            g.k[i] = chroma_index<uint32_t>(e, r, c);
+            g.px[i] = 0;
+        }
+    }
+    g.k0 = g.k[0];
+    g.yw = s.template y_word<false>(j0);
+    g.bw = s.c_word(1, (uint64_t)g.k0);
+    g.rw = s.c_word(2, (uint64_t)g.k0);
+    return g;
+}
+
+// position i of a chunk as a packed pixel; t / kt: the chroma term of the chunk's previous position and the sample it belongs to
+template <int SRC, int FMT, int CH>
+__device__ __forceinline__ uint32_t view_chunk_pixel(const DecArgs &e, gcbyte_t fb, const ViewChunk<CH> &g, int i, ChromaTerm &t, uint32_t &kt)
+{
+    if (SRC == S_YCC)
+        return FMT == F_ARGB ? finish_y<F_ARGB>(g.px[i] & 0xFFu, chroma_term_q<F_ARGB>((g.px[i] >> 8) & 0xFFu, (g.px[i] >> 16) & 0xFFu)) : g.px[i];
+    const uint32_t qy = dec_q<SRC>(e, 0), qb = dec_q<SRC>(e, 1), qr = dec_q<SRC>(e, 2);
+    if (i == 0 || g.k[i] != kt) {
+        const uint32_t d = g.k[i] - g.k0;
+        uint32_t cb, cr;
+        if (d < 4u) { cb = code_at(g.bw, d, qb); cr = code_at(g.rw, d, qr); }          // a window holds 32 / q >= 4 codes
+        else { const DecPlanes<SRC> s{e, fb}; cb = s.c_one(1, (uint64_t)g.k[i]); cr = s.c_one(2, (uint64_t)g.k[i]); }   // a chunk across stream rows
+        t = chroma_term_q<FMT>(cb, cr);
+        kt = g.k[i];
+    }
+    return finish_y<FMT>(code_at(g.yw, (uint32_t)i, qy), t);
+}
+
+// The boxes of a lane: VIEW_PX consecutive output pixels whose boxes start at (xs + m S, ys).  WHOLE: every position a box touches lies
+// inside it (the view's origin is a multiple of f, S >= f) and a box row is whole chunks (ncx % CH == 0) -- every weight is f * f, so
+// the sums are taken over the positions and the f * f goes into view_mean's shift; no overlap is computed and no load is clamped.
+template <int LS, int SRC, int FMT, bool WHOLE>
+__device__ __forceinline__ void view_walk(const ViewArgs &v, gcbyte_t fb, uint32_t xs, uint32_t ys, ViewSum a[VIEW_PX])
+{
+    constexpr uint32_t S = 1u << LS;
+    constexpr int CH = S >= 4u ? 4 : (int)S;
+    const DecArgs &e = v.d;
+    const uint32_t lf = (uint32_t)e.lf;
+    const uint32_t dr0 = ys >> lf, dr1 = (ys + S - 1u) >> lf;
+    uint32_t c0[VIEW_PX], c1[VIEW_PX];
+#pragma unroll
+    for (int m = 0; m < VIEW_PX; ++m) {
+        c0[m] = (xs + (uint32_t)m * S) >> lf;
+        c1[m] = (xs + (uint32_t)m * S + S - 1u) >> lf;
+        a[m] = ViewSum{0u, 0u};
+    }
+    // (neither loop is unrolled: with the cheap YCbCr body hipcc unrolled them eightfold at S = 1 and took all 256 VGPRs)
+#pragma unroll 1
+    for (uint32_t iy = 0; iy < (uint32_t)v.ncy; ++iy) {
+        const uint32_t wy = WHOLE ? 1u : view_overlap(dr0 + iy, lf, ys, S);   // 0 on a row past the box: it loads the box's last row again
+        const uint32_t row = (WHOLE ? dr0 + iy : min(dr0 + iy, dr1)) * (uint32_t)e.Wo;
+#pragma unroll 1
+        for (uint32_t ix = 0; ix < (uint32_t)v.ncx; ix += (uint32_t)CH) {
+            ViewChunk<CH> g[VIEW_PX];
+#pragma unroll
+            for (int m = 0; m < VIEW_PX; ++m)
+                g[m] = view_load<SRC, CH>(e, fb, row + (WHOLE ? c0[m] + ix : min(c0[m] + ix, c1[m])), row + c1[m]);
+#pragma unroll
+            for (int m = 0; m < VIEW_PX; ++m) {
+                ChromaTerm ct = {0, 0, 0, 0u};
+                uint32_t kt = 0;
+#pragma unroll
+                for (int i = 0; i < CH; ++i) {
+                    const uint32_t px = view_chunk_pixel<SRC, FMT, CH>(e, fb, g[m], i, ct, kt);
+                    if (WHOLE) { a[m].lo += px & 0x00FF00FFu; a[m].hi += (px >> 8) & 0x00FF00FFu; continue; }
+                    // column c0 + ix + i of the box; past c1 the weight is 0, whatever the chunk holds there
+                    view_add(a[m], px, wy * view_overlap(c0[m] + ix + (uint32_t)i, lf, xs + (uint32_t)m * S, S));
+                }
+            }
+        }
+    }
+}
+
+template <int LS, int SRC, int FMT, bool NT>
+__global__ void __launch_bounds__(256) k_view(ViewArgs v)
+{
+    constexpr uint32_t S = 1u << LS;
+    constexpr int CH = S >= 4u ? 4 : (int)S;
+    const uint32_t t = blockIdx.x * (uint32_t)v.T + threadIdx.x;          // units <= 2^28
+    if (t >= (uint32_t)v.units) return;
+    const uint32_t r = (uint32_t)(((uint64_t)t * v.mU) >> v.kU), pc = t - r * (uint32_t)v.U;
+    const uint32_t ys = (uint32_t)v.y0 + r * S, xs = (uint32_t)v.x0 + (uint32_t)VIEW_PX * pc * S;
+    const gcbyte_t fb = dec_src(v.d);
+    ViewSum a[VIEW_PX];
+    u32x4 piece;
+    if (v.whole && v.ncx % CH == 0) {                                     // (uniform)
+        view_walk<LS, SRC, FMT, true>(v, fb, xs, ys, a);
+        const int sh = LS - v.d.lf;                                       // (f f sum + s s / 2) >> 2 LS == (sum + n / 2) >> log2 n, n = (s / f)^2
+        piece = u32x4{view_mean(a[0], sh), view_mean(a[1], sh), view_mean(a[2], sh), view_mean(a[3], sh)};
+    } else {
+        view_walk<LS, SRC, FMT, false>(v, fb, xs, ys, a);
+        piece = u32x4{view_mean<LS>(a[0]), view_mean<LS>(a[1]), view_mean<LS>(a[2]), view_mean<LS>(a[3])};
+    }
+    px_st4n<NT>(v.view_px, view_dst(v), r * (uint32_t)v.vw + (uint32_t)VIEW_PX * pc, piece);
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 using DecFn = void (*)(DecArgs);
@@ -262,6 +463,23 @@ static DecFn decode_kernel(DecodeKind kind, int src_format, int out_format, int 
                     return with_const<1, 2, 4, 8>(f, [](auto ff) -> DecFn { return k_decode<SRC, FMT, CSIC_CONST(ff), NT>; });
                 else                                                      // factor 1 from planes is k_rbits / k_recon
                     return with_const<2, 4, 8>(f, [](auto ff) -> DecFn { return k_decode<SRC, FMT, CSIC_CONST(ff), NT>; });
+            });
+        });
+    });
+}
+
+using ViewFn = void (*)(ViewArgs);
+
+static ViewFn view_kernel(const ViewPlan &vp, int src_format, int out_format, bool nt)
+{
+    if (src_format == S_ARGB) { src_format = S_YCC; out_format = F_YCC; }          // as decode_kernel: a plain copy under the box
+    return with_const<F_ARGB, F_YCC>(out_format, [&](auto fmt) {
+        return with_const<S_BITS, S_PLANAR, S_YCC>(src_format, [&](auto s) -> ViewFn {
+            constexpr int SRC = CSIC_CONST(s), FMT = CSIC_CONST(fmt);
+            if (vp.kind == VIEW_GEN) return k_view_gen<SRC, FMT>;
+            return with_const<true, false>(nt, [&](auto n) -> ViewFn {
+                constexpr bool NT = CSIC_CONST(n);
+                return with_const<0, 1, 2, 3, 4>(vp.ls, [](auto l) -> ViewFn { return k_view<CSIC_CONST(l), SRC, FMT, NT>; });
             });
         });
     });
@@ -351,6 +569,85 @@ int csic_decode_host(csic_plan *plan, const void *src, size_t src_bytes, int32_t
     }
     if (st != CSIC_OK) return st;
     if (!dev.ok()) return set_error(CSIC_EHIP, "csic_decode_host: %s", hipGetErrorString(dev.error()));
+    clear_error();
+    return CSIC_OK;
+}
+
+const char *csic_decode_view_kernel_name(const csic_plan *plan, int32_t src_format, int32_t out_format, const csic_view *view)
+{
+    static thread_local char buf[96];
+    if (!plan || !view || decode_check_formats(src_format, out_format) != CSIC_OK || check_view(plan->g, *view) != CSIC_OK) return "";
+    ViewPlan vp;                                                        // one frame in aligned buffers
+    plan_view(plan->g, plan->tune, *view, 0, 1, &vp);
+    view_kernel_name(vp, plan->tune, src_format, out_format, buf, sizeof buf);
+    return buf;
+}
+
+int csic_decode_view_device(csic_plan *plan, const void *d_src, int32_t src_format, const csic_view *view, void *d_out, int32_t out_format,
+                            int32_t nframes, void *hip_stream)
+{
+    if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
+    if (!view) return set_error(CSIC_EINVAL_NULL, "view is NULL");
+    if (!d_src || !d_out) return set_error(CSIC_EINVAL_NULL, "device buffer is NULL");
+    if (nframes <= 0) return set_error(CSIC_EINVAL_SIZE, "nframes must be positive. Got %d", nframes);
+    int st = decode_check_formats(src_format, out_format);
+    if (st != CSIC_OK) return st;
+    const Geometry &g = plan->g;
+    st = check_view(g, *view);
+    if (st != CSIC_OK) return st;
+    const bool planar = dec_is_planar(src_format);
+    if (planar && ((uintptr_t)d_src & 255u)) return set_error(CSIC_EINVAL_SIZE, "a planar frame buffer must be 256-byte aligned");
+    if (((uintptr_t)d_src & 3u) || ((uintptr_t)d_out & 3u)) return set_error(CSIC_EINVAL_SIZE, "source and output must be 4-byte aligned");
+    if ((int64_t)g.W * g.H >= ((int64_t)1 << 31)) return set_error(CSIC_EINVAL_SIZE, "frame too large for csic_decode_view_device");
+    ViewPlan vp;                                                        // kind, threads and blocks: csic_select.cpp
+    plan_view(g, plan->tune, *view, (uintptr_t)d_out, nframes, &vp);
+    const ViewFn fn = view_kernel(vp, src_format, out_format, !plan->tune.no_nt);
+    ViewArgs a;
+    std::memset(&a, 0, sizeof a);
+    fill_dec_args(plan, src_format, &a.d);
+    a.view_px = (int64_t)view->width * view->height;
+    a.units = vp.units;
+    a.x0 = view->x0; a.y0 = view->y0; a.vw = view->width; a.vh = view->height; a.ls = vp.ls;
+    a.ncx = vp.ncx; a.ncy = vp.ncy;
+    a.whole = view->scale >= g.f && view->x0 % g.f == 0 && view->y0 % g.f == 0;
+    a.U = vp.units_per_row; a.T = vp.T;
+    magic_div((uint32_t)a.U, &a.mU, &a.kU);
+    CSIC_DEVICE_SCOPE(plan->device);
+    st = for_frame_batches(nframes, [&](int f0, int nz) {
+        a.d.src = static_cast<const uint8_t *>(d_src) + (int64_t)f0 * a.d.src_frame_bytes;
+        a.dst = static_cast<uint32_t *>(d_out) + (int64_t)f0 * a.view_px;
+        return launch(fn, dim3(vp.grid.x, 1, (unsigned)nz), dim3(vp.block.x, 1, 1), static_cast<hipStream_t>(hip_stream), a);
+    });
+    if (st != CSIC_OK) return st;
+    clear_error();
+    return CSIC_OK;
+}
+
+int csic_decode_view_host(csic_plan *plan, const void *src, size_t src_bytes, int32_t src_format, const csic_view *view, uint32_t *out,
+                          size_t out_px, int32_t out_format, int32_t nframes)
+{
+    if (!plan) return set_error(CSIC_EINVAL_NULL, "plan is NULL");
+    if (!view) return set_error(CSIC_EINVAL_NULL, "view is NULL");
+    if (!src || !out) return set_error(CSIC_EINVAL_NULL, "host buffer is NULL");
+    if (nframes <= 0) return set_error(CSIC_EINVAL_SIZE, "nframes must be positive. Got %d", nframes);
+    int st = decode_check_formats(src_format, out_format);
+    if (st != CSIC_OK) return st;
+    st = check_view(plan->g, *view);
+    if (st != CSIC_OK) return st;
+    const size_t need_src = (size_t)nframes * (size_t)dec_src_frame_bytes(plan, src_format);
+    const size_t need_out = (size_t)nframes * (size_t)view->width * (size_t)view->height;
+    if (src_bytes != need_src) return set_error(CSIC_EINVAL_SIZE, "expected %zu source bytes (%d frames), got %zu", need_src, nframes, src_bytes);
+    if (out_px != need_out) return set_error(CSIC_EINVAL_SIZE, "expected room for %zu output pixels (%d frames), got %zu", need_out, nframes, out_px);
+    CSIC_DEVICE_SCOPE(plan->device);
+    DeviceStaging dev;
+    void *d_src = dev.alloc(need_src), *d_out = dev.alloc(need_out * 4);
+    dev.to_device(d_src, src, need_src);
+    if (dev.ok()) {
+        st = csic_decode_view_device(plan, d_src, src_format, view, d_out, out_format, nframes, nullptr);
+        if (st == CSIC_OK) { dev.to_host(out, d_out, need_out * 4); dev.sync(); }
+    }
+    if (st != CSIC_OK) return st;
+    if (!dev.ok()) return set_error(CSIC_EHIP, "csic_decode_view_host: %s", hipGetErrorString(dev.error()));
     clear_error();
     return CSIC_OK;
 }

@@ -620,4 +620,50 @@ void decode_kernel_name(const DecodePlan &pp, const Geometry &g, const Tune &t, 
     }
 }
 
+// ---- view decode ------------------------------------------------------------------------------------------------------------
+int check_view(const Geometry &g, const csic_view &v)
+{
+    const int s = v.scale;
+    if (s != 1 && s != 2 && s != 4 && s != 8 && s != 16)
+        return set_error(CSIC_EINVAL_SIZE, "a view's scale is 1, 2, 4, 8 or 16. Got %d", s);
+    if (v.x0 < 0 || v.y0 < 0 || v.width < 1 || v.height < 1 || (int64_t)v.x0 + (int64_t)v.width * s > g.W || (int64_t)v.y0 + (int64_t)v.height * s > g.H)
+        return set_error(CSIC_EINVAL_SIZE, "the view %d x %d at (%d, %d), scale %d, does not lie inside the %d x %d frame", v.width, v.height,
+                         v.x0, v.y0, s, g.W, g.H);
+    return CSIC_OK;
+}
+
+// the most decimated cells a box of s pixels can touch along one axis when boxes start at origin + k s
+static int view_cells(int origin, int s, int f)
+{
+    if (s >= f) return s / f + (origin % f != 0 ? 1 : 0);      // f divides s: every box starts at the same offset inside a cell
+    return origin % s != 0 ? 2 : 1;                            // s divides f: a box that starts at a multiple of s stays inside one cell
+}
+
+int plan_view(const Geometry &g, const Tune &t, const csic_view &v, uintptr_t align_bits, int nframes, ViewPlan *pp)
+{
+    const int64_t px = (int64_t)v.width * v.height;
+    const int nz = nframes < 65535 ? nframes : 65535;
+    const bool general = t.variant == 9 || t.force_generic || t.no_vec;
+    pp->kind = (general || (align_bits & 15u) || v.width % VIEW_PX != 0 || px > ((int64_t)1 << 30)) ? VIEW_GEN : VIEW_FAST;
+    pp->ls = 0;
+    while ((1 << pp->ls) < v.scale) ++pp->ls;
+    pp->units_per_row = pp->kind == VIEW_FAST ? v.width / VIEW_PX : v.width;
+    pp->units = (int64_t)pp->units_per_row * v.height;
+    pp->ncx = view_cells(v.x0, v.scale, g.f);
+    pp->ncy = view_cells(v.y0, v.scale, g.f);
+    // a lane of k_view walks 4 boxes: one-wave blocks spread a small view over the device; k_view_gen as k_decode_gen
+    plane_flat(pp->units, 1, tune_block_threads(t, pp->kind == VIEW_FAST ? 64 : 256), nz, pp);
+    pp->bdx = pp->bdy = pp->row_step = 0;
+    return CSIC_OK;
+}
+
+void view_kernel_name(const ViewPlan &pp, const Tune &t, int src_format, int out_format, char *buf, size_t len)
+{
+    // an ARGB source runs the YCbCr -> YCbCr instantiation, as in decode_kernel_name
+    const char *fmt = out_format == CSIC_FMT_ARGB8888 && src_format != CSIC_FMT_ARGB8888 ? "argb" : "ycc";
+    const char *src = src_format == CSIC_FMT_PLANAR_BITS ? "bits" : src_format == CSIC_FMT_PLANAR ? "planar" : "ycc";
+    if (pp.kind == VIEW_FAST) snprintf(buf, len, "k_view<s%d,%s,%s,%s>", 1 << pp.ls, src, fmt, !t.no_nt ? "nt" : "cached");
+    else snprintf(buf, len, "k_view_gen<%s,%s>", src, fmt);
+}
+
 } // namespace csic

@@ -1,7 +1,7 @@
 // csic_select.h -- the host-only planner: which packed kernel a parameter set takes (select_kernel), what it is called
 // (kernel_name) and with what grid, block and kernel arguments it is launched (plan_launch); which kernel the measurement units
 // take (measure_kind, measure_kernel_name); and the same three decisions for the plane units (plan_planar, plan_planar_bits,
-// plan_reconstruct, plan_decode and their name functions).  Pure integer arithmetic on csic_params, Geometry, the layouts of
+// plan_reconstruct, plan_decode, plan_view and their name functions).  Pure integer arithmetic on csic_params, Geometry, the layouts of
 // csic_internal.h and the tuning knobs: no HIP header, no device; csic_kernels.hip turns a KernelId into a function pointer
 // (resolve), csic_measure.h and the plane units a kind into one, and tests/cpp/launch_table.cpp prints the whole table on a
 // machine without a GPU.
@@ -153,5 +153,25 @@ void planar_kernel_name(PlanarKind kind, const csic_params &p, const Geometry &g
 void planar_bits_kernel_name(BitsKind kind, const csic_params &p, const Geometry &g, const Tune &t, char *buf, size_t len);
 void reconstruct_kernel_name(int src_format, int out_format, bool fast, const Tune &t, char *buf, size_t len);
 void decode_kernel_name(const DecodePlan &pp, const Geometry &g, const Tune &t, int src_format, int out_format, char *buf, size_t len);
+
+// ---- view decode (csic_decode_view_*, csic_decode.hip) ----------------------------------------------------------------------
+constexpr int VIEW_PX = 4;                      // output pixels per lane of k_view (one 16-byte store)
+enum ViewKind { VIEW_GEN, VIEW_FAST };
+// T lanes per block along x, one UNIT per lane: VIEW_PX consecutive output pixels of a row (k_view; units_per_row = width / 4) or
+// one output pixel (k_view_gen; units_per_row = width); grid.x * T >= units = units_per_row * view.height.  ncx / ncy: the most
+// decimated columns / rows one s x s box can touch -- s / f, one more where the view's origin is no multiple of f; 1 or 2 at s < f.
+struct ViewPlan : PlaneLaunch {
+    ViewKind kind;
+    int32_t ls;                                 // log2 scale
+    int32_t units_per_row, ncx, ncy;
+    int64_t units;
+};
+// CSIC_OK, or CSIC_EINVAL_SIZE for a scale outside {1, 2, 4, 8, 16} or a source rectangle that leaves the frame (64-bit arithmetic)
+int check_view(const Geometry &g, const csic_view &v);
+// csic_decode_view_device for a checked view; align_bits: the output pointer.  The fast kernel is taken when view.width % 4 == 0, the
+// output is 16-byte aligned, the view has at most 2^30 pixels and no knob (variant 9, NO_VECTOR, FORCE_GENERIC) asks for the general one.
+int plan_view(const Geometry &g, const Tune &t, const csic_view &v, uintptr_t align_bits, int nframes, ViewPlan *pp);
+// "k_view<s8,bits,argb,nt>", "k_view_gen<planar,ycc>"
+void view_kernel_name(const ViewPlan &pp, const Tune &t, int src_format, int out_format, char *buf, size_t len);
 
 } // namespace csic

@@ -552,6 +552,42 @@ int  csic_decode_host(csic_plan *plan, const void *src, size_t src_bytes, int32_
                       int32_t out_format, int32_t nframes);
 const char *csic_decode_kernel_name(const csic_plan *plan, int32_t src_format, int32_t out_format);
 
+/* ---- view decode: a cropped, box-reduced window of a compressed frame ---------------------------------------------------------
+ * csic_decode_* produce the whole frame.  csic_decode_view_* produce a window of it, reduced by an s x s box, without writing the
+ * frame: a thumbnail of all of it, or full detail of a part of it.
+ *
+ * Definition.  Let `decode` be csic_decode_*'s frame for the same plan, source format and output format, and s = view->scale, one
+ * of 1, 2, 4, 8, 16.  For 0 <= r < view->height, 0 <= c < view->width and each of the four bytes b of a packed pixel
+ *     view(r, c).b = ( SUM over i < s, j < s of decode(y0 + r s + i, x0 + c s + j).b  +  (s s >> 1) ) >> (2 log2 s)
+ * -- the average is taken over the decoded BYTES, after the inverse transform and its clamps, not over the samples (for an ARGB
+ * output that is a different number from transforming an average); the fourth byte is treated like the others (it is constant in
+ * `decode`, so it comes through unchanged); s = 1 is a crop of `decode`, bit for bit.  There is no partial box and no division.
+ * Worked vector, s = 2, the four decoded pixels of one box -> the view's pixel:
+ *     FF102030 FF112131 FF122232 FF142434 -> FF122232      (B: 30 + 31 + 32 + 34 = C7 hex, + 2, >> 2 = 32 hex)
+ *     FF000000 FF000001 FF0000FF FF000100 -> FF000040      (B: 0 + 1 + FF + 0 = 100 hex -> 40; G: 0 + 0 + 0 + 1 -> (1 + 2) >> 2 = 0)
+ * view->width and view->height count OUTPUT pixels; the source rectangle must lie inside the frame: x0, y0 >= 0, width, height >= 1,
+ * x0 + width s <= the plan's width and y0 + height s <= the plan's height, evaluated in 64 bits.  A rectangle that does not, and a
+ * scale outside the set, are refused with CSIC_EINVAL_SIZE.  Source and output formats, the refused ARGB -> YCbCr pair, the alignment
+ * rules (256-byte aligned planar frames; a packed source or an output that is only 4-byte aligned works), HOLD_DECIMATE and AVG and
+ * all six orders are as for csic_decode_*.  Output: view->width * view->height pixels per frame, back to back; the one view applies
+ * to all `nframes` frames.
+ * csic_decode_view_device : asynchronous on `hip_stream`, no allocation, no synchronisation, hipGraph-capturable; NULL arguments fail
+ *             with CSIC_EINVAL_NULL and nframes <= 0, a bad view or a bad format with their codes before any device is touched.  More
+ *             than 65535 frames go out as several launches.
+ * csic_decode_view_host   : the same from and to host memory, synchronous, allocates its staging; src_bytes as for csic_decode_host,
+ *             out_px = nframes * view->width * view->height (CSIC_EINVAL_SIZE otherwise).
+ * csic_decode_view_kernel_name : the kernel csic_decode_view_device takes for one frame in 16-byte aligned buffers ("" for a refused
+ *             format pair or view): k_view<...>, a lane per 4 output pixels and 16-byte stores, when view->width % 4 == 0, else
+ *             k_view_gen<...>, a lane per output pixel.  The string belongs to the calling thread until its next call of this function.
+ * CSIC_TUNE_VARIANT 9, CSIC_TUNE_NO_VECTOR and CSIC_TUNE_FORCE_GENERIC select the general kernel; CSIC_TUNE_NONTEMPORAL and
+ * CSIC_TUNE_BLOCK_THREADS apply as in csic_decode_device. */
+typedef struct csic_view { int32_t x0, y0, width, height, scale; } csic_view;   /* width, height: OUTPUT pixels */
+int  csic_decode_view_device(csic_plan *plan, const void *d_src, int32_t src_format, const csic_view *view, void *d_out,
+                             int32_t out_format, int32_t nframes, void *hip_stream);
+int  csic_decode_view_host(csic_plan *plan, const void *src, size_t src_bytes, int32_t src_format, const csic_view *view, uint32_t *out,
+                           size_t out_px, int32_t out_format, int32_t nframes);
+const char *csic_decode_view_kernel_name(const csic_plan *plan, int32_t src_format, int32_t out_format, const csic_view *view);
+
 /* Row pitches, in pixels, at which frames of this plan stream fastest when the CALLER lays them out
  * (csic_process_pitched_device).  Measured on 2048- to 16384-pixel rows x every factor x 13 (input pad, output pad) pairs
  * (tools/probe_pitch2.py, profiles/r04_probe_pitch.jsonl, r04_probe_pitch_f1flat.jsonl): on the round-4 kernels packed rows are

@@ -109,6 +109,12 @@ struct PlanarBitsFrame {
     std::vector<uint8_t> bytes;                                   // layout.frame_bytes long
 };
 
+// A window of a decoded frame for ImageCompressorTop::decodeView (csic.h: csic_view): the source rectangle starts at (x0, y0) and
+// covers width * scale x height * scale decoded pixels; width and height count OUTPUT pixels; scale is 1, 2, 4, 8 or 16.
+struct View : csic_view {
+    View(int x0_, int y0_, int width_, int height_, int scale_ = 1) : csic_view{x0_, y0_, width_, height_, scale_} {}
+};
+
 // A .csic file (csic.h: csic_container_*): `nframes` bit-packed planar frame buffers of one parameter set, layout.frame_bytes apart
 // in `bytes`.  Host only -- none of the three functions needs a GPU.  File and format errors surface as csic::RuntimeError with
 // status CSIC_EIO / CSIC_EFORMAT.
@@ -679,6 +685,29 @@ public:
     const char *decodeKernelName(PixelFormat src_format, PixelFormat f = PixelFormat::ARGB8888)
     {
         return csic_decode_kernel_name(plan(PixelFormat::ARGB8888), (int32_t)src_format, (int32_t)f);
+    }
+    // View decode (csic_decode_view_*): the window of the decoded frame that starts at (view.x0, view.y0), reduced by a view.scale x
+    // view.scale box -- view.width x view.height pixels per frame, each the rounded mean of the decoded pixels under its box.
+    std::vector<uint32_t> decodeView(const void *src, size_t src_bytes, const View &view, PixelFormat src_format = PixelFormat::PLANAR_BITS,
+                                     PixelFormat f = PixelFormat::ARGB8888, int nframes = 1)
+    {
+        const bool sized = view.width > 0 && view.height > 0 && nframes > 0;
+        std::vector<uint32_t> out(sized ? (size_t)view.width * (size_t)view.height * (size_t)nframes : 1);   // (1: a view without pixels is the library's to refuse)
+        check(csic_decode_view_host(plan(PixelFormat::ARGB8888), src, src_bytes, (int32_t)src_format, &view, out.data(), out.size(), (int32_t)f, nframes));
+        return out;
+    }
+    std::vector<uint32_t> decodeView(const PlanarBitsFrame &fr, const View &view, PixelFormat f = PixelFormat::ARGB8888)
+    {
+        return decodeView(fr.bytes.data(), fr.bytes.size(), view, PixelFormat::PLANAR_BITS, f, 1);
+    }
+    void decodeViewDevice(const void *d_src, PixelFormat src_format, const View &view, void *d_out, int nframes, void *hip_stream,
+                          PixelFormat f = PixelFormat::ARGB8888)
+    {
+        check(csic_decode_view_device(plan(PixelFormat::ARGB8888), d_src, (int32_t)src_format, &view, d_out, (int32_t)f, nframes, hip_stream));
+    }
+    const char *decodeViewKernelName(PixelFormat src_format, const View &view, PixelFormat f = PixelFormat::ARGB8888)
+    {
+        return csic_decode_view_kernel_name(plan(PixelFormat::ARGB8888), (int32_t)src_format, (int32_t)f, &view);
     }
     const csic_params &params() const { return params_; }
     // what row pitch (pixels, input / output) a caller that owns its surfaces should allocate for csic_process_pitched_device
